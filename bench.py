@@ -48,6 +48,43 @@ def synthetic_batch(cfg, B, frames, seed, device):
     return audio, video, labels, labels[:, :32].clone()
 
 
+DUMP_LIMIT = 64 << 20        # --dump-outputs: bytes written in all
+DUMP_SAMPLE = 4 << 20        # elements kept of a flat output too large to write whole (a fixed, seeded choice of positions)
+
+
+def trainable_state(trainer):
+    """The buffers one train step reads and updates besides its batch: LoRA masters, Adam moments, device step state, skip count."""
+    return [trainer.model.llm_engine.lora_p, trainer.m, trainer.v, trainer.state, trainer.skipped]
+
+
+def restore_trainable_state(trainer, saved):
+    """Copy a trainable_state() snapshot back into the live buffers (same storage: captured step graphs stay valid) and refresh the
+    padded adapter images the step reads."""
+    for dst, src in zip(trainable_state(trainer), saved):
+        dst.copy_(src)
+    trainer.model.llm_engine.pack_lora()
+
+
+def dump_outputs(out_dir, loss, eng):
+    """What the timed step hands its caller, as of the last timed step: the mean loss, the updated LoRA parameters (the flat fp32 master
+    buffer the optimizer writes) and the LoRA gradients that update was made from.  float32 .npy files; a flat buffer larger than
+    DUMP_SAMPLE elements is written as the DUMP_SAMPLE elements at fixed, seeded positions (sorted), so that runs of two builds with the
+    same arguments compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu()}
+    for name, buf in (("lora_params", eng.lora_p), ("lora_grads", eng.lora_g)):
+        flat = buf.detach().float().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays[name] = flat.cpu()
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    import numpy as np
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy().astype(np.float32))
+
+
 PMC_SUMMARY = "profiles/r03_pmc_hbm_summary_b16.txt"
 TIMING_EVERY = 10
 
@@ -267,6 +304,9 @@ def main():
     ap.add_argument("--no-decode", action="store_true", help="skip the greedy-decode leg")
     ap.add_argument("--no-config5", action="store_true", help="skip the variants.config5_fp8 leg (BASELINE configs[4] in fp8 and bf16, B=4 x 750 frames)")
     ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (loss, LoRA parameters, "
+                    "LoRA gradients) as DIR/<name>.npy (rank 0).  That step starts from the seeded initial trainable state (LoRA "
+                    "parameters, Adam moments, step count; restored just before it), so its inputs are the same every run")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying the captured hipGraph")
     ap.add_argument("--tiny", action="store_true", help="tiny model (plumbing check)")
     ap.add_argument("--whisper", default="openai/whisper-small", help="audio encoder by name (BASELINE config = whisper-small; config 5: openai/whisper-large-v3)")
@@ -274,6 +314,8 @@ def main():
     ap.add_argument("--llm", default="meta-llama/Llama-2-7b-hf", help="LLM architecture by name (BASELINE config = Llama-2-7B); e.g. "
                     "meta-llama/Meta-Llama-3-8B or TinyLlama/TinyLlama-1.1B for the grouped-query family")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -322,6 +364,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # --dump-outputs: the dumped step's starting state is an input like its batch.  The steps before it sum their LoRA gradients
+    # with fp32 atomics, so the state they leave differs from run to run, and Adam amplifies that; the seeded initial state does not
+    initial_state = [t.clone() for t in trainable_state(trainer)] if args.dump_outputs else None
     loss = None
     for _ in range(args.warmup):
         loss = trainer.train_step(audio, video, labels, prompt)
@@ -343,6 +388,8 @@ def main():
     for i in range(args.steps):
         if i:
             marks[i].record()
+        if initial_state is not None and i == args.steps - 1:
+            restore_trainable_state(trainer, initial_state)
         if timing:
             on = i % TIMING_EVERY == 0
             L.check(lib.avllm_profile_enable(1 if on else 0))
@@ -362,6 +409,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt)
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:              # before the secondary legs, which take further optimizer steps
+        dump_outputs(args.dump_outputs, loss, model.llm_engine)
     host_leg = None
     if not args.no_host_inputs and not args.tiny and world == 1:      # secondary legs run at N = 1 only: the scaling runs time the contract's step and nothing else
         host_leg = host_inputs_leg(args, cfg, model, trainer, labels, prompt, dev, rank, world, barrier)
