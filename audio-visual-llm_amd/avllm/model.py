@@ -350,14 +350,19 @@ class ClipWhisperModel:
     # ------------------------------------------------------------------ generation
     @torch.no_grad()
     def generate(self, audio=None, video=None, prompt=None, pixel_values=None, max_new_tokens=100, do_sample=False,
-                 temperature=1.0, top_p=0.9, max_length=None):
-        """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search; returns NEW tokens only [B, <=max_new_tokens]."""
+                 temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None):
+        """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search, or with do_sample=True its sampling: temperature -> top_k
+        (HF's GenerationConfig default 50; 0 = off) -> top_p -> one draw per row on the device (ops.sample_rows).  seed=None draws the
+        seed from torch's default CPU generator, so torch.manual_seed makes a sampled run repeat; row b draws with seed + b.
+        With do_sample=False, temperature / top_k / top_p are ignored.  Returns NEW tokens only [B, <=max_new_tokens]."""
         if video is None and pixel_values is not None:
             video = pixel_values
         if max_new_tokens is None:
             max_new_tokens = max_length if max_length is not None else 100
         if do_sample:
-            raise NotImplementedError("do_sample=True: the reference's decode path is greedy (decode.py:544-549)")
+            ops.check_sampling(temperature, top_k, top_p)
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         original = self.modality
         if audio is not None and video is not None:
             self.modality = "both"
@@ -376,11 +381,16 @@ class ClipWhisperModel:
         eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
         unfinished = torch.ones(B, dtype=torch.bool, device=x.device)
         out = []
+        row_seeds = torch.arange(B, dtype=torch.int32, device=x.device) if do_sample else None
         for step in range(max_new_tokens):
-            nxt = ops.argmax_rows(logits)
-            if eos is not None:
-                nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
-                unfinished = unfinished & (nxt != eos)
+            if do_sample:
+                nxt = ops.sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=unfinished if eos is not None else None,
+                                      eos=eos, pad=pad, row_seeds=row_seeds)
+            else:
+                nxt = ops.argmax_rows(logits)
+                if eos is not None:
+                    nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
+                    unfinished = unfinished & (nxt != eos)
             out.append(nxt)
             if step + 1 == max_new_tokens or (eos is not None and not bool(unfinished.any())):
                 break

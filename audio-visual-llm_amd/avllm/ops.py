@@ -170,6 +170,40 @@ def argmax_rows(logits2d):
     return out
 
 
+def check_sampling(temperature, top_k, top_p):
+    """The argument rules of HF's TemperatureLogitsWarper / TopKLogitsWarper / TopPLogitsWarper."""
+    if not (float(temperature) > 0.0 and float(temperature) < float("inf")):
+        raise ValueError(f"temperature must be a strictly positive float, got {temperature}")
+    if not (0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"top_p must be a float in (0, 1], got {top_p}")
+    if int(top_k) != top_k or int(top_k) < 0:
+        raise ValueError(f"top_k must be a non-negative integer, got {top_k}")
+
+
+def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, eos=None, pad=None, row_seeds=None):
+    """One sampled token per row of fp32/bf16 logits [rows, V]: temperature -> top-k (0 = off) -> top-p -> draw (csrc/sample.hip).
+    seed: uint32 (row r uses seed + row_seeds[r] when row_seeds, an int32 device tensor [rows], is given); step: int, or an int32 device
+    tensor of one element (read by the kernel).  unfinished: optional bool [rows], updated in place: finished rows get pad, a row that draws
+    eos is finished.  Returns int64 [rows]."""
+    check_sampling(temperature, top_k, top_p)
+    rows, V = logits.shape
+    out = torch.empty(rows, device=logits.device, dtype=torch.int64)
+    step_dev = None
+    if torch.is_tensor(step):
+        assert step.dtype == torch.int32 and step.numel() == 1 and step.is_cuda
+        step_dev, step = step, 0
+    if unfinished is not None:
+        assert unfinished.dtype == torch.bool and unfinished.shape == (rows,) and unfinished.is_contiguous()
+    if row_seeds is not None:
+        assert row_seeds.dtype == torch.int32 and row_seeds.shape == (rows,) and row_seeds.is_contiguous()
+    eos = -1 if eos is None else int(eos)
+    pad = (eos if eos >= 0 else 0) if pad is None else int(pad)
+    L.check(L.load().avllm_sample_rows(L.ptr(logits), _ld(logits), rows, V, float(temperature), int(top_k), float(top_p),
+                                       int(seed) & 0xFFFFFFFF, L.ptr(row_seeds), int(step), L.ptr(step_dev), L.ptr(unfinished), eos, pad,
+                                       L.ptr(out), L.dt_of(logits), L.stream_ptr()))
+    return out
+
+
 def embedding(table, ids):
     ids = ids.contiguous()
     out = torch.empty(*ids.shape, table.shape[1], device=table.device, dtype=table.dtype)

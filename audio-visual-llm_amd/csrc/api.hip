@@ -78,6 +78,11 @@ int avllm_ce_fwd(const void* logits, int64_t ld, const int64_t* labels, int32_t 
 int avllm_ce_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* row_lse, const float* count, float grad_scale,
                  void* dlogits, int32_t B, int32_t T, int32_t V, int32_t dtype, void* stream) { return av_ce_bwd(logits, ld, labels, row_lse, count, grad_scale, dlogits, B, T, V, dtype, ST); }
 int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, int64_t* out, int32_t dtype, void* stream) { return av_argmax_rows(logits, ld, rows, V, out, dtype, ST); }
+int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
+                      const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
+                      int64_t* out, int32_t dtype, void* stream) {
+    return av_sample_rows(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, dtype, ST);
+}
 int avllm_embedding(const void* table, const int64_t* ids, void* out, int64_t n, int32_t d, int32_t dtype, void* stream) { return av_embedding(table, ids, out, n, d, dtype, ST); }
 int avllm_cast(const void* src, int32_t sdt, void* dst, int32_t ddt, int64_t n, void* stream) { return av_cast(src, sdt, dst, ddt, n, ST); }
 int avllm_dropout(const void* x, void* y, int64_t rows, int32_t d, uint32_t seed, float p, int32_t dtype, void* stream) { return av_dropout(x, y, rows, d, seed, p, dtype, ST); }

@@ -30,6 +30,9 @@ int av_ce_fwd(const void* logits, long ld, const int64_t* labels, int B, int T, 
 int av_ce_bwd(const void* logits, long ld, const int64_t* labels, const float* row_lse, const float* count,
               float grad_scale, void* dlogits, int B, int T, int V, int dtype, hipStream_t st);
 int av_argmax_rows(const void* logits, long ld, long rows, int V, int64_t* out, int dtype, hipStream_t st);
+int av_sample_rows(const void* logits, long ld, long rows, int V, float temperature, int top_k, float top_p, uint32_t seed,
+                   const uint32_t* row_seeds, int step, const int* step_dev, uint8_t* unfinished, long long eos, long long pad,
+                   int64_t* out, int dtype, hipStream_t st);
 int av_embedding(const void* table, const int64_t* ids, void* out, long n, int d, int dtype, hipStream_t st);
 int av_cast(const void* src, int sdt, void* dst, int ddt, long n, hipStream_t st);
 int av_whisper_im2col1(const float* mel, void* cols, int B, int n_mels, int T, int Kpad, int dtype, hipStream_t st);

@@ -206,6 +206,16 @@ int avllm_attention_fwd_mxq(const void* q, const void* k, const void* v, void* o
 int avllm_ce_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* row_lse, const float* count,
                  float grad_scale, void* dlogits, int32_t B, int32_t T, int32_t V, int32_t dtype, void* stream);
 int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, int64_t* out, int32_t dtype, void* stream);
+/* One sampled token per row (GenerationMixin with do_sample=True, clip_whisper_model.py:1326-1340): HF's TemperatureLogitsWarper
+ * (logits / temperature), TopKLogitsWarper (top_k > 0: keys below the k-th largest scaled logit dropped, ties kept; 0 = off) and
+ * TopPLogitsWarper (top_p < 1: in descending order, the shortest prefix whose tail mass is <= 1 - top_p, plus every token whose scaled logit
+ * equals that of the last kept one), then an inverse-CDF draw over the kept tokens in vocabulary-index order with the uniform
+ * u = hash(seed + (row_seeds ? row_seeds[r] : 0), step + (step_dev ? *step_dev : 0)): a row's token depends on its logits, its seed and the
+ * step only.  top_k == 1 is avllm_argmax_rows exactly.  unfinished (optional, one byte per row): rows with 0 get pad; a row that draws eos
+ * (eos >= 0) is cleared.  temperature > 0, 0 < top_p <= 1, top_k >= 0, V <= 524288; deterministic (integer reductions only). */
+int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
+                      const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
+                      int64_t* out, int32_t dtype, void* stream);
 /* out[i,:] = table[ids[i],:] ; llm.get_input_embeddings() (clip_whisper_model.py:464-487) */
 int avllm_embedding(const void* table, const int64_t* ids, void* out, int64_t n, int32_t d, int32_t dtype, void* stream);
 int avllm_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);

@@ -7,7 +7,9 @@ manifest to the lines of the .wrd file (:318-372, with the path-less id as a sec
 `batch_decode`, per-utterance and corpus WER, and the same files: decode_<ts>.log, results_<ts>.txt (the reference's table),
 wer_<ts>.txt ("Overall WER" / "Total samples").
 
-Additions of this build (not reference flags): --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
+Additions of this build (not reference flags): --do_sample / --top_p (default 0.9) / --top_k (default 50) (sampled `generate`:
+temperature -> top-k -> top-p on the device, its seed drawn after torch.manual_seed(--seed); without --do_sample decoding stays
+greedy and --temperature is ignored, as in the reference), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -46,6 +48,9 @@ def parse_args(argv=None):
     p.add_argument("--text_key", type=str, default="text")
     p.add_argument("--output_file", type=str, default="decode_results.json")
     # ---- this build's additions
+    p.add_argument("--do_sample", action="store_true", help="sample instead of greedy decoding (temperature, top_k, top_p)")
+    p.add_argument("--top_p", type=float, default=0.9)
+    p.add_argument("--top_k", type=int, default=50, help="0 turns top-k off")
     p.add_argument("--load_lora", action="store_true")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
@@ -154,7 +159,8 @@ def main(argv=None):
         try:
             audio = None if (audio is None or a.modality == "video") else audio.to(dev)
             video = None if (video is None or a.modality == "audio") else video.to(dev)
-            ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature)
+            ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
+                                 do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k)
             out = model.tokenizer.batch_decode(ids.cpu(), skip_special_tokens=True)
             if a.calculate_loss:
                 lab = model.tokenizer(list(texts), padding="max_length", truncation=True, max_length=256, return_tensors="pt").input_ids
