@@ -350,15 +350,29 @@ class ClipWhisperModel:
     # ------------------------------------------------------------------ generation
     @torch.no_grad()
     def generate(self, audio=None, video=None, prompt=None, pixel_values=None, max_new_tokens=100, do_sample=False,
-                 temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None):
+                 temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False,
+                 return_sequence_scores=False):
         """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search, or with do_sample=True its sampling: temperature -> top_k
         (HF's GenerationConfig default 50; 0 = off) -> top_p -> one draw per row on the device (ops.sample_rows).  seed=None draws the
         seed from torch's default CPU generator, so torch.manual_seed makes a sampled run repeat; row b draws with seed + b.
-        With do_sample=False, temperature / top_k / top_p are ignored.  Returns NEW tokens only [B, <=max_new_tokens]."""
+        With do_sample=False, temperature / top_k / top_p are ignored.  Returns NEW tokens only [B, <=max_new_tokens].
+        num_beams > 1: HF's beam search (see _beam_search; length_penalty, early_stopping in {True, False, "never"} as in HF); returns the
+        best hypothesis per item, padded with pad_token_id, and with return_sequence_scores=True also HF's sequences_scores [B]."""
         if video is None and pixel_values is not None:
             video = pixel_values
         if max_new_tokens is None:
             max_new_tokens = max_length if max_length is not None else 100
+        if int(num_beams) != num_beams or num_beams < 1:
+            raise ValueError(f"num_beams must be a positive integer, got {num_beams}")
+        if num_beams > 1:
+            if do_sample:
+                raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
+            if num_beams > ops.BEAM_MAX_BEAMS:
+                raise ValueError(f"num_beams must be at most {ops.BEAM_MAX_BEAMS}, got {num_beams}")
+            if early_stopping not in (True, False, "never"):
+                raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+        elif return_sequence_scores:
+            raise ValueError("return_sequence_scores needs num_beams > 1 (HF returns sequences_scores for beam search only)")
         if do_sample:
             ops.check_sampling(temperature, top_k, top_p)
             if seed is None:
@@ -374,6 +388,8 @@ class ClipWhisperModel:
             x = self._llm_inputs(audio, video, prompt)
         finally:
             self.modality = original
+        if num_beams > 1:
+            return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores)
         eng = self.llm_engine
         B, S, _ = x.shape
         kc, vc = eng.alloc_cache(B, S + max_new_tokens)
@@ -396,3 +412,91 @@ class ClipWhisperModel:
                 break
             logits = eng.decode_step(nxt, S + step, kc, vc)
         return torch.stack(out, dim=1)
+
+    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores):
+        """GenerationMixin._beam_search (transformers 5.x, generation/utils.py) for inputs_embeds x [B, S, d]: decoder_prompt_len = 0, so a
+        hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
+        the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
+        (_get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic,
+        _beam_search_has_unfinished_sequences) restated on small device tensors, and ops.kv_gather_rows reordering only the generated
+        positions [S, S + step): every beam of an item shares the prefix [0, S), which is copied once from the B-row prefill cache.
+        Equal scores keep candidate order (stable sorts where HF calls torch.topk).  One host sync per step, for the stopping test.
+        B*nb <= 16 rows take the fused bf16 token step (LlamaEngine.decode_is_fused); more rows take the general step."""
+        eng = self.llm_engine
+        dev = x.device
+        B, S, _ = x.shape
+        R, k, N = B * nb, 2 * nb, max_new_tokens
+        eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
+        kc0, vc0 = eng.alloc_cache(B, S)
+        logits, _ = eng.prefill(x, kc0, vc0)
+        kc, vc = eng.alloc_cache(R, S + N)
+        ops.kv_gather_rows(kc0, vc0, kc, vc, torch.arange(R, device=dev, dtype=torch.int32) // nb, 0, S)    # prefix broadcast
+        del kc0, vc0
+        logits = logits.repeat_interleave(nb, dim=0)                # step 0: every beam of an item sees the prefill logits
+        NEG = -1.0e9
+        running_seq = torch.full((B, nb, N), pad, dtype=torch.int64, device=dev)
+        sequences = running_seq.clone()
+        running_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
+        running_scores[:, 1:] = NEG
+        beam_scores = torch.full((B, nb), NEG, dtype=torch.float32, device=dev)
+        lengths = torch.zeros((B, nb), dtype=torch.int64, device=dev)             # generated length of each finished hypothesis
+        is_sent_finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
+        unsatisfied = torch.ones((B, 1), dtype=torch.bool, device=dev)
+        top_mask = torch.arange(k, device=dev) < nb
+        offset = (torch.arange(B, device=dev, dtype=torch.int32) * nb)[:, None]
+        done_host = torch.zeros(1, dtype=torch.bool).pin_memory()
+        ev = torch.cuda.Event()
+        for cur in range(N):
+            # _get_top_k_continuations
+            topk_lp, topk_beam, topk_tok = ops.beam_topk(logits, running_scores.view(-1), nb, k)
+            topk_seq = torch.gather(running_seq, 1, topk_beam.long()[:, :, None].expand(B, k, N)).clone()
+            topk_seq[:, :, cur] = topk_tok
+            topk_parent = topk_beam + offset
+            # stopping criteria: EOS, or max_length reached
+            if cur + 1 >= N:
+                hits = torch.ones((B, k), dtype=torch.bool, device=dev)
+            elif eos is not None:
+                hits = topk_tok == eos
+            else:
+                hits = torch.zeros((B, k), dtype=torch.bool, device=dev)
+            # _get_running_beams_for_next_iteration
+            topk_running_lp = topk_lp + hits.to(torch.float32) * NEG
+            nxt = torch.sort(topk_running_lp, dim=1, descending=True, stable=True)[1][:, :nb]
+            running_seq = torch.gather(topk_seq, 1, nxt[:, :, None].expand(B, nb, N))
+            running_scores = torch.gather(topk_running_lp, 1, nxt)
+            parent = torch.gather(topk_parent, 1, nxt)
+            # _update_finished_beams
+            just = hits & top_mask[None, :]
+            fin_lp = topk_lp / ((cur + 1) ** length_penalty)
+            full = torch.all(is_sent_finished, dim=-1, keepdim=True) & (early_stopping is True)
+            fin_lp += full.to(torch.float32) * NEG
+            fin_lp += (~unsatisfied).to(torch.float32) * NEG
+            fin_lp += (~just) * NEG
+            m_scores = torch.cat((beam_scores, fin_lp), dim=1)
+            sel = torch.sort(m_scores, dim=1, descending=True, stable=True)[1][:, :nb]
+            sequences = torch.gather(torch.cat((sequences, topk_seq), dim=1), 1, sel[:, :, None].expand(B, nb, N))
+            beam_scores = torch.gather(m_scores, 1, sel)
+            lengths = torch.gather(torch.cat((lengths, torch.full((B, k), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, sel)
+            is_sent_finished = torch.gather(torch.cat((is_sent_finished, just), dim=1), 1, sel)
+            if cur + 1 >= N:                                        # every candidate hit max_length: HF's loop ends here
+                break
+            # _check_early_stop_heuristic at cur_len = cur + 1, then _beam_search_has_unfinished_sequences
+            if early_stopping == "never" and length_penalty > 0.0:
+                best_len = N
+            else:
+                best_len = cur + 1
+            best_running = running_scores[:, :1] / (best_len ** length_penalty)
+            worst_finished = torch.where(is_sent_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], NEG)
+            unsatisfied = unsatisfied & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
+            done = ~(torch.any(unsatisfied) & ~(torch.all(is_sent_finished) & (early_stopping is True)) & ~torch.all(hits))
+            done_host.copy_(done.view(1), non_blocking=True)
+            ev.record()
+            # the next token step is queued before the host waits on the stopping test (only the small copy above is awaited)
+            ops.kv_gather_rows(kc, vc, kc, vc, parent.view(-1).to(torch.int32), S, S + cur)
+            logits = eng.decode_step(running_seq[:, :, cur].reshape(-1), S + cur, kc, vc)
+            ev.synchronize()
+            if bool(done_host[0]):
+                break
+        L = int(lengths[:, 0].max())
+        out = sequences[:, 0, :L].clone()
+        return (out, beam_scores[:, 0].clone()) if return_scores else out

@@ -204,6 +204,65 @@ def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, 
     return out
 
 
+BEAM_MAX_BEAMS, BEAM_MAX_K = 16, 32
+
+
+def beam_topk(logits, beam_scores, num_beams, k):
+    """Beam-search candidates (csrc/beam.hip): for each batch item b, the k best of beam_scores[b*nb + j] + log_softmax(logits[b*nb + j])[v]
+    over all nb*V pairs, sorted descending, equal scores by the lower flat index j*V + v first.  logits: f32 [B*nb, V] (row stride free);
+    beam_scores: f32 [B*nb].  Returns (scores f32 [B, k], beams int32 [B, k], tokens int64 [B, k])."""
+    nb, k = int(num_beams), int(k)
+    if not 1 <= nb <= BEAM_MAX_BEAMS:
+        raise ValueError(f"num_beams must be in [1, {BEAM_MAX_BEAMS}], got {num_beams}")
+    if not 1 <= k <= BEAM_MAX_K:
+        raise ValueError(f"k must be in [1, {BEAM_MAX_K}], got {k}")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_cuda:
+        raise ValueError("beam_topk: logits must be a 2-d float32 device tensor")
+    rows, V = logits.shape
+    if rows % nb:
+        raise ValueError(f"beam_topk: {rows} logits rows are not a multiple of num_beams = {nb}")
+    if k > nb * V:
+        raise ValueError(f"beam_topk: k = {k} > num_beams * V = {nb * V}")
+    if beam_scores.dtype != torch.float32 or beam_scores.numel() != rows or not beam_scores.is_cuda:
+        raise ValueError(f"beam_topk: beam_scores must be float32 [{rows}] on the device")
+    beam_scores = beam_scores.contiguous()
+    B = rows // nb
+    lib = L.load()
+    ws = torch.empty(lib.avllm_beam_topk_workspace_bytes(rows, V, k), device=logits.device, dtype=torch.uint8)
+    scores = torch.empty(B, k, device=logits.device, dtype=torch.float32)
+    beams = torch.empty(B, k, device=logits.device, dtype=torch.int32)
+    tokens = torch.empty(B, k, device=logits.device, dtype=torch.int64)
+    L.check(lib.avllm_beam_topk(L.ptr(logits), _ld(logits), B, nb, V, L.ptr(beam_scores), k, L.ptr(scores), L.ptr(beams), L.ptr(tokens),
+                                L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return scores, beams, tokens
+
+
+def kv_gather_rows(k_src, v_src, k_dst, v_dst, parent, t0, t1):
+    """dst[l, r, t, :] = src[l, parent[r], t, :] for t in [t0, t1), on K and V (csrc/beam.hip).  Caches: contiguous [layers, rows, T, dkv],
+    f32 or bf16; src may have fewer rows and another T than dst; src is dst gives an in-place reorder (correct for any parent map).
+    parent: int32 [dst rows] on the device; entries outside [0, src rows) leave that row untouched."""
+    for t in (k_src, v_src, k_dst, v_dst):
+        if t.dim() != 4 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("kv_gather_rows: caches must be contiguous 4-d device tensors [layers, rows, T, dkv]")
+    if k_src.shape != v_src.shape or k_dst.shape != v_dst.shape:
+        raise ValueError("kv_gather_rows: K and V caches must have equal shapes")
+    if len({k_src.dtype, v_src.dtype, k_dst.dtype, v_dst.dtype}) != 1:
+        raise ValueError("kv_gather_rows: all caches must have one dtype")
+    Ls, Rs, Ts, D = k_src.shape
+    Ld, Rd, Td, Dd = k_dst.shape
+    if Ls != Ld or D != Dd:
+        raise ValueError(f"kv_gather_rows: src {tuple(k_src.shape)} and dst {tuple(k_dst.shape)} differ in layers or width")
+    if (k_src.data_ptr() == k_dst.data_ptr()) != (v_src.data_ptr() == v_dst.data_ptr()):
+        raise ValueError("kv_gather_rows: K and V must both be in place or both out of place")
+    if parent.dtype != torch.int32 or parent.shape != (Rd,) or not parent.is_contiguous() or not parent.is_cuda:
+        raise ValueError(f"kv_gather_rows: parent must be a contiguous int32 device tensor [{Rd}]")
+    t0, t1 = int(t0), int(t1)
+    if not 0 <= t0 <= t1 <= min(Ts, Td):
+        raise ValueError(f"kv_gather_rows: positions [{t0}, {t1}) outside the caches (T = {Ts}, {Td})")
+    L.check(L.load().avllm_kv_gather_rows(L.ptr(k_src), L.ptr(v_src), Rs, Ts, L.ptr(k_dst), L.ptr(v_dst), Rd, Td, Ls, D, L.ptr(parent),
+                                          t0, t1, L.dt_of(k_dst), L.stream_ptr()))
+
+
 def embedding(table, ids):
     ids = ids.contiguous()
     out = torch.empty(*ids.shape, table.shape[1], device=table.device, dtype=table.dtype)

@@ -83,6 +83,15 @@ int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, f
                       int64_t* out, int32_t dtype, void* stream) {
     return av_sample_rows(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, dtype, ST);
 }
+size_t avllm_beam_topk_workspace_bytes(int64_t rows, int32_t V, int32_t k) { return av_beam_topk_workspace_bytes(rows, V, k); }
+int avllm_beam_topk(const float* logits, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,
+                    float* out_scores, int32_t* out_beams, int64_t* out_tokens, void* ws, size_t ws_bytes, void* stream) {
+    return av_beam_topk(logits, ld, B, num_beams, V, beam_scores, k, out_scores, out_beams, out_tokens, ws, ws_bytes, ST);
+}
+int avllm_kv_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
+                         int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, int32_t dtype, void* stream) {
+    return av_kv_gather_rows(k_src, v_src, src_rows, src_T, k_dst, v_dst, dst_rows, dst_T, layers, dkv, parent, t0, t1, dtype, ST);
+}
 int avllm_embedding(const void* table, const int64_t* ids, void* out, int64_t n, int32_t d, int32_t dtype, void* stream) { return av_embedding(table, ids, out, n, d, dtype, ST); }
 int avllm_cast(const void* src, int32_t sdt, void* dst, int32_t ddt, int64_t n, void* stream) { return av_cast(src, sdt, dst, ddt, n, ST); }
 int avllm_dropout(const void* x, void* y, int64_t rows, int32_t d, uint32_t seed, float p, int32_t dtype, void* stream) { return av_dropout(x, y, rows, d, seed, p, dtype, ST); }

@@ -216,6 +216,26 @@ int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, i
 int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
                       const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
                       int64_t* out, int32_t dtype, void* stream);
+/* Beam-search candidate selection (GenerationMixin._beam_search with num_beams > 1, clip_whisper_model.py:1326-1340; transformers
+ * generation/utils.py `log_softmax` + `_get_top_k_continuations`).  logits: f32 rows r = b*num_beams + j of length V, row stride ld;
+ * beam_scores: f32 [B*num_beams] running sums of log-probabilities (-1e9 and -inf allowed).  For each batch item b, the k best of
+ * score(j, v) = beam_scores[r] + ((logits[r][v] - max_r) - log(sum exp(logits[r] - max_r))) (torch.log_softmax in fp32) over all
+ * num_beams*V pairs, sorted by score descending; equal scores go to the lower flat index j*V + v first.  A row contributes only its k
+ * largest raw logits (equal logits: lower index first).  Outputs [B, k]: out_scores (f32), out_beams (j, int32), out_tokens (v, int64).
+ * 1 <= num_beams <= 16, 1 <= k <= 32, k <= num_beams*V, otherwise AV_ERR_ARG.  ws: device scratch of at least
+ * avllm_beam_topk_workspace_bytes(B*num_beams, V, k) bytes.  Two launches; deterministic. */
+size_t avllm_beam_topk_workspace_bytes(int64_t rows, int32_t V, int32_t k);
+int avllm_beam_topk(const float* logits, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,
+                    float* out_scores, int32_t* out_beams, int64_t* out_tokens, void* ws, size_t ws_bytes, void* stream);
+/* KV-cache row gather for beam search (the `_reorder_cache` / `Cache.reorder_cache(beam_idx)` step of GenerationMixin._beam_search):
+ * dst[l, r, t, :] = src[l, parent[r], t, :] for every layer l < layers, row r < dst_rows and position t0 <= t < t1, on K and V.  The caches
+ * are [layers, rows, T, dkv] contiguous (f32 or bf16, any dkv); src may have fewer rows than dst (prefix broadcast after prefill) and another
+ * T.  parent: int32 [dst_rows] on the device; a row whose parent is outside [0, src_rows) is left untouched.  In place (k_src == k_dst and
+ * v_src == v_dst, equal shapes) is correct for every parent map with no scratch: one workgroup owns a (tensor, layer, position, column
+ * chunk) slice for all rows, stages every row's source in LDS, and writes only after a barrier; rows with parent[r] == r are skipped.
+ * dst_rows <= 2048.  t0 == t1 is a no-op. */
+int avllm_kv_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
+                         int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, int32_t dtype, void* stream);
 /* out[i,:] = table[ids[i],:] ; llm.get_input_embeddings() (clip_whisper_model.py:464-487) */
 int avllm_embedding(const void* table, const int64_t* ids, void* out, int64_t n, int32_t d, int32_t dtype, void* stream);
 int avllm_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);

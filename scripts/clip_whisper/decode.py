@@ -9,7 +9,8 @@ wer_<ts>.txt ("Overall WER" / "Total samples").
 
 Additions of this build (not reference flags): --do_sample / --top_p (default 0.9) / --top_k (default 50) (sampled `generate`:
 temperature -> top-k -> top-p on the device, its seed drawn after torch.manual_seed(--seed); without --do_sample decoding stays
-greedy and --temperature is ignored, as in the reference), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
+greedy and --temperature is ignored, as in the reference), --num_beams (default 1: greedy or sampled as above) / --length_penalty
+(default 1.0) (HF beam search, the best hypothesis per utterance), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -51,6 +52,8 @@ def parse_args(argv=None):
     p.add_argument("--do_sample", action="store_true", help="sample instead of greedy decoding (temperature, top_k, top_p)")
     p.add_argument("--top_p", type=float, default=0.9)
     p.add_argument("--top_k", type=int, default=50, help="0 turns top-k off")
+    p.add_argument("--num_beams", type=int, default=1, help="beam search with this many beams (1 = greedy / sampling)")
+    p.add_argument("--length_penalty", type=float, default=1.0, help="beam search: scores are divided by length ** length_penalty")
     p.add_argument("--load_lora", action="store_true")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
@@ -160,7 +163,8 @@ def main(argv=None):
             audio = None if (audio is None or a.modality == "video") else audio.to(dev)
             video = None if (video is None or a.modality == "audio") else video.to(dev)
             ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
-                                 do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k)
+                                 do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k, num_beams=a.num_beams,
+                                 length_penalty=a.length_penalty)
             out = model.tokenizer.batch_decode(ids.cpu(), skip_special_tokens=True)
             if a.calculate_loss:
                 lab = model.tokenizer(list(texts), padding="max_length", truncation=True, max_length=256, return_tensors="pt").input_ids
