@@ -11,7 +11,14 @@ random tensors of the true shapes (no checkpoints offline).  All arithmetic runs
 
 Rank 0 prints ONE JSON line (contract in the task statement): whole-job samples/s, plus
   roofline     -- the dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs / summed HIP-event time, live, vs 2.5 PF/s
-  cpu_baseline -- the CPU oracle timed on this box's host cores: ONE complete B=1 train step at full depth (rank 0, N=1 only).
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print.  With --full (rank 0, N=1 only) the same line
+also carries the secondary legs, each run after the timed steps and the dump:
+  config.host_inputs   -- the step fed from pinned host memory (raw uint8 frames + 16 kHz samples, H2D on a copy stream)
+  decode               -- greedy token steps on the KV cache, with and without the LoRA adapters
+  variants.config5_fp8 -- BASELINE configs[4] (whisper-large-v3 + ViT-L/14 -> Mistral-7B, 4 x 750 frames) in bf16 and fp8
+  cpu_baseline         -- the CPU oracle timed on the host cores: ONE complete B=1 train step at full depth.
+
+    python bench.py --full
 """
 import argparse
 import ctypes
@@ -296,6 +303,9 @@ def main():
     ap.add_argument("--precision", default="bf16", help="bf16 (BASELINE configs[1..3]) | fp32 | fp8 (BASELINE configs[4]: block-scaled fp8 on the frozen "
                     "projections of the forward pass; use with --whisper openai/whisper-large-v3 --clip openai/clip-vit-large-patch14 "
                     "--llm mistralai/Mistral-7B-v0.1 --frames 750)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the secondary legs (host-input leg, decode leg, "
+                    "variants.config5_fp8, CPU baseline; rank 0 at N = 1 only, each can still be skipped with its --no-* option).  Off: the run "
+                    "sets up, warms up, times the steps, writes --dump-outputs and prints the result line, nothing else")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", default="full", choices=["sample", "full"], help="full (default, BASELINE.md §2): one complete B=1 train step of the oracle "
                     "at full depth, every frame, forward + backward (~20-35 s of host time); sample: a bounded slice of one B=1 step extrapolated by layer / "
@@ -411,14 +421,16 @@ def main():
     final_loss = float(loss)
     if args.dump_outputs and rank == 0:              # before the secondary legs, which take further optimizer steps
         dump_outputs(args.dump_outputs, loss, model.llm_engine)
+    # secondary legs: --full only, and at N = 1 only (the scaling runs time the contract's step and nothing else)
+    full = args.full and world == 1
     host_leg = None
-    if not args.no_host_inputs and not args.tiny and world == 1:      # secondary legs run at N = 1 only: the scaling runs time the contract's step and nothing else
+    if full and not args.no_host_inputs and not args.tiny:
         host_leg = host_inputs_leg(args, cfg, model, trainer, labels, prompt, dev, rank, world, barrier)
     decode_leg = None
-    if rank == 0 and world == 1 and not args.no_decode and not args.tiny:
+    if full and rank == 0 and not args.no_decode and not args.tiny:
         decode_leg = decode_bench(model, cfg, args, dev)
     variants = None
-    if rank == 0 and world == 1 and not args.no_config5 and not args.tiny and default_llm and args.precision == "bf16":
+    if full and rank == 0 and not args.no_config5 and not args.tiny and default_llm and args.precision == "bf16":
         # the main model's step graphs and activations go first: the variant is another 7B model with 30 s batches
         trainer._graphs = {}
         torch.cuda.empty_cache()
@@ -459,7 +471,7 @@ def main():
         else:
             out["roofline"] = {"bound": "mfma", "achieved": round(value / world * FLOP_PER_CLIP / 1e12, 2), "peak": MFMA_BF16_PEAK / 1e12,
                                "unit": "TFLOP/s", "frac": round(frac_e2e, 4), "traffic": None}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             from oracle import cpu_baseline
             out["cpu_baseline"] = cpu_baseline.run_full(frames=args.frames) if args.cpu_baseline == "full" else cpu_baseline.run(frames=args.frames)
         print(json.dumps(out), flush=True)
