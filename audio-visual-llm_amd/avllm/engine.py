@@ -189,9 +189,13 @@ class LlamaEngine:
     (A [r,d], B [dout,r]; dout = d, or kv_heads*head_dim for k/v under grouped-query attention) so a layer's gradient bucket is one contiguous slice of `lora_g` for the DDP all-reduce.
     """
 
-    def __init__(self, sd, cfg, lora_cfg=None, lora_sd=None, dtype=torch.bfloat16, device="cuda", training=True, fp8=False):
+    def __init__(self, sd, cfg, lora_cfg=None, lora_sd=None, dtype=torch.bfloat16, device="cuda", training=True, fp8=False, decode_fp8=False):
         self.cfg, self.lcfg, self.dtype, self.device, self.training = cfg, lora_cfg, dtype, device, training
         self.fp8 = bool(fp8)
+        # weight-only fp8 token step (include/avllm.h avllm_llama.decode_fp8): the fused decode path streams e4m3 codes + layout-2 exponents
+        self.decode_fp8 = bool(decode_fp8)
+        if self.decode_fp8 and dtype != torch.bfloat16:
+            raise ValueError("decode_fp8 needs the bf16 engine")
         self.keep = []
         d, f = cfg.hidden, cfg.ffn
         self.use_lora = lora_cfg is not None
@@ -224,8 +228,22 @@ class LlamaEngine:
         if training:
             m.lm_head_t = put(head.t()).data_ptr()
         m.fp8 = int(self.fp8)
-        if self.fp8:
-            m.lm_head8, m.slm_head8 = _fp8_images(head, self.keep)
+
+        def images(w):
+            """(codes, layout-1 image, layout-2 exponents) pointers of a frozen matrix for the fp8 modes that are on (None otherwise); the
+            token step's exponents share the codes of the training forward's image when both modes are on (re-quantising writes the same bytes)."""
+            q = s = e = None
+            if self.fp8:
+                q, s = ops.mx_quantize(w, 1)
+                self.keep += [q, s]
+            if self.decode_fp8:
+                q, e = ops.mx_quantize(w, 2, q=q)
+                self.keep += [q, e]
+            return tuple(None if t is None else t.data_ptr() for t in (q, s, e))
+
+        m.decode_fp8 = int(self.decode_fp8)
+        if self.fp8 or self.decode_fp8:
+            m.lm_head8, m.slm_head8, m.elm_head8 = images(head)
         self.layers = (L.LlamaLayer * cfg.layers)()
         # ---- LoRA masters / grads / padded operand images
         self.per_layer = sum(r * (d + do) for do in self.douts)
@@ -255,11 +273,11 @@ class LlamaEngine:
             if training:
                 ly.wqkv_t, ly.wo_t = put(wqkv.t()).data_ptr(), put(wo.t()).data_ptr()
                 ly.wgu_t, ly.wdown_t = put(wgu.t()).data_ptr(), put(wdown.t()).data_ptr()
-            if self.fp8:
-                ly.wqkv8, ly.sqkv8 = _fp8_images(wqkv, self.keep)
-                ly.wo8, ly.so8 = _fp8_images(wo, self.keep)
-                ly.wgu8, ly.sgu8 = _fp8_images(wgu, self.keep)
-                ly.wdown8, ly.sdown8 = _fp8_images(wdown, self.keep)
+            if self.fp8 or self.decode_fp8:
+                ly.wqkv8, ly.sqkv8, ly.eqkv8 = images(wqkv)
+                ly.wo8, ly.so8, ly.eo8 = images(wo)
+                ly.wgu8, ly.sgu8, ly.egu8 = images(wgu)
+                ly.wdown8, ly.sdown8, ly.edown8 = images(wdown)
             if self.use_lora:
                 es = self.img_A.element_size()
                 for j in range(4):
@@ -390,6 +408,18 @@ class LlamaEngine:
     def decode_is_fused(self, B):
         """True when a token step of B sequences takes the fused bf16 path (tests and benchmarks assert which path they measured)."""
         return bool(L.load().avllm_llama_decode_is_fused(C.byref(self.desc), B))
+
+    def decode_streams_fp8(self, B):
+        """True when a token step of B sequences streams the fp8 weight images (decode_fp8 and the fused path: B <= 16)."""
+        return bool(L.load().avllm_llama_decode_streams_fp8(C.byref(self.desc), B))
+
+    def streamed_weight_bytes(self, B):
+        """Bytes of frozen weights a token step of B sequences actually reads: frozen_weight_bytes() on the bf16 matrices, or one byte per
+        element plus one exponent byte per 32 elements when the step streams fp8."""
+        if not self.decode_streams_fp8(B):
+            return self.frozen_weight_bytes()
+        n = self.frozen_weight_bytes() // 2
+        return n + n // 32
 
     def alloc_cache(self, B, Tmax):
         shape = (self.cfg.layers, B, Tmax, self.dkv)

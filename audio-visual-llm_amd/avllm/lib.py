@@ -52,7 +52,8 @@ class LoraMod(C.Structure):
 
 class LlamaLayer(C.Structure):
     _fields_ = [(n, vp) for n in ("ln1_w", "ln2_w", "wqkv", "wo", "wgu", "wdown", "wqkv_t", "wo_t", "wgu_t", "wdown_t")] + \
-               [("lora", LoraMod * 4)] + [(n, vp) for n in ("wqkv8", "sqkv8", "wo8", "so8", "wgu8", "sgu8", "wdown8", "sdown8")]
+               [("lora", LoraMod * 4)] + [(n, vp) for n in ("wqkv8", "sqkv8", "wo8", "so8", "wgu8", "sgu8", "wdown8", "sdown8")] + \
+               [(n, vp) for n in ("eqkv8", "eo8", "egu8", "edown8")]
 
 
 class Llama(C.Structure):
@@ -60,7 +61,8 @@ class Llama(C.Structure):
                [(n, f32) for n in ("eps", "theta", "lora_scale", "lora_dropout")] + [("dropout_seed", C.c_uint32)] + \
                [(n, vp) for n in ("dropout_seed_dev", "embed", "norm_w", "lm_head", "lm_head_t")] + [("layer", C.POINTER(LlamaLayer))] + \
                [("fp8", i32), ("lm_head8", vp), ("slm_head8", vp)] + \
-               [(n, f32) for n in ("rope_factor", "rope_low_freq_factor", "rope_high_freq_factor")] + [("rope_orig_ctx", i32)]
+               [(n, f32) for n in ("rope_factor", "rope_low_freq_factor", "rope_high_freq_factor")] + [("rope_orig_ctx", i32)] + \
+               [("decode_fp8", i32), ("elm_head8", vp)]
 
 
 class GemmF8Desc(C.Structure):
@@ -73,7 +75,7 @@ class DecProjDesc(C.Structure):
     _fields_ = [("A", vp), ("lda", i64), ("W", vp), ("ldw", i64), ("norm_w", vp), ("eps", f32), ("M", i32), ("K", i32), ("N", i32), ("mode", i32),
                 ("C", vp), ("ldc", i64), ("out_f32", i32), ("R", vp), ("ldr", i64), ("dq", i32), ("dkv", i32), ("hd", i32), ("rope", vp),
                 ("kc", vp), ("vc", vp), ("Tmax", i32), ("pos", i32), ("pos_dev", vp),
-                ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32)]
+                ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32), ("W8", vp), ("E8", vp)]
 
 
 class StepState(C.Structure):
@@ -157,6 +159,7 @@ _SIGS = {
     "avllm_llama_decode_step": ([C.POINTER(Llama), vp, i32, i32, vp, vp, i32, vp, vp, sz, vp], i32),
     "avllm_llama_decode_step_at": ([C.POINTER(Llama), vp, i32, i32, vp, vp, vp, i32, vp, vp, sz, vp], i32),
     "avllm_llama_decode_is_fused": ([C.POINTER(Llama), i32], i32),
+    "avllm_llama_decode_streams_fp8": ([C.POINTER(Llama), i32], i32),
     "avllm_pos_advance": ([vp, i32, vp], i32),
     "avllm_dec_proj": ([C.POINTER(DecProjDesc), vp], i32),
     "avllm_gemm_f8_takes_quantised_output": ([C.POINTER(GemmF8Desc)], i32),

@@ -52,7 +52,7 @@ class ClipWhisperModel:
                  lora_r=16, lora_alpha=32, lora_dropout=0.05, freeze_encoders=True, freeze_llm=False, modality="both",
                  max_seq_len=256, fusion_scale=0.5, connector_type="simple", _provided_tokenizer=None, _provided_llm=None,
                  _provided_whisper=None, _provided_clip=None, *, precision=None, config: ModelCfg | None = None,
-                 weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False):
+                 weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16"):
         if use_4bit:
             raise NotImplementedError("use_4bit (bitsandbytes nf4) is out of scope of the MI355X hot path (SURVEY.md §8)")
         if not freeze_encoders:
@@ -79,6 +79,14 @@ class ClipWhisperModel:
         # on the block-scaled fp8 matrix pipe; attention, norms, LoRA terms, loss and the whole backward pass as in "bf16"
         self.fp8 = precision == "fp8"
         self.precision = precision
+        # decode_weights="fp8": generate()'s token steps (greedy, sampling, beam search) stream the LLM's frozen projections as e4m3 codes with
+        # one E8M0 exponent per 32 elements (weight-only; activations, KV cache and logits as in bf16).  Prefill and steps of more than 16
+        # rows keep the bf16 weights.  A runtime choice: not saved with the model.
+        if decode_weights not in ("bf16", "fp8"):
+            raise ValueError(f"decode_weights must be bf16|fp8, got {decode_weights!r}")
+        if decode_weights == "fp8" and precision == "fp32":
+            raise ValueError("decode_weights='fp8' needs precision bf16 or fp8 (the fp8 token step is a bf16-activation path)")
+        self.decode_weights = decode_weights
         self.dtype = torch.float32 if precision == "fp32" else torch.bfloat16
         self.training = True
         self._drop_step = 0
@@ -100,7 +108,7 @@ class ClipWhisperModel:
         self.whisper_engine = WhisperEngine(W["whisper"], cfg.whisper, self.dtype, device, fp8=self.fp8) if modality in ("audio", "both") else None
         self.clip_engine = ClipEngine(W["clip"], cfg.clip, self.dtype, device, fp8=self.fp8) if modality in ("video", "both") else None
         self.llm_engine = LlamaEngine(W["llama"], cfg.llama, cfg.lora if use_lora else None, W.get("lora"), self.dtype, device,
-                                      training=True, fp8=self.fp8)
+                                      training=True, fp8=self.fp8, decode_fp8=decode_weights == "fp8")
         self._setup_projections(W)
         self.lora_param = None
         if use_lora:

@@ -393,13 +393,18 @@ def gemm_tn_multi(big, smalls, outs, r, alpha=1.0, seeds=None, p=0.0, shared=Fal
     return outs
 
 
-def mx_quantize(x, layout=0):
+def mx_quantize(x, layout=0, q=None):
     """x [R,K] bf16/f32 -> (q uint8 [R,K] e4m3, scale image uint8 tensor): OCP-MX block scaling, 32 elements per E8M0 scale.
-    layout 0 = activation side, 1 = weight side of avllm_gemm_f8."""
+    layout 0 = activation side, 1 = weight side of avllm_gemm_f8; layout 2 = decode side: the scales are the exponent matrix uint8 [R, K/32]
+    (E8M0 biased by 127) of dec_proj's fp8 weight form.  `q`: optional [R, K] uint8 output for the codes (the same for every layout)."""
     lib = L.load()
     R, K = x.shape
-    q = torch.empty(R, K, device=x.device, dtype=torch.uint8)
-    s = torch.zeros(lib.avllm_mx_scale_bytes(R, K), device=x.device, dtype=torch.uint8)
+    if q is None:
+        q = torch.empty(R, K, device=x.device, dtype=torch.uint8)
+    if layout == 2:
+        s = torch.zeros(R, K // 32, device=x.device, dtype=torch.uint8)
+    else:
+        s = torch.zeros(lib.avllm_mx_scale_bytes(R, K), device=x.device, dtype=torch.uint8)
     L.check(lib.avllm_mx_quantize(L.ptr(x), _ld(x), R, K, L.ptr(q), K, L.ptr(s), layout, L.dt_of(x), L.stream_ptr()))
     return q, s
 
@@ -441,16 +446,21 @@ def norm_mxq(x, w, b=None, eps=1e-5, want_y=False, want_rstd=False):
 
 
 def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=False, rope=None, kc=None, vc=None, pos=0, pos_dev=None, dq=0, dkv=0, hd=0,
-             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0):
+             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None):
     """One projection of a decode token step (avllm_dec_proj): A [M<=16, K] bf16, W [rows, K] bf16.
     mode 0: out[M, rows] = rmsnorm?(A) . W^T (+ R);  mode 1: W = [gate; up], out[M, rows/2] = silu(gate) * up;
-    mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev)."""
+    mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev).
+    fp8 weight form: W8 = e4m3 codes uint8 [rows, K], E8 = exponents uint8 [rows, K/32] (mx_quantize(w, 2)); W may then be None."""
     M, K = A.shape
     d = L.DecProjDesc()
-    d.A, d.lda, d.W, d.ldw, d.M, d.K, d.mode = L.ptr(A), _ld(A), L.ptr(W), _ld(W), M, K, mode
+    Wr = W8 if W8 is not None else W
+    d.A, d.lda, d.M, d.K, d.mode = L.ptr(A), _ld(A), M, K, mode
+    d.W, d.ldw = L.ptr(W), _ld(Wr)
+    if W8 is not None:
+        d.W8, d.E8 = L.ptr(W8), L.ptr(E8)
     if norm_w is not None:
         d.norm_w, d.eps = L.ptr(norm_w), eps
-    N = W.shape[0] // 2 if mode == 1 else W.shape[0]
+    N = Wr.shape[0] // 2 if mode == 1 else Wr.shape[0]
     d.N = N
     if out is None:
         out = torch.empty(M, dq if mode == 2 else N, device=A.device, dtype=torch.float32 if out_f32 else torch.bfloat16)

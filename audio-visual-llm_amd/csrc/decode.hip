@@ -13,6 +13,14 @@
 // dec_proj: M <= 16 activation rows ride as one MFMA operand, a workgroup owns 16 weight rows (a contiguous 16*K*2-byte block of
 // HBM), its 8 waves split K, each wave keeps a ring of DEPTH 1 KiB weight loads in flight (non-temporal: the stream must not evict
 // the activations from L2) and the 8 partial 16x16 tiles meet in LDS.
+//
+// fp8 weight form (W8 != NULL, dec_proj_f8_kernel): the weight rows are e4m3 codes [*, K] with one E8M0 exponent per 32 elements along K
+// (E8 [*, K/32] row-major, biased by 127: avllm_mx_quantize layout 2).  One 16-byte code load covers TWO K-steps of a lane, so inside each
+// pair of steps the K elements are dealt as  lane (fr, fq), step 2p + s:  elements 64 p + 16 fq + 8 s + [0, 8)  (the bf16 form: 32 j + 8 fq),
+// the activation and norm-weight addresses follow that order, and v_cvt_scalef32_pk_bf16_fp8 turns the codes into the same bf16 MFMA
+// operand (exact: e4m3 x 2^e is a bf16 value).  The wave's K range and the 8-way split are those of the bf16 form; only the grouping of
+// elements into the 32-wide MFMA steps differs, so the result is the bf16 form's on the dequantised weights up to fp32 summation order.
+// A group's loads: [norm] exponent dword, then activation loads as in the bf16 form and 2 code loads instead of 4 weight loads.
 #include "common.h"
 #include "avllm_internal.h"
 #include <type_traits>
@@ -39,6 +47,7 @@ struct DecArgs {
     // (columns 64 j .. 64 j + r of module j; made by a PLAIN launch over the A images), lb[j] the padded B image [rows, 64] of module j
     // (QKV: j = q, k, v; otherwise j = 0).  Added in the epilogue, before RoPE.
     const float* lt; long ldlt; const bf16* lb[3]; float lscale; int lr;
+    const uint8_t* W8; const uint8_t* E8;   // fp8 weight form: codes [*, ldw bytes per row], exponents [*, K/32]
 };
 
 // fragment row fr (0..15) of workgroup b -> weight row, and the logical output column it produces
@@ -63,10 +72,10 @@ __device__ __forceinline__ int dec_wrow(const DecArgs& a, int b, int fr, int& co
 // 16-byte global loads the compiler's wait-count pass does not see: the ring below keeps 8 K-steps per wave in flight and waits with
 // exact vmcnt values (loads return in issue order), which clang does not do for a register ring (it drains to vmcnt(0) every trip).
 typedef u32x4 frag;
-template <int OFF> __device__ __forceinline__ void gld(frag& r, const bf16* p) {
+template <int OFF> __device__ __forceinline__ void gld(frag& r, const void* p) {
     asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
 }
-template <int OFF> __device__ __forceinline__ void gld_nt(frag& r, const bf16* p) {
+template <int OFF> __device__ __forceinline__ void gld_nt(frag& r, const void* p) {
     asm volatile("global_load_dwordx4 %0, %1, off offset:%2 nt" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
 }
 template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag& c) {
@@ -74,6 +83,15 @@ template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag&
 }
 template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
+}
+template <int OFF> __device__ __forceinline__ void gld_dw(unsigned& r, const void* p) {
+    asm volatile("global_load_dword %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
+}
+template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag& c, unsigned& e) {
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(e) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, unsigned& e) {
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(a), "+v"(b), "+v"(e) : "n"(N));
 }
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
@@ -96,9 +114,13 @@ template <int J> __device__ __forceinline__ frag row_bcast(frag v) { return dpp4
 //   down when that step is consumed; MFMA output columns >= 8 are garbage nobody reads);  M <= 4: 1 (four steps per load).
 // The norm weights of the 4 steps come in ONE load (lane row fr & 3 holds step fr & 3) and reach all rows through a row broadcast.
 template <int AL, bool NORM> struct DecGrp { frag wb[4], xa[AL], gw; };
+template <int AL, bool NORM> struct DecGrp8 { frag wb[2], xa[AL], gw; unsigned ex; };     // fp8: 2 code loads + the 4 exponents of 16 rows
 
-template <bool NORM, int AL, bool LORA>
-__global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) {
+// fp8 form: element offset of step j (0..3) of a 128-column group for lane column fq (the bf16 form's is 32 j + 8 fq)
+__device__ __forceinline__ int dec_koff8(int j, int fq) { return 64 * (j >> 1) + 16 * fq + 8 * (j & 1); }
+
+template <bool NORM, int AL, bool LORA, bool F8>
+__device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     __shared__ float part[DW][16][17];      // [wave][n][m]
     __shared__ float ssq[DW][16];
     __shared__ float fin[16][17];           // [m][n]
@@ -115,28 +137,45 @@ __global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) {
     const long k0 = ((long)w * ub + (w < ue ? w : ue)) << 7;
     int col;
     const int wr = dec_wrow(a, blockIdx.x, fr, col);
-    const bf16* ap = a.A + (long)ar * a.lda + k0 + asub * 32 + fq * 8;
+    const bf16* ap = F8 ? a.A + (long)ar * a.lda + k0 + dec_koff8(asub, fq) : a.A + (long)ar * a.lda + k0 + asub * 32 + fq * 8;
     const bf16* bp = a.W + (long)wr * a.ldw + k0 + fq * 8;
-    const bf16* gp = NORM ? a.norm_w + k0 + (fr & 3) * 32 + fq * 8 : a.A;
+    const uint8_t* bp8 = a.W8 + (long)wr * a.ldw + k0 + fq * 16;                     // fp8: codes of steps 2p, 2p+1 at byte 64 p
+    const uint8_t* ep = a.E8 + (long)wr * (a.K >> 5) + (k0 >> 5);                     // fp8: the row's 4 exponents of a group = one dword
+    const int esh = 8 * (fq >> 1);                                                    // fp8: byte of the lane's block within the pair
+    const bf16* gp = NORM ? (F8 ? a.norm_w + k0 + dec_koff8(fr & 3, fq) : a.norm_w + k0 + (fr & 3) * 32 + fq * 8) : a.A;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float ss = 0.f;
-    constexpr int LG = 4 + AL + (NORM ? 1 : 0);          // loads per group, issued as: [norm] then per step: [activation if the step starts a load] weight
-    typedef DecGrp<AL, NORM> Grp;
+    // loads per group, issued as: [norm] then per step: [activation if the step starts a load] weight.  fp8: [norm] exponents, then per step:
+    // [activation] [codes if the step starts a pair]
+    constexpr int LG = F8 ? 2 + 1 + AL + (NORM ? 1 : 0) : 4 + AL + (NORM ? 1 : 0);
+    typedef std::conditional_t<F8, DecGrp8<AL, NORM>, DecGrp<AL, NORM>> Grp;
     Grp ga, gb;
     auto issue = [&](Grp& g, int grp) {
         if constexpr (NORM) gld<0>(g.gw, gp + (long)grp * 128);
+        if constexpr (F8) gld_dw<0>(g.ex, ep + (long)grp * 4);
         static_for<0, 4>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if constexpr (j % SPL == 0) gld<64 * j>(g.xa[j / SPL], ap + (long)grp * 128);
-            gld_nt<64 * j>(g.wb[j], bp + (long)grp * 128);
+            if constexpr (F8) {
+                if constexpr (j % SPL == 0) gld<2 * (64 * (j >> 1) + 8 * (j & 1))>(g.xa[j / SPL], ap + (long)grp * 128);
+                if constexpr (j % 2 == 0) gld_nt<32 * j>(g.wb[j / 2], bp8 + (long)grp * 128);
+            } else {
+                if constexpr (j % SPL == 0) gld<64 * j>(g.xa[j / SPL], ap + (long)grp * 128);
+                gld_nt<64 * j>(g.wb[j], bp + (long)grp * 128);
+            }
         });
     };
     auto step = [&](Grp& g, auto jc, auto behind) {      // wait for step j of this group (`behind` younger groups in flight), multiply
         constexpr int j = decltype(jc)::value;
-        constexpr int through = (NORM ? 1 : 0) + (j / SPL + 1) + (j + 1);            // loads of this group issued up to and including weight j
+        // loads of this group issued up to and including weight j (fp8: the exponents and the codes of step j's pair)
+        constexpr int through = F8 ? (NORM ? 1 : 0) + 1 + (j / SPL + 1) + (j / 2 + 1) : (NORM ? 1 : 0) + (j / SPL + 1) + (j + 1);
         constexpr int N = LG - through + decltype(behind)::value * LG;
-        if constexpr (NORM) wait_vm<N>(g.wb[j], g.xa[j / SPL], g.gw);
-        else wait_vm<N>(g.wb[j], g.xa[j / SPL]);
+        if constexpr (F8) {
+            if constexpr (NORM) wait_vm<N>(g.wb[j / 2], g.xa[j / SPL], g.gw, g.ex);
+            else wait_vm<N>(g.wb[j / 2], g.xa[j / SPL], g.ex);
+        } else {
+            if constexpr (NORM) wait_vm<N>(g.wb[j], g.xa[j / SPL], g.gw);
+            else wait_vm<N>(g.wb[j], g.xa[j / SPL]);
+        }
         frag xr = g.xa[j / SPL];
         if constexpr (j % SPL != 0) xr = row_from_higher<RPL * (j % SPL)>(xr);
         bf16x8 x = __builtin_bit_cast(bf16x8, xr);
@@ -149,7 +188,17 @@ __global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) {
                 x[e] = (bf16)(xf * (float)gv[e]);
             }
         }
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, g.wb[j]), x, acc, 0, 0, 0);      // D[n][m]
+        bf16x8 wv;
+        if constexpr (F8) {         // 8 codes of this step (dwords 2 (j & 1), +1 of the pair's load) x 2^(e - 127) of the lane's block
+            const float sc = __uint_as_float(((g.ex >> (16 * (j >> 1) + esh)) & 0xffu) << 23);
+            const unsigned c0 = g.wb[j / 2][2 * (j & 1)], c1 = g.wb[j / 2][2 * (j & 1) + 1];
+            const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, true);
+            const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, true);
+            wv = (bf16x8){p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+        } else {
+            wv = __builtin_bit_cast(bf16x8, g.wb[j]);
+        }
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, x, acc, 0, 0, 0);      // D[n][m]
     };
     auto consume = [&](Grp& g, auto behind) { static_for<0, 4>([&](auto jc) { step(g, jc, behind); }); };
     const std::integral_constant<int, 0> none{};
@@ -254,6 +303,11 @@ __global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) {
     else a.vc[((long)m * a.Tmax + pos) * a.dkv + ocol - a.dq - a.dkv] = (bf16)o;
 }
 
+template <bool NORM, int AL, bool LORA>
+__global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, false>(a); }
+template <bool NORM, int AL, bool LORA>
+__global__ __launch_bounds__(DW * 64, 2) void dec_proj_f8_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, true>(a); }
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // Single-token attention over the cache, ONE pass: a group of G = hd/8 lanes owns cache rows t = g, g + R, ... and carries a running
 // (max, sum, weighted V) triple; K and V rows of a trip are all requested before the first is used.  Groups are merged through
@@ -357,7 +411,10 @@ static int dec_launch(DecArgs& a, hipStream_t st) {
     const int grid = a.mode == DEC_SWIGLU ? a.N / 8 : a.N / 16;
 #define DEC_LAUNCH(NORMV, ALV)                                                                                                   \
     do {                                                                                                                       \
-        if (a.lt) hipLaunchKernelGGL((dec_proj_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);               \
+        if (a.W8) {                                                                                                            \
+            if (a.lt) hipLaunchKernelGGL((dec_proj_f8_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
+            else hipLaunchKernelGGL((dec_proj_f8_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);             \
+        } else if (a.lt) hipLaunchKernelGGL((dec_proj_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
         else hipLaunchKernelGGL((dec_proj_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);                    \
     } while (0)
     const int ev = av_knob(AV_KNOB_DEC_AL);       // experiment knob: force the activation-load form (4 = one load per step)
@@ -370,12 +427,17 @@ static int dec_launch(DecArgs& a, hipStream_t st) {
 }
 
 int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
-    AV_CHECK_ARG(d && d->A && d->W, "dec_proj: null operand");
+    AV_CHECK_ARG(d && d->A && (d->W || d->W8), "dec_proj: null operand");
     AV_CHECK_ARG(d->mode >= DEC_PLAIN && d->mode <= DEC_QKV, "dec_proj: mode %d", d->mode);
     AV_CHECK_ARG(av_dec_proj_supported(AV_BF16, d->M, d->K, d->N, d->mode, d->hd),
                  "dec_proj: bf16, 1 <= M <= 16 (M=%d), K %% 128 == 0 (K=%d), N %% 16 == 0 (%% 8 for SwiGLU; N=%d)", d->M, d->K, d->N);
     AV_CHECK_ARG(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->lda >= d->K && d->ldw >= d->K, "dec_proj: rows must be 16-byte aligned and hold K elements");
+    AV_CHECK_ARG(!d->W8 || (d->E8 && ((uintptr_t)d->W8 & 15) == 0 && d->ldw % 16 == 0 && ((uintptr_t)d->E8 & 3) == 0),
+                 "dec_proj(fp8 weights): codes W8 16-byte aligned with rows of ldw %% 16 == 0 bytes (ldw=%ld), exponents E8 [rows, K/32] 4-byte aligned",
+                 (long)d->ldw);
     DecArgs a = {};
+    a.W8 = (const uint8_t*)d->W8; a.E8 = (const uint8_t*)d->E8;
+    if (a.W8) a.W = nullptr;
     a.A = (const bf16*)d->A; a.lda = d->lda; a.W = (const bf16*)d->W; a.ldw = d->ldw; a.norm_w = (const bf16*)d->norm_w; a.eps = d->eps;
     a.M = d->M; a.K = d->K; a.N = d->N; a.mode = d->mode;
     a.C = d->C; a.ldc = d->ldc; a.out_f32 = d->out_f32; a.R = (const bf16*)d->R; a.ldr = d->ldr;

@@ -239,6 +239,15 @@ int check_llama(const avllm_llama* m) {
     AV_CHECK_ARG(m->d % m->heads == 0 && m->d % 64 == 0 && m->ffn % 64 == 0, "llama: d=%d ffn=%d must be multiples of 64", m->d, m->ffn);
     AV_CHECK_ARG(m->layers > 0 && m->layers <= 256, "llama: layers=%d", m->layers);
     AV_CHECK_ARG(m->kv_heads >= 0 && (m->kv_heads == 0 || m->heads % m->kv_heads == 0), "llama: heads=%d kv_heads=%d", m->heads, m->kv_heads);
+    if (m->decode_fp8) {
+        AV_CHECK_ARG(m->dtype == AV_BF16 && m->d % 128 == 0 && m->ffn % 128 == 0 && m->vocab % 16 == 0 && m->lm_head8 && m->elm_head8,
+                     "llama: decode_fp8 needs bf16, d and ffn multiples of 128, vocab a multiple of 16 and the lm_head codes + exponents");
+        for (int l = 0; l < m->layers; ++l) {
+            const avllm_llama_layer& P = m->layer[l];
+            AV_CHECK_ARG(P.wqkv8 && P.eqkv8 && P.wo8 && P.eo8 && P.wgu8 && P.egu8 && P.wdown8 && P.edown8,
+                         "llama layer %d: decode_fp8 without the fp8 codes and layout-2 exponents", l);
+        }
+    }
     return AV_OK;
 }
 // grouped-query geometry: q is d wide, k and v are dkv = kv_heads*hd wide; the fused row is [q | k | v] = qw columns
@@ -754,12 +763,14 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         AV_TRY(av_dec_proj(&p, st));
         p = {};
     }
+    const bool f8 = m->decode_fp8 != 0;      // weight-only fp8: the four projections stream codes + exponents (decode.hip, fp8 weight form)
     p.A = w.x; p.lda = d; p.W = P.wqkv; p.ldw = d; p.norm_w = P.ln1_w; p.eps = m->eps; p.M = B; p.K = d; p.N = qw; p.mode = 2;
     p.C = w.qkv; p.ldc = qw; p.dq = d; p.dkv = dkv; p.hd = hd; p.rope = w.rope_tab; p.kc = kcl; p.vc = vcl; p.Tmax = Tmax; p.pos = pos; p.pos_dev = pos_dev;
     if (lora) {
         p.lora_t = w.lt; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale;
         for (int j = 0; j < 3; ++j) p.lora_b[j] = P.lora[j].B_pad;
     }
+    if (f8) { p.W8 = P.wqkv8; p.E8 = P.eqkv8; }
     AV_TRY(av_dec_proj(&p, st));
     AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
     p = {};
@@ -770,12 +781,15 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
     }
     p.A = w.att; p.lda = d; p.W = P.wo; p.ldw = d; p.M = B; p.K = d; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
     if (lora) { p.lora_t = w.lt + 3 * AVLLM_LORA_PAD; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale; p.lora_b[0] = P.lora[3].B_pad; }
+    if (f8) { p.W8 = P.wo8; p.E8 = P.eo8; }
     AV_TRY(av_dec_proj(&p, st));
     p = {};
     p.A = w.x; p.lda = d; p.W = P.wgu; p.ldw = d; p.norm_w = P.ln2_w; p.eps = m->eps; p.M = B; p.K = d; p.N = f; p.mode = 1; p.C = w.hmid; p.ldc = f;
+    if (f8) { p.W8 = P.wgu8; p.E8 = P.egu8; }
     AV_TRY(av_dec_proj(&p, st));
     p = {};
     p.A = w.hmid; p.lda = f; p.W = P.wdown; p.ldw = f; p.M = B; p.K = f; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
+    if (f8) { p.W8 = P.wdown8; p.E8 = P.edown8; }
     return av_dec_proj(&p, st);
 }
 
@@ -797,6 +811,7 @@ extern "C" int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* i
             avllm_dec_proj_desc p = {};
             p.A = w.x; p.lda = d; p.W = m->lm_head; p.ldw = d; p.norm_w = m->norm_w; p.eps = m->eps; p.M = B; p.K = d; p.N = m->vocab; p.mode = 0;
             p.C = logits; p.ldc = m->vocab; p.out_f32 = 1;
+            if (m->decode_fp8) { p.W8 = m->lm_head8; p.E8 = m->elm_head8; }
             return av_dec_proj(&p, st);
         }
     } else {
@@ -810,6 +825,11 @@ extern "C" int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* i
 }
 
 extern "C" int avllm_llama_decode_is_fused(const avllm_llama* m, int32_t B) { return m && check_llama(m) == AV_OK && llama_decode_fused_ok(m, B) ? 1 : 0; }
+// decode_fp8 is honoured on the fused path only (check_llama guarantees vocab % 16 == 0, so lm_head is folded there too); B > 16 and a
+// disabled fused path read the bf16 matrices
+extern "C" int avllm_llama_decode_streams_fp8(const avllm_llama* m, int32_t B) {
+    return m && check_llama(m) == AV_OK && m->decode_fp8 && llama_decode_fused_ok(m, B) ? 1 : 0;
+}
 
 extern "C" int avllm_llama_decode_step(const avllm_llama* m, const int64_t* ids, int32_t B, int32_t pos, void* kcache,
                                        void* vcache, int32_t Tmax, float* logits, void* ws, size_t ws_bytes, void* stream) {

@@ -15,6 +15,8 @@
 //          layout 1 (weights, MFMA "A" side):      row = 128 (rb >> 1) + 32 (j >> 1) + 4 (j & 1) + 8 (fr >> 2) + (fr & 3),  j = 4 (rb & 1) + i
 //              -- the column-interleaved fragment order of the 256x256 kernels (gemm.hip WP_BOFF): tiles 2p / 2p+1 give a lane 8
 //              consecutive output columns, stored straight from the accumulators.
+//   layout 2 (decode weights, avllm_dec_proj's fp8 form): not an image but the plain exponent matrix uint8 [R, K/32], row-major, E8M0 biased
+//          by 127 (R * K / 32 bytes): a 16-row decode slab reads a row's four exponents of a 128-column group as one dword.  Same codes.
 // Operand layout of v_mfma_scale_f32_16x16x128_f8f6f4 (measured: tools/ubench/mfma_scale_probe.hip): lane (r, G) (r = lane & 15 the
 // row / column, G = lane >> 4) holds in VGPRs 0-3 the K elements [16 G, 16 G + 16) and in VGPRs 4-7 the elements [64 + 16 G, 64 + 16 G + 16)
 // of the 128-element K-step -- the 16-byte chunks G and 4 + G of a 128-byte row -- and its scale register carries the E8M0 byte of MX
@@ -33,7 +35,7 @@ typedef __attribute__((ext_vector_type(8))) int v8i;
 typedef __attribute__((ext_vector_type(4))) int v4i;
 
 __host__ __device__ __forceinline__ int mx_row(int layout, int rb, int i, int fr) {
-    if (layout == 0) return 64 * rb + 16 * i + fr;
+    if (layout != 1) return 64 * rb + 16 * i + fr;
     const int j = 4 * (rb & 1) + i;
     return 128 * (rb >> 1) + 32 * (j >> 1) + 4 * (j & 1) + 8 * (fr >> 2) + (fr & 3);
 }
@@ -84,8 +86,9 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const T* __restrict__ x, 
             *(u32x4*)qp = (u32x4){pk[0], pk[1], pk[2], pk[3]};
             *(u32x4*)(qp + 16) = (u32x4){pk[4], pk[5], pk[6], pk[7]};
             word |= (uint32_t)(e + 127) << (8 * i);
+            if (layout == 2) ((uint8_t*)simg)[(long)row * nkb + kb] = (uint8_t)(e + 127);
         }
-        simg[(((long)(kb >> 2) * RB + rb) * 4 + (kb & 3)) * 16 + fr] = word;
+        if (layout != 2) simg[(((long)(kb >> 2) * RB + rb) * 4 + (kb & 3)) * 16 + fr] = word;
     }
 }
 
@@ -182,7 +185,7 @@ extern "C" size_t avllm_mx_scale_bytes(int32_t R, int32_t K) { return (size_t)(K
 int av_mx_quantize(const void* x, long ldx, int R, int K, void* q, long ldq, void* scales, int layout, int dtype, hipStream_t st) {
     AV_CHECK_ARG(x && q && scales && R > 0 && K > 0, "mx_quantize: null/empty");
     AV_CHECK_ARG(K % 128 == 0 && ldx % 8 == 0 && ldq % 16 == 0, "mx_quantize: K=%d must be a multiple of 128 (16-byte aligned rows)", K);
-    AV_CHECK_ARG(layout == 0 || layout == 1, "mx_quantize: layout %d", layout);
+    AV_CHECK_ARG(layout >= 0 && layout <= 2, "mx_quantize: layout %d", layout);
     const int RB = mx_groups(R);
     const long total = (long)RB * 16 * (K / 32);
     long blocks = (total + 255) / 256;

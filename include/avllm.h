@@ -105,7 +105,8 @@ int avllm_lora_dx_masked(const void* const* T, const int64_t* ldt, const void* c
  * such mode (clip_whisper_model.py:164: only use_fp16); these entry points give nn.Linear's y = act(x W^T + b) + R on
  * v_mfma_scale_f32_16x16x128_f8f6f4 with fp32 accumulation, bf16 output.
  * avllm_mx_quantize: x [R,K] (bf16 or f32, row stride ldx) -> q uint8 [R,K] (row stride ldq bytes) + the scale image of
- * avllm_mx_scale_bytes(R,K) bytes.  layout 0 = activation side, 1 = weight side (csrc/fp8.hip, "Formats"). */
+ * avllm_mx_scale_bytes(R,K) bytes.  layout 0 = activation side, 1 = weight side (csrc/fp8.hip, "Formats").  layout 2 = the decode side:
+ * `scales` is the plain exponent matrix uint8 [R, K/32] (E8M0, biased by 127, row-major: R*K/32 bytes), the E8 of avllm_dec_proj. */
 size_t avllm_mx_scale_bytes(int32_t R, int32_t K);
 int avllm_mx_quantize(const void* x, int64_t ldx, int32_t R, int32_t K, void* q, int64_t ldq, void* scales, int32_t layout, int32_t dtype,
                       void* stream);
@@ -392,6 +393,9 @@ typedef struct avllm_llama_layer {
     /* fp8 mode (avllm_llama.fp8 != 0): forward-pass images of the four frozen matrices (avllm_mx_quantize layout 1).  The backward pass keeps
      * using the bf16 transposed images: gradients are not quantised. */
     const void *wqkv8, *sqkv8, *wo8, *so8, *wgu8, *sgu8, *wdown8, *sdown8;
+    /* fp8 token step (avllm_llama.decode_fp8 != 0): the exponent matrices [rows, K/32] (avllm_mx_quantize layout 2) of the codes wqkv8, wo8,
+     * wgu8, wdown8 above, which the token step then streams instead of the bf16 matrices.  Unused otherwise. */
+    const void *eqkv8, *eo8, *egu8, *edown8;
 } avllm_llama_layer;
 
 typedef struct avllm_llama {
@@ -415,6 +419,12 @@ typedef struct avllm_llama {
      * high_freq_factor, original_max_position_embeddings; HF:modeling_rope_utils.py _compute_llama3_parameters).  0 = plain RoPE. */
     float rope_factor, rope_low_freq_factor, rope_high_freq_factor;
     int32_t rope_orig_ctx;
+    /* 1: weight-only fp8 token step.  When the fused path applies (avllm_llama_decode_is_fused: B <= 16), the q|k|v, o, gate|up, down
+     * projections and lm_head of avllm_llama_decode_step(_at) stream the e4m3 codes (wqkv8 .. wdown8, lm_head8) with the layout-2 exponents
+     * (eqkv8 .. edown8, elm_head8) instead of the bf16 matrices; activations, KV cache, attention, norms, adapters and logits are unchanged.
+     * Needs bf16, d, ffn multiples of 128 and vocab a multiple of 16.  B > 16 and prefill stay on the bf16 matrices.  Independent of fp8. */
+    int32_t decode_fp8;
+    const void* elm_head8;
 } avllm_llama;
 
 size_t avllm_llama_train_workspace_bytes(const avllm_llama* m, int32_t B, int32_t S);
@@ -458,6 +468,8 @@ int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* ids, int32_t
 /* 1 when a token step of B sequences on this model takes the fused bf16 path (one launch per projection + one attention launch per
  * layer), 0 when it takes the general path: tests and benchmarks assert which one they measured. */
 int avllm_llama_decode_is_fused(const avllm_llama* m, int32_t B);
+/* 1 when a token step of B sequences streams the fp8 weight images (decode_fp8 set and the fused path taken), 0 when it reads bf16. */
+int avllm_llama_decode_streams_fp8(const avllm_llama* m, int32_t B);
 int avllm_pos_advance(int32_t* pos_dev, int32_t by, void* stream);
 
 /* One projection of a decode token step (bf16, 1 <= M <= 16 rows, K % 128 == 0): C = epilogue(rmsnorm?(A) . W^T).  Every weight row
@@ -486,6 +498,11 @@ typedef struct avllm_dec_proj_desc {
     const float* lora_t; int64_t ld_lora_t;
     const void* lora_b[3];
     int32_t lora_r; float lora_scale;
+    /* fp8 weight form: W8 != NULL streams the weight rows as e4m3 codes [rows, K] (row stride ldw BYTES, ldw % 16 == 0, 16-byte aligned) with
+     * E8 = their E8M0 exponents [rows, K/32] uint8, row-major, biased by 127 (avllm_mx_quantize layout 2); W is then ignored.  Every mode,
+     * the norm fold, residual, outputs and adapters as above: the product is the bf16 form's on the weights codes * 2^(E8 - 127) (exact in
+     * bf16), summed in a different fp32 order inside each 64-column pair of K-steps. */
+    const void* W8; const void* E8;
 } avllm_dec_proj_desc;
 int avllm_dec_proj(const avllm_dec_proj_desc* d, void* stream);
 /* Single-query attention over the cache rows [0, Tk + *tk_dev) (tk_dev may be NULL) of kc/vc [B][Tmax][(H/kv_group)*hd]: one pass with
