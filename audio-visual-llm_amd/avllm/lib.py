@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("AVLLM_LIB_PATH") or os.path.join(_HERE, "libavllm.so"
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_SILU = 0, 1, 2, 3
+GEMM_KERNELS = ("SMALLM", "SKINNY64", "128", "RING", "H16", "HP16", "W4", "WP4", "DP", "F32")      # AVLLM_GEMM_<name> of avllm.h, by id
 LORA_PAD = 64
 
 i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
@@ -93,8 +94,10 @@ LAYER_CB = C.CFUNCTYPE(None, i32, vp)
 _SIGS = {
     "avllm_version": ([], i32),
     "avllm_gemm": ([C.POINTER(GemmDesc), vp], i32),
+    "avllm_gemm_plan": ([C.POINTER(GemmDesc), C.POINTER(i32)], i32),
     "avllm_set_gemm_variant": ([i32], i32),
     "avllm_set_knob": ([C.c_char_p, i32], i32),
+    "avllm_get_knob": ([C.c_char_p, C.POINTER(i32)], i32),
     "avllm_attention_fwd_mxq": ([vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, i64, i64, i64, f32, vp], i32),
     "avllm_im2col_k3": ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "avllm_groupnorm_tokens": ([vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp], i32),
@@ -198,21 +201,21 @@ class AvllmError(RuntimeError):
 
 
 class knob:
-    """with knob("DECODE_FUSED", 0): ...   -- one of the library's A/B switches for the duration of the block (include/avllm.h
-    avllm_set_knob; the table is otherwise filled once per process from AVLLM_<NAME>)."""
-    _defaults = {"DECODE_FUSED": 1, "DEC_AL": 0, "LORA_UNBATCHED": 0, "F8_UNFUSED_QUANT": 0, "F8_FAST": 1, "ATTN_SHORT": 1,
-                 "NARROW_EPILOGUE": 0, "TN_CHUNK": 0, "GEMM_DBG": 0, "GEMM_GW": 0}
+    """with knob("DECODE_FUSED", 0): ...   -- one of the library's A/B switches for the duration of the block, then back to the value it had
+    (include/avllm.h avllm_set_knob; the table is otherwise filled once per process from AVLLM_<NAME>)."""
 
     def __init__(self, name, value):
-        self.name, self.value = name, int(value)
+        self.name, self.value = name.encode(), int(value)
 
     def __enter__(self):
-        check(load().avllm_set_knob(self.name.encode(), self.value))
+        prev = i32()
+        check(load().avllm_get_knob(self.name, C.byref(prev)))
+        self.prev = prev.value
+        check(load().avllm_set_knob(self.name, self.value))
         return self
 
     def __exit__(self, *a):
-        env = os.environ.get("AVLLM_" + self.name)
-        check(load().avllm_set_knob(self.name.encode(), int(env) if env is not None else self._defaults[self.name]))
+        check(load().avllm_set_knob(self.name, self.prev))
 
 
 def check(rc: int):

@@ -15,11 +15,12 @@ def _ld(t):
 
 
 def gemm(A, B, out=None, bias=None, R=None, A2=None, B2=None, act=L.ACT_NONE, alpha=1.0, out_f32=False,
-         r_mod=0, remap=None, M=None, a_drop=None, n_valid=0, drop=None):
+         r_mod=0, remap=None, M=None, a_drop=None, n_valid=0, drop=None, plan=False):
     """out[M,N] = act(alpha*(A.B^T + A2.B2^T) + bias) + R.  A [M,K] (row stride free), B [N,K].
     a_drop=(seed, p): A is replaced by dropout(A) on the fly (bf16, N == 64 only).
     drop=(seed, p): the product (before +R) is multiplied by the dropout mask keep(seed, m*N+n, p)/(1-p) -- the adapter's
-    input-gradient GEMM of the training backward (csrc/engine.hip)."""
+    input-gradient GEMM of the training backward (csrc/engine.hip).
+    plan=True: nothing runs; returns the name (L.GEMM_KERNELS) of the kernel this call gets."""
     lib = L.load()
     M = A.shape[0] if M is None else M
     N, K = B.shape[0], B.shape[1]
@@ -44,6 +45,10 @@ def gemm(A, B, out=None, bias=None, R=None, A2=None, B2=None, act=L.ACT_NONE, al
     if drop is not None:
         d.drop_seed, d.drop_p = drop[0] & 0xFFFFFFFF, drop[1]
     d.n_valid = n_valid
+    if plan:
+        k = L.i32()
+        L.check(lib.avllm_gemm_plan(C.byref(d), C.byref(k)))
+        return L.GEMM_KERNELS[k.value]
     L.check(lib.avllm_gemm(C.byref(d), L.stream_ptr()))
     return out
 

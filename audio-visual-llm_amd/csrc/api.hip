@@ -19,7 +19,7 @@ int av_set_error(int code, const char* fmt, ...) {
 #include <string.h>
 static const struct { const char* name; int dflt; } g_knob_def[AV_KNOB_COUNT] = {
     {"DECODE_FUSED", 1}, {"DEC_AL", 0}, {"LORA_UNBATCHED", 0}, {"F8_UNFUSED_QUANT", 0}, {"F8_FAST", 1}, {"ATTN_SHORT", 1},
-    {"NARROW_EPILOGUE", 0}, {"TN_CHUNK", 0}, {"GEMM_DBG", 0}, {"GEMM_GW", 0}};
+    {"NARROW_EPILOGUE", 0}, {"TN_CHUNK", 0}, {"GEMM_DBG", 0}, {"GEMM_GW", 0}, {"GEMM_VARIANT", 0}};
 static int g_knob[AV_KNOB_COUNT];
 static std::once_flag g_knob_once;
 static void knob_init() {
@@ -34,20 +34,43 @@ int av_knob(int id) {
     std::call_once(g_knob_once, knob_init);
     return g_knob[id];
 }
+static int* knob_slot(const char* name) {
+    std::call_once(g_knob_once, knob_init);
+    for (int i = 0; name && i < AV_KNOB_COUNT; ++i)
+        if (!strcmp(name, g_knob_def[i].name)) return &g_knob[i];
+    return nullptr;
+}
+
+int av_device(int* ncu) {
+    static int g_ncu[AV_MAX_DEVICES];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const int slot = dev & (AV_MAX_DEVICES - 1);
+    if (!g_ncu[slot] && hipDeviceGetAttribute(&g_ncu[slot], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) g_ncu[slot] = 256;
+    *ncu = g_ncu[slot];
+    return slot;
+}
 
 #define ST ((hipStream_t)stream)
 extern "C" {
 int avllm_set_knob(const char* name, int32_t value) {
-    AV_CHECK_ARG(name, "set_knob: null name");
-    std::call_once(g_knob_once, knob_init);
-    for (int i = 0; i < AV_KNOB_COUNT; ++i)
-        if (!strcmp(name, g_knob_def[i].name)) { g_knob[i] = value; return AV_OK; }
-    return av_set_error(AV_ERR_ARG, "set_knob: unknown knob '%s'", name);
+    int* k = knob_slot(name);
+    AV_CHECK_ARG(k, "set_knob: unknown knob '%s'", name ? name : "(null)");
+    *k = value;
+    return AV_OK;
 }
+int avllm_get_knob(const char* name, int32_t* value) {
+    const int* k = knob_slot(name);
+    AV_CHECK_ARG(k && value, "get_knob: unknown knob '%s'", name ? name : "(null)");
+    *value = *k;
+    return AV_OK;
+}
+int avllm_set_gemm_variant(int v) { return avllm_set_knob("GEMM_VARIANT", v); }
 const char* avllm_last_error(void) { return g_err; }
 int avllm_version(void) { return 100; }
 
 int avllm_gemm(const avllm_gemm_desc* d, void* stream) { return av_gemm(d, ST); }
+int avllm_gemm_plan(const avllm_gemm_desc* d, int32_t* kernel) { AV_CHECK_ARG(kernel, "gemm_plan: null kernel"); return av_gemm_plan(d, kernel); }
 int avllm_gemm_tn(const void* P, int64_t ldp, int32_t I, const void* Q, int64_t ldq, int32_t J, int32_t M, float* out,
                   int64_t ldo, float alpha, int32_t dtype, void* stream) { return av_gemm_tn(P, ldp, I, Q, ldq, J, M, out, ldo, alpha, dtype, ST); }
 int avllm_gemm_tn_drop(const void* P, int64_t ldp, int32_t I, const void* Q, int64_t ldq, int32_t J, int32_t M, float* out,

@@ -3,7 +3,14 @@
 #include <hip/hip_runtime.h>
 #include "../../include/avllm.h"
 
+// The current device (0 when the runtime cannot say), as an index below AV_MAX_DEVICES for the launchers' per-device "dynamic LDS limit raised"
+// flags, and its CU count (cached per device; 256 when the runtime cannot say): the grid of the persistent kernels.
+#define AV_MAX_DEVICES 64
+int av_device(int* ncu);
+int av_gemm_plan(const avllm_gemm_desc* d, int* kernel);
 int av_gemm(const avllm_gemm_desc* d, hipStream_t st);
+bool av_gemm_dp_ok(const avllm_gemm_desc* d);                                              // gemm_dp.hip: the calls its kernel takes, and its
+int av_gemm_dp(const avllm_gemm_desc* d, hipStream_t st, int dbg, int dev, int ncu);       // launch, for av_gemm alone
 int av_gemm_tn(const void* P, long ldp, int I, const void* Q, long ldq, int J, int M, float* out, long ldo,
                float alpha, int dtype, hipStream_t st, uint32_t drop_seed = 0, float drop_p = 0.f, const uint32_t* seed_dev = nullptr);
 int av_layernorm(const void* x, const void* w, const void* b, void* y, long rows, int d, float eps, int dtype, hipStream_t st);

@@ -467,15 +467,12 @@ int av_gemm_f8_fast(const avllm_gemm_f8_desc* d, hipStream_t st, bool* taken) {
     *taken = false;
     if (!f8_fast_takes(d)) return AV_OK;
     const int xtiles = av_cdiv(d->M, TM) * av_cdiv(d->N, TN);
-    static bool attr[64] = {};
-    static int ncu[64] = {};
-    int dev = 0;
-    AV_HIP(hipGetDevice(&dev));
-    dev &= 63;
-    if (!attr[dev]) {
+    static bool raised[AV_MAX_DEVICES];
+    int ncu;
+    const int dev = av_device(&ncu);
+    if (!raised[dev]) {
         AV_HIP(hipFuncSetAttribute((const void*)gemm_f8_wp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F8_LDS));
-        AV_HIP(hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        attr[dev] = true;
+        raised[dev] = true;
     }
     F8Args g;
     g.A = (const uint8_t*)d->A; g.B = (const uint8_t*)d->B; g.SA = (const uint32_t*)d->SA; g.SB = (const uint32_t*)d->SB;
@@ -487,7 +484,7 @@ int av_gemm_f8_fast(const avllm_gemm_f8_desc* d, hipStream_t st, bool* taken) {
 #endif
     g.C = d->C; g.ldc = d->ldc; g.bias = d->bias; g.R = d->R; g.ldr = d->ldr; g.act = d->act; g.M = d->M; g.N = d->N;
     g.Cq = (uint8_t*)d->Cq; g.SCq = (uint32_t*)d->SCq; g.ldcq = d->ldcq;
-    hipLaunchKernelGGL(gemm_f8_wp_kernel, dim3(xtiles < ncu[dev] ? xtiles : ncu[dev]), dim3(256), F8_LDS, st, g);
+    hipLaunchKernelGGL(gemm_f8_wp_kernel, dim3(xtiles < ncu ? xtiles : ncu), dim3(256), F8_LDS, st, g);
     AV_LAUNCH_CHECK();
     *taken = true;
     return AV_OK;

@@ -1371,17 +1371,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgsF g) {
 
 }  // namespace
 
-// Per-device launch state: the CU count and the "dynamic LDS limit raised" flags belong to the device the call runs on
-// (one process may drive several GPUs; hipFuncSetAttribute applies to the current device's copy of the code object).
-struct GemmDevState { int ncu = 0; bool attr_base = false, attr_wp = false, attr_w = false, attr_h = false; };
-static GemmDevState g_gemm_dev[64];
-static GemmDevState* gemm_dev_state() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    GemmDevState* s = &g_gemm_dev[dev & 63];
-    if (!s->ncu && hipDeviceGetAttribute(&s->ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) s->ncu = 256;
-    return s;
-}
 #ifdef AVLLM_GEMM_STAMPS
 extern "C" int avllm_debug_read_gemm_stamps(unsigned long long* host, int32_t n) {
     AV_HIP(hipDeviceSynchronize());
@@ -1389,131 +1378,132 @@ extern "C" int avllm_debug_read_gemm_stamps(unsigned long long* host, int32_t n)
     return AV_OK;
 }
 #endif
-static int g_gemm_variant = -1;     // 0 auto, 1 128x128, 2 256x128 ring, 5 256x256 16-wave, 6 256x256 16-wave persistent, 7 256x256 4-wave, 8 256x256 4-wave persistent (lean epilogue only), 9 256x128 persistent, two workgroups per CU (gemm_dp.hip; lean epilogue only)
-bool av_gemm_dp_ok(const avllm_gemm_desc* d);
-int av_gemm_dp(const avllm_gemm_desc* d, hipStream_t st, int dbg);
-extern "C" int avllm_set_gemm_variant(int v) { g_gemm_variant = v; return 0; }
 bool av_prof_enabled();
 void av_prof_before(hipStream_t st);
 void av_prof_after(hipStream_t st, double flops);
 
-int av_gemm(const avllm_gemm_desc* d, hipStream_t st) {
+// What the kernel choice and the launch both need of a call: whether the LDS-staged epilogue with 16-byte stores can take it (GemmArgs::wide_epi)
+// and its number of 256x256 tiles.
+static bool gemm_wide_ok(const avllm_gemm_desc* d) {
+    const size_t osz = d->out_f32 || d->dtype == AV_F32 ? 4 : 2;
+    return d->dtype == AV_BF16 && d->N % 8 == 0 && ((uintptr_t)d->C % 16 == 0) && (d->ldc * osz) % 16 == 0 &&
+           (!d->bias || (uintptr_t)d->bias % 16 == 0) && (!d->R || ((uintptr_t)d->R % 16 == 0 && d->ldr % 8 == 0)) &&
+           !av_knob(AV_KNOB_NARROW_EPILOGUE);
+}
+static int gemm_xtiles(const avllm_gemm_desc* d) { return av_cdiv(d->M, HBM_) * av_cdiv(d->N, HBN_); }
+
+// Which kernel a call gets (AVLLM_GEMM_* of avllm.h), or the error av_gemm reports for it.  Pure: the descriptor and the knob table
+// (GEMM_VARIANT, NARROW_EPILOGUE) decide; operand pointers are looked at for alignment only.  DESIGN.md "Which GEMM kernel a call gets".
+int av_gemm_plan(const avllm_gemm_desc* d, int* kernel) {
     AV_CHECK_ARG(d && d->A && d->B && d->C, "gemm: null operand");
     AV_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
     AV_CHECK_ARG(d->K % 64 == 0 && d->K2 % 64 == 0, "gemm: K (%d) and K2 (%d) must be multiples of 64", d->K, d->K2);
     AV_CHECK_ARG(d->K2 == 0 || (d->A2 && d->B2), "gemm: K2>0 needs A2/B2");
     AV_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 8 == 0 && d->ldc % 4 == 0, "gemm: leading dims must keep 16-byte rows");
     AV_CHECK_ARG(d->dtype == AV_F32 || d->dtype == AV_BF16, "gemm: dtype %d", d->dtype);
-    EpiParams e;
+    const int variant = av_knob(AV_KNOB_GEMM_VARIANT) > 0 ? av_knob(AV_KNOB_GEMM_VARIANT) : 0;      // 0 = automatic
+    const bool bf = d->dtype == AV_BF16, big = d->M > 128;
+    const int kk = d->K + d->K2, xtiles = gemm_xtiles(d);
+    // the persistent kernels' epilogues take nothing but bias / activation / plain residual
+    const bool lean_ok = gemm_wide_ok(d) && d->alpha == 1.f && d->drop_p <= 0.f && d->g_in <= 0 && !d->out_f32 && d->r_mod <= 0;
+    // the 256x256 kernels keep 32-bit element offsets of their staging rows: operands must stay below 2^32 elements
+    const bool fits32 = (double)d->M * (double)(d->lda > d->lda2 ? d->lda : d->lda2) < 4.0e9 &&
+                        (double)d->N * (double)(d->ldb > d->ldb2 ? d->ldb : d->ldb2) < 4.0e9;
+    // automatic choice (tools/gemm_bench.py on MI355X): 256x256 whenever it fills the chip, 256x128 ring for very long K with few tiles,
+    // else 128x128 with two workgroups per CU.  Of the 256x256 kernels the one-shot 4-wave one takes the non-lean calls with long K (fixed cost
+    // 10.9 us per tile + 1.43 us per K-step against 7.7 + 1.67 for the 16-wave kernel, tools/gemm_ktile_sweep.py; small grids favour the
+    // 16-wave kernel a little longer)
+    const bool auto_h = variant == 0 && xtiles >= 200 && fits32;
+    const bool auto_w = auto_h && (kk >= 4096 || (kk >= 2048 && xtiles >= 1024));
+    const bool auto_l = variant == 0 && !auto_h && d->K >= 16384;
+    if (bf && d->M <= 16 && d->N % 16 == 0 && d->K % (32 * SK_WAVES) == 0 && d->K2 % 32 == 0 && d->g_in == 0 && d->drop_p <= 0.f &&
+        d->a_drop_p <= 0.f && variant == 0)                                    // a_drop: the rank-side kernel below owns the fused mask
+        *kernel = AVLLM_GEMM_SMALLM;
+    else if (bf && d->N == 64 && d->K2 == 0 && !d->bias && !d->R && d->act == AV_ACT_NONE && d->g_in == 0 && d->drop_p <= 0.f &&
+               d->K % (32 * SK_WAVES) == 0 && (d->M >= 256 || d->a_drop_p > 0.f)) {
+        AV_CHECK_ARG(d->a_drop_p <= 0.f || d->lda == d->K, "gemm: a_drop needs the full contiguous [M,K] activation as A");
+        AV_CHECK_ARG(d->n_valid >= 0 && d->n_valid <= 64, "gemm: n_valid=%d", d->n_valid);
+        *kernel = AVLLM_GEMM_SKINNY64;
+    } else if (d->a_drop_p > 0.f)
+        return av_set_error(AV_ERR_UNSUPPORTED, "gemm: a_drop_p is only implemented by the bf16 N==64 rank-side kernel (K %% 256 == 0)");
+    else if (!bf) *kernel = AVLLM_GEMM_F32;
+    else if (big && variant == 9 && lean_ok && av_gemm_dp_ok(d)) *kernel = AVLLM_GEMM_DP;      // A/B variant, never chosen automatically (gemm_dp.hip: why)
+    else if (big && (variant == 8 || auto_h) && lean_ok && kk >= 128) *kernel = AVLLM_GEMM_WP4;
+    else if (big && (variant == 7 || auto_w) && kk >= 128) *kernel = AVLLM_GEMM_W4;
+    else if (big && (variant == 5 || variant == 6 || auto_h)) {
+        AV_CHECK_ARG(fits32 || variant == 6, "gemm: operand too large for the 256x256 kernel's 32-bit row offsets");
+        *kernel = variant == 6 ? AVLLM_GEMM_HP16 : AVLLM_GEMM_H16;
+    } else if (big && (variant == 2 || auto_l)) *kernel = AVLLM_GEMM_RING;
+    else *kernel = AVLLM_GEMM_128;                                   // a forced variant that cannot take the call ends here too
+    return AV_OK;
+}
+
+// hipFuncSetAttribute applies to the current device's copy of the code object: one "dynamic LDS limit raised" flag per device and kernel.
+static bool g_lds_raised[AV_MAX_DEVICES][AVLLM_GEMM_KERNELS];
+#define AV_RAISE_LDS(KERNEL, BYTES) AV_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES))
+#define AV_LAUNCH(KERNEL, GRID, BLOCK, LDS, ...) hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(BLOCK), LDS, st, __VA_ARGS__)
+#define AV_LAUNCH_LDS(KERNEL, GRID, BLOCK, LDS) do { if (!raised) AV_RAISE_LDS(KERNEL, LDS); AV_LAUNCH(KERNEL, GRID, BLOCK, LDS, g); } while (0)
+
+int av_gemm(const avllm_gemm_desc* d, hipStream_t st) {
+    int kernel;
+    AV_TRY(av_gemm_plan(d, &kernel));
+    const int xtiles = gemm_xtiles(d);
+    GemmArgs g;
+    g.A = (const bf16*)d->A; g.B = (const bf16*)d->B; g.A2 = (const bf16*)d->A2; g.B2 = (const bf16*)d->B2;
+    g.lda = d->lda; g.ldb = d->ldb; g.lda2 = d->lda2; g.ldb2 = d->ldb2; g.K = d->K; g.K2 = d->K2;
+    g.wide_epi = gemm_wide_ok(d);
+    // Tall shapes can walk the tiles in column groups whose weight panels fit an XCD's L2 beside the streaming activation panels.
+    // Measured (profiles/r03_pmc_gemm_shapes.txt, gpurun_out/r3_gw_sweep.log): the fabric reads of the CLIP fc1 fall from 8.8x to 4.6x
+    // the algorithmic bytes (qkv 5.3x -> 4.1x) and the launch gets no faster (fc1 1688 -> 1670 us at width 6, 1751 at 4; qkv 1263 ->
+    // 1293 .. 1324): these launches are not bound by their read traffic.  So the walk stays row-major; knob GEMM_GW = n forces a width.
+    g.gw = av_knob(AV_KNOB_GEMM_GW) > 0 ? av_knob(AV_KNOB_GEMM_GW) : 0;
+#ifdef AVLLM_EXPERIMENT_KNOBS
+    g.dbg = av_knob(AV_KNOB_GEMM_DBG);
+#else
+    g.dbg = 0;
+#endif
+    EpiParams& e = g.e;
     e.C = d->C; e.ldc = d->ldc; e.out_f32 = d->out_f32 || d->dtype == AV_F32; e.bias = d->bias; e.R = d->R; e.ldr = d->ldr;
     e.r_mod = d->r_mod; e.g_in = d->g_in; e.g_out = d->g_out; e.g_off = d->g_off;
     e.alpha = d->alpha; e.act = d->act; e.M = d->M; e.N = d->N;
     e.drop_seed = d->drop_seed; e.drop_p = d->drop_p; e.seed_dev = d->seed_dev;
+    int ncu;
+    const int dev = av_device(&ncu);
+    const bool raised = g_lds_raised[dev][kernel];
+    const int pgrid = xtiles < ncu ? xtiles : ncu;      // persistent kernels: one workgroup per CU
     const bool prof = av_prof_enabled();
     if (prof) av_prof_before(st);
-    const size_t osz = e.out_f32 ? 4 : 2;
-    const bool wide_ok = d->dtype == AV_BF16 && d->N % 8 == 0 && ((uintptr_t)d->C % 16 == 0) && (d->ldc * osz) % 16 == 0 &&
-                         (!d->bias || (uintptr_t)d->bias % 16 == 0) && (!d->R || ((uintptr_t)d->R % 16 == 0 && d->ldr % 8 == 0)) &&
-                         !av_knob(AV_KNOB_NARROW_EPILOGUE);
-    if (d->dtype == AV_BF16 && d->M <= 16 && d->N % 16 == 0 && d->K % (32 * SK_WAVES) == 0 && d->K2 % 32 == 0 && d->g_in == 0 &&
-        d->drop_p <= 0.f && d->a_drop_p <= 0.f && g_gemm_variant <= 0) {      // a_drop: the rank-side kernel below owns the fused mask
-        GemmArgs g;
-        g.A = (const bf16*)d->A; g.B = (const bf16*)d->B; g.A2 = (const bf16*)d->A2; g.B2 = (const bf16*)d->B2;
-        g.lda = d->lda; g.ldb = d->ldb; g.lda2 = d->lda2; g.ldb2 = d->ldb2; g.K = d->K; g.K2 = d->K2; g.e = e;
-        g.wide_epi = wide_ok; g.dbg = 0; g.gw = 0;
-        hipLaunchKernelGGL(gemm_smallm_kernel, dim3(d->N / 16), dim3(SK_WAVES * 64), 0, st, g);
-    } else if (d->dtype == AV_BF16 && d->N == 64 && d->K2 == 0 && !d->bias && !d->R && d->act == AV_ACT_NONE && d->g_in == 0 && d->drop_p <= 0.f &&
-               d->K % (32 * SK_WAVES) == 0 && (d->M >= 256 || d->a_drop_p > 0.f)) {
-        AV_CHECK_ARG(d->a_drop_p <= 0.f || d->lda == d->K, "gemm: a_drop needs the full contiguous [M,K] activation as A");
-        AV_CHECK_ARG(d->n_valid >= 0 && d->n_valid <= 64, "gemm: n_valid=%d", d->n_valid);
+    switch (kernel) {
+    case AVLLM_GEMM_SMALLM: AV_LAUNCH(gemm_smallm_kernel, d->N / 16, SK_WAVES * 64, 0, g); break;
+    case AVLLM_GEMM_SKINNY64: {                   // <fused dropout of A, 16-column groups of B that hold values>
+        static const decltype(&gemm_skinny64_kernel<true, 1>) skinny[2][3] = {
+            {gemm_skinny64_kernel<true, 1>, gemm_skinny64_kernel<true, 2>, gemm_skinny64_kernel<true, 4>},
+            {gemm_skinny64_kernel<false, 1>, gemm_skinny64_kernel<false, 2>, gemm_skinny64_kernel<false, 4>}};
+        const bool drop = d->a_drop_p > 0.f;
         const int nv = d->n_valid > 0 ? (d->n_valid + 15) / 16 : 4;
-#define AV_SKINNY(DROPV, NVV, SEED, P) hipLaunchKernelGGL((gemm_skinny64_kernel<DROPV, NVV>), dim3(av_cdiv(d->M, 16)), dim3(SK_WAVES * 64), 0, st, \
-            (const bf16*)d->A, d->lda, (const bf16*)d->B, d->ldb, d->M, d->K, d->alpha, d->C, d->ldc, e.out_f32, SEED, P, d->seed_dev)
-        if (d->a_drop_p > 0.f) {
-            if (nv == 1) AV_SKINNY(true, 1, d->a_drop_seed, d->a_drop_p);
-            else if (nv == 2) AV_SKINNY(true, 2, d->a_drop_seed, d->a_drop_p);
-            else AV_SKINNY(true, 4, d->a_drop_seed, d->a_drop_p);
-        } else {
-            if (nv == 1) AV_SKINNY(false, 1, 0u, 0.f);
-            else if (nv == 2) AV_SKINNY(false, 2, 0u, 0.f);
-            else AV_SKINNY(false, 4, 0u, 0.f);
-        }
-#undef AV_SKINNY
-    } else if (d->a_drop_p > 0.f) {
-        return av_set_error(AV_ERR_UNSUPPORTED, "gemm: a_drop_p is only implemented by the bf16 N==64 rank-side kernel (K %% 256 == 0)");
-    } else if (d->dtype == AV_BF16) {
-        GemmArgs g;
-        g.A = (const bf16*)d->A; g.B = (const bf16*)d->B; g.A2 = (const bf16*)d->A2; g.B2 = (const bf16*)d->B2;
-        g.lda = d->lda; g.ldb = d->ldb; g.lda2 = d->lda2; g.ldb2 = d->ldb2; g.K = d->K; g.K2 = d->K2; g.e = e;
-        g.wide_epi = wide_ok;
-        {   // Tall shapes can walk the tiles in column groups whose weight panels fit an XCD's L2 beside the streaming activation panels.
-            // Measured (profiles/r03_pmc_gemm_shapes.txt, gpurun_out/r3_gw_sweep.log): the fabric reads of the CLIP fc1 fall from 8.8x to 4.6x
-            // the algorithmic bytes (qkv 5.3x -> 4.1x) and the launch gets no faster (fc1 1688 -> 1670 us at width 6, 1751 at 4; qkv 1263 ->
-            // 1293 .. 1324): these launches are not bound by their read traffic.  So the walk stays row-major; knob GEMM_GW = n forces a width.
-            const int forced = av_knob(AV_KNOB_GEMM_GW);
-            g.gw = forced > 0 ? forced : 0;
-        }
-#ifdef AVLLM_EXPERIMENT_KNOBS
-        g.dbg = av_knob(AV_KNOB_GEMM_DBG);
-#else
-        g.dbg = 0;
-#endif
-        GemmDevState* ds = gemm_dev_state();
-        if (!ds->attr_base) {
-            AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE_BYTES));
-            AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_l_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LNSTAGE * LSTAGE));
-            ds->attr_base = true;
-        }
-        const int variant = g_gemm_variant >= 0 ? g_gemm_variant : (g_gemm_variant = getenv("AVLLM_GEMM_VARIANT") ? atoi(getenv("AVLLM_GEMM_VARIANT")) : 0);
-        constexpr int XBM = 256, XBN = 256;
-        const int xtiles = av_cdiv(d->M, XBM) * av_cdiv(d->N, XBN);
-        // automatic choice (tools/gemm_bench.py on MI355X): 256x256 / 16 waves whenever it fills the chip, 256x128 ring for very
-        // long K with few tiles, else 128x128 with two workgroups per CU
-        // the 16-wave kernel keeps 32-bit element offsets of its staging rows: operands must stay below 2^32 elements
-        const bool fits32 = (double)d->M * (double)(d->lda > d->lda2 ? d->lda : d->lda2) < 4.0e9 &&
-                            (double)d->N * (double)(d->ldb > d->ldb2 ? d->ldb : d->ldb2) < 4.0e9;
-        const bool auto_h = variant == 0 && xtiles >= 200 && fits32;   // 4-wave kernel for long K (fixed cost 10.9 us per tile + 1.43 us per K-step against
-        // 7.7 + 1.67 for the 16-wave kernel, tools/gemm_ktile_sweep.py; small grids favour the 16-wave kernel a little longer)
-        const bool auto_l = variant == 0 && !auto_h && d->K >= 16384;
-        const bool lean_ok = wide_ok && d->alpha == 1.f && d->drop_p <= 0.f && d->g_in <= 0 && !e.out_f32 && d->r_mod <= 0;
-        if (d->M > 128 && variant == 9 && lean_ok && av_gemm_dp_ok(d)) {           // A/B variant, never chosen automatically (gemm_dp.hip: why)
-            AV_TRY(av_gemm_dp(d, st, g.dbg));
-        } else if (d->M > 128 && (variant == 8 || auto_h) && lean_ok && d->K + d->K2 >= 128) {
-            if (!ds->attr_wp) {
-                AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_wp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS));
-                AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_wp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, WP_LDS));
-                ds->attr_wp = true;
-            }
-            const int ncu8 = ds->ncu;
-            if (d->K2 > 0) hipLaunchKernelGGL(gemm_bf16_wp_kernel<true>, dim3(xtiles < ncu8 ? xtiles : ncu8), dim3(256), WP_LDS, st, g);
-            else hipLaunchKernelGGL(gemm_bf16_wp_kernel<false>, dim3(xtiles < ncu8 ? xtiles : ncu8), dim3(256), WP_LDS, st, g);
-        } else if (d->M > 128 && (variant == 7 || (auto_h && (d->K + d->K2 >= 4096 || (d->K + d->K2 >= 2048 && xtiles >= 1024)))) && d->K + d->K2 >= 128) {
-            if (!ds->attr_w) { AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_w_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HSTAGE)); ds->attr_w = true; }
-            hipLaunchKernelGGL(gemm_bf16_w_kernel, dim3(xtiles), dim3(256), 2 * HSTAGE, st, g);
-        } else if (d->M > 128 && (variant == 5 || variant == 6 || auto_h)) {
-            AV_CHECK_ARG(fits32 || variant == 6, "gemm: operand too large for the 256x256 kernel's 32-bit row offsets");
-            if (!ds->attr_h) {
-                AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HSTAGE));
-                AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_hp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * HSTAGE));
-                ds->attr_h = true;
-            }
-            const int ncu = ds->ncu;
-            if (variant != 6) hipLaunchKernelGGL(gemm_bf16_h_kernel, dim3(xtiles), dim3(1024), 2 * HSTAGE, st, g);
-            else hipLaunchKernelGGL(gemm_bf16_hp_kernel, dim3(xtiles < ncu ? xtiles : ncu), dim3(1024), 2 * HSTAGE, st, g);
-        } else if (d->M > 128 && (variant == 2 || auto_l)) {
-            const int tiles = av_cdiv(d->M, LBM) * av_cdiv(d->N, LBN);
-            hipLaunchKernelGGL(gemm_bf16_l_kernel, dim3(tiles), dim3(512), LNSTAGE * LSTAGE, st, g);
-        } else {
-            const int tiles = av_cdiv(d->M, BM) * av_cdiv(d->N, BN);
-            hipLaunchKernelGGL(gemm_bf16_kernel, dim3(tiles), dim3(256), 4 * TILE_BYTES, st, g);
-        }
-    } else {
-        GemmArgsF g;
-        g.A = (const float*)d->A; g.B = (const float*)d->B; g.A2 = (const float*)d->A2; g.B2 = (const float*)d->B2;
-        g.lda = d->lda; g.ldb = d->ldb; g.lda2 = d->lda2; g.ldb2 = d->ldb2; g.K = d->K; g.K2 = d->K2; g.e = e;
-        const int tiles = av_cdiv(d->M, FM) * av_cdiv(d->N, FN);
-        hipLaunchKernelGGL(gemm_f32_kernel, dim3(tiles), dim3(256), 0, st, g);
+        AV_LAUNCH(skinny[!drop][nv == 1 ? 0 : nv == 2 ? 1 : 2], av_cdiv(d->M, 16), SK_WAVES * 64, 0, g.A, d->lda, g.B, d->ldb, d->M, d->K, d->alpha,
+                  d->C, d->ldc, e.out_f32, drop ? d->a_drop_seed : 0u, drop ? d->a_drop_p : 0.f, d->seed_dev);
+        break;
     }
+    case AVLLM_GEMM_128: AV_LAUNCH_LDS(gemm_bf16_kernel, av_cdiv(d->M, BM) * av_cdiv(d->N, BN), 256, 4 * TILE_BYTES); break;
+    case AVLLM_GEMM_RING: AV_LAUNCH_LDS(gemm_bf16_l_kernel, av_cdiv(d->M, LBM) * av_cdiv(d->N, LBN), 512, LNSTAGE * LSTAGE); break;
+    case AVLLM_GEMM_H16: AV_LAUNCH_LDS(gemm_bf16_h_kernel, xtiles, 1024, 2 * HSTAGE); break;
+    case AVLLM_GEMM_HP16: AV_LAUNCH_LDS(gemm_bf16_hp_kernel, pgrid, 1024, 2 * HSTAGE); break;
+    case AVLLM_GEMM_W4: AV_LAUNCH_LDS(gemm_bf16_w_kernel, xtiles, 256, 2 * HSTAGE); break;
+    case AVLLM_GEMM_WP4:
+        if (!raised) { AV_RAISE_LDS(gemm_bf16_wp_kernel<false>, WP_LDS); AV_RAISE_LDS(gemm_bf16_wp_kernel<true>, WP_LDS); }
+        if (d->K2 > 0) AV_LAUNCH(gemm_bf16_wp_kernel<true>, pgrid, 256, WP_LDS, g);
+        else AV_LAUNCH(gemm_bf16_wp_kernel<false>, pgrid, 256, WP_LDS, g);
+        break;
+    case AVLLM_GEMM_DP: AV_TRY(av_gemm_dp(d, st, g.dbg, dev, ncu)); break;      // launches without a check of its own: the AV_LAUNCH_CHECK below is its launch check
+    case AVLLM_GEMM_F32: {
+        GemmArgsF f;
+        f.A = (const float*)d->A; f.B = (const float*)d->B; f.A2 = (const float*)d->A2; f.B2 = (const float*)d->B2;
+        f.lda = d->lda; f.ldb = d->ldb; f.lda2 = d->lda2; f.ldb2 = d->ldb2; f.K = d->K; f.K2 = d->K2; f.e = e;
+        AV_LAUNCH(gemm_f32_kernel, av_cdiv(d->M, FM) * av_cdiv(d->N, FN), 256, 0, f); break;
+    }
+    }
+    g_lds_raised[dev][kernel] = true;             // every hipFuncSetAttribute above succeeded, or AV_HIP has returned
     if (prof) av_prof_after(st, 2.0 * d->M * (double)d->N * (double)(d->K + d->K2));
     AV_LAUNCH_CHECK();
     return AV_OK;

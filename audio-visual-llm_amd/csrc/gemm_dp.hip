@@ -306,9 +306,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_dp_kernel(DpArgs g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // in-flight DMA writes must not outlive the workgroup's LDS allocation
 }
 
-struct DpDevState { int ncu = 0; bool attr = false; };
-DpDevState g_dp_dev[64];
-
 }  // namespace
 
 // The calls this kernel takes: what gemm.hip calls the lean epilogue (bf16, alpha = 1, no dropout / row remap / broadcast residual, 16-byte aligned
@@ -321,23 +318,21 @@ bool av_gemm_dp_ok(const avllm_gemm_desc* d) {
     return ldA * 2 < (1l << 24) && ldB * 2 < (1l << 24);             // __umul24 row offsets
 }
 
-int av_gemm_dp(const avllm_gemm_desc* d, hipStream_t st, int dbg) {
-    AV_CHECK_ARG(av_gemm_dp_ok(d), "gemm (two-workgroup kernel): call outside its lean form");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    DpDevState* s = &g_dp_dev[dev & 63];
-    if (!s->ncu && hipDeviceGetAttribute(&s->ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) s->ncu = 256;
-    if (!s->attr) {
+// Called by av_gemm alone, for a call av_gemm_plan gave to this kernel (so av_gemm_dp_ok holds), with the current device and its CU count;
+// av_gemm checks the launch.
+int av_gemm_dp(const avllm_gemm_desc* d, hipStream_t st, int dbg, int dev, int ncu) {
+    static bool raised[AV_MAX_DEVICES];
+    if (!raised[dev]) {
         AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_dp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DLDS));
         AV_HIP(hipFuncSetAttribute((const void*)gemm_bf16_dp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DLDS));
-        s->attr = true;
+        raised[dev] = true;
     }
     DpArgs g;
     g.A = (const bf16*)d->A; g.B = (const bf16*)d->B; g.A2 = (const bf16*)d->A2; g.B2 = (const bf16*)d->B2;
     g.lda = d->lda; g.ldb = d->ldb; g.lda2 = d->lda2; g.ldb2 = d->ldb2; g.K = d->K; g.K2 = d->K2; g.M = d->M; g.N = d->N;
     g.C = (bf16*)d->C; g.ldc = d->ldc; g.bias = (const bf16*)d->bias; g.R = (const bf16*)d->R; g.ldr = d->ldr; g.act = d->act; g.dbg = dbg;
     const int per_cu = (dbg & 0x80) ? 1 : 2;                         // experiment: one workgroup per CU
-    const int ntiles = av_cdiv(d->M, DTM) * av_cdiv(d->N, DTN), grid = ntiles < per_cu * s->ncu ? ntiles : per_cu * s->ncu;
+    const int ntiles = av_cdiv(d->M, DTM) * av_cdiv(d->N, DTN), grid = ntiles < per_cu * ncu ? ntiles : per_cu * ncu;
     if (d->K2 > 0) hipLaunchKernelGGL(gemm_bf16_dp_kernel<true>, dim3(grid), dim3(256), DLDS, st, g);
     else hipLaunchKernelGGL(gemm_bf16_dp_kernel<false>, dim3(grid), dim3(256), DLDS, st, g);
     return AV_OK;

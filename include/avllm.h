@@ -59,17 +59,26 @@ typedef struct avllm_gemm_desc {
     const uint32_t* seed_dev;           /* optional DEVICE word added to drop_seed / a_drop_seed at run time (see avllm_step_state) */
 } avllm_gemm_desc;
 int avllm_gemm(const avllm_gemm_desc* d, void* stream);
-/* A/B testing only: force one bf16 tiling (0 = automatic choice; same values as env AVLLM_GEMM_VARIANT): 1 = 128x128, 2 = 256x128 ring, 5 / 6 = 256x256
- * with 16 waves (one-shot / persistent), 7 / 8 = 256x256 with 4 waves (one-shot / persistent: the default for every lean-epilogue call on a chip-filling
- * grid), 9 = 256x128 persistent with two workgroups per CU (csrc/gemm_dp.hip).  A variant that cannot take a call leaves it to the automatic choice. */
+/* Which kernel avllm_gemm runs for a call: *kernel = one of the ids below, or the error avllm_gemm itself would return.  Pure host code (no
+ * device needed, no operand read: pointers count for their alignment only); the descriptor and the knobs "GEMM_VARIANT" / "NARROW_EPILOGUE"
+ * decide.  DESIGN.md "Which GEMM kernel a call gets" lists the conditions. */
+enum { AVLLM_GEMM_SMALLM, AVLLM_GEMM_SKINNY64, AVLLM_GEMM_128, AVLLM_GEMM_RING, AVLLM_GEMM_H16, AVLLM_GEMM_HP16, AVLLM_GEMM_W4, AVLLM_GEMM_WP4,
+       AVLLM_GEMM_DP, AVLLM_GEMM_F32, AVLLM_GEMM_KERNELS };
+int avllm_gemm_plan(const avllm_gemm_desc* d, int32_t* kernel);
+/* A/B testing only: avllm_set_knob("GEMM_VARIANT", v).  Forces one bf16 tiling (<= 0 = automatic choice): 1 = 128x128, 2 = 256x128 ring, 5 / 6 =
+ * 256x256 with 16 waves (one-shot / persistent), 7 / 8 = 256x256 with 4 waves (one-shot / persistent: the default for every lean-epilogue call on a
+ * chip-filling grid), 9 = 256x128 persistent with two workgroups per CU (csrc/gemm_dp.hip).  Any forced variant switches the M <= 16 kernel off; the
+ * N == 64 rank-side kernel and the fp32 kernel keep their calls.  A call the forced variant cannot take (M <= 128; 7 / 8 / 9: K + K2 < 128; 8 / 9: an
+ * epilogue that is not lean) runs on the 128x128 kernel, not on the automatic choice; 5 on operands of 2^32 elements or more is an error. */
 int avllm_set_gemm_variant(int v);
 /* A/B testing only: the library's experiment switches live in ONE table that is filled once per process from the environment
  * (AVLLM_<NAME>) and changed afterwards only through this call.  Names: "DECODE_FUSED" (0 = general 10-launch decode layer),
  * "DEC_AL" (force an activation-load form of avllm_dec_proj: 2 | 4), "LORA_UNBATCHED" (1 = one launch per adapter), "F8_UNFUSED_QUANT"
  * (1 = separate quantiser passes), "F8_FAST" (0 = reference-grade fp8 GEMM), "ATTN_SHORT" (0 = general attention kernel for T <= 272),
- * "NARROW_EPILOGUE", "TN_CHUNK", "GEMM_GW" (tile-column group width of the persistent GEMM's walk on tall shapes: 0 = row-major walk,
+ * "NARROW_EPILOGUE", "TN_CHUNK", "GEMM_VARIANT" (avllm_set_gemm_variant above), "GEMM_GW" (tile-column group width of the persistent GEMM's walk on tall shapes: 0 = row-major walk,
  * n = groups of n columns), "GEMM_DBG" (only read by builds made with -DAVLLM_EXPERIMENT_KNOBS).  Unknown name -> error. */
 int avllm_set_knob(const char* name, int32_t value);
+int avllm_get_knob(const char* name, int32_t* value);      /* the value in force (to put it back after an A/B block) */
 
 /* out[I,J] (f32, row stride ldo) += alpha * sum_m P[m,i]*Q[m,j]; LoRA dA/dB (autograd of peft lora.Linear) */
 int avllm_gemm_tn(const void* P, int64_t ldp, int32_t I, const void* Q, int64_t ldq, int32_t J, int32_t M,

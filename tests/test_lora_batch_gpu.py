@@ -97,15 +97,14 @@ def test_batched_and_unbatched_steps_agree(dev, monkeypatch):
     res = {}
     from avllm import lib as Lk
     for mode in ("batched", "unbatched"):
-        Lk.check(Lk.load().avllm_set_knob(b"LORA_UNBATCHED", 1 if mode == "unbatched" else 0))
-        m = ClipWhisperModel(device=dev, max_seq_len=64, config=cfg, precision="bf16", seed=3, synthetic_weights=True, lora_dropout=0.1).train()
-        eng = m.llm_engine
-        eng.lora_p.normal_(0, 0.02, generator=g.manual_seed(9))
-        eng.pack_lora()
-        out = m(audio=audio, video=video, labels=labels)
-        out["loss"].backward()
-        res[mode] = (float(out["loss"].detach()), eng.lora_g.clone())
-    Lk.check(Lk.load().avllm_set_knob(b"LORA_UNBATCHED", 0))
+        with Lk.knob("LORA_UNBATCHED", 1 if mode == "unbatched" else 0):
+            m = ClipWhisperModel(device=dev, max_seq_len=64, config=cfg, precision="bf16", seed=3, synthetic_weights=True, lora_dropout=0.1).train()
+            eng = m.llm_engine
+            eng.lora_p.normal_(0, 0.02, generator=g.manual_seed(9))
+            eng.pack_lora()
+            out = m(audio=audio, video=video, labels=labels)
+            out["loss"].backward()
+            res[mode] = (float(out["loss"].detach()), eng.lora_g.clone())
     # the loss is a float atomicAdd over ~80 rows (sum ~ 480, fp32 ulp 3e-5): the order of the adds moves the mean by a few 1e-7 from launch to launch
     assert abs(res["batched"][0] - res["unbatched"][0]) < 1e-5
     assert rel_l2(res["batched"][1], res["unbatched"][1]) < 1e-4

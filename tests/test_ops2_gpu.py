@@ -184,17 +184,13 @@ def test_attention_grouped_query(dev, dtype, impl, B, T, H, Hkv, hd):
 def test_every_gemm_tiling_agrees(dev, variant):
     """All bf16 tilings compiled into the library (A/B variants included) compute the same epilogue-fused GEMM."""
     from avllm import lib as L
-    lib = L.load()
     M, N, K, K2 = 700, 520, 256, 64
     A, B = rnd(M, K, dtype=torch.bfloat16, seed=41), rnd(N, K, dtype=torch.bfloat16, seed=42)
     A2, B2 = rnd(M, K2, dtype=torch.bfloat16, seed=43), rnd(N, K2, dtype=torch.bfloat16, seed=44)
     bias, R = rnd(N, dtype=torch.bfloat16, seed=45), rnd(M, N, dtype=torch.bfloat16, seed=46)
     ref = torch.nn.functional.gelu(A.float() @ B.float().t() + A2.float() @ B2.float().t() + bias.float()) + R.float()
-    try:
-        lib.avllm_set_gemm_variant(variant)
+    with L.knob("GEMM_VARIANT", variant):
         out = ops.gemm(A, B, bias=bias, R=R, A2=A2, B2=B2, act=L.ACT_GELU)
-    finally:
-        lib.avllm_set_gemm_variant(0)
     close(out, ref, 0.3, 2e-2, f"gemm variant {variant}")
 
 
@@ -203,9 +199,7 @@ def test_gemm_4wave_kernel_ksteps_edges_epilogues(dev, K, K2):
     """The 4-wave 256x256 kernel (in-place LDS refill, two K-steps of prefetch): even and odd K-step counts, the minimum of two, a LoRA
     segment of one and two K-steps, M and N edges inside a tile, both epilogues, in-place residual, f32 output, row remap."""
     from avllm import lib as L
-    lib = L.load()
-    try:
-        lib.avllm_set_gemm_variant(7)
+    with L.knob("GEMM_VARIANT", 7):
         for M, N in ((900, 520), (257, 516), (512, 256)):           # ragged edges / narrow epilogue (N % 8 != 0) / exact tiles
             A, B = rnd(M, K, dtype=torch.bfloat16, seed=71), rnd(N, K, dtype=torch.bfloat16, seed=72)
             A2 = rnd(M, K2, dtype=torch.bfloat16, seed=73) if K2 else None
@@ -223,25 +217,19 @@ def test_gemm_4wave_kernel_ksteps_edges_epilogues(dev, K, K2):
         ops.gemm(A, B, out=out, R=pos, r_mod=9, remap=(9, 10, 1), M=900)
         close(out.view(100, 10, 256)[:, 1:], (A.float() @ B.float().t()).view(100, 9, 256) + pos.float(), 0.02 * math.sqrt(K), 2e-2, "4-wave remap")
         assert out.view(100, 10, 256)[:, 0].abs().max().item() == 0
-    finally:
-        lib.avllm_set_gemm_variant(0)
 
 
 def test_gemm_auto_dispatch_long_k_matches_16wave(dev):
     """K >= 4096 with a chip-filling grid goes to the 4-wave kernel by itself; the 16-wave kernel must give the same numbers (same
     MFMA, same K order inside a K-step; accumulation order across the two k-halves is identical too -> bit-equal bf16 outputs)."""
     from avllm import lib as L
-    lib = L.load()
     M, N, K, K2 = 4096, 4096, 4096, 64
     A, B = rnd(M, K, dtype=torch.bfloat16, seed=81), rnd(N, K, dtype=torch.bfloat16, seed=82, scale=K ** -0.5)
     A2, B2 = rnd(M, K2, dtype=torch.bfloat16, seed=83), rnd(N, K2, dtype=torch.bfloat16, seed=84, scale=0.1)
     R = rnd(M, N, dtype=torch.bfloat16, seed=85)
     auto = ops.gemm(A, B, R=R, A2=A2, B2=B2)
-    try:
-        lib.avllm_set_gemm_variant(5)
+    with L.knob("GEMM_VARIANT", 5):
         ref16 = ops.gemm(A, B, R=R, A2=A2, B2=B2)
-    finally:
-        lib.avllm_set_gemm_variant(0)
     assert torch.equal(auto, ref16)
     rows = torch.randperm(M, device=dev)[:64]
     ref = A[rows].float() @ B.float().t() + A2[rows].float() @ B2.float().t() + R[rows].float()
@@ -254,7 +242,6 @@ def test_gemm_persistent_kernel_many_tiles(dev, K, K2, act):
     boundaries, odd and even K-step counts so the buffer parity flips between tiles), ragged M / N edges, bias + in-place residual +
     activation: bit-equal to the 16-wave kernel (same MFMA order, same single rounding) and within bf16 tolerance of fp32 torch."""
     from avllm import lib as L
-    lib = L.load()
     M, N = 4300, 4360                                              # 17 x 18 = 306 tiles on 256 CUs
     A, B = rnd(M, K, dtype=torch.bfloat16, seed=91), rnd(N, K, dtype=torch.bfloat16, seed=92, scale=K ** -0.5)
     A2 = rnd(M, K2, dtype=torch.bfloat16, seed=93) if K2 else None
@@ -262,14 +249,11 @@ def test_gemm_persistent_kernel_many_tiles(dev, K, K2, act):
     bias, x = rnd(N, dtype=torch.bfloat16, seed=95), rnd(M, N, dtype=torch.bfloat16, seed=96)
     code = {"none": L.ACT_NONE, "gelu": L.ACT_GELU, "quick_gelu": L.ACT_QUICK_GELU}[act]
     outs = {}
-    try:
-        for variant in (8, 5):
-            lib.avllm_set_gemm_variant(variant)
+    for variant in (8, 5):
+        with L.knob("GEMM_VARIANT", variant):
             o = x.clone()
             ops.gemm(A, B, out=o, bias=bias, R=o, A2=A2, B2=B2, act=code)
             outs[variant] = o
-    finally:
-        lib.avllm_set_gemm_variant(0)
     assert torch.equal(outs[8], outs[5])
     rows = torch.cat([torch.randperm(M, device=dev)[:48], torch.tensor([0, 255, 256, M - 1], device=dev)])
     acc = A[rows].float() @ B.float().t() + (A2[rows].float() @ B2.float().t() if K2 else 0.0) + bias.float()
@@ -286,7 +270,6 @@ def test_gemm_two_workgroup_kernel_many_tiles(dev, M, N, K, K2, act, resid):
     and two macro steps, ragged M / N edges and tiles smaller than a workgroup's, every lean epilogue form (plain, bias, bias + activation,
     in-place residual with and without bias): bit-equal to the 16-wave kernel (same MFMA, same k order per accumulator, one rounding)."""
     from avllm import lib as L
-    lib = L.load()
     A, B = rnd(M, K, dtype=torch.bfloat16, seed=191), rnd(N, K, dtype=torch.bfloat16, seed=192, scale=K ** -0.5)
     A2 = rnd(M, K2, dtype=torch.bfloat16, seed=193) if K2 else None
     B2 = rnd(N, K2, dtype=torch.bfloat16, seed=194, scale=0.1) if K2 else None
@@ -294,14 +277,11 @@ def test_gemm_two_workgroup_kernel_many_tiles(dev, M, N, K, K2, act, resid):
     code = {"none": L.ACT_NONE, "gelu": L.ACT_GELU, "quick_gelu": L.ACT_QUICK_GELU}[act]
     for bias in ((rnd(N, dtype=torch.bfloat16, seed=195), None) if act == "none" else (rnd(N, dtype=torch.bfloat16, seed=195),)):
         outs = {}
-        try:
-            for variant in (9, 5):
-                lib.avllm_set_gemm_variant(variant)
+        for variant in (9, 5):
+            with L.knob("GEMM_VARIANT", variant):
                 o = x.clone()
                 ops.gemm(A, B, out=o, bias=bias, R=o if resid else None, A2=A2, B2=B2, act=code)
                 outs[variant] = o
-        finally:
-            lib.avllm_set_gemm_variant(0)
         nd = int((outs[9] != outs[5]).sum())
         assert nd == 0, f"{nd} of {M * N} values differ (bias={bias is not None}); first at {(outs[9] != outs[5]).nonzero()[:4].tolist()}"
     rows = torch.cat([torch.randperm(M, device=dev)[:48], torch.tensor([0, min(255, M - 1), min(256, M - 1), M - 1], device=dev)])
@@ -333,9 +313,7 @@ def test_gemm_16wave_narrow_and_wide_epilogues(dev):
     """The 256x256 kernel's two epilogues: N % 8 != 0 or unaligned pointers take the per-lane path, everything else the
     LDS-staged 16-byte path; both with row remap / broadcast residual / in-place residual / f32 output."""
     from avllm import lib as L
-    lib = L.load()
-    try:
-        lib.avllm_set_gemm_variant(5)
+    with L.knob("GEMM_VARIANT", 5):
         M, K = 900, 128
         for N in (516, 520):                                   # narrow, wide
             A, B = rnd(M, K, dtype=torch.bfloat16, seed=61), rnd(N, K, dtype=torch.bfloat16, seed=62)
@@ -356,8 +334,6 @@ def test_gemm_16wave_narrow_and_wide_epilogues(dev):
         ref = (A.float() @ B.float().t()).view(100, 9, N) + pos.float()
         close(out.view(100, 10, N)[:, 1:], ref, 0.1, 2e-2, "remap + broadcast residual (wide)")
         assert out.view(100, 10, N)[:, 0].abs().max().item() == 0
-    finally:
-        lib.avllm_set_gemm_variant(0)
 
 
 @pytest.mark.parametrize("T", [1, 10, 16, 17, 50, 197, 208, 209, 257, 272])

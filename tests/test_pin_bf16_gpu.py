@@ -269,12 +269,8 @@ def test_g3_bench_shape_bf16_with_lora_dropout(dev, llama7b_layer):
     # (p = 0.05: the two masks differ on ~2p of the elements -> relative error ~ sqrt(2p/(1-p)) = 0.32, three times the bar)
     assert rel_l2(grads["layers.0.o_proj.lora_A"], og2["layers.0.o_proj.lora_A"]) > 2.5 * Bar.BF16_GRAD_TENSOR_REL_L2
     # the same step through the 16-wave tiling (every projection) against the automatic choice (persistent 4-wave)
-    lib = L.load()
-    try:
-        lib.avllm_set_gemm_variant(5)
+    with L.knob("GEMM_VARIANT", 5):
         loss5, logits5, grads5 = _engine_step(eng, x.to(dev), labels.to(dev), dropout=p, seed=4242)
-    finally:
-        lib.avllm_set_gemm_variant(0)
     assert abs(loss5 - loss) < 2e-3, (loss5, loss)
     assert rel_l2(logits5, logits) < 5e-3, rel_l2(logits5, logits)
     assert rel_l2(torch.cat([grads5[k].flatten() for k in keys]), torch.cat([grads[k].flatten() for k in keys])) < 1e-2

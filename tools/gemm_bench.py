@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""GEMM micro-benchmark on the shapes of the hot path (random bf16 data).  AVLLM_GEMM_VARIANT=1 forces the 128x128 kernel."""
+"""GEMM micro-benchmark on the shapes of the hot path (random bf16 data).  Each line names the kernel the call got; AVLLM_GEMM_VARIANT=1 in the
+environment (knob GEMM_VARIANT, include/avllm.h) forces the 128x128 kernel."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "audio-visual-llm_amd"))
@@ -48,7 +49,8 @@ def main():
             e1.record(); torch.cuda.synchronize()
             ms2 = e0.elapsed_time(e1) / n
             extra = f"   | hipBLASLt {ms2*1000:9.1f} us {2*M*N*K/ms2/1e9:8.1f} TF/s"
-        print(f"{tag:18s} M={M:6d} N={N:5d} K={K:5d}  {ms*1000:9.1f} us  {2*M*N*K/ms/1e9:8.1f} TF/s{extra}", flush=True)
+        kernel = ops.gemm(A, B, out=out, bias=bias, act=act, R=R, plan=True)
+        print(f"{tag:18s} M={M:6d} N={N:5d} K={K:5d}  {kernel:6s} {ms*1000:9.1f} us  {2*M*N*K/ms/1e9:8.1f} TF/s{extra}", flush=True)
 
 if __name__ == "__main__":
     main()

@@ -8,15 +8,13 @@ import torch
 from avllm import ops, lib as L
 
 def run(M, N, K, tag):
-    lib = L.load()
     A = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
     B = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * K ** -0.5
     out = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     line = f"{tag:12s} M={M} N={N} K={K}:"
     for name, variant, dbg in (("v8", 8, 0), ("v8 row0", 8, 0x10000), ("v8 tile0", 8, 0x40000), ("v9", 9, 0), ("v9 row0", 9, 0x40), ("v9 tile0", 9, 0x800)):
-        lib.avllm_set_gemm_variant(variant)
-        with L.knob("GEMM_DBG", dbg):
+        with L.knob("GEMM_VARIANT", variant), L.knob("GEMM_DBG", dbg):
             best = 1e9
             for rep in range(3):
                 ops.gemm(A, B, out=out)
@@ -26,7 +24,6 @@ def run(M, N, K, tag):
                 e1.record(); torch.cuda.synchronize()
                 best = min(best, e0.elapsed_time(e1) / 6)
         line += f"  {name} {best * 1000:.0f} us ({2.0 * M * N * K / best / 1e12:.2f} PF/s)"
-    lib.avllm_set_gemm_variant(0)
     print(line, flush=True)
 
 run(394000, 2304, 768, "clip qkv")

@@ -7,7 +7,6 @@ sys.path.insert(0, os.path.join(ROOT, "audio-visual-llm_amd"))
 import torch
 from avllm import ops, lib as L
 
-lib = L.load()
 SHAPES = [(394000, 2304, 768, "clip qkv (bias)", 0, 0), (394000, 3072, 768, "clip fc1 + quick-GELU", L.ACT_QUICK_GELU, 0), ]
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 for M, N, K, tag, act, resid in SHAPES:
@@ -16,9 +15,8 @@ for M, N, K, tag, act, resid in SHAPES:
     out = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
     bias = torch.randn(N, device="cuda", dtype=torch.bfloat16) if "llama" not in tag else None
     line = f"{tag:24s}"
-    lib.avllm_set_gemm_variant(8)
     for name, dbg in [("as shipped", 0), ("no epilogue", 1), ("epilogue arithmetic, one store", 7 << 20), ("as shipped again", 0), ("row0", 0x10000), ("row0, arithmetic, one store", 0x10000 | (7 << 20)), ("row0 no epilogue", 0x10001)]:
-        with L.knob("GEMM_DBG", dbg):
+        with L.knob("GEMM_VARIANT", 8), L.knob("GEMM_DBG", dbg):
             best = 1e9
             for rep in range(3):
                 ops.gemm(A, B, out=out, bias=bias, act=act, R=out if resid else None)
@@ -28,5 +26,4 @@ for M, N, K, tag, act, resid in SHAPES:
                 e1.record(); torch.cuda.synchronize()
                 best = min(best, e0.elapsed_time(e1) / 5)
         line += f"  {name} {best * 1000:.0f} us ({2.0 * M * N * K / best / 1e12:.2f})"
-    lib.avllm_set_gemm_variant(0)
     print(line, flush=True)

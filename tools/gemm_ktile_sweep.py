@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-tile fixed cost of the 256x256 GEMM kernels: time the CLIP qkv shape (M=394000, N=2304) at K = 128..1536 and fit
-t = tiles/256 * (fixed + K/64 * per_kstep).  AVLLM_GEMM_VARIANT picks the kernel (5 = 16 waves, 7 = 4 waves)."""
+t = tiles/256 * (fixed + K/64 * per_kstep).  AVLLM_GEMM_VARIANT in the environment (knob GEMM_VARIANT) picks the kernel (5 = 16 waves, 7 = 4 waves)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "audio-visual-llm_amd"))

@@ -8,23 +8,21 @@ import torch
 from avllm import ops, lib as L
 
 def run(M, N, K, tag, variant):
-    lib = L.load()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     out = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
     line = f"v{variant} {tag:12s} M={M} N={N} K={K}:"
     for pad in [int(p) for p in os.environ.get("PADS", "0,64,128,192,320,1088").split(",")]:
         A = torch.randn(M, K + pad, device="cuda", dtype=torch.bfloat16)[:, :K]
         B = (torch.randn(N, K + pad, device="cuda", dtype=torch.bfloat16) * K ** -0.5)[:, :K]
-        lib.avllm_set_gemm_variant(variant)
         best = 1e9
-        for rep in range(3):
-            ops.gemm(A, B, out=out)
-            e0.record()
-            for _ in range(6):
+        with L.knob("GEMM_VARIANT", variant):
+            for rep in range(3):
                 ops.gemm(A, B, out=out)
-            e1.record(); torch.cuda.synchronize()
-            best = min(best, e0.elapsed_time(e1) / 6)
-        lib.avllm_set_gemm_variant(0)
+                e0.record()
+                for _ in range(6):
+                    ops.gemm(A, B, out=out)
+                e1.record(); torch.cuda.synchronize()
+                best = min(best, e0.elapsed_time(e1) / 6)
         line += f"  pad {pad}: {best * 1000:.0f} us ({2.0 * M * N * K / best / 1e12:.2f} PF/s)"
         del A, B
     print(line, flush=True)

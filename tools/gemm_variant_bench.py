@@ -19,7 +19,6 @@ SHAPES = [  # (M, N, K, K2, epilogue, tag)
 
 def main():
     dev = "cuda"
-    lib = L.load()
     variants = [int(v) for v in os.environ.get("VARIANTS", "8,9").split(",")]
     only = os.environ.get("ONLY")
     for M, N, K, K2, epi, tag in SHAPES:
@@ -36,18 +35,15 @@ def main():
         n = 16 if M < 100000 else 6
         res = {v: [] for v in variants}
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        try:
-            for rep in range(3):
-                for v in variants:
-                    lib.avllm_set_gemm_variant(v)
+        for rep in range(3):
+            for v in variants:
+                with L.knob("GEMM_VARIANT", v):
                     ops.gemm(A, B, out=out, bias=bias, act=act, R=R, A2=A2, B2=B2)
                     e0.record()
                     for _ in range(n):
                         ops.gemm(A, B, out=out, bias=bias, act=act, R=R, A2=A2, B2=B2)
                     e1.record(); torch.cuda.synchronize()
                     res[v].append(e0.elapsed_time(e1) / n)
-        finally:
-            lib.avllm_set_gemm_variant(0)
         fl = 2.0 * M * N * (K + K2)
         line = f"{tag:24s} M={M:6d} N={N:5d} K={K:5d}+{K2:2d}"
         for v in variants:
