@@ -126,6 +126,8 @@ _SIGS = {
     "avllm_sample_rows": ([vp, i64, i64, i32, f32, i32, f32, C.c_uint32, vp, i32, vp, vp, i64, i64, vp, i32, vp], i32),
     "avllm_beam_topk_workspace_bytes": ([i64, i32, i32], sz),
     "avllm_beam_topk": ([vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp], i32),
+    "avllm_beam_topk_logprobs": ([vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp], i32),
+    "avllm_logits_process": ([vp, i64, i64, i32, vp, i64, vp, i32, vp, f32, i32, i32, i64, i32, i32, vp], i32),
     "avllm_kv_gather_rows": ([vp, vp, i32, i64, vp, vp, i32, i64, i32, i32, vp, i32, i32, i32, vp], i32),
     "avllm_embedding": ([vp, vp, vp, i64, i32, i32, vp], i32),
     "avllm_cast": ([vp, i32, vp, i32, i64, vp], i32),

@@ -359,13 +359,17 @@ class ClipWhisperModel:
     @torch.no_grad()
     def generate(self, audio=None, video=None, prompt=None, pixel_values=None, max_new_tokens=100, do_sample=False,
                  temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False,
-                 return_sequence_scores=False):
+                 return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
         """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search, or with do_sample=True its sampling: temperature -> top_k
         (HF's GenerationConfig default 50; 0 = off) -> top_p -> one draw per row on the device (ops.sample_rows).  seed=None draws the
         seed from torch's default CPU generator, so torch.manual_seed makes a sampled run repeat; row b draws with seed + b.
         With do_sample=False, temperature / top_k / top_p are ignored.  Returns NEW tokens only [B, <=max_new_tokens].
         num_beams > 1: HF's beam search (see _beam_search; length_penalty, early_stopping in {True, False, "never"} as in HF); returns the
-        best hypothesis per item, padded with pad_token_id, and with return_sequence_scores=True also HF's sequences_scores [B]."""
+        best hypothesis per item, padded with pad_token_id, and with return_sequence_scores=True also HF's sequences_scores [B].
+        repetition_penalty (> 0, 1.0 = off), no_repeat_ngram_size (0 = off) and min_new_tokens are HF's logits processors of those names, in
+        every mode, applied on the device (ops.logits_process) to a row's generated tokens, which is all HF's processors see with
+        inputs_embeds: on the logits before the argmax or the sampling chain, and in beam search on the log-probabilities (log-softmax
+        first, as HF's _beam_search does).  With the three defaults nothing is launched."""
         if video is None and pixel_values is not None:
             video = pixel_values
         if max_new_tokens is None:
@@ -385,6 +389,12 @@ class ClipWhisperModel:
             ops.check_sampling(temperature, top_k, top_p)
             if seed is None:
                 seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        proc = None
+        if ops.check_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens):
+            if max_new_tokens > ops.LOGITS_PROCESS_MAX_HISTORY:
+                raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_new_tokens support at most {ops.LOGITS_PROCESS_MAX_HISTORY} "
+                                 f"new tokens, got max_new_tokens = {max_new_tokens}")
+            proc = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens))
         original = self.modality
         if audio is not None and video is not None:
             self.modality = "both"
@@ -397,7 +407,7 @@ class ClipWhisperModel:
         finally:
             self.modality = original
         if num_beams > 1:
-            return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores)
+            return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores, proc)
         eng = self.llm_engine
         B, S, _ = x.shape
         kc, vc = eng.alloc_cache(B, S + max_new_tokens)
@@ -406,7 +416,12 @@ class ClipWhisperModel:
         unfinished = torch.ones(B, dtype=torch.bool, device=x.device)
         out = []
         row_seeds = torch.arange(B, dtype=torch.int32, device=x.device) if do_sample else None
+        # the processors' history: row b's generated tokens (pad after its EOS, as HF feeds them); the kernel itself appends the last token
+        hist = torch.full((B, max_new_tokens), pad, dtype=torch.int64, device=x.device) if proc else None
+        nxt = None
         for step in range(max_new_tokens):
+            if proc:
+                ops.logits_process(logits, hist, step, *proc, eos=eos, append=nxt)
             if do_sample:
                 nxt = ops.sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=unfinished if eos is not None else None,
                                       eos=eos, pad=pad, row_seeds=row_seeds)
@@ -421,7 +436,7 @@ class ClipWhisperModel:
             logits = eng.decode_step(nxt, S + step, kc, vc)
         return torch.stack(out, dim=1)
 
-    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores):
+    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores, proc=None):
         """GenerationMixin._beam_search (transformers 5.x, generation/utils.py) for inputs_embeds x [B, S, d]: decoder_prompt_len = 0, so a
         hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
         the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
@@ -429,7 +444,10 @@ class ClipWhisperModel:
         _beam_search_has_unfinished_sequences) restated on small device tensors, and ops.kv_gather_rows reordering only the generated
         positions [S, S + step): every beam of an item shares the prefix [0, S), which is copied once from the B-row prefill cache.
         Equal scores keep candidate order (stable sorts where HF calls torch.topk).  One host sync per step, for the stopping test.
-        B*nb <= 16 rows take the fused bf16 token step (LlamaEngine.decode_is_fused); more rows take the general step."""
+        B*nb <= 16 rows take the fused bf16 token step (LlamaEngine.decode_is_fused); more rows take the general step.
+        proc = (repetition_penalty, no_repeat_ngram_size, min_new_tokens): HF runs its logits processors between the log_softmax and the
+        addition of the running beam scores, on running_sequences[:, :, :cur]; ops.logits_process(log_softmax=True) does both on the
+        B*nb rows and beam_topk then takes the rows as log-probabilities."""
         eng = self.llm_engine
         dev = x.device
         B, S, _ = x.shape
@@ -456,7 +474,9 @@ class ClipWhisperModel:
         ev = torch.cuda.Event()
         for cur in range(N):
             # _get_top_k_continuations
-            topk_lp, topk_beam, topk_tok = ops.beam_topk(logits, running_scores.view(-1), nb, k)
+            if proc:
+                ops.logits_process(logits, running_seq.view(R, N), cur, *proc, eos=eos, log_softmax=True)
+            topk_lp, topk_beam, topk_tok = ops.beam_topk(logits, running_scores.view(-1), nb, k, logprobs=bool(proc))
             topk_seq = torch.gather(running_seq, 1, topk_beam.long()[:, :, None].expand(B, k, N)).clone()
             topk_seq[:, :, cur] = topk_tok
             topk_parent = topk_beam + offset

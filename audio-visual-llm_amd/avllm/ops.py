@@ -3,6 +3,7 @@ all arithmetic happens in libavllm.so on the current torch stream."""
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 
 import torch
 
@@ -209,13 +210,59 @@ def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, 
     return out
 
 
+LOGITS_PROCESS_MAX_HISTORY = 1024
+
+
+def check_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens):
+    """The argument rules of HF's RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor / MinNewTokensLengthLogitsProcessor
+    (no_repeat_ngram_size = 0 turns the n-gram ban off, as in GenerationConfig).  Returns True when any of the three is on."""
+    p = repetition_penalty
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not (0.0 < float(p) < float("inf")):
+        raise ValueError(f"repetition_penalty must be a strictly positive float, got {p!r}")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+    return float(p) != 1.0 or no_repeat_ngram_size > 0 or min_new_tokens > 0
+
+
+def logits_process(scores, history, cur, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos=None, log_softmax=False,
+                   append=None):
+    """HF's repetition-penalty, no-repeat-n-gram and min-new-tokens processors, in that order, IN PLACE on scores [rows, V] (f32 or bf16,
+    row stride free) before argmax_rows / sample_rows / beam_topk(logprobs=True) (csrc/logits_process.hip).  history: int64 [rows, ld] on
+    the device, row r's first `cur` entries are its generated tokens; cur: int, or an int32 device tensor of one element (read by the
+    kernel; then ld <= LOGITS_PROCESS_MAX_HISTORY).  eos: the model's EOS id or None (min_new_tokens then does nothing).  log_softmax (f32
+    only): the row is first replaced by its log-softmax: HF's beam search runs the processors on log-probabilities.  append: optional int64
+    [rows], stored at history[:, cur-1] before the history is read.  Returns scores."""
+    check_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+    if scores.dim() != 2 or not scores.is_cuda or scores.stride(1) != 1:
+        raise ValueError("logits_process: scores must be a 2-d device tensor with unit column stride")
+    rows, V = scores.shape
+    cur_dev = None
+    if torch.is_tensor(cur):
+        assert cur.dtype == torch.int32 and cur.numel() == 1 and cur.is_cuda
+        cur_dev, cur = cur, 0
+    if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or not history.is_cuda or \
+            (history.shape[1] > 1 and history.stride(1) != 1):
+        raise ValueError(f"logits_process: history must be an int64 device tensor [{rows}, ld] with unit column stride")
+    if append is not None:
+        assert append.dtype == torch.int64 and append.shape == (rows,) and append.is_contiguous() and append.is_cuda
+    ldh = history.stride(0) if rows > 1 and history.shape[1] > 0 else history.shape[1]
+    if cur_dev is None and int(cur) > history.shape[1]:
+        raise ValueError(f"logits_process: history length {cur} > the {history.shape[1]} columns of history")
+    L.check(L.load().avllm_logits_process(L.ptr(scores), _ld(scores), rows, V, L.ptr(history) if history.numel() else None, ldh, L.ptr(append),
+                                          int(cur), L.ptr(cur_dev), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
+                                          -1 if eos is None else int(eos), int(bool(log_softmax)), L.dt_of(scores), L.stream_ptr()))
+    return scores
+
+
 BEAM_MAX_BEAMS, BEAM_MAX_K = 16, 32
 
 
-def beam_topk(logits, beam_scores, num_beams, k):
+def beam_topk(logits, beam_scores, num_beams, k, logprobs=False):
     """Beam-search candidates (csrc/beam.hip): for each batch item b, the k best of beam_scores[b*nb + j] + log_softmax(logits[b*nb + j])[v]
     over all nb*V pairs, sorted descending, equal scores by the lower flat index j*V + v first.  logits: f32 [B*nb, V] (row stride free);
-    beam_scores: f32 [B*nb].  Returns (scores f32 [B, k], beams int32 [B, k], tokens int64 [B, k])."""
+    beam_scores: f32 [B*nb].  logprobs=True: the rows are log-probabilities already (logits_process(..., log_softmax=True)) and are added
+    to beam_scores as they are.  Returns (scores f32 [B, k], beams int32 [B, k], tokens int64 [B, k])."""
     nb, k = int(num_beams), int(k)
     if not 1 <= nb <= BEAM_MAX_BEAMS:
         raise ValueError(f"num_beams must be in [1, {BEAM_MAX_BEAMS}], got {num_beams}")
@@ -237,8 +284,9 @@ def beam_topk(logits, beam_scores, num_beams, k):
     scores = torch.empty(B, k, device=logits.device, dtype=torch.float32)
     beams = torch.empty(B, k, device=logits.device, dtype=torch.int32)
     tokens = torch.empty(B, k, device=logits.device, dtype=torch.int64)
-    L.check(lib.avllm_beam_topk(L.ptr(logits), _ld(logits), B, nb, V, L.ptr(beam_scores), k, L.ptr(scores), L.ptr(beams), L.ptr(tokens),
-                                L.ptr(ws), ws.numel(), L.stream_ptr()))
+    fn = lib.avllm_beam_topk_logprobs if logprobs else lib.avllm_beam_topk
+    L.check(fn(L.ptr(logits), _ld(logits), B, nb, V, L.ptr(beam_scores), k, L.ptr(scores), L.ptr(beams), L.ptr(tokens), L.ptr(ws), ws.numel(),
+               L.stream_ptr()))
     return scores, beams, tokens
 
 

@@ -109,7 +109,17 @@ int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, f
 size_t avllm_beam_topk_workspace_bytes(int64_t rows, int32_t V, int32_t k) { return av_beam_topk_workspace_bytes(rows, V, k); }
 int avllm_beam_topk(const float* logits, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,
                     float* out_scores, int32_t* out_beams, int64_t* out_tokens, void* ws, size_t ws_bytes, void* stream) {
-    return av_beam_topk(logits, ld, B, num_beams, V, beam_scores, k, out_scores, out_beams, out_tokens, ws, ws_bytes, ST);
+    return av_beam_topk(logits, ld, B, num_beams, V, beam_scores, k, out_scores, out_beams, out_tokens, ws, ws_bytes, 0, ST);
+}
+int avllm_beam_topk_logprobs(const float* logprobs, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,
+                             float* out_scores, int32_t* out_beams, int64_t* out_tokens, void* ws, size_t ws_bytes, void* stream) {
+    return av_beam_topk(logprobs, ld, B, num_beams, V, beam_scores, k, out_scores, out_beams, out_tokens, ws, ws_bytes, 1, ST);
+}
+int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int64_t* history, int64_t ldh, const int64_t* append, int32_t cur,
+                         const int32_t* cur_dev, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens, int64_t eos,
+                         int32_t log_softmax, int32_t dtype, void* stream) {
+    return av_logits_process(scores, ld, rows, V, history, ldh, append, cur, cur_dev, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
+                             log_softmax, dtype, ST);
 }
 int avllm_kv_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
                          int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, int32_t dtype, void* stream) {

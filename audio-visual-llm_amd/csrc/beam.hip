@@ -9,6 +9,8 @@
 //            k largest logits (equal logits: lower index first);
 //   launch 2 (merge_kernel): one workgroup per batch item, one wave per beam: the wave folds its row's segments into M_r, Z_r and the row's top
 //            k, scores them, and wave 0 picks the item's top k of the nb*k scored candidates.
+// Rows that are log-probabilities already (logprobs: avllm_logits_process normalised them and applied HF's processors, which beam search runs on
+// log-probabilities) are scored as beam_scores[r] + x[r][v]; the selection is the same, and -inf entries order below every finite one.
 // Keys are 64-bit: an order-preserving uint32 image of the float above 0xffffffff - index, so one unsigned max picks the larger value and,
 // among equal values, the lower index.  A selection step is k rounds of a wave-wide max over keys held in registers (k <= 32, no LDS sort).
 //
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(SEG_NT) void seg_kernel(const float* __restrict__ l
 // grid B, nb waves.  Wave j: row r = b*nb + j.
 __global__ __launch_bounds__(MAX_NB * AV_WAVE) void merge_kernel(const uint64_t* __restrict__ seg_keys, const float* __restrict__ seg_stat,
                                                                  int nb, int V, int k, int nseg, const float* __restrict__ beam_scores,
-                                                                 float* __restrict__ out_scores, int32_t* __restrict__ out_beams,
+                                                                 int logprobs, float* __restrict__ out_scores, int32_t* __restrict__ out_beams,
                                                                  int64_t* __restrict__ out_tokens) {
     __shared__ uint64_t cand[MAX_NB * MAX_K];
     const int b = blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6, r = b * nb + j;
@@ -154,7 +156,7 @@ __global__ __launch_bounds__(MAX_NB * AV_WAVE) void merge_kernel(const uint64_t*
         uint64_t sc = 0;
         if (rk != 0) {
             const float x = unkey((uint32_t)(rk >> 32));
-            const float lp = (x - M) - lz;
+            const float lp = logprobs ? x : (x - M) - lz;
             sc = mkkey(bs + lp, (uint32_t)j * (uint32_t)V + key_idx(rk));
         }
         cand[j * k + lane] = sc;
@@ -233,7 +235,7 @@ size_t av_beam_topk_workspace_bytes(long rows, int V, int k) {
 }
 
 int av_beam_topk(const float* logits, long ld, int B, int nb, int V, const float* beam_scores, int k, float* out_scores, int32_t* out_beams,
-                 int64_t* out_tokens, void* ws, size_t ws_bytes, hipStream_t st) {
+                 int64_t* out_tokens, void* ws, size_t ws_bytes, int logprobs, hipStream_t st) {
     AV_CHECK_ARG(logits && beam_scores && out_scores && out_beams && out_tokens && ws, "beam_topk: null pointer");
     AV_CHECK_ARG(B > 0 && V > 0 && ld >= V, "beam_topk: bad shape (B %d, V %d, ld %ld)", B, V, ld);
     AV_CHECK_ARG(nb >= 1 && nb <= MAX_NB, "beam_topk: num_beams must be in [1, %d] (got %d)", MAX_NB, nb);
@@ -249,7 +251,7 @@ int av_beam_topk(const float* logits, long ld, int B, int nb, int V, const float
     float* seg_stat = (float*)(seg_keys + (size_t)rows * nseg * k);
     hipLaunchKernelGGL(seg_kernel, dim3(nseg, (unsigned)rows), dim3(SEG_NT), 0, st, logits, ld, V, k, nseg, seg_keys, seg_stat);
     AV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(merge_kernel, dim3(B), dim3(nb * AV_WAVE), 0, st, seg_keys, seg_stat, nb, V, k, nseg, beam_scores, out_scores,
+    hipLaunchKernelGGL(merge_kernel, dim3(B), dim3(nb * AV_WAVE), 0, st, seg_keys, seg_stat, nb, V, k, nseg, beam_scores, logprobs, out_scores,
                        out_beams, out_tokens);
     AV_LAUNCH_CHECK();
     return AV_OK;

@@ -237,6 +237,30 @@ int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, f
 size_t avllm_beam_topk_workspace_bytes(int64_t rows, int32_t V, int32_t k);
 int avllm_beam_topk(const float* logits, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,
                     float* out_scores, int32_t* out_beams, int64_t* out_tokens, void* ws, size_t ws_bytes, void* stream);
+/* avllm_beam_topk for rows that are log-probabilities already (avllm_logits_process with log_softmax = 1): score(j, v) =
+ * beam_scores[r] + logprobs[r][v], everything else as above.  Entries of -inf (banned tokens) order below every finite score, so one is
+ * returned only when an item has fewer than k finite candidates. */
+int avllm_beam_topk_logprobs(const float* logprobs, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,
+                             float* out_scores, int32_t* out_beams, int64_t* out_tokens, void* ws, size_t ws_bytes, void* stream);
+/* The logits processors of `self.llm.generate(**gen_kwargs)` (clip_whisper_model.py:1324-1340) for repetition_penalty, no_repeat_ngram_size
+ * and min_new_tokens, in place on scores [rows, V] (f32 or bf16, row stride ld) before avllm_argmax_rows / avllm_sample_rows /
+ * avllm_beam_topk_logprobs, in GenerationMixin._get_logits_processor's order.  history: int64 [rows, ldh] on the device, row r's first
+ * n = cur + (cur_dev ? *cur_dev : 0) entries are its generated tokens (with inputs_embeds HF's processors see nothing else); entries
+ * outside [0, V) are ignored.
+ *   RepetitionPenaltyLogitsProcessor(p), p > 0, off at 1: every distinct token t of the history gets s[t] < 0 ? s[t] * p : s[t] / p
+ *     (IEEE division), computed once from the unprocessed score however often t occurs.
+ *   NoRepeatNGramLogitsProcessor(g), off at 0: when n + 1 >= g, every i with history[i : i+g-1] == history[n-g+1 : n] bans
+ *     history[i+g-1] (-inf); g == 1 bans every token of the history.
+ *   MinNewTokensLengthLogitsProcessor(0, m, eos): while n < m, s[eos] = -inf; nothing when eos < 0.
+ * log_softmax = 1 (f32 only; beam search, where HF applies the processors to log-probabilities): the row is first replaced by
+ * (s - max) - log(sum exp(s - max)), so the normaliser is that of the unprocessed logits.
+ * append (optional, int64 [rows]): stored at history[r][n-1] before the history is read (the token chosen since the previous call), which
+ * spares the token loop a copy launch.  n <= 1024: a larger cur is AV_ERR_ARG, and with cur_dev ldh <= 1024 is required (the kernel
+ * clamps n to ldh).  One launch, one workgroup per row, O(n) work plus three passes over V with log_softmax; deterministic.  With every
+ * processor off, log_softmax = 0 and no append, nothing is launched. */
+int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int64_t* history, int64_t ldh, const int64_t* append, int32_t cur,
+                         const int32_t* cur_dev, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens, int64_t eos,
+                         int32_t log_softmax, int32_t dtype, void* stream);
 /* KV-cache row gather for beam search (the `_reorder_cache` / `Cache.reorder_cache(beam_idx)` step of GenerationMixin._beam_search):
  * dst[l, r, t, :] = src[l, parent[r], t, :] for every layer l < layers, row r < dst_rows and position t0 <= t < t1, on K and V.  The caches
  * are [layers, rows, T, dkv] contiguous (f32 or bf16, any dkv); src may have fewer rows than dst (prefix broadcast after prefill) and another

@@ -10,7 +10,8 @@ wer_<ts>.txt ("Overall WER" / "Total samples").
 Additions of this build (not reference flags): --do_sample / --top_p (default 0.9) / --top_k (default 50) (sampled `generate`:
 temperature -> top-k -> top-p on the device, its seed drawn after torch.manual_seed(--seed); without --do_sample decoding stays
 greedy and --temperature is ignored, as in the reference), --num_beams (default 1: greedy or sampled as above) / --length_penalty
-(default 1.0) (HF beam search, the best hypothesis per utterance), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
+(default 1.0) (HF beam search, the best hypothesis per utterance), --repetition_penalty (default 1.0) / --no_repeat_ngram_size (default 0) /
+--min_new_tokens (default 0) (HF's logits processors of those names, on the device, in every decoding mode), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -54,6 +55,9 @@ def parse_args(argv=None):
     p.add_argument("--top_k", type=int, default=50, help="0 turns top-k off")
     p.add_argument("--num_beams", type=int, default=1, help="beam search with this many beams (1 = greedy / sampling)")
     p.add_argument("--length_penalty", type=float, default=1.0, help="beam search: scores are divided by length ** length_penalty")
+    p.add_argument("--repetition_penalty", type=float, default=1.0, help="> 1 lowers the score of every token already generated (1.0 = off)")
+    p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size is generated twice (0 = off)")
+    p.add_argument("--min_new_tokens", type=int, default=0, help="EOS is not generated before this many new tokens")
     p.add_argument("--decode_weights", type=str, choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the token steps stream the LLM's frozen projections as block-scaled e4m3 (needs bf16; prefill stays bf16)")
     p.add_argument("--load_lora", action="store_true")
@@ -166,7 +170,8 @@ def main(argv=None):
             video = None if (video is None or a.modality == "audio") else video.to(dev)
             ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
                                  do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k, num_beams=a.num_beams,
-                                 length_penalty=a.length_penalty)
+                                 length_penalty=a.length_penalty, repetition_penalty=a.repetition_penalty,
+                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens)
             out = model.tokenizer.batch_decode(ids.cpu(), skip_special_tokens=True)
             if a.calculate_loss:
                 lab = model.tokenizer(list(texts), padding="max_length", truncation=True, max_length=256, return_tensors="pt").input_ids
