@@ -116,6 +116,9 @@ _SIGS = {
     "avllm_rmsnorm_fwd": ([vp, vp, vp, vp, i64, i32, f32, i32, vp], i32),
     "avllm_rmsnorm_bwd": ([vp, vp, vp, vp, vp, vp, i64, i32, i32, vp], i32),
     "avllm_rope": ([vp, i64, i64, i32, i32, i32, i32, f32, i32, i32, vp], i32),
+    "avllm_rope_table": ([vp, i32, i32, i32, f32, vp, f32, f32, f32, i32, vp], i32),
+    "avllm_rope_tab": ([vp, i64, i64, i32, i32, i32, vp, i32, i32, vp], i32),
+    "avllm_kv_append": ([vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     "avllm_swiglu_fwd": ([vp, vp, i64, i32, i32, vp], i32),
     "avllm_swiglu_bwd": ([vp, vp, vp, i64, i32, i32, vp], i32),
     "avllm_attention_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, f32, i32, i32, i32, i32, vp], i32),

@@ -96,6 +96,31 @@ def rope_(x2d, T, heads, hd, pos0=0, theta=10000.0, inverse=False):
     return x2d
 
 
+def rope_table(T, hd, pos0=0, theta=10000.0, pos_dev=None, scaling=None, device="cuda"):
+    """cos/sin table f32 [T, hd/2, 2] of positions pos0 (+ *pos_dev, an int32 device tensor of one element) + t (avllm_rope_table), the form
+    the engine runs.  scaling = (factor, low_freq_factor, high_freq_factor, original_max_position_embeddings): HF's "llama3" rule."""
+    tab = torch.empty(T, hd // 2, 2, device=device, dtype=torch.float32)
+    if pos_dev is not None:
+        assert pos_dev.dtype == torch.int32 and pos_dev.numel() == 1 and pos_dev.is_cuda
+    f, lo, hi, octx = scaling if scaling else (1.0, 1.0, 4.0, 0)
+    L.check(L.load().avllm_rope_table(L.ptr(tab), T, hd, pos0, theta, L.ptr(pos_dev), f, lo, hi, int(octx), L.stream_ptr()))
+    return tab
+
+
+def rope_tab_(x2d, T, heads, hd, tab, inverse=False):
+    """In place on a [rows, heads*hd] view (row stride free): row r is rotated by table row r % T (avllm_rope_tab)."""
+    assert tab.dtype == torch.float32 and tab.is_contiguous() and tab.numel() == T * hd
+    L.check(L.load().avllm_rope_tab(L.ptr(x2d), _ld(x2d), x2d.shape[0], T, heads, hd, L.ptr(tab), int(inverse), L.dt_of(x2d), L.stream_ptr()))
+    return x2d
+
+
+def kv_append(k, v, kc, vc, T, pos0):
+    """kc[b, pos0 + t, :] = k[b*T + t, :] and the same for v (avllm_kv_append): k, v [B*T, d] views with one row stride, caches [B, Tmax, d] contiguous."""
+    B, Tmax, d = kc.shape
+    assert k.shape == (B * T, d) and v.shape == k.shape and _ld(k) == _ld(v) and kc.is_contiguous() and vc.is_contiguous() and vc.shape == kc.shape
+    L.check(L.load().avllm_kv_append(L.ptr(k), L.ptr(v), _ld(k), L.ptr(kc), L.ptr(vc), B, T, pos0, Tmax, d, L.dt_of(kc), L.stream_ptr()))
+
+
 def swiglu_fwd(gu):
     M, F2 = gu.shape
     h = torch.empty(M, F2 // 2, device=gu.device, dtype=gu.dtype)
@@ -151,22 +176,40 @@ def attention_bwd(qkv, o, dout, lse, B, T, H, hd, causal, scale=None, impl=0, kv
     return dqkv
 
 
+def _ce_ld(logits):
+    """The one row stride the CE kernels take: logits [B,T,V] must be rows of stride ld >= V, ld % 8 == 0, laid out as a [B*T, ld] matrix."""
+    B, T, V = logits.shape
+    ld = logits.stride(1) if T > 1 else (logits.stride(0) if B > 1 else (V + 7) // 8 * 8)
+    if logits.stride(2) != 1 or (B > 1 and logits.stride(0) != T * ld) or ld < V or ld % 8:
+        raise ValueError(f"cross entropy: logits {tuple(logits.shape)} with strides {tuple(logits.stride())} are not [B*T] rows of one stride "
+                         "(a multiple of 8, >= V)")
+    return ld
+
+
 def ce_fwd(logits, labels):
-    """logits [B,T,V], labels int64 [B,T] (-100 = ignore) -> (row_lse [B*T], loss_sum [1], count [1])."""
+    """logits [B,T,V] (row stride free: a [:, :, :V] view of a padded buffer is fine), labels int64 [B,T] (-100 = ignore)
+    -> (row_lse [B*T], acc = [loss_sum, count])."""
     B, T, V = logits.shape
     row_lse = torch.empty(B * T, device=logits.device, dtype=torch.float32)
     acc = torch.zeros(2, device=logits.device, dtype=torch.float32)
-    L.check(L.load().avllm_ce_fwd(L.ptr(logits), logits.stride(1), L.ptr(labels), B, T, V, L.ptr(row_lse), L.ptr(acc), L.ptr(acc) + 4,
+    L.check(L.load().avllm_ce_fwd(L.ptr(logits), _ce_ld(logits), L.ptr(labels), B, T, V, L.ptr(row_lse), L.ptr(acc), L.ptr(acc) + 4,
                                   L.dt_of(logits), L.stream_ptr()))
     return row_lse, acc
 
 
-def ce_bwd(logits, labels, row_lse, acc, grad_scale=1.0):
+def ce_bwd(logits, labels, row_lse, acc, grad_scale=1.0, out=None):
+    """dlogits = grad_scale / count * (softmax - onehot) on scored rows.  The kernel takes ONE row stride for logits and dlogits, so the
+    gradient is allocated with the strides of `logits` (torch.empty_like would make a padded view dense); out: a tensor of the same shape,
+    dtype and strides to write into; out = logits is the in-place form the engine uses."""
     B, T, V = logits.shape
-    dl = torch.empty_like(logits)
-    L.check(L.load().avllm_ce_bwd(L.ptr(logits), logits.stride(1), L.ptr(labels), L.ptr(row_lse), L.ptr(acc) + 4, grad_scale, L.ptr(dl),
+    ld = _ce_ld(logits)
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), device=logits.device, dtype=logits.dtype)
+    elif out.shape != logits.shape or out.stride() != logits.stride() or out.dtype != logits.dtype or out.device != logits.device:
+        raise ValueError("ce_bwd: out must have the shape, strides, dtype and device of logits")
+    L.check(L.load().avllm_ce_bwd(L.ptr(logits), ld, L.ptr(labels), L.ptr(row_lse), L.ptr(acc) + 4, grad_scale, L.ptr(out),
                                   B, T, V, L.dt_of(logits), L.stream_ptr()))
-    return dl
+    return out
 
 
 def argmax_rows(logits2d):

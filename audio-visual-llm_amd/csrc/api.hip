@@ -83,6 +83,17 @@ int avllm_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float*
                       int64_t rows, int32_t d, int32_t dtype, void* stream) { return av_rmsnorm_bwd(dy, x, w, rstd, dres_in, dx_out, rows, d, dtype, ST); }
 int avllm_rope(void* x, int64_t ld, int64_t rows, int32_t T, int32_t heads, int32_t hd, int32_t pos0, float theta,
                int32_t inverse, int32_t dtype, void* stream) { return av_rope(x, ld, rows, T, heads, hd, pos0, theta, inverse, dtype, ST); }
+int avllm_rope_table(float* tab, int32_t T, int32_t hd, int32_t pos0, float theta, const int32_t* pos_dev, float factor,
+                     float low_freq_factor, float high_freq_factor, int32_t orig_ctx, void* stream) {
+    AvRopeScale sc;
+    sc.factor = factor; sc.low_freq_factor = low_freq_factor; sc.high_freq_factor = high_freq_factor; sc.orig_ctx = orig_ctx;
+    AV_CHECK_ARG(orig_ctx <= 0 || (factor > 0.f && low_freq_factor > 0.f && high_freq_factor > low_freq_factor), "rope_table: bad llama3 scaling");
+    return av_rope_table(tab, T, hd, pos0, theta, ST, pos_dev, sc);
+}
+int avllm_rope_tab(void* x, int64_t ld, int64_t rows, int32_t T, int32_t heads, int32_t hd, const float* tab, int32_t inverse,
+                   int32_t dtype, void* stream) { return av_rope_tab(x, ld, rows, T, heads, hd, tab, inverse, dtype, ST); }
+int avllm_kv_append(const void* k, const void* v, int64_t ld, void* kc, void* vc, int32_t B, int32_t T, int32_t pos0, int32_t Tmax,
+                    int32_t d, int32_t dtype, void* stream) { return av_kv_append(k, v, ld, kc, vc, B, T, pos0, Tmax, d, dtype, ST); }
 int avllm_swiglu_fwd(const void* gu, void* h, int64_t M, int32_t F, int32_t dtype, void* stream) { return av_swiglu_fwd(gu, h, M, F, dtype, ST); }
 int avllm_swiglu_bwd(const void* dh, const void* gu, void* dgu, int64_t M, int32_t F, int32_t dtype, void* stream) { return av_swiglu_bwd(dh, gu, dgu, M, F, dtype, ST); }
 int avllm_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int32_t B, int32_t Tq, int32_t Tk,

@@ -25,7 +25,9 @@ __global__ void im2col_k3_kernel(const T* __restrict__ x, T* __restrict__ cols, 
     }
 }
 
-// grid (G, B): one workgroup per (item, group); two passes over the [T, C/G] slab (second pass normalises, applies w, b and the activation)
+// grid (G, B): one workgroup per (item, group); three passes over the [T, C/G] slab (it stays in L2): the mean; the variance as the mean of
+// (x - mean)^2, with the residual sum of (x - mean) correcting the mean's own rounding (the corrected two-pass form: E[x^2] - mean^2 in fp32 loses
+// log2(mean^2 / var) bits, i.e. everything once |mean| / sigma reaches ~3e3, and a conv bias puts real inputs there); then normalise, w, b, activation
 template <typename T>
 __global__ __launch_bounds__(256) void groupnorm_tokens_kernel(const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ bb,
                                                                T* __restrict__ y, int Tn, int C, int G, float eps, int act) {
@@ -34,16 +36,25 @@ __global__ __launch_bounds__(256) void groupnorm_tokens_kernel(const T* __restri
     const T* xb = x + (long)b * Tn * C + (long)g * cg;
     T* yb = y + (long)b * Tn * C + (long)g * cg;
     const long n = (long)Tn * c8;
-    float s = 0.f, ss = 0.f;
+    const float cnt = (float)Tn * (float)cg;
+    float s = 0.f;
     for (long i = threadIdx.x; i < n; i += 256) {
         float v[8];
         load_f<8>(xb + (i / c8) * C + (i % c8) * 8, v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { s += v[j]; ss += v[j] * v[j]; }
+        for (int j = 0; j < 8; ++j) s += v[j];
     }
-    const float cnt = (float)Tn * (float)cg;
-    const float mean = block_sum(s, red) / cnt;
-    const float var = fmaxf(block_sum(ss, red) / cnt - mean * mean, 0.f);
+    float mean = block_sum(s, red) / cnt;
+    float ds = 0.f, dd = 0.f;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        float v[8];
+        load_f<8>(xb + (i / c8) * C + (i % c8) * 8, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float u = v[j] - mean; ds += u; dd += u * u; }
+    }
+    const float dm = block_sum(ds, red) / cnt;
+    const float var = fmaxf(block_sum(dd, red) / cnt - dm * dm, 0.f);
+    mean += dm;
     const float rstd = rsqrtf(var + eps);
     for (long i = threadIdx.x; i < n; i += 256) {
         const int c = (int)(i % c8) * 8;

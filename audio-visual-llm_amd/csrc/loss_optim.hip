@@ -82,7 +82,10 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logit
     }
 }
 
-// first index of the maximum (torch.argmax tie rule on exact ties: lowest index)
+// The lowest index of the maximum, with NaN read as -inf: torch.argmax on every row without NaN (exact ties: lowest index), and always an index
+// in [0, V).  A thread that meets nothing above -inf keeps "no index"; a row where that holds for every thread is all -inf / NaN and gives 0,
+// the lowest index of its maximum.  (The scan loop is the hot part and stays one compare per element; the old kernel returned 2^31 - 1 there,
+// which generate() then handed to the embedding gather.)
 template <typename T>
 __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ x, long ld, int V, int64_t* __restrict__ out) {
     __shared__ float bv[256];
@@ -99,18 +102,29 @@ __global__ __launch_bounds__(256) void argmax_kernel(const T* __restrict__ x, lo
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[blockIdx.x] = bi[0];
+    if (threadIdx.x == 0) out[blockIdx.x] = bi[0] == 0x7fffffff ? 0 : bi[0];
+}
+
+// One thread's share of sum g^2 (grid-stride over 16-byte vectors, block 0 takes the n % 4 tail).  With few blocks a thread adds > 1e5 squares:
+// one running fp32 sum would lose sqrt(count) half-ulps (3.7 ulp of the total at n = 40 * 2^20 in one block), so each vector lane keeps its own
+// sum and every 32 vectors those are folded into a second level: the longest chain of additions is count / 128 + 32 instead of count.
+__device__ __forceinline__ float sumsq_thread(const float* __restrict__ g, long n) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+    const long n4 = n >> 2;
+    int k = 0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 v = *(const f32x4*)(g + i * 4);
+        a0 += v[0] * v[0]; a1 += v[1] * v[1]; a2 += v[2] * v[2]; a3 += v[3] * v[3];
+        if (++k == 32) { t0 += a0; t1 += a1; t2 += a2; t3 += a3; a0 = a1 = a2 = a3 = 0.f; k = 0; }
+    }
+    float s = ((t0 + a0) + (t1 + a1)) + ((t2 + a2) + (t3 + a3));
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s += v * v; }
+    return s;
 }
 
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long n, float* __restrict__ out) {
     __shared__ float red[8];
-    float s = 0.f;
-    const long n4 = n >> 2;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const f32x4 v = *(const f32x4*)(g + i * 4);
-        s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s += v * v; }
+    float s = sumsq_thread(g, n);
     s = block_sum(s, red);
     if (threadIdx.x == 0) atomicAdd(out, s);
 }
@@ -121,13 +135,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 // they stay bit-identical.
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, long n, float* __restrict__ partials) {
     __shared__ float red[8];
-    float s = 0.f;
-    const long n4 = n >> 2;
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-        const f32x4 v = *(const f32x4*)(g + i * 4);
-        s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s += v * v; }
+    float s = sumsq_thread(g, n);
     s = block_sum(s, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
@@ -219,7 +227,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const T* __restrict__ P, l
 int av_ce_fwd(const void* logits, long ld, const int64_t* labels, int B, int T, int V, float* row_lse, float* loss_sum,
               float* count, int dtype, hipStream_t st) {
     AV_CHECK_ARG(logits && labels && row_lse && loss_sum && count && B > 0 && T > 0 && V > 0, "ce_fwd: bad args");
-    AV_CHECK_ARG(ld % 8 == 0, "ce_fwd: ld must be a multiple of 8");
+    AV_CHECK_ARG(ld % 8 == 0 && ld >= V, "ce_fwd: ld must be a multiple of 8 and >= V");
     if (dtype == AV_F32) hipLaunchKernelGGL((ce_fwd_kernel<float>), dim3((long)B * T), dim3(256), 0, st, (const float*)logits, ld, labels, T, V, row_lse, loss_sum, count);
     else hipLaunchKernelGGL((ce_fwd_kernel<bf16>), dim3((long)B * T), dim3(256), 0, st, (const bf16*)logits, ld, labels, T, V, row_lse, loss_sum, count);
     AV_LAUNCH_CHECK();
@@ -228,7 +236,8 @@ int av_ce_fwd(const void* logits, long ld, const int64_t* labels, int B, int T, 
 
 int av_ce_bwd(const void* logits, long ld, const int64_t* labels, const float* row_lse, const float* count,
               float grad_scale, void* dlogits, int B, int T, int V, int dtype, hipStream_t st) {
-    AV_CHECK_ARG(logits && labels && row_lse && count && dlogits, "ce_bwd: bad args");
+    AV_CHECK_ARG(logits && labels && row_lse && count && dlogits && B > 0 && T > 0 && V > 0, "ce_bwd: bad args");
+    AV_CHECK_ARG(ld % 8 == 0 && ld >= V, "ce_bwd: ld must be a multiple of 8 and >= V (one row stride for logits and dlogits)");
     if (dtype == AV_F32) hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3((long)B * T), dim3(256), 0, st, (const float*)logits, ld, labels, row_lse, count, grad_scale, (float*)dlogits, T, V);
     else hipLaunchKernelGGL((ce_bwd_kernel<bf16>), dim3((long)B * T), dim3(256), 0, st, (const bf16*)logits, ld, labels, row_lse, count, grad_scale, (bf16*)dlogits, T, V);
     AV_LAUNCH_CHECK();

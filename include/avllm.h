@@ -187,6 +187,14 @@ int avllm_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float*
  * inverse=1 applies the transpose rotation (backward).  HF:models/llama/modeling_llama.py:129-160 */
 int avllm_rope(void* x, int64_t ld, int64_t rows, int32_t T, int32_t heads, int32_t hd, int32_t pos0, float theta,
                int32_t inverse, int32_t dtype, void* stream);
+/* The same rotation from a cos/sin table, the form the model runs (one table per call instead of powf/cosf/sinf per element and layer):
+ * avllm_rope_table fills tab [T][hd/2][2] = (cos, sin) of (pos0 (+ *pos_dev, optional device word) + t) * inv_freq_i in fp32.  orig_ctx > 0
+ * applies HF's "llama3" frequency rule (modeling_rope_utils.py _compute_llama3_parameters) with factor / low_freq_factor /
+ * high_freq_factor; orig_ctx == 0 is plain RoPE and ignores them.  avllm_rope_tab rotates x in place with row r reading table row r % T. */
+int avllm_rope_table(float* tab, int32_t T, int32_t hd, int32_t pos0, float theta, const int32_t* pos_dev, float factor,
+                     float low_freq_factor, float high_freq_factor, int32_t orig_ctx, void* stream);
+int avllm_rope_tab(void* x, int64_t ld, int64_t rows, int32_t T, int32_t heads, int32_t hd, const float* tab, int32_t inverse,
+                   int32_t dtype, void* stream);
 /* h = silu(g)*u with gu = [g | u] ([M,2F]); HF:models/llama/modeling_llama.py:175 */
 int avllm_swiglu_fwd(const void* gu, void* h, int64_t M, int32_t F, int32_t dtype, void* stream);
 int avllm_swiglu_bwd(const void* dh, const void* gu, void* dgu, int64_t M, int32_t F, int32_t dtype, void* stream);
@@ -270,6 +278,10 @@ int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int6
  * dst_rows <= 2048.  t0 == t1 is a no-op. */
 int avllm_kv_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
                          int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, int32_t dtype, void* stream);
+/* KV-cache append of the general decode path: kc[b, pos0 + t, :] = k[b * T + t, :] (and v -> vc) for t < T; k, v rows of stride ld elements
+ * (slices of the fused q|k|v buffer), caches [B, Tmax, d] contiguous.  pos0 + T <= Tmax and d % 4 == 0, else AV_ERR_ARG. */
+int avllm_kv_append(const void* k, const void* v, int64_t ld, void* kc, void* vc, int32_t B, int32_t T, int32_t pos0, int32_t Tmax,
+                    int32_t d, int32_t dtype, void* stream);
 /* out[i,:] = table[ids[i],:] ; llm.get_input_embeddings() (clip_whisper_model.py:464-487) */
 int avllm_embedding(const void* table, const int64_t* ids, void* out, int64_t n, int32_t d, int32_t dtype, void* stream);
 int avllm_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, int64_t n, void* stream);
