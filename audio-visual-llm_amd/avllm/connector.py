@@ -5,33 +5,80 @@ built from the same library calls (round 3): avllm_gemm for every Linear / Conv1
 avllm_act_residual, avllm_attention_fwd.  Parameters live in torch modules of the reference's own layout, so its state dicts load as they are.
 One deliberate difference: the nn.MultiheadAttention inside `attention` / `adaptive` carries dropout 0.1, which the reference applies whenever
 the model is in train() mode (torch's RNG stream, not reproducible elsewhere); here the connectors always compute the eval-mode function
-(no gradient reaches them anyway: SURVEY.md fact 4)."""
+(no gradient reaches them unless the model is built with train_connectors=True, which covers `simple` only: SURVEY.md fact 4).
+
+train_connectors=True (`simple`): weight and bias are fp32 master parameters with requires_grad=True (the reference's use_fp16 path is autocast
+over fp32 parameters too); in bf16 mode the GEMM reads a bf16 operand image that refresh() rewrites after every update, as pack_lora does for
+the adapters.  A training forward keeps the rows it projected in a static buffer: they are the X of the weight gradient dW = dY^T X."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
+from . import lib as L_
 from . import ops
 
 
 class SimpleModalityConnector(nn.Module):
-    def __init__(self, input_dim, output_dim, device="cuda", dtype=torch.float32, max_seq_len=None, **kwargs):
+    def __init__(self, input_dim, output_dim, device="cuda", dtype=torch.float32, max_seq_len=None, trainable=False, **kwargs):
         super().__init__()
         self.input_dim, self.output_dim, self.device, self.dtype = input_dim, output_dim, device, dtype
+        self.trainable = bool(trainable)
         self.linear = nn.Linear(input_dim, output_dim)            # parameter storage; compute is ops.gemm
         nn.init.xavier_uniform_(self.linear.weight)
         nn.init.zeros_(self.linear.bias)
+        self.keep_input = False                                   # set by the model around a training forward (train_connectors=True)
+        self.saved_input = None
+        if self.trainable:
+            from .engine import Workspace
+            self.linear = self.linear.to(device=device, dtype=torch.float32)      # fp32 masters; requires_grad stays True
+            self._w_img = self._b_img = None
+            self._saved_ws = Workspace(device)
+            self.refresh()
+            return
         self.linear = self.linear.to(device=device, dtype=dtype)
         for p in self.parameters():
-            p.requires_grad_(False)                               # no gradient reaches the connectors (SURVEY.md fact 4)
+            p.requires_grad_(False)                               # no gradient reaches the connectors without train_connectors (SURVEY.md fact 4)
+
+    def refresh(self):
+        """bf16 mode with trainable masters: rewrite the operand image the projection reads (after an optimizer step or a load)."""
+        if not self.trainable or self.dtype == torch.float32:
+            return
+        w, b = self.linear.weight.detach(), self.linear.bias.detach()
+        if self._w_img is None:
+            self._w_img, self._b_img = torch.empty_like(w, dtype=self.dtype), torch.empty_like(b, dtype=self.dtype)
+        lib = L_.load()
+        for src, dst in ((w, self._w_img), (b, self._b_img)):
+            L_.check(lib.avllm_cast(L_.ptr(src), L_.F32, L_.ptr(dst), L_.dt_of(dst), src.numel(), L_.stream_ptr()))
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        res = super().load_state_dict(state_dict, *args, **kwargs)
+        self.refresh()
+        return res
+
+    def operands(self):
+        """(weight, bias) as the projection reads them: the parameters themselves, or the bf16 image of trainable fp32 masters."""
+        if self.trainable and self.dtype != torch.float32:
+            return self._w_img, self._b_img
+        return self.linear.weight.detach(), self.linear.bias.detach()
 
     def forward(self, x):
         if x.dtype != self.dtype:
             x = ops.cast(x, self.dtype)
         shp = x.shape
-        if x.dim() == 3 and not x.is_contiguous():
-            x = x.contiguous()                                    # row-sliced view (first L frames of each item): one strided copy, then ONE projection
-        y = ops.gemm(x.reshape(-1, shp[-1]), self.linear.weight, bias=self.linear.bias)
+        if self.trainable and self.keep_input:
+            # the rows projected here are the X of dW = dY^T X: they go into a static buffer (stable under graph capture; the copy is also the
+            # one strided copy a row-sliced view needs) and the projection reads them from there
+            n = x.numel() * x.element_size()
+            x2 = self._saved_ws.get(n)[:n].view(self.dtype).view(-1, shp[-1])
+            x2.view(shp).copy_(x)
+            self.saved_input = x2
+        else:
+            if x.dim() == 3 and not x.is_contiguous():
+                x = x.contiguous()                                # row-sliced view (first L frames of each item): one strided copy, then ONE projection
+            x2 = x.reshape(-1, shp[-1])
+        w, b = self.operands()
+        y = ops.gemm(x2, w, bias=b)
         return y.view(*shp[:-1], self.output_dim)
 
 
@@ -54,7 +101,7 @@ class DeepModalityConnector(nn.Module):
                 nn.init.zeros_(mod.bias)
         self.to(device=device, dtype=dtype)
         for p in self.parameters():
-            p.requires_grad_(False)                               # no gradient reaches the connectors
+            p.requires_grad_(False)                               # never trained: train_connectors covers `simple` only
 
     def forward(self, x):
         from . import lib as L
@@ -76,7 +123,7 @@ class DeepModalityConnector(nn.Module):
 def _freeze(mod, device, dtype):
     mod.to(device=device, dtype=dtype)
     for p in mod.parameters():
-        p.requires_grad_(False)                                   # no gradient reaches the connectors
+        p.requires_grad_(False)                                   # never trained: train_connectors covers `simple` only
 
 
 def _xavier(mod):
@@ -207,6 +254,8 @@ ModalityConnector = SimpleModalityConnector
 def create_modality_connector(connector_type, input_dim, output_dim, device="cuda", dtype=torch.float32, **kwargs):
     """modality_connector.py:383-399."""
     import logging
+    if kwargs.get("trainable") and connector_type != "simple":
+        raise NotImplementedError(f"train_connectors=True supports connector_type='simple' only, got {connector_type!r}")
     if connector_type == "simple":
         return SimpleModalityConnector(input_dim, output_dim, device, dtype, **kwargs)
     if connector_type == "conv":

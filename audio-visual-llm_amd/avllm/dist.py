@@ -57,9 +57,14 @@ class LoraGradReducer:
     def layers_done(self, lo: int, hi: int):
         """Graph-replayed backward pieces: all-reduce the contiguous gradient slice of decoder layers lo..hi (inclusive) on the side stream,
         ordered after everything enqueued on the compute stream so far (the piece that produced it)."""
+        if self.enabled:
+            self.bucket_done(self.g[lo * self.per_layer:(hi + 1) * self.per_layer])
+
+    def bucket_done(self, bucket: torch.Tensor):
+        """SUM all-reduce of one more flat gradient buffer on the side stream, ordered after everything enqueued on the compute stream so far
+        (the connector gradient of train_connectors=True: one bucket after the last backward piece), joined in finish()."""
         if not self.enabled:
             return
-        bucket = self.g[lo * self.per_layer:(hi + 1) * self.per_layer]
         if self.cuda:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())

@@ -361,10 +361,12 @@ class LlamaEngine:
         self.gen = getattr(self, "gen", 0) + 1          # identifies whose activations the workspace holds (checked by _LoraLoss.backward)
         return logits
 
-    def bwd(self, grad_scale=1.0, count=None, after_layer=None, layer_hi=None, layer_lo=0):
+    def bwd(self, grad_scale=1.0, count=None, after_layer=None, layer_hi=None, layer_lo=0, dx_embeds=None):
         """Accumulates LoRA grads into self.lora_g (zero it first).  `count` = device float tensor holding the
         (possibly all-reduced) number of scored tokens; defaults to this rank's.  layer_hi/layer_lo: run only that piece of the
-        backward pass (decoder layers layer_hi .. layer_lo; pieces in descending order, avllm_llama_lora_bwd_layers)."""
+        backward pass (decoder layers layer_hi .. layer_lo; pieces in descending order, avllm_llama_lora_bwd_layers).
+        dx_embeds: [B,S,d] tensor of the engine dtype that receives d loss / d inputs_embeds when the piece reaches layer 0
+        (avllm_llama_lora_bwd_layers_dx; the connectors' gradient starts there)."""
         lib = L.load()
         if self._last is None:
             raise RuntimeError("LlamaEngine.bwd() without a preceding fwd_loss()")
@@ -375,6 +377,12 @@ class LlamaEngine:
         cnt = self.acc[1:2] if count is None else count
         cb = L.LAYER_CB(lambda l, u: after_layer(l)) if after_layer is not None else L.LAYER_CB(0)
         hi = self.cfg.layers - 1 if layer_hi is None else layer_hi
+        if dx_embeds is not None:
+            if dx_embeds.dtype != self.dtype or dx_embeds.numel() != B * S * self.cfg.hidden or not dx_embeds.is_contiguous():
+                raise ValueError(f"LlamaEngine.bwd(): dx_embeds must be a contiguous [{B},{S},{self.cfg.hidden}] {self.dtype} tensor")
+            L.check(lib.avllm_llama_lora_bwd_layers_dx(C.byref(self.desc), L.ptr(labels), B, S, L.ptr(cnt), grad_scale, L.ptr(ws), ws.numel(),
+                                                       hi, layer_lo, cb, None, L.ptr(dx_embeds), L.stream_ptr()))
+            return
         L.check(lib.avllm_llama_lora_bwd_layers(C.byref(self.desc), L.ptr(labels), B, S, L.ptr(cnt), grad_scale, L.ptr(ws), ws.numel(),
                                                 hi, layer_lo, cb, None, L.stream_ptr()))
 

@@ -85,6 +85,11 @@ class StepState(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class AdamwSeg(C.Structure):
+    """avllm_adamw_seg: one flat buffer of a multi-segment AdamW step (avllm_adamw_step_multi)."""
+    _fields_ = [("p", vp), ("m", vp), ("v", vp), ("g", vp), ("n", i64), ("weight_decay", f32), ("reserved", i32)]
+
+
 class Schedule(C.Structure):
     _fields_ = [("base_lr", f32), ("beta1", f32), ("beta2", f32), ("warmup_steps", i32), ("total_steps", i32), ("rank", C.c_uint32)]
 
@@ -141,6 +146,10 @@ _SIGS = {
     "avllm_clip_patchify": ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "avllm_clip_cls_rows": ([vp, vp, vp, i32, i32, i32, i32, vp], i32),
     "avllm_fuse_pool": ([vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, i32, vp], i32),
+    "avllm_fuse_pool_bwd": ([vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp], i32),
+    "avllm_gemm_wgrad": ([vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, f32, i32, vp], i32),
+    "avllm_grad_sumsq_det_multi": ([C.POINTER(vp), C.POINTER(i64), i32, vp, i32, vp, vp], i32),
+    "avllm_adamw_step_multi": ([C.POINTER(AdamwSeg), i32, f32, f32, f32, f32, i32, vp, f32, f32, vp, vp, vp, vp], i32),
     "avllm_grad_sumsq": ([vp, i64, vp, vp], i32),
     "avllm_grad_sumsq_det": ([vp, i64, vp, i32, vp, vp], i32),
     "avllm_adamw_step": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp, f32, f32, vp, vp, vp, vp], i32),
@@ -151,6 +160,7 @@ _SIGS = {
     "avllm_lora_dx_masked": ([C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_uint32), i32, i32, vp, i64, vp, i64, i32,
                               i32, f32, vp, i32, vp], i32),
     "avllm_llama_lora_bwd_layers": ([C.POINTER(Llama), vp, i32, i32, vp, f32, vp, sz, i32, i32, LAYER_CB, vp, vp], i32),
+    "avllm_llama_lora_bwd_layers_dx": ([C.POINTER(Llama), vp, i32, i32, vp, f32, vp, sz, i32, i32, LAYER_CB, vp, vp, vp], i32),
     "avllm_lora_pack": ([vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, i32, vp], i32),
     "avllm_profile_begin": ([i32], i32),
     "avllm_profile_enable": ([i32], i32),

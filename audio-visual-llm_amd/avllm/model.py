@@ -9,6 +9,9 @@ Differences that are deliberate and documented:
     modules' state_dict()s, from `weights=`, or -- only with `synthetic_weights=True` -- from a seeded synthetic
     initialisation of the named architecture (a path that is none of these raises FileNotFoundError).
   * freeze_encoders=False / use_4bit=True are refused (out of scope).
+  * train_connectors=True (default False) trains the two modality connectors with the encoders frozen: the reference's freeze_encoders=False
+    gradient (clip_whisper_model.py:1096-1106,1136-1146) restricted to the four connector tensors, which does not depend on whether the
+    encoders receive one too.  connector_type "simple", precision fp32 | bf16, use_lora=True.
 """
 from __future__ import annotations
 
@@ -27,10 +30,11 @@ from .tokenizer import load_tokenizer
 
 
 class _LoraLoss(torch.autograd.Function):
-    """Makes `out["loss"].backward()` (trainer/clip_whisper_trainer.py:454) drive avllm_llama_lora_bwd."""
+    """Makes `out["loss"].backward()` (trainer/clip_whisper_trainer.py:454) drive avllm_llama_lora_bwd; with train_connectors=True the four
+    connector parameters are inputs too and receive their gradients from the same backward pass."""
 
     @staticmethod
-    def forward(ctx, lora_param, model, loss_value):
+    def forward(ctx, lora_param, model, loss_value, *connector_params):
         ctx.model = model
         ctx.gen = model.llm_engine.gen
         return loss_value.clone()
@@ -42,8 +46,12 @@ class _LoraLoss(torch.autograd.Function):
         if eng.gen != ctx.gen:
             raise RuntimeError("loss.backward(): another training forward ran since this loss was computed; its activations were overwritten")
         eng.lora_g.zero_()
-        eng.bwd(grad_scale=float(grad_out))
-        return eng.lora_g.clone(), None, None
+        if not m.train_connectors:
+            eng.bwd(grad_scale=float(grad_out))
+            return eng.lora_g.clone(), None, None
+        eng.bwd(grad_scale=float(grad_out), dx_embeds=m._dx_embeds_buffer())
+        m.connector_backward()
+        return (eng.lora_g.clone(), None, None) + tuple(g.clone() for g in m.connector_grad_views())
 
 
 class ClipWhisperModel:
@@ -52,7 +60,8 @@ class ClipWhisperModel:
                  lora_r=16, lora_alpha=32, lora_dropout=0.05, freeze_encoders=True, freeze_llm=False, modality="both",
                  max_seq_len=256, fusion_scale=0.5, connector_type="simple", _provided_tokenizer=None, _provided_llm=None,
                  _provided_whisper=None, _provided_clip=None, *, precision=None, config: ModelCfg | None = None,
-                 weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16"):
+                 weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16",
+                 train_connectors: bool = False):
         if use_4bit:
             raise NotImplementedError("use_4bit (bitsandbytes nf4) is out of scope of the MI355X hot path (SURVEY.md §8)")
         if not freeze_encoders:
@@ -87,6 +96,14 @@ class ClipWhisperModel:
         if decode_weights == "fp8" and precision == "fp32":
             raise ValueError("decode_weights='fp8' needs precision bf16 or fp8 (the fp8 token step is a bf16-activation path)")
         self.decode_weights = decode_weights
+        self.train_connectors = bool(train_connectors)
+        if self.train_connectors:
+            if connector_type != "simple":
+                raise NotImplementedError(f"train_connectors=True supports connector_type='simple' only, got {connector_type!r}")
+            if precision == "fp8":
+                raise NotImplementedError("train_connectors=True supports precision fp32 | bf16, not fp8")
+            if not use_lora:
+                raise ValueError("train_connectors=True needs use_lora=True: the LoRA backward pass is the only LLM backward pass in the library")
         self.dtype = torch.float32 if precision == "fp32" else torch.bfloat16
         self.training = True
         self._drop_step = 0
@@ -173,8 +190,10 @@ class ClipWhisperModel:
     def save_pretrained(self, output_dir):
         """Directory layout of clip_whisper_model.py:738-798 for the tensors this build owns."""
         os.makedirs(output_dir, exist_ok=True)
-        torch.save(self.audio_connector.state_dict(), os.path.join(output_dir, "audio_connector.pt"))
-        torch.save(self.video_connector.state_dict(), os.path.join(output_dir, "video_connector.pt"))
+        # train_connectors=True: the parameters are views of one flat buffer and torch.save writes a view's whole storage, so they are cloned
+        own = (lambda sd: {k: v.detach().clone() for k, v in sd.items()}) if self.train_connectors else (lambda sd: sd)
+        torch.save(own(self.audio_connector.state_dict()), os.path.join(output_dir, "audio_connector.pt"))
+        torch.save(own(self.video_connector.state_dict()), os.path.join(output_dir, "video_connector.pt"))
         import json
         cfg = dict(modality=self.modality, max_seq_len=self.max_seq_len, fusion_scale=self.fusion_scale, use_lora=self.use_lora,
                    lora_r=self.lora_r, lora_alpha=self.lora_alpha, connector_type=self.connector_type,
@@ -215,13 +234,73 @@ class ClipWhisperModel:
         # two builds with the same seed are the same model, which the reference's unseeded nn.Linear init does not give
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(0x5EED + int(self._seed))
-            self.audio_connector = create_modality_connector(self.connector_type, self.audio_dim, self.llm_dim, self.device, self.dtype)
-            self.video_connector = create_modality_connector(self.connector_type, self.video_dim, self.llm_dim, self.device, self.dtype)
+            kw = {"trainable": True} if self.train_connectors else {}
+            self.audio_connector = create_modality_connector(self.connector_type, self.audio_dim, self.llm_dim, self.device, self.dtype, **kw)
+            self.video_connector = create_modality_connector(self.connector_type, self.video_dim, self.llm_dim, self.device, self.dtype, **kw)
         if W is not None:
             if "audio_connector" in W:
                 self.audio_connector.load_state_dict(W["audio_connector"])
             if "video_connector" in W:
                 self.video_connector.load_state_dict(W["video_connector"])
+        if self.train_connectors:
+            self._flatten_connectors()
+
+    def _flatten_connectors(self):
+        """train_connectors=True: the four fp32 masters become views of ONE flat buffer `conn_p` in named_parameters() order (audio weight,
+        audio bias, video weight, video bias) with the gradient buffer `conn_g` beside it, as the LoRA tensors live in lora_p / lora_g: the
+        trainer's clip + AdamW and the data-parallel all-reduce each take them as one more flat buffer."""
+        from .engine import Workspace
+        ps = [p for c in (self.audio_connector, self.video_connector) for p in c.parameters()]
+        n = sum(p.numel() for p in ps)
+        self.conn_p = torch.empty(n, dtype=torch.float32, device=ps[0].device)
+        self.conn_g = torch.zeros(n, dtype=torch.float32, device=ps[0].device)
+        self.conn_slices, off = [], 0
+        for p in ps:
+            view = self.conn_p[off:off + p.numel()].view(p.shape)
+            view.copy_(p.detach())
+            p.data = view
+            self.conn_slices.append((off, off + p.numel(), tuple(p.shape)))
+            off += p.numel()
+        self._conn_ws = {k: Workspace(self.device) for k in ("dx", "da", "dv")}
+        self._conn_geo = None
+
+    def connector_grad_views(self, buf=None):
+        """The four gradient tensors [audio W, audio b, video W, video b] as views of conn_g (or of a buffer laid out like it)."""
+        buf = self.conn_g if buf is None else buf
+        return [buf[a:b].view(shape) for a, b, shape in self.conn_slices]
+
+    def refresh_connectors(self):
+        """After an update of the fp32 masters: rewrite the bf16 operand images (nothing to do in fp32 mode)."""
+        self.audio_connector.refresh()
+        self.video_connector.refresh()
+
+    def _static(self, key, shape):
+        n = 1
+        for d in shape:
+            n *= d
+        n *= 4 if self.dtype == torch.float32 else 2
+        return self._conn_ws[key].get(n)[:n].view(self.dtype).view(shape)
+
+    def _dx_embeds_buffer(self):
+        """Static [B,S,d] buffer for d loss / d inputs_embeds of the last training forward (LlamaEngine.bwd(dx_embeds=...))."""
+        _, _, _, _, S, B = self._conn_geo
+        return self._static("dx", (B, S, self.llm_dim))
+
+    def connector_backward(self):
+        """dx_embeds -> fuse / pool adjoint -> the two weight gradients and bias gradients, written into conn_g (overwritten, not
+        accumulated).  The connectors' INPUT gradient is not formed: the encoders are frozen.  An input that was absent in the forward
+        leaves its connector's gradient as zeros."""
+        Ta, Tv, P, Lc, S, B = self._conn_geo
+        D = self.llm_dim
+        da = self._static("da", (B, Ta, D)) if Ta else None
+        dv = self._static("dv", (B, Tv, D)) if Tv else None
+        ops.fuse_pool_bwd(self._dx_embeds_buffer(), Ta, Tv, P, Lc, self.fusion_scale, da=da, dv=dv)
+        gWa, gba, gWv, gbv = self.connector_grad_views()
+        for dy, conn, gW, gb in ((da, self.audio_connector, gWa, gba), (dv, self.video_connector, gWv, gbv)):
+            if dy is None:
+                gW.zero_(); gb.zero_()
+            else:
+                ops.gemm_wgrad(dy.view(-1, D), conn.saved_input, dW=gW, db=gb)
 
     def _get_llm_dim(self):
         return self.cfg.llama.hidden
@@ -286,12 +365,20 @@ class ClipWhisperModel:
             return None, v, v.shape[1]
         raise ValueError("No valid inputs provided - both audio and video are None")
 
-    def _llm_inputs(self, audio, video, prompt, S_out=None):
-        a, v, Lc = self._features(audio, video)
+    def _llm_inputs(self, audio, video, prompt, S_out=None, keep=False):
+        """keep (train_connectors=True, training forward): the connectors keep the rows they project and the fusion geometry is recorded,
+        which is all connector_backward() needs -- no second encoder pass."""
+        self.audio_connector.keep_input = self.video_connector.keep_input = bool(keep)
+        try:
+            a, v, Lc = self._features(audio, video)
+        finally:
+            self.audio_connector.keep_input = self.video_connector.keep_input = False
         pe = self._embed_prompt(prompt)
         P = pe.shape[1] if pe is not None else 0
         B = (a if a is not None else v).shape[0]
         S = P + Lc if S_out is None else S_out
+        if keep:
+            self._conn_geo = (a.shape[1] if a is not None else 0, v.shape[1] if v is not None else 0, P, Lc, S, B)
         return ops.fuse_pool(a, v, pe, Lc, S, self.fusion_scale, self.llm_dim, B)
 
     def encode(self, audio=None, video=None, prompt=None):
@@ -332,11 +419,14 @@ class ClipWhisperModel:
         else:
             labels = None
         if self.training and labels is not None:
-            x = self._llm_inputs(audio, video, prompt, S_out=labels.shape[1])       # adaptive pool / interpolate (:577-585)
+            x = self._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors)       # adaptive pool / interpolate (:577-585)
             logits = self.llm_engine.fwd_loss(x, labels, want_logits=True, **self._dropout_args())
             acc = self.llm_engine.acc
             loss = acc[0] / acc[1]
-            if self.lora_param is not None and self.lora_param.requires_grad:
+            if self.train_connectors:
+                cps = [p for c in (self.audio_connector, self.video_connector) for p in c.parameters()]
+                loss = _LoraLoss.apply(self.lora_param, self, loss, *cps)
+            elif self.lora_param is not None and self.lora_param.requires_grad:
                 loss = _LoraLoss.apply(self.lora_param, self, loss)
             return {"loss": loss, "logits": logits}
         x = self._llm_inputs(audio, video, prompt)

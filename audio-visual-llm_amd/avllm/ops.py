@@ -431,6 +431,53 @@ def fuse_pool(a, v, prompt_emb, L_, S_out, fusion_scale, D, B):
     return out
 
 
+def fuse_pool_bwd(dx, Ta, Tv, P, L_, fusion_scale, want_a=True, want_v=True, da=None, dv=None):
+    """The adjoint of fuse_pool (avllm_fuse_pool_bwd): dx [B,S_out,D] -> (da [B,Ta,D] | None, dv [B,Tv,D] | None).  Ta / Tv are the forward's row
+    counts (0 = that input was absent); want_a / want_v choose the outputs; da / dv: preallocated outputs (static buffers of a captured step)."""
+    dx = dx.contiguous()
+    B, S_out, D = dx.shape
+    if want_a and Ta and da is None:
+        da = torch.empty(B, Ta, D, device=dx.device, dtype=dx.dtype)
+    if want_v and Tv and dv is None:
+        dv = torch.empty(B, Tv, D, device=dx.device, dtype=dx.dtype)
+    da = da if want_a and Ta else None
+    dv = dv if want_v and Tv else None
+    L.check(L.load().avllm_fuse_pool_bwd(L.ptr(dx), L.ptr(da), Ta, L.ptr(dv), Tv, P, B, L_, S_out, D, fusion_scale, L.dt_of(dx), L.stream_ptr()))
+    return da, dv
+
+
+def gemm_wgrad(dY, X, alpha=1.0, dW=None, db=None, want_db=True):
+    """dW [N,K] (fp32) = alpha * dY^T . X and db [N] (fp32) = alpha * column sums of dY, for dY [M,N], X [M,K] (avllm_gemm_wgrad: no atomics)."""
+    M, N = dY.shape
+    K = X.shape[1]
+    if X.shape[0] != M or X.dtype != dY.dtype:
+        raise ValueError(f"gemm_wgrad: dY {tuple(dY.shape)} {dY.dtype} and X {tuple(X.shape)} {X.dtype} do not match")
+    if dW is None:
+        dW = torch.empty(N, K, device=dY.device, dtype=torch.float32)
+    if db is None and want_db:
+        db = torch.empty(N, device=dY.device, dtype=torch.float32)
+    L.check(L.load().avllm_gemm_wgrad(L.ptr(dY), _ld(dY), L.ptr(X), _ld(X), M, N, K, L.ptr(dW), _ld(dW), L.ptr(db), alpha, L.dt_of(dY),
+                                      L.stream_ptr()))
+    return dW, db
+
+
+def grad_sumsq_multi(gs, out, partials):
+    """out = sum over the buffers `gs` (in order) of sum g^2, in a fixed order (avllm_grad_sumsq_det_multi)."""
+    n = len(gs)
+    ptrs = (L.vp * n)(*[L.ptr(g) for g in gs])
+    lens = (L.i64 * n)(*[g.numel() for g in gs])
+    L.check(L.load().avllm_grad_sumsq_det_multi(ptrs, lens, n, L.ptr(partials), partials.numel(), L.ptr(out), L.stream_ptr()))
+
+
+def adamw_step_multi(segs, lr, step, sumsq=None, max_norm=0.0, beta1=0.9, beta2=0.95, eps=1e-8, prescale=1.0, guard=None, skipped=None, state=None):
+    """One AdamW step over several flat fp32 buffers under one guard decision (avllm_adamw_step_multi).  segs: (p, g, m, v, weight_decay) each."""
+    arr = (L.AdamwSeg * len(segs))()
+    for a, (p, g, m, v, wd) in zip(arr, segs):
+        a.p, a.g, a.m, a.v, a.n, a.weight_decay = L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), wd
+    L.check(L.load().avllm_adamw_step_multi(arr, len(segs), lr, beta1, beta2, eps, step, L.ptr(sumsq), max_norm, prescale, L.ptr(guard),
+                                            L.ptr(skipped), L.ptr(state), L.stream_ptr()))
+
+
 def grad_sumsq(g, out, partials=None):
     """out += sum g^2 (float atomics), or -- with a `partials` scratch tensor (float32, <= 1024 used) -- out = sum g^2 in a fixed order."""
     if partials is not None:

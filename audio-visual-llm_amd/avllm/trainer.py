@@ -3,6 +3,9 @@
 same constructor keywords, batch layouts, return dict and output files.  The step is:
   encoders (HIP) -> fuse/pool (HIP) -> Llama+LoRA fwd+loss (HIP) -> bwd (HIP) [-> RCCL all-reduce, overlapped]
   -> clip_grad_norm_ + AdamW fused on the flat LoRA buffer (HIP) -> cosine LR.
+With a model built with train_connectors=True the backward pass also leaves d(inputs_embeds), the fusion / pooling adjoint and the two weight
+gradients fill the flat connector gradient (one sequential chain after the piece that ends at layer 0), and ONE clip + ONE AdamW step cover
+the LoRA buffer and the connector buffer together (weights decayed, biases not: _setup_optimizer :183-197).
 No `loss.item()` inside the step: the loss stays on the device and is read once per log interval.
 
 The step is graph-replayable: everything that changes from step to step (learning rate, Adam's bias corrections, the LoRA dropout
@@ -54,6 +57,11 @@ class ClipWhisperTrainer:
         self.skipped = torch.zeros(1, device=eng.lora_p.device, dtype=torch.float32)      # optimizer steps skipped on a non-finite loss / gradient
         self.reducer = LoraGradReducer(eng.lora_g, eng.per_layer, eng.cfg.layers)
         dev = eng.lora_p.device
+        # train_connectors=True: the connectors' Adam moments, flat like model.conn_p / model.conn_g (audio W, audio b, video W, video b)
+        self.train_connectors = bool(getattr(model, "train_connectors", False))
+        if self.train_connectors:
+            self.cm = torch.zeros_like(model.conn_p)
+            self.cv = torch.zeros_like(model.conn_p)
         # avllm_step_state on the device: step count, this step's lr / bias corrections / dropout seed
         self.state = torch.zeros(ctypes.sizeof(L.StepState), dtype=torch.uint8, device=dev)
         self._seed_ptr = self.state.data_ptr() + L.StepState.dropout_seed.offset
@@ -101,7 +109,7 @@ class ClipWhisperTrainer:
         model, eng = self.model, self.model.llm_engine
         ops.step_advance(self.state, self.learning_rate, self.total_steps, self.warmup_steps, rank=self._rank)
         labels = model._prep_labels(labels)
-        x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1])
+        x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors)
         p = float(model.lora_dropout) if (model.training and model.use_lora and model.lora_dropout) else 0.0
         eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr)
 
@@ -117,10 +125,36 @@ class ClipWhisperTrainer:
         if i == 0:
             eng.lora_g.zero_()
         hi, lo = self._piece_range(i)
+        if self.train_connectors and lo == 0:
+            # the piece that ends at layer 0 also leaves d(inputs_embeds); the connector backward follows it on the same stream
+            eng.bwd(grad_scale=1.0, count=eng.acc[1:2], after_layer=per_layer_cb, layer_hi=hi, layer_lo=lo, dx_embeds=self.model._dx_embeds_buffer())
+            self.model.connector_backward()
+            return
         eng.bwd(grad_scale=1.0, count=eng.acc[1:2], after_layer=per_layer_cb, layer_hi=hi, layer_lo=lo)
+
+    def _connector_segments(self):
+        """(p, g, m, v, weight_decay) per connector tensor: weights decay, biases do not (_setup_optimizer :183-197)."""
+        m = self.model
+        return [(m.conn_p[a:b], m.conn_g[a:b], self.cm[a:b], self.cv[a:b], self.weight_decay if len(shape) == 2 else 0.0)
+                for a, b, shape in m.conn_slices]
+
+    def _part_opt_connectors(self):
+        """clip_grad_norm_(model.parameters()) is ONE global norm over connector and LoRA gradients (trainer :457-460), formed in a fixed
+        order; the update of every buffer is ONE launch under one guard decision, so a non-finite step is skipped -- and counted, and the
+        step count taken back -- exactly once, with no buffer touched."""
+        eng = self.model.llm_engine
+        ops.grad_sumsq_multi([self.model.conn_g, eng.lora_g], self.sumsq, self._sumsq_parts)
+        segs = self._connector_segments() + [(eng.lora_p, eng.lora_g, self.m, self.v, self.weight_decay)]
+        ops.adamw_step_multi(segs, 0.0, 0, sumsq=self.sumsq, max_norm=self.grad_clip or 0.0, guard=eng.acc[0:1], skipped=self.skipped,
+                             state=self.state)
+        eng.pack_lora()
+        self.model.refresh_connectors()
+        torch.div(eng.acc[0], eng.acc[1], out=self._loss_buf)
 
     def _part_opt(self):
         eng = self.model.llm_engine
+        if self.train_connectors:
+            return self._part_opt_connectors()
         ops.grad_sumsq(eng.lora_g, self.sumsq, partials=self._sumsq_parts)
         # NaN/Inf guard of trainer :444-452 without a host sync: a non-finite (all-reduced) loss sum or gradient norm makes the update a
         # no-op on every rank alike (the all-reduce spreads the NaN), leaving lora_p, m and v untouched; `skipped_steps` counts them and
@@ -151,6 +185,8 @@ class ClipWhisperTrainer:
                 self._part_bwd(i)
                 hi, lo = self._piece_range(i)
                 self.reducer.layers_done(lo, hi)
+        if self.train_connectors:
+            self.reducer.bucket_done(self.model.conn_g)      # one more bucket after the last backward piece, in every step path alike
         self.reducer.finish()
         self._part_opt()
 
@@ -200,6 +236,8 @@ class ClipWhisperTrainer:
             g.replay()
             hi, lo = self._piece_range(i)
             self.reducer.layers_done(lo, hi)
+        if self.train_connectors:
+            self.reducer.bucket_done(self.model.conn_g)
         self.reducer.finish()
         st["opt"].replay()
 
@@ -351,17 +389,26 @@ class ClipWhisperTrainer:
         path = os.path.join(self.output_dir, name)
         eng = self.model.llm_engine
         state, n = {}, 0
+        no_decay = []
+        if self.train_connectors:
+            # connectors first, then LoRA: named_parameters() order, as a torch optimizer over the reference's parameter list numbers them
+            for cm, cv, (_, _, shape) in zip(self.model.connector_grad_views(self.cm), self.model.connector_grad_views(self.cv), self.model.conn_slices):
+                state[n] = {"step": torch.tensor(float(self.global_step)), "exp_avg": cm.detach().cpu().clone(), "exp_avg_sq": cv.detach().cpu().clone()}
+                if len(shape) == 1:
+                    no_decay.append(n)
+                n += 1
         mv, vv = eng.lora_views(self.m), eng.lora_views(self.v)
-        for i, key in enumerate(self._lora_keys()):
+        for key in self._lora_keys():
             _, _, _, _, _, li, _, mod, ab, _, _ = key.split(".")
             short = f"layers.{li}.{mod}.{ab}"
-            state[i] = {"step": torch.tensor(float(self.global_step)), "exp_avg": mv[short].detach().cpu().clone(), "exp_avg_sq": vv[short].detach().cpu().clone()}
+            state[n] = {"step": torch.tensor(float(self.global_step)), "exp_avg": mv[short].detach().cpu().clone(), "exp_avg_sq": vv[short].detach().cpu().clone()}
             n += 1
         group = {"lr": self.lr_at(self.global_step), "betas": (0.9, 0.95), "eps": 1e-8, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None, "initial_lr": self.learning_rate,
-                 "params": list(range(n))}
+                 "params": [i for i in range(n) if i not in no_decay]}
+        groups = [group] + ([dict(group, weight_decay=0.0, params=no_decay)] if no_decay else [])      # biases: weight_decay 0 (:183-197)
         torch.save({"epoch": epoch, "model_state_dict": self.model.state_dict(),
-                    "optimizer_state_dict": {"state": state, "param_groups": [group]},
+                    "optimizer_state_dict": {"state": state, "param_groups": groups},
                     "scheduler_state_dict": {"T_max": self.total_steps, "eta_min": 0.0, "base_lrs": [self.learning_rate], "last_epoch": self.global_step,
                                              "_step_count": self.global_step + 1, "_last_lr": [self.lr_at(self.global_step)]},
                     "train_losses": self.train_losses, "val_losses": self.val_losses, "best_val_loss": self.best_val_loss}, path)
@@ -382,6 +429,14 @@ class ClipWhisperTrainer:
         elif "state" in o:
             ids = sorted(int(k) for k, st in o["state"].items() if isinstance(st, dict) and "exp_avg" in st)
             keys = self._lora_keys()
+            if self.train_connectors and len(ids) == len(keys) + 4:      # connectors first (named_parameters() order), then LoRA
+                cms, cvs = self.model.connector_grad_views(self.cm), self.model.connector_grad_views(self.cv)
+                for idx, cm, cv in zip(ids[:4], cms, cvs):
+                    st = o["state"][idx] if idx in o["state"] else o["state"][str(idx)]
+                    if tuple(st["exp_avg"].shape) != tuple(cm.shape):
+                        raise ValueError(f"optimizer state {idx} has shape {tuple(st['exp_avg'].shape)}, the connector tensor is {tuple(cm.shape)}")
+                    cm.copy_(st["exp_avg"]); cv.copy_(st["exp_avg_sq"])
+                ids = ids[4:]
             if len(ids) != len(keys):
                 raise ValueError(f"optimizer state has {len(ids)} tensors with moments, the model has {len(keys)} LoRA tensors")
             mv, vv = eng.lora_views(self.m), eng.lora_views(self.v)

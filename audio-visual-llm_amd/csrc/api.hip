@@ -145,6 +145,17 @@ int avllm_clip_patchify(const float* frames, void* cols, int32_t N, int32_t S, i
 int avllm_clip_cls_rows(const void* ce, const void* pos, void* x, int32_t N, int32_t tokens, int32_t d, int32_t dtype, void* stream) { return av_clip_cls_rows(ce, pos, x, N, tokens, d, dtype, ST); }
 int avllm_fuse_pool(const void* a, int32_t Ta, const void* v, int32_t Tv, const void* pe, int32_t P, void* out, int32_t B, int32_t L,
                     int32_t S_out, int32_t D, float fs, int32_t dtype, void* stream) { return av_fuse_pool(a, Ta, v, Tv, pe, P, out, B, L, S_out, D, fs, dtype, ST); }
+int avllm_fuse_pool_bwd(const void* dx, void* da, int32_t Ta, void* dv, int32_t Tv, int32_t P, int32_t B, int32_t L, int32_t S_out, int32_t D,
+                        float fs, int32_t dtype, void* stream) { return av_fuse_pool_bwd(dx, da, Ta, dv, Tv, P, B, L, S_out, D, fs, dtype, ST); }
+int avllm_gemm_wgrad(const void* dY, int64_t ldy, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, float* dW, int64_t ldw, float* db,
+                     float alpha, int32_t dtype, void* stream) { return av_gemm_wgrad(dY, ldy, X, ldx, M, N, K, dW, ldw, db, alpha, dtype, ST); }
+int avllm_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int32_t nbuf, float* partials, int32_t nparts, float* sumsq, void* stream) {
+    return av_grad_sumsq_det_multi(g, n, nbuf, partials, nparts, sumsq, ST);
+}
+int avllm_adamw_step_multi(const avllm_adamw_seg* segs, int32_t nseg, float lr, float b1, float b2, float eps, int32_t step, const float* sumsq,
+                           float max_norm, float prescale, const float* guard, float* skipped, const avllm_step_state* state, void* stream) {
+    return av_adamw_step_multi(segs, nseg, lr, b1, b2, eps, step, sumsq, max_norm, prescale, guard, skipped, state, ST);
+}
 int avllm_grad_sumsq(const float* g, int64_t n, float* sumsq, void* stream) { return av_grad_sumsq(g, n, sumsq, ST); }
 int avllm_grad_sumsq_det(const float* g, int64_t n, float* partials, int32_t nparts, float* sumsq, void* stream) { return av_grad_sumsq_det(g, n, partials, nparts, sumsq, ST); }
 int avllm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,

@@ -311,6 +311,70 @@ __global__ void fuse_pool_kernel(const T* __restrict__ a, int Ta, const T* __res
     }
 }
 
+// The adjoint of fuse_pool_kernel for a and v, in gather form: block (t, b) owns source row t of both inputs, i.e. virtual row j = P + t, and adds
+// the dx rows i whose window / stencil names j in ascending i (fp32, no atomics: bit-reproducible).  The candidate range [i0, i1] is a superset
+// found from j; membership and weight are then decided by the forward's own expressions, so both sides agree on every boundary.
+template <typename T, int VEC>
+__global__ void fuse_pool_bwd_kernel(const T* __restrict__ dx, T* __restrict__ da, int Ta, T* __restrict__ dv, int Tv, int P, int L,
+                                     int S_out, int D, float fs) {
+    const int b = blockIdx.y, t = blockIdx.x;
+    const int Lt = P + L, j = P + t;
+    const bool both = Ta > 0 && Tv > 0;
+    const float scale = (Lt < S_out && S_out > 1) ? (float)(Lt - 1) / (float)(S_out - 1) : 0.f;
+    int i0 = 0, i1 = -1;                  // t >= L: the forward truncated this row, its gradient is zero
+    if (t < L) {
+        if (Lt == S_out) { i0 = i1 = j; }
+        else if (Lt > S_out) {            // windows [floor(i Lt / S), ceil((i + 1) Lt / S)) that contain j
+            i0 = (int)(((long)j * S_out) / Lt);
+            i1 = (int)((((long)(j + 1)) * S_out - 1) / Lt);
+        } else if (scale > 0.f) {         // stencil rows lo = floor(scale i), hi = lo + 1: scale i in (j - 1, j + 1), widened by one row each way
+            i0 = (int)floorf((float)(j - 1) / scale) - 1;
+            i1 = (int)ceilf((float)(j + 1) / scale) + 1;
+        } else { i0 = 0; i1 = S_out - 1; }
+        i0 = i0 < 0 ? 0 : i0;
+        i1 = i1 > S_out - 1 ? S_out - 1 : i1;
+    }
+    for (int c = (int)threadIdx.x * VEC; c < D; c += (int)blockDim.x * VEC) {
+        float g[VEC], r[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) g[k] = 0.f;
+        for (int i = i0; i <= i1; ++i) {
+            const T* src = dx + ((long)b * S_out + i) * D + c;
+            if (Lt == S_out) {
+                load_f<VEC>(src, g);
+            } else if (Lt > S_out) {
+                const int s = (int)(((long)i * Lt) / S_out);
+                const int e = (int)((((long)(i + 1)) * Lt + S_out - 1) / S_out);
+                if (j < s || j >= e) continue;
+                const float cnt = (float)(e - s);
+                load_f<VEC>(src, r);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) g[k] += r[k] / cnt;
+            } else {
+                const float sp = scale * i;
+                const int lo = (int)sp;
+                const int hi = lo + 1 < Lt ? lo + 1 : Lt - 1;
+                if (lo != j && hi != j) continue;
+                const float w1 = sp - (float)lo, w0 = 1.0f - w1;
+                const float wgt = (lo == j ? w0 : 0.f) + (hi == j ? w1 : 0.f);      // lo == hi at the clamped last row: both weights
+                load_f<VEC>(src, r);
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) g[k] += wgt * r[k];
+            }
+        }
+        if (da && t < Ta) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) r[k] = both ? fs * g[k] : g[k];
+            store_f<VEC>(da + ((long)b * Ta + t) * D + c, r);
+        }
+        if (dv && t < Tv) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) r[k] = both ? (1.0f - fs) * g[k] : g[k];
+            store_f<VEC>(dv + ((long)b * Tv + t) * D + c, r);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- LoRA operand packing
 template <typename T>
 __global__ void lora_pack_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int r, int din, int dout,
@@ -516,6 +580,20 @@ int av_fuse_pool(const void* a, int Ta, const void* v, int Tv, const void* promp
     const dim3 grid(S_out, B), block(D / 4 < 256 ? (D / 4 + 63) / 64 * 64 : 256);
     if (dtype == AV_F32) hipLaunchKernelGGL((fuse_pool_kernel<float>), grid, block, 0, st, (const float*)a, Ta, (const float*)v, Tv, (const float*)prompt_emb, P, (float*)out, L, S_out, D, fs);
     else hipLaunchKernelGGL((fuse_pool_kernel<bf16>), grid, block, 0, st, (const bf16*)a, Ta, (const bf16*)v, Tv, (const bf16*)prompt_emb, P, (bf16*)out, L, S_out, D, fs);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_fuse_pool_bwd(const void* dx, void* da, int Ta, void* dv, int Tv, int P, int B, int L, int S_out, int D, float fs, int dtype, hipStream_t st) {
+    AV_CHECK_ARG(dx && (da || dv) && B > 0 && L > 0 && S_out > 0 && P >= 0 && D > 0 && D % 4 == 0, "fuse_pool_bwd: bad args");
+    AV_CHECK_ARG((!da || Ta > 0) && (!dv || Tv > 0) && Ta >= 0 && Tv >= 0, "fuse_pool_bwd: an output without rows (Ta=%d Tv=%d)", Ta, Tv);
+    const int rows = (da ? Ta : 0) > (dv ? Tv : 0) ? (da ? Ta : 0) : (dv ? Tv : 0);
+    // bf16 rows of whole 16-byte vectors take them; everything else 4 elements per thread (the forward's form)
+    const int vec = dtype == AV_BF16 && D % 8 == 0 ? 8 : 4;
+    const dim3 grid(rows, B), block(D / vec < 256 ? (D / vec + 63) / 64 * 64 : 256);
+    if (dtype == AV_F32) hipLaunchKernelGGL((fuse_pool_bwd_kernel<float, 4>), grid, block, 0, st, (const float*)dx, (float*)da, Ta, (float*)dv, Tv, P, L, S_out, D, fs);
+    else if (vec == 8) hipLaunchKernelGGL((fuse_pool_bwd_kernel<bf16, 8>), grid, block, 0, st, (const bf16*)dx, (bf16*)da, Ta, (bf16*)dv, Tv, P, L, S_out, D, fs);
+    else hipLaunchKernelGGL((fuse_pool_bwd_kernel<bf16, 4>), grid, block, 0, st, (const bf16*)dx, (bf16*)da, Ta, (bf16*)dv, Tv, P, L, S_out, D, fs);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

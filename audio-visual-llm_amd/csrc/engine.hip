@@ -486,6 +486,12 @@ extern "C" int avllm_llama_lora_bwd(const avllm_llama* m, const int64_t* labels,
 extern "C" int avllm_llama_lora_bwd_layers(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
                                            float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
                                            avllm_layer_cb after_layer, void* user, void* stream) {
+    return avllm_llama_lora_bwd_layers_dx(m, labels, B, S, count, grad_scale, ws, ws_bytes, layer_hi, layer_lo, after_layer, user, nullptr, stream);
+}
+
+extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
+                                              float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
+                                              avllm_layer_cb after_layer, void* user, void* dx_embeds, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     AV_TRY(check_llama(m));
     AV_CHECK_ARG(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi < m->layers, "llama_lora_bwd_layers: bad layer range [%d, %d]", layer_lo, layer_hi);
@@ -599,7 +605,7 @@ extern "C" int avllm_llama_lora_bwd_layers(const avllm_llama* m, const int64_t* 
             if (lj.ld_at != 3 * AVLLM_LORA_PAD ||
                 (const char*)lj.AT_pad != (const char*)P.lora[0].AT_pad + (size_t)j * AVLLM_LORA_PAD * es) contiguous = false;
         }
-        if (l > 0) {      // d(inputs_embeds) is not needed: encoders/connectors are frozen
+        if (l > 0 || dx_embeds) {      // layer 0: d(inputs_embeds) only when the caller trains the connectors (frozen otherwise: SURVEY.md fact 4)
             AV_CHECK_ARG(!any || contiguous || drop, "llama_lora_bwd: q/k/v AT_pad images must be the three 64-column slices of one [d,192] matrix");
             g = gemm_desc(dt, w.dqkv, qw, P.wqkv_t, qw, w.dxn, d, M, d, qw);
             if (any && !drop) { g.A2 = w.dtqkv; g.lda2 = 3 * AVLLM_LORA_PAD; g.B2 = P.lora[0].AT_pad; g.ldb2 = 3 * AVLLM_LORA_PAD; g.K2 = 3 * AVLLM_LORA_PAD; }
@@ -624,7 +630,7 @@ extern "C" int avllm_llama_lora_bwd_layers(const avllm_llama* m, const int64_t* 
                     AV_TRY(av_gemm(&gm, st));
                 }
             }
-            AV_TRY(av_rmsnorm_bwd(w.dxn, resid[l], P.ln1_w, a.rstd1, w.dres, w.dres, M, d, dt, st));
+            AV_TRY(av_rmsnorm_bwd(w.dxn, resid[l], P.ln1_w, a.rstd1, w.dres, l > 0 ? w.dres : dx_embeds, M, d, dt, st));      // layer 0: d resid[0]
         }
         if (after_layer) after_layer(l, user);
     }

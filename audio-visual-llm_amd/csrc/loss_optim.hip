@@ -182,6 +182,46 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     }
 }
 
+// The same rule over several segments (LoRA buffer, connector weights, connector biases: each with its own decay) as ONE optimizer step: every
+// block takes the same guard decision from the same two words, and block (0, 0) alone does the bookkeeping of a skipped step, once.
+// Segment i owns the workgroups [first[i], first[i + 1]) of the one-dimensional grid, sized by its own length: a 4096-element bias does not
+// launch the thousands of workgroups the LoRA buffer needs.
+struct AdamSegs { avllm_adamw_seg s[8]; int first[9]; int nseg; };
+__global__ void adamw_multi_kernel(AdamSegs segs, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
+                                   const float* __restrict__ sumsq, float max_norm, float prescale, const float* __restrict__ guard,
+                                   float* __restrict__ skipped, avllm_step_state* __restrict__ state) {
+    if (state) { lr = state->lr; bc1 = state->bc1; bc2_sqrt = state->bc2_sqrt; }
+    const bool bad = (sumsq && !isfinite(sumsq[0])) || (guard && !isfinite(guard[0]));
+    if (bad) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (skipped) atomicAdd(skipped, 1.0f);
+            if (state) { atomicAdd(&state->skipped, 1.0f); if (state->step > 0) state->step -= 1; }      // see adamw_kernel
+        }
+        return;
+    }
+    float coef = prescale;
+    if (sumsq && max_norm > 0.f) {
+        const float norm = sqrtf(sumsq[0]) * prescale;
+        coef *= fminf(1.0f, max_norm / (norm + 1e-6f));
+    }
+    int si = 0;
+    while (si + 1 < segs.nseg && (int)blockIdx.x >= segs.first[si + 1]) ++si;
+    const avllm_adamw_seg& sg = segs.s[si];
+    float* __restrict__ p = sg.p; float* __restrict__ m = sg.m; float* __restrict__ v = sg.v;
+    const float* __restrict__ g = sg.g;
+    const float wd = sg.weight_decay;
+    const long nblk = segs.first[si + 1] - segs.first[si];
+    for (long i = (blockIdx.x - segs.first[si]) * (long)blockDim.x + threadIdx.x; i < sg.n; i += nblk * blockDim.x) {
+        const float gi = g[i] * coef;
+        float pi = p[i] * (1.0f - lr * wd);
+        const float mi = m[i] * b1 + gi * (1.0f - b1);
+        const float vi = v[i] * b2 + gi * gi * (1.0f - b2);
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        pi -= (lr / bc1) * (mi / denom);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+}
+
 // out[i,j] += alpha * sum_m P[m,i] Q[m,j].  One of I,J is the LoRA rank (<=64), the other the model width.
 // Tile: 64 (i) x 64 (j) outputs per block, M split over gridDim.z chunks, fp32 atomics into `out`
 // (<= 32 adders per element; float atomics keep the sum in fp32 -- MI355X_MICROARCH "Global float atomics").
@@ -282,6 +322,50 @@ int av_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr
     long blocks = (n + 255) / 256;
     blocks = blocks > 4096 ? 4096 : blocks;
     hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, sumsq, max_norm, grad_prescale, guard, skipped, (avllm_step_state*)state);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int nbuf, float* partials, int nparts, float* sumsq, hipStream_t st) {
+    AV_CHECK_ARG(g && n && sumsq && partials && nbuf >= 1 && nbuf <= 8 && nparts >= nbuf, "grad_sumsq_det_multi: bad args");
+    // The <= 1024 partial slots are shared between the buffers in proportion to their lengths (at least one each), so a large buffer keeps
+    // its share of the chip whatever precedes it; the split depends on the lengths alone, so the order of the additions is fixed.
+    const int slots = nparts > 1024 ? 1024 : nparts;
+    long total = 0;
+    for (int i = 0; i < nbuf; ++i) {
+        AV_CHECK_ARG(g[i] && n[i] > 0, "grad_sumsq_det_multi: buffer %d is empty", i);
+        total += n[i];
+    }
+    int used = 0;
+    for (int i = 0; i < nbuf; ++i) {      // buffer i's partials follow buffer i-1's: the final pass adds them in index order
+        long share = (long)((double)n[i] / (double)total * (double)(slots - nbuf)) + 1;
+        long blocks = (n[i] / 4 + 255) / 256;
+        blocks = blocks < 1 ? 1 : (blocks > share ? share : blocks);
+        hipLaunchKernelGGL(sumsq_partial_kernel, dim3(blocks), dim3(256), 0, st, g[i], (long)n[i], partials + used);
+        used += (int)blocks;
+    }
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, partials, used, sumsq);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_adamw_step_multi(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq, float max_norm,
+                        float grad_prescale, const float* guard, float* skipped, const avllm_step_state* state, hipStream_t st) {
+    AV_CHECK_ARG(segs && nseg >= 1 && nseg <= 8 && (step >= 1 || state), "adamw_multi: bad args");
+    AdamSegs a = {};
+    a.nseg = nseg;
+    for (int i = 0; i < nseg; ++i) {
+        AV_CHECK_ARG(segs[i].p && segs[i].g && segs[i].m && segs[i].v && segs[i].n > 0, "adamw_multi: segment %d is null / empty", i);
+        a.s[i] = segs[i];
+        long blocks = (segs[i].n + 255) / 256;
+        blocks = blocks > 4096 ? 4096 : blocks;      // as avllm_adamw_step sizes a buffer of this length
+        a.first[i + 1] = a.first[i] + (int)blocks;
+    }
+    if (step < 1) step = 1;
+    const float bc1 = 1.0f - (float)pow((double)b1, step);
+    const float bc2s = (float)sqrt(1.0 - pow((double)b2, step));
+    hipLaunchKernelGGL(adamw_multi_kernel, dim3(a.first[nseg]), dim3(256), 0, st, a, lr, b1, b2, eps, bc1, bc2s, sumsq, max_norm, grad_prescale, guard,
+                       skipped, (avllm_step_state*)state);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

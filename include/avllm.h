@@ -87,6 +87,15 @@ int avllm_gemm_tn(const void* P, int64_t ldp, int32_t I, const void* Q, int64_t 
 int avllm_gemm_tn_drop(const void* P, int64_t ldp, int32_t I, const void* Q, int64_t ldq, int32_t J, int32_t M,
                        float* out, int64_t ldo, float alpha, uint32_t drop_seed, float drop_p, int32_t dtype, void* stream);
 
+/* Weight gradient of a Linear (autograd of nn.Linear: SimpleModalityConnector.linear, modality_connector.py:25-44, reached by the loss when
+ * the connectors train, clip_whisper_model.py:1096-1106,1136-1146):  dW[N,K] (f32, row stride ldw, OVERWRITTEN) = alpha * dY^T . X with
+ * dY [M,N] (row stride ldy) and X [M,K] (row stride ldx), both row-major over the reduction index m and of `dtype`; db[N] (f32, may be NULL)
+ * = alpha * sum_m dY[m,n].  One workgroup owns an output tile for the whole of M and db is summed in a fixed order: no float atomics, two
+ * launches are bit-identical.  bf16: both operands through LDS, MFMA fragments by transposed LDS reads, fp32 accumulators; fp32: a scalar
+ * kernel (parity mode).  Any M >= 1; N, K, ldy, ldx must be multiples of 8 and dY, X 16-byte aligned (anything else is refused). */
+int avllm_gemm_wgrad(const void* dY, int64_t ldy, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, float* dW, int64_t ldw,
+                     float* db, float alpha, int32_t dtype, void* stream);
+
 /* The q / k / v adapters of one decoder layer batched (bf16, rank <= 16, 1..3 adapters; peft lora.Linear on q_proj, k_proj, v_proj,
  * clip_whisper_model.py:961-1005).  Rank-side products C_j[M,64] = alpha * A_j[M,K_j] B_j[R,K_j]^T (columns >= 16 written as zeros):
  * shared != 0: every adapter reads A[0] through its own dropout mask (forward lora_A(dropout(x))); shared == 0: adapter j reads A[j]
@@ -310,6 +319,14 @@ int avllm_clip_cls_rows(const void* class_emb, const void* pos, void* x, int32_t
 int avllm_fuse_pool(const void* a, int32_t Ta, const void* v, int32_t Tv, const void* prompt_emb, int32_t P,
                     void* out, int32_t B, int32_t L, int32_t S_out, int32_t D, float fusion_scale, int32_t dtype,
                     void* stream);
+/* The adjoint of avllm_fuse_pool with respect to a and v (autograd through clip_whisper_model.py:320-374,426-450,621-707; the prompt's P
+ * virtual rows receive no gradient here).  dx [B,S_out,D]; da [B,Ta,D] and / or dv [B,Tv,D] are OVERWRITTEN (either may be NULL).  Ta, Tv
+ * describe the forward call: Ta == 0 or Tv == 0 means that input was absent (the other alone, scale 1); with both present da carries
+ * fusion_scale and dv 1 - fusion_scale.  Rows t >= L of a longer input are written as zeros (the forward truncated them).  Gather form: every
+ * output element adds the dx rows whose pooling window / interpolation stencil names it, in ascending row order, in fp32: no atomics, two
+ * launches are bit-identical. */
+int avllm_fuse_pool_bwd(const void* dx, void* da, int32_t Ta, void* dv, int32_t Tv, int32_t P, int32_t B, int32_t L, int32_t S_out,
+                        int32_t D, float fusion_scale, int32_t dtype, void* stream);
 /* clip_grad_norm_ + AdamW (trainer/clip_whisper_trainer.py:457-464,171-232) on a flat fp32 buffer, no host sync:
  * sumsq accumulates sum(g^2); the step reads it, clips with coef=min(1,max_norm/(sqrt(sumsq)+1e-6)).
  * Non-finite guard (trainer :444-452 skips backward + optimizer on a NaN/Inf loss): when *sumsq or *guard (e.g. the step's
@@ -324,6 +341,23 @@ int avllm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 /* state_dev != NULL: lr and the bias corrections come from *state_dev (the `lr` and `step` arguments are ignored); a skipped step is
  * also counted in state_dev->skipped and takes state_dev->step back by one, so that neither the schedule nor Adam's bias corrections
  * advance on it (the reference skips optimizer.step() AND scheduler.step(), trainer/clip_whisper_trainer.py:444-452). */
+/* The same two operations over several flat buffers as ONE optimizer step (clip_grad_norm_(model.parameters()) is one global norm,
+ * trainer :457-460; _setup_optimizer :183-197 gives weights `weight_decay` and biases 0): the sum of squares runs over the nbuf buffers in
+ * index order with fixed-order partials (nparts >= nbuf; the <= 1024 slots are shared in proportion to the buffers' lengths), and the AdamW launch updates every segment (host array, nseg <= 8) under ONE
+ * guard decision: a non-finite *sumsq / *guard leaves every segment untouched, adds 1 to *skipped and to state_dev->skipped once and takes
+ * state_dev->step back once. */
+int avllm_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int32_t nbuf, float* partials, int32_t nparts, float* sumsq,
+                               void* stream);
+typedef struct avllm_adamw_seg {
+    float *p, *m, *v;
+    const float* g;
+    int64_t n;
+    float weight_decay;
+    int32_t reserved;
+} avllm_adamw_seg;
+int avllm_adamw_step_multi(const avllm_adamw_seg* segs, int32_t nseg, float lr, float beta1, float beta2, float eps, int32_t step,
+                           const float* sumsq, float max_norm, float grad_prescale, const float* guard, float* skipped,
+                           const avllm_step_state* state_dev, void* stream);
 /* build the four padded operand images of one LoRA pair from the fp32 masters A [r,din], B [dout,r]:
  * A_pad [64,din], AT_pad [din,64] (row stride ld_at), B_pad [dout,64], BT_pad [64,dout] in `dtype` */
 int avllm_lora_pack(const float* A, const float* Bm, int32_t r, int32_t din, int32_t dout, void* A_pad, void* AT_pad,
@@ -495,6 +529,14 @@ int avllm_llama_lora_bwd(const avllm_llama* m, const int64_t* labels, int32_t B,
 int avllm_llama_lora_bwd_layers(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
                                 float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
                                 avllm_layer_cb after_layer, void* user, void* stream);
+/* The same with the gradient of the loss with respect to inputs_embeds (what the connectors need when they train: with
+ * freeze_encoders=False the reference's autograd carries it on through encode(), clip_whisper_model.py:1096-1106,1136-1146).  dx_embeds
+ * [B*S, d] in the engine dtype, may be NULL (= the call above).  When it is given and the piece reaches layer_lo == 0, layer 0 also runs
+ * the dqkv . Wqkv product with the adapters' input gradient and the input-RMSNorm backward that layers > 0 run, and d resid[0] is left in
+ * dx_embeds.  The workspace layout is unchanged. */
+int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
+                                   float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
+                                   avllm_layer_cb after_layer, void* user, void* dx_embeds, void* stream);
 
 /* Inference: prefill on inputs_embeds and single-token steps with a KV cache (llm.generate,
  * clip_whisper_model.py:1337-1340 -> GenerationMixin greedy).  kcache/vcache [layers][B][Tmax][d].

@@ -24,6 +24,8 @@ def parse_args():
     p.add_argument("--fp16", action="store_true", default=None); p.add_argument("--use_4bit", action="store_true", default=None)
     p.add_argument("--no_lora", action="store_true"); p.add_argument("--lora_r", type=int); p.add_argument("--lora_alpha", type=int)
     p.add_argument("--connector_type", default=None); p.add_argument("--max_grad_norm", type=float)
+    p.add_argument("--train_connectors", action="store_true", default=None,
+                   help="train the two modality connectors (encoders stay frozen); YAML key model.train_connectors")
     p.add_argument("--log_interval", type=int); p.add_argument("--save_every", type=int); p.add_argument("--resume_from")
     p.add_argument("--save_steps", type=int, default=None, help="stored by the trainer and never acted on, as in the reference (clip_whisper_trainer.py:94-102)")
     p.add_argument("--log_param_updates", action="store_true", help="accepted for command-line compatibility; the reference stores it and never reads it (:118)")
@@ -59,7 +61,7 @@ def main():
     cfg = merged(a.config, {"output_dir": a.output_dir, "path": a.data_path, "llm_path": a.llm_path, "whisper_model": a.whisper_model,
                             "clip_model": a.clip_model, "modality": a.modality, "batch_size": a.batch_size, "num_epochs": a.max_epochs,
                             "learning_rate": a.learning_rate, "max_seq_len": a.max_seq_len, "use_fp16": a.fp16, "use_4bit": a.use_4bit,
-                            "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type,
+                            "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type, "train_connectors": a.train_connectors,
                             "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
                             "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None})
     os.makedirs(cfg["output_dir"], exist_ok=True)
@@ -81,7 +83,8 @@ def main():
                              lora_r=cfg.get("lora_r", 16), lora_alpha=cfg.get("lora_alpha", 32), lora_dropout=cfg.get("lora_dropout", 0.05),
                              freeze_encoders=cfg.get("freeze_encoders", True), modality=cfg.get("modality", "both"),
                              max_seq_len=cfg.get("max_seq_len", 256), fusion_scale=cfg.get("fusion_scale", 0.5),
-                             connector_type=cfg.get("connector_type", "simple"), synthetic_weights=a.synthetic_weights or a.tiny, **kw)
+                             connector_type=cfg.get("connector_type", "simple"), train_connectors=bool(cfg.get("train_connectors", False)),
+                             synthetic_weights=a.synthetic_weights or a.tiny, **kw)
     if a.synthetic:
         frames = a.frames if not a.tiny else 5
         ds = SyntheticClips(a.synthetic, model.cfg, frames, model.tokenizer, cfg.get("seed", 42))
