@@ -134,17 +134,27 @@ def swiglu_bwd(dh, gu):
     return dgu
 
 
-def attention_fwd(qkv, B, T, H, hd, causal, scale=None, impl=0, want_lse=True, kv_heads=None):
-    """qkv [B*T, (H + 2*kv_heads)*hd] fused rows [q | k | v] -> (o [B*T, H*hd], lse [B,H,T])."""
+def attention_fwd(qkv, B, T, H, hd, causal, scale=None, impl=0, want_lse=True, kv_heads=None, Tk=None, k=None, v=None, out=None):
+    """qkv [B*T, (H + 2*kv_heads)*hd] fused rows [q | k | v] -> (o [B*T, H*hd], lse [B,H,T]).
+    k=, v= (both or neither): separate operands, each a [rows, heads*hd] view with its own row stride; qkv is then q alone [B*T, H*hd] and k, v
+    hold B*Tk rows (Tk defaults to T; causal query t sees keys <= t + Tk - T).  out=: a [B*T, H*hd] view to write o into (row stride free)."""
     d = H * hd
     dkv = (kv_heads or H) * hd
-    o = torch.empty(B * T, d, device=qkv.device, dtype=qkv.dtype)
+    Tk = T if Tk is None else Tk
+    assert (k is None) == (v is None) and (k is not None or Tk == T)
+    o = torch.empty(B * T, d, device=qkv.device, dtype=qkv.dtype) if out is None else out
+    assert o.shape == (B * T, d) and o.dtype == qkv.dtype
     lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32) if want_lse else None
     es = qkv.element_size()
     scale = hd ** -0.5 if scale is None else scale
     p = L.ptr(qkv)
-    L.check(L.load().avllm_attention_fwd(p, p + d * es, p + (d + dkv) * es, L.ptr(o), L.ptr(lse), B, T, T, H, hd, _ld(qkv), _ld(qkv),
-                                         _ld(qkv), d, scale, int(causal), L.dt_of(qkv), impl, kv_heads or 0, L.stream_ptr()))
+    if k is None:
+        pk, pv, ldk, ldv = p + d * es, p + (d + dkv) * es, _ld(qkv), _ld(qkv)
+    else:
+        assert qkv.shape == (B * T, d) and k.shape == (B * Tk, dkv) and v.shape == k.shape and k.dtype == qkv.dtype and v.dtype == qkv.dtype
+        pk, pv, ldk, ldv = L.ptr(k), L.ptr(v), _ld(k), _ld(v)
+    L.check(L.load().avllm_attention_fwd(p, pk, pv, L.ptr(o), L.ptr(lse), B, T, Tk, H, hd, _ld(qkv), ldk, ldv, _ld(o), scale, int(causal),
+                                         L.dt_of(qkv), impl, kv_heads or 0, L.stream_ptr()))
     return o, lse
 
 
@@ -162,17 +172,25 @@ def attention_fwd_mxq(qkv, B, T, H, hd, scale=None):
     return q, s
 
 
-def attention_bwd(qkv, o, dout, lse, B, T, H, hd, causal, scale=None, impl=0, kv_heads=None):
+def attention_bwd(qkv, o, dout, lse, B, T, H, hd, causal, scale=None, impl=0, kv_heads=None, rope_tab=None, out=None):
+    """-> dqkv [dq | dk | dv] in qkv's layout (out=: a view of qkv's shape to write into, row stride free).  rope_tab (ops.rope_table's f32
+    [T, hd/2, 2]): the inverse rotary is fused into dq | dk (avllm_attention_bwd_rope: bf16, impl 0, head_dim 64 / 128 only)."""
     d = H * hd
     dkv = (kv_heads or H) * hd
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.empty_like(qkv) if out is None else out
+    assert dqkv.shape == qkv.shape and dqkv.dtype == qkv.dtype
     delta = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
     es = qkv.element_size()
     scale = hd ** -0.5 if scale is None else scale
     p, g = L.ptr(qkv), L.ptr(dqkv)
-    L.check(L.load().avllm_attention_bwd(p, p + d * es, p + (d + dkv) * es, L.ptr(o), L.ptr(dout), L.ptr(lse), g, g + d * es, g + (d + dkv) * es,
-                                         L.ptr(delta), B, T, H, hd, _ld(qkv), _ld(qkv), _ld(qkv), d, _ld(dqkv), _ld(dqkv), _ld(dqkv),
-                                         scale, int(causal), L.dt_of(qkv), impl, kv_heads or 0, L.stream_ptr()))
+    args = (p, p + d * es, p + (d + dkv) * es, L.ptr(o), L.ptr(dout), L.ptr(lse), g, g + d * es, g + (d + dkv) * es,
+            L.ptr(delta), B, T, H, hd, _ld(qkv), _ld(qkv), _ld(qkv), d, _ld(dqkv), _ld(dqkv), _ld(dqkv),
+            scale, int(causal), L.dt_of(qkv), impl, kv_heads or 0)
+    if rope_tab is None:
+        L.check(L.load().avllm_attention_bwd(*args, L.stream_ptr()))
+    else:
+        assert rope_tab.dtype == torch.float32 and rope_tab.is_contiguous() and rope_tab.numel() == T * hd
+        L.check(L.load().avllm_attention_bwd_rope(*args, L.ptr(rope_tab), L.stream_ptr()))
     return dqkv
 
 

@@ -286,7 +286,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
 //   S^T[key][query] = K . Q^T      A = K rows from LDS (ds_read_b128, 160-byte rows: conflict free), B = the wave's Q rows (registers)
 //   row max          over the lane's 4 NKB registers, then across the four lane groups that share a query (2 cross-lane steps)
 //   P = exp2(S * scale*log2e - max)                                                        (the only transcendental per score)
-//   l   += 1^T . P^T               the row SUM is one more MFMA with an all-ones A operand instead of 4 NKB VALU adds
+//   l   += 1^T . P^T               the row SUM is one more MFMA with an all-ones A operand instead of 4 NKB VALU adds: the sum of the bf16-ROUNDED
+//                                  P, which is the right normaliser for O (numerator and denominator carry the same roundings).  The LSE is
+//                                  not formed from it: each rounded p is off by up to 2^-8 relative, so log l would be off by up to 2^-8
+//                                  absolute, where the LSE is otherwise an fp32 quantity good to 1e-6, and the backward recomputes P from it.
+//                                  The WLSE form adds the unrounded P in fp32 beside the MFMA, for the LSE only; the form without an LSE
+//                                  (the encoders' forward) has no such adds.
 //   O^T += V^T . P^T               P's registers, converted pairwise to bf16, ARE the B operand (key order permuted inside a 32-key
 //                                  step: elements 0..3 = keys 4g..4g+3 of the first 16-key block, 4..7 = the same of the second);
 //                                  V^T fragments come from the row-major V image through ds_read_b64_tr_b16 in that same order.
@@ -300,7 +305,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
 // FULLK: the sequence uses every key block (nkb == NKB, e.g. CLIP's 197 tokens = 13 blocks), decided at launch: as a run-time branch the
 // compiler hoisted the OTHER form's per-block "is this key inside T" masks above it (52 compares, 96 v_writelane of spilled scalar masks:
 // as many instructions as a whole query block, paid by every wave).
-template <int NKB, int NW, bool QOUT, bool FULLK>
+template <int NKB, int NW, bool QOUT, bool FULLK, bool WLSE>
 __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
                                                           bf16* __restrict__ o, float* __restrict__ lse, int T, int H, long ldq, long ldk,
                                                           long ldv, long ldo, float scale_log2e, int G, uint8_t* __restrict__ oq, long ldoq,
@@ -395,6 +400,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict
         const float msc = m * scale_log2e;
         // ---- P, row sum and O^T
         f32x4 lacc = zero4, oacc[4] = {zero4, zero4, zero4, zero4};
+        float lsum = 0.f;                                         // WLSE: this lane's share of the row sum of the unrounded P
 #pragma unroll
         for (int st = 0; st < NPV; ++st) {
             if (FULL || 2 * st < nkb) {
@@ -403,8 +409,11 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict
                 const f32x4 s1 = sc[second ? 2 * st + 1 : 2 * st];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    pb[i] = (bf16)__builtin_amdgcn_exp2f(fmaf(sc[2 * st][i], scale_log2e, -msc));
-                    pb[4 + i] = second ? (bf16)__builtin_amdgcn_exp2f(fmaf(s1[i], scale_log2e, -msc)) : (bf16)0.f;
+                    const float p0 = __builtin_amdgcn_exp2f(fmaf(sc[2 * st][i], scale_log2e, -msc));
+                    const float p1 = second ? __builtin_amdgcn_exp2f(fmaf(s1[i], scale_log2e, -msc)) : 0.f;
+                    if constexpr (WLSE) lsum += p0 + p1;
+                    pb[i] = (bf16)p0;
+                    pb[4 + i] = (bf16)p1;
                 }
                 lacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb, lacc, 0, 0, 0);
                 const char* vr = v_lds + (32 * st + 4 * g + (i16 >> 2)) * VS + (4 * (i16 & 3)) * 2;
@@ -420,7 +429,11 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict
         }
         // every row of lacc is the row sum: lane (fr, *) holds l of query q0 + fr
         const float l = lacc[0], inv = 1.0f / l;
-        if (lse && fq == 0 && q0 + fr < T) lse[((long)b * H + hh) * T + q0 + fr] = (msc + log2f(l)) * 0.69314718055994531f;
+        if constexpr (WLSE) {                                     // the four lane groups of a query hold disjoint keys
+            lsum += __shfl_xor(lsum, 16);
+            lsum += __shfl_xor(lsum, 32);
+            if (fq == 0 && q0 + fr < T) lse[((long)b * H + hh) * T + q0 + fr] = (msc + log2f(lsum)) * 0.69314718055994531f;
+        }
         // ---- output: O^T[16t + 4fq + i][query fr] -> 16 x 32 bf16 scratch (two halves of the head dim) -> 16-byte row chunks
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
@@ -480,22 +493,26 @@ template <int NKB, int NW>
 int launch_fwd_short(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int H, long ldq, long ldk, long ldv,
                      long ldo, float scale, hipStream_t st, int G, void* oq = nullptr, long ldoq = 0, void* osc = nullptr) {
     constexpr int LDS = NKB * 16 * 160 + ((NKB + 1) / 2) * 32 * 160 + NW * 16 * 80;
+    AV_CHECK_ARG(!(oq && lse), "attention_fwd_short: the quantised-output form writes no LSE");
     static bool attr[64] = {};
     int dev = 0;
     AV_HIP(hipGetDevice(&dev));
     if (!attr[dev & 63]) {
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         attr[dev & 63] = true;
     }
     const int RBo = (int)(((long)B * T + 255) / 256 * 4);            // mx_groups(rows) of fp8.hip: 64-row groups, padded to whole 256-row tiles
     const bool fullk = ((T + 15) >> 4) == NKB;
-#define AV_SHORT(QV, FV, OQ, LDOQ, OSC, RB) hipLaunchKernelGGL((attn_fwd_short<NKB, NW, QV, FV>), dim3(H, B), dim3(NW * 64), LDS, st, (const bf16*)q, (const bf16*)k, \
+#define AV_SHORT(QV, FV, LV, OQ, LDOQ, OSC, RB) hipLaunchKernelGGL((attn_fwd_short<NKB, NW, QV, FV, LV>), dim3(H, B), dim3(NW * 64), LDS, st, (const bf16*)q, (const bf16*)k, \
         (const bf16*)v, (bf16*)o, lse, T, H, ldq, ldk, ldv, ldo, scale * 1.4426950408889634f, G, OQ, LDOQ, OSC, RB)
-    if (oq) { if (fullk) AV_SHORT(true, true, (uint8_t*)oq, ldoq, (uint8_t*)osc, RBo); else AV_SHORT(true, false, (uint8_t*)oq, ldoq, (uint8_t*)osc, RBo); }
-    else { if (fullk) AV_SHORT(false, true, nullptr, 0, nullptr, 0); else AV_SHORT(false, false, nullptr, 0, nullptr, 0); }
+    if (oq) { if (fullk) AV_SHORT(true, true, false, (uint8_t*)oq, ldoq, (uint8_t*)osc, RBo); else AV_SHORT(true, false, false, (uint8_t*)oq, ldoq, (uint8_t*)osc, RBo); }
+    else if (lse) { if (fullk) AV_SHORT(false, true, true, nullptr, 0, nullptr, 0); else AV_SHORT(false, false, true, nullptr, 0, nullptr, 0); }
+    else { if (fullk) AV_SHORT(false, true, false, nullptr, 0, nullptr, 0); else AV_SHORT(false, false, false, nullptr, 0, nullptr, 0); }
 #undef AV_SHORT
     AV_LAUNCH_CHECK();
     return AV_OK;

@@ -220,6 +220,14 @@ int avllm_attention_bwd(const void* q, const void* k, const void* v, const void*
                         int32_t H, int32_t hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddq,
                         int64_t lddk, int64_t lddv, float scale, int32_t causal, int32_t dtype, int32_t impl,
                         int32_t kv_heads, void* stream);
+/* avllm_attention_bwd with the inverse rotary embedding fused into dq | dk (the form the bf16 train step runs): rope_tab [T][hd/2][2] from
+ * avllm_rope_table; the gradients leave with respect to the PRE-RoPE q and k, as avllm_attention_bwd followed by avllm_rope_tab(inverse = 1)
+ * on dq and dk.  Only the bf16 MFMA kernels (impl 0, head_dim 64 / 128) fuse it: any other form with a table is refused (argument error).  NULL = no rotation. */
+int avllm_attention_bwd_rope(const void* q, const void* k, const void* v, const void* o, const void* dout,
+                             const float* lse, void* dq, void* dk, void* dv, float* delta_ws, int32_t B, int32_t T,
+                             int32_t H, int32_t hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddq,
+                             int64_t lddk, int64_t lddv, float scale, int32_t causal, int32_t dtype, int32_t impl,
+                             int32_t kv_heads, const float* rope_tab, void* stream);
 /* shifted causal-LM cross entropy (HF:loss/loss_utils.py:49-71): row (b,t) is scored against labels[b,t+1],
  * ignore_index -100 and the last position.  loss_sum/count are ACCUMULATED (zero them first). row_lse [B*T]. */
 int avllm_ce_fwd(const void* logits, int64_t ld, const int64_t* labels, int32_t B, int32_t T, int32_t V,

@@ -182,3 +182,132 @@ def atomic_sum_term(n_adds, total):
     2^-24 total = 6.9 standard deviations (7.6e-6 relative at 1024 adds; the worst case n_adds * 2^-24 would be 6e-5 and hide a dropped tail).
     The fixed-order form avllm_grad_sumsq_det is held to fp32_bar alone."""
     return 4.0 * n_adds ** 0.5 * U32 * abs(total)
+
+
+# ---- attention against float64 (tests/test_attention_pin_gpu.py, references and the host emulation in tests/refs64_attention.py).  As above, no
+# number here comes from a kernel's output.  A round-to-nearest to bf16 (8 significant bits: spacing 2^-7 in [1, 2)) moves x by at most half a
+# spacing, 2^-8 relative for x just above a power of two and 2^-9 just below the next: the BOUND is 2^-8 = 2 x the 2^-9 the text above calls u
+# (which is the size relative to the top of the binade).
+BF16_U = 2.0 ** -8
+# Rounding P to bf16 before the PV product.  The kernel forms o~ = sum_j p_j (1 + d_j) v_j / l with |d_j| <= u.
+#   * l from the UNROUNDED p (attn_fwd_mfma): o~ - o = sum_j w_j d_j v_j, so |o~ - o| <= u sum_j w_j |v_j| (w = the float64 softmax).
+#   * l from the ROUNDED p (attn_fwd_short): o~ = sum w (1 + d) v / sum w (1 + d) = o + sum w d (v - o) / (1 + sum w d), so
+#     |o~ - o| <= u sum_j w_j |v_j - o| / (1 - u).
+# Both are worst-case bounds (every d_j at +-u with the sign of its term), so the factor on the term is 1, times 1 / (1 - u) <= 1 + 2^-7 for the
+# second form; the online softmax changes nothing (a tile's p is rounded relative to the running max of its time and later multiplied by fp32
+# rescale factors, whose error the fp32 bar underneath carries).  A random-sign estimate would be sqrt(sum w^2) times smaller, which is what
+# a correct kernel typically shows; a missing or extra key moves o by w_j |v_j - o|, the size of ONE term of the sum.
+ATTN_P_ROUND = BF16_U * (1.0 + 2.0 ** -7)
+
+
+def attn_out_bar(o64, w64_term, fp32_bar_value, rounded=True):
+    """bf16 attention output, elementwise: 2^-8 |o| for the one final rounding (BF16_OUT_REL) + the P-rounding term above (w64_term = sum_j w_j |v_j - o|
+    or sum_j w_j |v_j|, whichever the kernel's row sum calls for; None for the scalar kernels, which never round P) + the fp32 bar of the arithmetic
+    underneath.  rounded=False (fp32 storage): the fp32 bar alone."""
+    if not rounded:
+        return fp32_bar_value + 0.0 * o64.abs()
+    bar = fp32_bar_value + BF16_OUT_REL * o64.abs()
+    return bar if w64_term is None else bar + ATTN_P_ROUND * w64_term
+
+
+def attn_lse_bar(lse64, lse_cpu32, Tk):
+    """LSE of either mode: the fp32 bar of the host's fp32 evaluation from the same inputs + what exp2 adds to a log-sum-exp over Tk terms
+    (ce_lse_expf_term).  Nothing for bf16: the scores are fp32 sums of exact bf16 products and the row sum is an fp32 sum of fp32 exponentials."""
+    return fp32_bar(lse64, lse_cpu32) + ce_lse_expf_term(Tk)
+
+
+def attn_count_lse_bar(n):
+    """count family (all scores 0): lse = ln n.  m = 0 and every p = 1 are exact and l = n is an exact integer, so what is left is log2 (v_log_f32,
+    1 ulp), the product with the fp32 literal ln 2 (half an ulp + the literal's own 2^-25) or logf, and the sum with m: 4 ulp of ln n, and 2 ulp of 1
+    absolute for n = 1, 2 where ln n is small.  One ulp is 2^-23 = 2 U32, so the factors below are 8 U32 and 4 U32.  ln(n + 1) - ln n = 3e-3 at
+    n = 330 is three orders above this."""
+    import torch
+    return 8.0 * U32 * torch.log(n.double()) + 4.0 * U32
+
+
+def attn_count_out_bar(o64, rounded=True):
+    """count family: p = 1 exactly and V holds small integers, so every partial sum is exact in fp32 and o = (sum over the visible keys) * (1 / n):
+    a reciprocal and a product, 2 ulp of |o| (= 4 U32 |o|: one ulp is 2 U32), + the final bf16 rounding; 1e-12 absolute is the float64 reference's
+    own roundoff (a mean that is exactly 0 comes out as 1e-17 there)."""
+    return (BF16_OUT_REL if rounded else 0.0) * o64.abs() + 4.0 * U32 * o64.abs() + 1e-12
+
+
+def attn_decode_weight_term(Tk, v):
+    """What the exp2 on the way to the softmax weights adds to a decode output that is not the count family's (there every p = 1 is exact): the
+    weights' relative error sums to ce_lse_expf_term(Tk) at most (the same sum that moves the LSE), and a weight error e_j moves
+    o = sum w_j v_j by e_j (v_j - o), bounded by the span of V, 2 max |v|."""
+    return ce_lse_expf_term(Tk) * 2.0 * float(v.double().abs().max())
+
+
+def attn_bwd_bar(ref64, emul):
+    """bf16 backward, one number per tensor (dq, dk, dv): the fp32_bar rule with the host emulation of the documented arithmetic in the place of cpu32:
+    4 x max |emul - ref64| measured inside the case (the 4 covers the different reduction order and a different draw of the same roundings: the
+    kernel's stored O and LSE differ from the emulation's in their last bit, so its delta and P round elsewhere), floored at 2 ulp OF BF16 of the
+    largest result (2 * 2^-8 max |ref|).  The tests add one more term to it, the fp32 bound underneath: attn_bwd_tensor_bar, below."""
+    e = float((emul.double() - ref64).abs().max())
+    return max(4.0 * e, 2.0 * BF16_OUT_REL * float(ref64.abs().max()))
+
+
+def attn_bwd_tensor_bar(ref64, yard, under_elem, rounded=True, rotated=False):
+    """The whole bar of one backward tensor (dq, dk or dv), or of the column slice of one kv head of it, as a number:
+        rounded (bf16 storage): attn_bwd_bar(ref64, yard) with yard = the host emulation;
+        fp32 storage:           fp32_bar(ref64, yard) with yard = the float64 restatement run in fp32 on the host;
+      + max(under_elem), the largest element of the DERIVED fp32 bound of the backward's own arithmetic (attn_bwd_elem_bars with no bf16 rounding
+        anywhere).  Neither yardstick's DISTANCE from the reference shows that error where the result is a cancellation (T = 1: dq = 0 exactly
+        in float64 and in both yardsticks, while a kernel leaves the fp32 noise of dP - delta there, so 4 x 0 would be the bar) or where
+        P = exp2(s - lse) is recomputed from a stored LSE (the restatement run in fp32 divides by the row sum instead and never forms a
+        difference of two numbers of size 20).  In bf16 storage the term is about 1e3 below the rest; in fp32 storage it is of the size of
+        fp32_bar itself, a few times it where the scores are large.
+      rotated (the inverse rotary was applied to this tensor): an output a c + b s takes the errors of both halves of its pair,
+        (|c| + |s|) max(under_elem) <= sqrt(2) max(under_elem); the rotation's own two products and one sum round at the size of the result
+        (3 fp32 half-ulps, which the floor of either rule covers)."""
+    rule = attn_bwd_bar if rounded else fp32_bar
+    return rule(ref64, yard) + (2.0 ** 0.5 if rotated else 1.0) * float(under_elem.max())
+
+
+def attn_bwd_rel_l2_bar(amp=0.0):
+    """bf16 backward, relative L2 per tensor, beside attn_bwd_bar.  Independent roundings of RMS u / sqrt(3) = 1.13e-3 lie on the way to each result:
+    the MFMA operand (P for dv, dS for dq and dk), the result itself, and the stored LSE's and scores' fp32 error (nothing at this scale): 2, plus
+    for dq and dk the stored O inside delta = rowsum(dO * O), whose weight relative to dS is `amp` (refs64_attention.delta_amplification: about 1
+    for centred V, mu / sigma for an offset V, large where dS is a cancellation): 1.13e-3 sqrt(2 + amp^2), and 4 x that as everywhere in this file."""
+    return 4.0 * 1.13e-3 * (2.0 + amp * amp) ** 0.5
+
+
+def attn_bwd_elem_bars(q, k, v, dout, B, T, H, Hkv, hd, causal, scale, rounded=True, p_rounded=True):
+    """Elementwise bars (bar_dq, bar_dk, bar_dv) of the backward from its float64 quantities, used where the result is structured and a per-tensor
+    maximum would hide a row (the count family).  With u = 2^-8 (0 where the kernel does not round that operand) and r_p the fp32 error of
+    P = exp2(s sl - lse log2e), 8 * 2^-24 (1 + |s scale| + |lse|) relative (two products rounded at the size of their result, the stored LSE's own
+    few ulp, v_exp_f32's 1 ulp, doubled):
+        |d P_ij|  <= w_ij (u + r_p)                              dv_j : sum_i |d P_ij| |dO_i|
+        |d delta_i| <= u sum_d |dO_id o_id|                      (the stored O is rounded once)
+        |d dS_ij| <= |dS_ij| (u + r_p) + w_ij scale (|d delta_i| + 8 * 2^-24 sum_d |dO_id v_jd|)
+        dq_i : sum_j |d dS_ij| |k_j|,    dk_j : sum_i |d dS_ij| |q_i|    (summed over the query heads of a group)
+    + 2^-8 |result| for the stored rounding + 2 fp32 ulp of the sum of magnitudes for the accumulation."""
+    import torch
+    import refs64_attention as A
+    hm = A.head_map(H, Hkv)
+    q4, k4, v4 = A._heads(q, B, T, H, hd, A.F64), A._heads(k, B, T, Hkv, hd, A.F64)[:, hm], A._heads(v, B, T, Hkv, hd, A.F64)[:, hm]
+    do4 = A._heads(dout, B, T, H, hd, A.F64)
+    vis = A.visible(T, T, causal)
+    o4, lse, w = A._fwd_core(q4, k4, v4, vis, scale)
+    s = (torch.einsum("bhid,bhjd->bhij", q4, k4) * scale).abs()
+    u = BF16_U if p_rounded else 0.0
+    uo = BF16_U if rounded else 0.0
+    r_p = 8.0 * U32 * (1.0 + s + lse.abs()[..., None])
+    dp = torch.einsum("bhid,bhjd->bhij", do4, v4)
+    delta = (do4 * o4).sum(-1, keepdim=True)
+    ds = w * (dp - delta) * scale
+    e_p = w * (u + r_p)
+    e_delta = uo * (do4 * o4).abs().sum(-1, keepdim=True)
+    e_dp = 8.0 * U32 * torch.einsum("bhid,bhjd->bhij", do4.abs(), v4.abs())
+    e_ds = ds.abs() * (u + r_p) + w * scale * (e_delta + e_dp)
+    acc = 4.0 * U32
+    dq4, dk4, dv4 = A._bwd_core(q4, k4, v4, do4, vis, scale)
+    bq = torch.einsum("bhij,bhjd->bhid", e_ds + acc * ds.abs(), k4.abs())
+    bk = A._group_sum(torch.einsum("bhij,bhid->bhjd", e_ds + acc * ds.abs(), q4.abs()), Hkv)
+    bv = A._group_sum(torch.einsum("bhij,bhid->bhjd", e_p + acc * w, do4.abs()), Hkv)
+    out = uo and BF16_OUT_REL
+    bq = bq + out * dq4.abs()
+    bk = bk + out * A._group_sum(dk4, Hkv).abs()
+    bv = bv + out * A._group_sum(dv4, Hkv).abs()
+    return A._rows(bq) + FP32_DENORM, A._rows(bk) + FP32_DENORM, A._rows(bv) + FP32_DENORM
