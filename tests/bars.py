@@ -311,3 +311,94 @@ def attn_bwd_elem_bars(q, k, v, dout, B, T, H, Hkv, hd, causal, scale, rounded=T
     bk = bk + out * A._group_sum(dk4, Hkv).abs()
     bv = bv + out * A._group_sum(dv4, Hkv).abs()
     return A._rows(bq) + FP32_DENORM, A._rows(bk) + FP32_DENORM, A._rows(bv) + FP32_DENORM
+
+
+# ---- GEMM against float64 (tests/test_gemm_pin_gpu.py, references, families and the host emulation in tests/refs64_gemm.py).  No number here comes
+# from a kernel's output.  The exact and locate families carry the bar 0: their operands are small integers, every product and partial sum is
+# an integer the fp32 accumulator holds exactly, and the result is representable in the output format, so ANY difference is an error.
+# For the other families the accumulator's error is bounded ELEMENTWISE on sum_abs = sum_k |a_k| |b_k| (bf16 x bf16 products are exact in fp32, so
+# only the additions round):
+#   f32   : v_mfma_f32_16x16x4_f32 is a k-ordered fmaf chain: (K + K2) roundings, each at most 2^-24 of the running sum <= sum_abs.
+#   mfma  : the bf16 MFMA's internal summation of its 32 products is not documented; any order of n - 1 round-to-nearest additions stays under
+#           n 2^-24 sum_abs.  GEMM_MFMA_ALLOW = 2 is for the one thing that bound assumes and the hardware may not do: round-to-NEAREST inside the
+#           instruction.  An adder that truncates the aligned addends loses up to one ulp per addition instead of half of one, i.e. 2 x.
+#   split8: SMALLM and SKINNY64 add the 8 waves' partials in LDS order: 8 more roundings at the size of sum_abs.
+#   tn    : gemm_tn adds up to 32 chunk partials with float atomics in arrival order onto the prior output: atomic_sum_term.
+GEMM_MFMA_ALLOW = 2.0
+
+
+def gemm_acc_bar(sum_abs, kk, kind):
+    """|fp32 accumulator - exact sum|, elementwise; kk = the reduction length (K + K2, or the rows M of gemm_tn)."""
+    if kind == "f32":
+        return kk * U32 * sum_abs
+    bar = GEMM_MFMA_ALLOW * kk * U32 * sum_abs
+    if kind == "split8":
+        bar = bar + 8.0 * U32 * sum_abs
+    return bar
+
+
+def gelu_fast_bar(z):
+    """|error| of act_apply_fast's GELU = 0.5 z (1 + erf_AS(z / sqrt 2)), elementwise, z float64.  With x = |z| / sqrt 2, t = rcp(1 + 0.3275911 x),
+    S(t) = sum |a_i| t^i and E = exp(-x^2): the Abramowitz-Stegun 7.1.26 formula is within 1.5e-7 of erf (common.h's comment); each of the five Horner
+    stages multiplies by t (relative error <= 4 half-ulps: a product, a sum, rcp's 1 ulp) and rounds twice: 30 half-ulps of S(t); exp2's argument is
+    two rounded products (2 x^2 half-ulps relative on E) and v_exp_f32 is 1 ulp (2 more); the subtraction from 1 rounds once.  The erf error is
+    multiplied by 0.5 |z|; the sum 1 + erf and the two products round once each at the size of the result."""
+    import math
+    import torch
+    x = z.abs() / math.sqrt(2.0)
+    t = 1.0 / (1.0 + 0.3275911 * x)
+    S = t * (0.254829592 + t * (0.284496736 + t * (1.421413741 + t * (1.453152027 + t * 1.061405429))))
+    E = torch.exp(-x * x)
+    e_erf = 1.5e-7 + U32 * (S * E * (32.0 + 2.0 * x * x) + 1.0)
+    y = 0.5 * z * (1.0 + torch.erf(z / math.sqrt(2.0)))
+    return 0.5 * z.abs() * e_erf + 3.0 * U32 * y.abs() + FP32_DENORM
+
+
+def gelu_libm_bar(z):
+    """act_apply's GELU: libm erff (a few ulp: 4 ulp of |erf| <= 1 taken), the product z / sqrt 2 (half an ulp of the argument, through
+    erf' <= 2 / sqrt pi), then the sum and two products as above."""
+    import math
+    import torch
+    y = 0.5 * z * (1.0 + torch.erf(z / math.sqrt(2.0)))
+    return 0.5 * z.abs() * (8.0 * U32 + U32 * z.abs() * torch.exp(-0.5 * z * z)) + 3.0 * U32 * y.abs() + FP32_DENORM
+
+
+def gemm_act_bar(z, act, libm=None):
+    """The activation's own error at the float64 pre-activation z.  libm: True = act_apply (f32, 4-column and small-M epilogues), False =
+    act_apply_fast (x * rcp(1 + exp2(c x)): silu_bar with one more ulp for v_rcp_f32 in place of the IEEE division), None = whichever is larger (a
+    kernel that takes either epilogue by alignment)."""
+    import torch
+    if act == 0:
+        return torch.zeros_like(z)
+    if act == 1:
+        lib, fast = gelu_libm_bar(z), gelu_fast_bar(z)
+    else:
+        k = 1.702 if act == 2 else 1.0
+        lib = silu_bar(z, k)
+        fast = lib + 2.0 * U32 * (z * torch.sigmoid(k * z)).abs() + FP32_DENORM * z.abs()      # v_rcp_f32 flushes a result below 2^-126 (1 + e > 2^126, k z < -87.3) that the
+                                                                                                # product with z would have brought back into the normal range; the division does not
+    return lib if libm is True else fast if libm is False else torch.maximum(lib, fast)
+
+
+def gemm_bar(ref, kk, kind, act=0, alpha=1.0, out_bf16=True, libm=None):
+    """Elementwise bar of one avllm_gemm call from its float64 reference `ref` (refs64_gemm.Ref: out, sum_abs, z, acc, mask).  The accumulator bar is
+    carried through alpha (one rounded product, one rounded sum with the bias), through |act'(z)| plus the activation's own error, through the mask's
+    scale (one rounded product), the residual sum rounds once at the size of the result, and a bf16 store adds BF16_OUT_REL |ref| -- ONCE: this is
+    the single-rounding statement the offset family (R = -z + noise) holds a kernel to."""
+    import refs64_gemm as G
+    e = abs(alpha) * gemm_acc_bar(ref.sum_abs, kk, kind) + U32 * ((alpha * ref.acc).abs() + ref.z.abs())
+    y = ref.z
+    if act:
+        y = G.act64(ref.z, act)
+        e = G.dact64(ref.z, act).abs() * e + gemm_act_bar(ref.z, act, libm)
+    if ref.mask is not None:
+        e = ref.mask * e + U32 * (y * ref.mask).abs()
+    e = e + U32 * ref.out.abs() + FP32_DENORM
+    return e + BF16_OUT_REL * ref.out.abs() if out_bf16 else e
+
+
+def gemm_tn_bar(ref, M, alpha, out0, mfma):
+    """gemm_tn / gemm_tn_drop, fp32 output: the chunk partials (MFMA: any-order bound with the allowance; scalar kernel: an M-long fmaf chain), the
+    product with alpha, and <= 32 float atomics in arrival order onto the prior output, whose running total stays under |out0| + |alpha| sum_abs."""
+    total = out0.abs() + abs(alpha) * ref.sum_abs
+    return abs(alpha) * gemm_acc_bar(ref.sum_abs, M, "mfma" if mfma else "f32") + U32 * (alpha * ref.acc).abs() + atomic_sum_term(32, total) + FP32_DENORM
