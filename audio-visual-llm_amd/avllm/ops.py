@@ -527,8 +527,11 @@ def lora_dx_masked(Ts, ATs, seeds, r, p, R=None, out=None, seed_dev=None):
 
 
 def lora_rank3(As, Bs, outs, r, alpha=1.0, seeds=None, p=0.0, shared=False, seed_dev=None):
-    """Batched rank-side products of up to 3 adapters (avllm_lora_rank3): outs[j][M,64] = alpha * A_j . Bs[j][r,K]^T (columns >= 16 zero).
-    shared=True: every adapter reads As[0] through its own dropout mask (seeds[j], p)."""
+    """Batched rank-side products of up to 3 adapters (avllm_lora_rank3): outs[j][M,64] = alpha * A_j . Bs[j][:r]^T, columns >= r zero.
+    Bs[j] is the PADDED image [>= 16, K]: the kernel is not told r, reads 16 rows of every B and writes all 16 products, so rows r..15 must be
+    zeros (avllm_lora_pack's layout); a true [r, K] tensor with r < 16 is an out-of-bounds read.  All 64 columns of every output are written.
+    shared=True: every adapter reads As[0] (contiguous [M, K]) through its own dropout mask (seeds[j], p); seed_dev: pointer to a device uint32
+    added to every seed."""
     n = len(Bs)
     arr = lambda ty, vals: (ty * n)(*vals)
     Aa = [As[0]] * n if shared else As

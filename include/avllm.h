@@ -97,9 +97,13 @@ int avllm_gemm_wgrad(const void* dY, int64_t ldy, const void* X, int64_t ldx, in
                      float* db, float alpha, int32_t dtype, void* stream);
 
 /* The q / k / v adapters of one decoder layer batched (bf16, rank <= 16, 1..3 adapters; peft lora.Linear on q_proj, k_proj, v_proj,
- * clip_whisper_model.py:961-1005).  Rank-side products C_j[M,64] = alpha * A_j[M,K_j] B_j[R,K_j]^T (columns >= 16 written as zeros):
- * shared != 0: every adapter reads A[0] through its own dropout mask (forward lora_A(dropout(x))); shared == 0: adapter j reads A[j]
- * (backward dt_j = s dy_j B_j). */
+ * clip_whisper_model.py:961-1005).  Rank-side products C_j[M,64] = alpha * A_j[M,K_j] B_j[:R,K_j]^T:
+ * shared != 0: every adapter reads A[0] through its own dropout mask (forward lora_A(dropout(x)); mask index m*K+k, seeds[j] (+ *seed_dev),
+ * needs lda == K); shared == 0: adapter j reads A[j] (backward dt_j = s dy_j B_j; no mask).  K_j % 256 == 0.
+ * What B must be: the kernel is not told R.  It reads SIXTEEN rows of every B_j (row stride ldb[j]) and writes all sixteen products, so B_j
+ * must have at least 16 readable rows and rows R..15 must be zeros: avllm_lora_pack's padded image.  A true [R, K] tensor with R < 16 is an
+ * out-of-bounds read.  What is then promised: every one of the 64 columns of C_j is written, columns >= R as zeros (R..15 are the products
+ * with B's zero rows, 16..63 are stored zeros: the K2 segment of the projection GEMM). */
 int avllm_lora_rank3(const void* const* A, const int64_t* lda, const int32_t* K, const void* const* B, const int64_t* ldb, void* const* C,
                      const int64_t* ldc, const uint32_t* seeds, int32_t nj, int32_t M, int32_t R, float alpha, float p,
                      const uint32_t* seed_dev, int32_t shared, int32_t dtype, void* stream);

@@ -402,3 +402,33 @@ def gemm_tn_bar(ref, M, alpha, out0, mfma):
     product with alpha, and <= 32 float atomics in arrival order onto the prior output, whose running total stays under |out0| + |alpha| sum_abs."""
     total = out0.abs() + abs(alpha) * ref.sum_abs
     return abs(alpha) * gemm_acc_bar(ref.sum_abs, M, "mfma" if mfma else "f32") + U32 * (alpha * ref.acc).abs() + atomic_sum_term(32, total) + FP32_DENORM
+
+
+# ---- LoRA adapter kernels against float64 (tests/test_lora_pin_gpu.py; references, families and the host emulation in tests/refs64_lora.py).  No
+# number here comes from a kernel's output; the exact and locate families carry the bar 0 (integer operands, every partial sum an integer the fp32
+# accumulator holds, the result representable in the output format).
+#   rank3    : the arithmetic of SKINNY64: 8 waves split K, MFMA partials added in LDS in wave order, times alpha, one bf16 rounding: gemm_bar's
+#              "split8".  The fused mask is part of the OPERAND (scaled survivors re-rounded to bf16, in the reference too), so it adds no term.
+#   tn_multi : the arithmetic of gemm_tn's MFMA kernel: chunk partials over 64-row slabs, times alpha, at most 32 float atomics (the chunk cap of
+#              tn_chunks) in arrival order onto the prior output: gemm_tn_bar.
+#   dx_masked: per adapter ONE 32-slot MFMA from a zero accumulator (any-order bound with the allowance, on S_j = sum |t| |a|), one rounded product
+#              with the mask's scale, then nj + 1 fp32 additions (the nj masked products onto a zero accumulator, then R) whose running total stays
+#              under sum_j |scale p_j| over the adapters the mask KEEPS + |R| (a dropped product adds an exact 0), the denormal floor, and
+#              BF16_OUT_REL |ref| ONCE: the header's "rounded once", which the offset family (R = -sum + noise) holds the kernel to.
+def lora_rank3_bar(ref, K, alpha):
+    return gemm_bar(ref, K, "split8", alpha=alpha, out_bf16=True)
+
+
+def lora_tn_multi_bar(ref, M, alpha, out0):
+    return gemm_tn_bar(ref, M, alpha, out0, mfma=True)
+
+
+def lora_dx_bar(ref):
+    """ref: refs64_lora.RefDx (out, prods, sum_abs, keeps, scale, R) -> elementwise bar, float64 [M, N]."""
+    import torch
+    e, total = torch.zeros_like(ref.out), ref.R.abs().clone()
+    for pj, sj, k in zip(ref.prods, ref.sum_abs, ref.keeps):
+        kept = k.to(ref.out.dtype)
+        e = e + kept * (ref.scale * GEMM_MFMA_ALLOW * 32.0 * U32 * sj + U32 * (ref.scale * pj).abs())
+        total = total + kept * (ref.scale * pj).abs()
+    return e + (len(ref.prods) + 1) * U32 * total + FP32_DENORM + BF16_OUT_REL * ref.out.abs()

@@ -9,6 +9,7 @@ pytestmark = pytest.mark.gpu
 
 import bars as Bar  # noqa: E402
 import refs64_connector as RC  # noqa: E402
+import refs64_gemm as G  # noqa: E402
 from avllm import ops  # noqa: E402
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16}
@@ -74,6 +75,23 @@ def test_gemm_wgrad_vs_float64(dev, M, N, K, dt):
     check(dW, rW, Bar.fp32_bar(rW, cW), f"gemm_wgrad dW {dt} M={M} N={N} K={K}")
     check(db, rb, Bar.fp32_bar(rb, cb), f"gemm_wgrad db {dt} M={M} N={N}")
     assert torch.equal(dW, dW2) and torch.equal(db, db2), "two launches differ"
+    # dW as a view (row 1, column 8 on, ldw = K + 16 > K) of a NaN buffer: the same bits, and everything outside the view is still NaN
+    buf = torch.full((N + 4, K + 16), float("nan"), device=dev, dtype=torch.float32)
+    ops.gemm_wgrad(dY.to(dev), X.to(dev), alpha, dW=buf[1:1 + N, 8:8 + K])
+    canary, over, _ = G.verify(buf, 1, 8, torch.arange(N, device=dev), K, dW.double(), 0.0)
+    assert canary == 0 and over == 0, f"gemm_wgrad {dt} M={M} N={N} K={K} into a view: {over} differ, {canary} canaries overwritten"
+    # the zero-bar families of tests/refs64_gemm.py (small integers: every partial sum is an integer the fp32 accumulator holds, alpha = 0.5 keeps
+    # it a half-integer): ANY difference is an error, and with the one-hot dY of "locate" a wrong value names its tile
+    for fam in G.ZERO_BAR:
+        p, q, _ = G.family_tn(fam, M, N, K)
+        ref = G.gemm_tn(p, q, alpha=0.5)
+        rb0 = 0.5 * p.double().sum(0)
+        assert torch.equal(ref.out, ref.out.float().double()) and torch.equal(rb0, rb0.float().double())
+        buf = torch.full((N + 4, K + 16), float("nan"), device=dev, dtype=torch.float32)
+        _, db0 = ops.gemm_wgrad(p.to(dtype).to(dev), q.to(dtype).to(dev), 0.5, dW=buf[1:1 + N, 8:8 + K])
+        canary, over, _ = G.verify(buf, 1, 8, torch.arange(N, device=dev), K, ref.out.to(dev), 0.0)
+        assert canary == 0 and over == 0, f"gemm_wgrad {fam} {dt} M={M} N={N} K={K}: {over} wrong, {canary} canaries overwritten"
+        assert torch.equal(db0.double().cpu(), rb0), f"gemm_wgrad db {fam} {dt} M={M} N={N}"
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
