@@ -189,13 +189,18 @@ class LlamaEngine:
     (A [r,d], B [dout,r]; dout = d, or kv_heads*head_dim for k/v under grouped-query attention) so a layer's gradient bucket is one contiguous slice of `lora_g` for the DDP all-reduce.
     """
 
-    def __init__(self, sd, cfg, lora_cfg=None, lora_sd=None, dtype=torch.bfloat16, device="cuda", training=True, fp8=False, decode_fp8=False):
+    def __init__(self, sd, cfg, lora_cfg=None, lora_sd=None, dtype=torch.bfloat16, device="cuda", training=True, fp8=False, decode_fp8=False,
+                 decode_fp4=False):
         self.cfg, self.lcfg, self.dtype, self.device, self.training = cfg, lora_cfg, dtype, device, training
         self.fp8 = bool(fp8)
         # weight-only fp8 token step (include/avllm.h avllm_llama.decode_fp8): the fused decode path streams e4m3 codes + layout-2 exponents
         self.decode_fp8 = bool(decode_fp8)
         if self.decode_fp8 and dtype != torch.bfloat16:
             raise ValueError("decode_fp8 needs the bf16 engine")
+        # weight-only fp4 token step (avllm_llama.decode_fp4): the four projections of a layer stream MXFP4 codes, lm_head streams e4m3
+        self.decode_fp4 = bool(decode_fp4)
+        if self.decode_fp4 and (dtype != torch.bfloat16 or self.decode_fp8):
+            raise ValueError("decode_fp4 needs the bf16 engine and excludes decode_fp8")
         self.keep = []
         d, f = cfg.hidden, cfg.ffn
         self.use_lora = lora_cfg is not None
@@ -229,21 +234,22 @@ class LlamaEngine:
             m.lm_head_t = put(head.t()).data_ptr()
         m.fp8 = int(self.fp8)
 
-        def images(w):
+        def images(w, decode8=self.decode_fp8):
             """(codes, layout-1 image, layout-2 exponents) pointers of a frozen matrix for the fp8 modes that are on (None otherwise); the
             token step's exponents share the codes of the training forward's image when both modes are on (re-quantising writes the same bytes)."""
             q = s = e = None
             if self.fp8:
                 q, s = ops.mx_quantize(w, 1)
                 self.keep += [q, s]
-            if self.decode_fp8:
+            if decode8:
                 q, e = ops.mx_quantize(w, 2, q=q)
                 self.keep += [q, e]
             return tuple(None if t is None else t.data_ptr() for t in (q, s, e))
 
         m.decode_fp8 = int(self.decode_fp8)
-        if self.fp8 or self.decode_fp8:
-            m.lm_head8, m.slm_head8, m.elm_head8 = images(head)
+        m.decode_fp4 = int(self.decode_fp4)
+        if self.fp8 or self.decode_fp8 or self.decode_fp4:
+            m.lm_head8, m.slm_head8, m.elm_head8 = images(head, self.decode_fp8 or self.decode_fp4)
         self.layers = (L.LlamaLayer * cfg.layers)()
         # ---- LoRA masters / grads / padded operand images
         self.per_layer = sum(r * (d + do) for do in self.douts)
@@ -278,6 +284,8 @@ class LlamaEngine:
                 ly.wo8, ly.so8, ly.eo8 = images(wo)
                 ly.wgu8, ly.sgu8, ly.egu8 = images(wgu)
                 ly.wdown8, ly.sdown8, ly.edown8 = images(wdown)
+            if self.decode_fp4:
+                self._fp4_images(ly, wqkv, wo, wgu, wdown)
             if self.use_lora:
                 es = self.img_A.element_size()
                 for j in range(4):
@@ -300,6 +308,14 @@ class LlamaEngine:
         self.acc = torch.zeros(2, dtype=torch.float32, device=device)     # [loss_sum, count]
         if self.use_lora:
             self.pack_lora()
+
+    def _fp4_images(self, ly, wqkv, wo, wgu, wdown):
+        """MXFP4 codes + exponents of one layer's four frozen matrices into its descriptor (tensors parked in self.keep)."""
+        for nm, wt in (("qkv", wqkv), ("o", wo), ("gu", wgu), ("down", wdown)):
+            q4, e4 = ops.mx4_quantize(wt)
+            self.keep += [q4, e4]
+            setattr(ly, "w" + nm + "4", q4.data_ptr())
+            setattr(ly, "e" + nm + "4", e4.data_ptr())
 
     # flat-buffer offsets of module j (0..3 = q,k,v,o) in layer i: (A range, B range)
     def _slices(self, i, j):
@@ -421,9 +437,18 @@ class LlamaEngine:
         """True when a token step of B sequences streams the fp8 weight images (decode_fp8 and the fused path: B <= 16)."""
         return bool(L.load().avllm_llama_decode_streams_fp8(C.byref(self.desc), B))
 
+    def decode_streams_fp4(self, B):
+        """True when a token step of B sequences streams the MXFP4 weight images (decode_fp4 and the fused path: B <= 16)."""
+        return bool(L.load().avllm_llama_decode_streams_fp4(C.byref(self.desc), B))
+
     def streamed_weight_bytes(self, B):
         """Bytes of frozen weights a token step of B sequences actually reads: frozen_weight_bytes() on the bf16 matrices, or one byte per
-        element plus one exponent byte per 32 elements when the step streams fp8."""
+        element plus one exponent byte per 32 elements when the step streams fp8, or half a byte per projection element, one byte per
+        lm_head element (e4m3) and one exponent byte per 32 elements of both when it streams fp4."""
+        if self.decode_streams_fp4(B):
+            proj = (self.frozen_weight_bytes() // 2) - self.cfg.vocab * self.cfg.hidden      # elements of the layers' projections
+            head = self.cfg.vocab * self.cfg.hidden
+            return proj // 2 + proj // 32 + head + head // 32
         if not self.decode_streams_fp8(B):
             return self.frozen_weight_bytes()
         n = self.frozen_weight_bytes() // 2

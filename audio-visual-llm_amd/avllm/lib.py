@@ -54,7 +54,8 @@ class LoraMod(C.Structure):
 class LlamaLayer(C.Structure):
     _fields_ = [(n, vp) for n in ("ln1_w", "ln2_w", "wqkv", "wo", "wgu", "wdown", "wqkv_t", "wo_t", "wgu_t", "wdown_t")] + \
                [("lora", LoraMod * 4)] + [(n, vp) for n in ("wqkv8", "sqkv8", "wo8", "so8", "wgu8", "sgu8", "wdown8", "sdown8")] + \
-               [(n, vp) for n in ("eqkv8", "eo8", "egu8", "edown8")]
+               [(n, vp) for n in ("eqkv8", "eo8", "egu8", "edown8")] + \
+               [(n, vp) for n in ("wqkv4", "wo4", "wgu4", "wdown4", "eqkv4", "eo4", "egu4", "edown4")]
 
 
 class Llama(C.Structure):
@@ -63,7 +64,7 @@ class Llama(C.Structure):
                [(n, vp) for n in ("dropout_seed_dev", "embed", "norm_w", "lm_head", "lm_head_t")] + [("layer", C.POINTER(LlamaLayer))] + \
                [("fp8", i32), ("lm_head8", vp), ("slm_head8", vp)] + \
                [(n, f32) for n in ("rope_factor", "rope_low_freq_factor", "rope_high_freq_factor")] + [("rope_orig_ctx", i32)] + \
-               [("decode_fp8", i32), ("elm_head8", vp)]
+               [("decode_fp8", i32), ("elm_head8", vp), ("decode_fp4", i32)]
 
 
 class GemmF8Desc(C.Structure):
@@ -76,7 +77,7 @@ class DecProjDesc(C.Structure):
     _fields_ = [("A", vp), ("lda", i64), ("W", vp), ("ldw", i64), ("norm_w", vp), ("eps", f32), ("M", i32), ("K", i32), ("N", i32), ("mode", i32),
                 ("C", vp), ("ldc", i64), ("out_f32", i32), ("R", vp), ("ldr", i64), ("dq", i32), ("dkv", i32), ("hd", i32), ("rope", vp),
                 ("kc", vp), ("vc", vp), ("Tmax", i32), ("pos", i32), ("pos_dev", vp),
-                ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32), ("W8", vp), ("E8", vp)]
+                ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32), ("W8", vp), ("E8", vp), ("W4", vp)]
 
 
 class StepState(C.Structure):
@@ -157,6 +158,7 @@ _SIGS = {
     "avllm_step_advance": ([vp, C.POINTER(Schedule), vp], i32),
     "avllm_mx_scale_bytes": ([i32, i32], sz),
     "avllm_mx_quantize": ([vp, i64, i32, i32, vp, i64, vp, i32, i32, vp], i32),
+    "avllm_mx4_quantize": ([vp, i64, i32, i32, vp, i64, vp, i32, vp], i32),
     "avllm_gemm_f8": ([C.POINTER(GemmF8Desc), vp], i32),
     "avllm_lora_dx_masked": ([C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_uint32), i32, i32, vp, i64, vp, i64, i32,
                               i32, f32, vp, i32, vp], i32),
@@ -179,6 +181,7 @@ _SIGS = {
     "avllm_llama_decode_step_at": ([C.POINTER(Llama), vp, i32, i32, vp, vp, vp, i32, vp, vp, sz, vp], i32),
     "avllm_llama_decode_is_fused": ([C.POINTER(Llama), i32], i32),
     "avllm_llama_decode_streams_fp8": ([C.POINTER(Llama), i32], i32),
+    "avllm_llama_decode_streams_fp4": ([C.POINTER(Llama), i32], i32),
     "avllm_pos_advance": ([vp, i32, vp], i32),
     "avllm_dec_proj": ([C.POINTER(DecProjDesc), vp], i32),
     "avllm_gemm_f8_takes_quantised_output": ([C.POINTER(GemmF8Desc)], i32),

@@ -573,6 +573,18 @@ def mx_quantize(x, layout=0, q=None):
     return q, s
 
 
+def mx4_quantize(x):
+    """x [R,K] bf16/f32 (K % 32 == 0) -> (codes uint8 [R, K/2], exponents uint8 [R, K/32]): OCP MXFP4 -- e2m1 elements, two per byte with
+    element 2i in the low nibble, one E8M0 exponent (biased by 127) per 32 elements; the W4 / E8 of dec_proj's fp4 weight form."""
+    R, K = x.shape
+    if K % 32:
+        raise ValueError(f"mx4_quantize: K={K} must be a multiple of 32")
+    q = torch.empty(R, K // 2, device=x.device, dtype=torch.uint8)
+    e = torch.empty(R, K // 32, device=x.device, dtype=torch.uint8)
+    L.check(L.load().avllm_mx4_quantize(L.ptr(x), _ld(x), R, K, L.ptr(q), K // 2, L.ptr(e), L.dt_of(x), L.stream_ptr()))
+    return q, e
+
+
 def gemm_f8(Aq, As, Bq, Bs, out=None, bias=None, R=None, act=L.ACT_NONE, quantised_out=False):
     """out[M,N] (bf16) = act(A.B^T + bias) + R on the block-scaled fp8 matrix pipe; (Aq, As) / (Bq, Bs) from mx_quantize(layout 0 / 1).
     quantised_out=True: returns (codes uint8 [M,N], scale image) = the e4m3 block-scaled result, quantised in the epilogue (no bf16 copy)."""
@@ -610,18 +622,21 @@ def norm_mxq(x, w, b=None, eps=1e-5, want_y=False, want_rstd=False):
 
 
 def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=False, rope=None, kc=None, vc=None, pos=0, pos_dev=None, dq=0, dkv=0, hd=0,
-             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None):
+             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None, W4=None):
     """One projection of a decode token step (avllm_dec_proj): A [M<=16, K] bf16, W [rows, K] bf16.
     mode 0: out[M, rows] = rmsnorm?(A) . W^T (+ R);  mode 1: W = [gate; up], out[M, rows/2] = silu(gate) * up;
     mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev).
-    fp8 weight form: W8 = e4m3 codes uint8 [rows, K], E8 = exponents uint8 [rows, K/32] (mx_quantize(w, 2)); W may then be None."""
+    fp8 weight form: W8 = e4m3 codes uint8 [rows, K], E8 = exponents uint8 [rows, K/32] (mx_quantize(w, 2)); W may then be None.
+    fp4 weight form: W4 = MXFP4 codes uint8 [rows, K/2], E8 = their exponents uint8 [rows, K/32] (mx4_quantize(w)); not together with W8."""
     M, K = A.shape
     d = L.DecProjDesc()
-    Wr = W8 if W8 is not None else W
+    Wr = W4 if W4 is not None else (W8 if W8 is not None else W)
     d.A, d.lda, d.M, d.K, d.mode = L.ptr(A), _ld(A), M, K, mode
     d.W, d.ldw = L.ptr(W), _ld(Wr)
     if W8 is not None:
         d.W8, d.E8 = L.ptr(W8), L.ptr(E8)
+    if W4 is not None:
+        d.W4, d.E8 = L.ptr(W4), L.ptr(E8)
     if norm_w is not None:
         d.norm_w, d.eps = L.ptr(norm_w), eps
     N = Wr.shape[0] // 2 if mode == 1 else Wr.shape[0]

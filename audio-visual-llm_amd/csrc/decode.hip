@@ -21,6 +21,14 @@
 // operand (exact: e4m3 x 2^e is a bf16 value).  The wave's K range and the 8-way split are those of the bf16 form; only the grouping of
 // elements into the 32-wide MFMA steps differs, so the result is the bf16 form's on the dequantised weights up to fp32 summation order.
 // A group's loads: [norm] exponent dword, then activation loads as in the bf16 form and 2 code loads instead of 4 weight loads.
+//
+// fp4 weight form (W4 != NULL, dec_proj_f4_kernel): the weight rows are OCP MXFP4 codes (e2m1, two per byte, element 2i in the LOW nibble:
+// the order in which v_cvt_scalef32_pk_bf16_fp4 delivers a byte's two results) with the same kind of exponent matrix (emax = 2;
+// avllm_mx4_quantize).  One 16-byte code load covers all FOUR K-steps of a lane:  lane (fr, fq) holds elements 32 fq + [0, 32) of its weight
+// row -- exactly one MX block, so its scale is byte fq of the row's exponent dword -- and step j multiplies elements 32 fq + 8 j + [0, 8)
+// (dword j of the load, four conversions).  Activation and norm-weight addresses follow that order.  A group is then 1 KiB of weights per
+// wave instead of 4, so the ring is deeper (DEC_D4 groups in flight) to keep a comparable number of bytes on the way.  Depths 2 and 6 were
+// measured against it and not kept (profiles/r08_decode_fp4_bench.txt).
 #include "common.h"
 #include "avllm_internal.h"
 #include <type_traits>
@@ -48,6 +56,7 @@ struct DecArgs {
     // (QKV: j = q, k, v; otherwise j = 0).  Added in the epilogue, before RoPE.
     const float* lt; long ldlt; const bf16* lb[3]; float lscale; int lr;
     const uint8_t* W8; const uint8_t* E8;   // fp8 weight form: codes [*, ldw bytes per row], exponents [*, K/32]
+    const uint8_t* W4;                      // fp4 weight form: codes [*, ldw bytes per row] (two per byte), exponents E8 [*, K/32]
 };
 
 // fragment row fr (0..15) of workgroup b -> weight row, and the logical output column it produces
@@ -119,7 +128,81 @@ template <int AL, bool NORM> struct DecGrp8 { frag wb[2], xa[AL], gw; unsigned e
 // fp8 form: element offset of step j (0..3) of a 128-column group for lane column fq (the bf16 form's is 32 j + 8 fq)
 __device__ __forceinline__ int dec_koff8(int j, int fq) { return 64 * (j >> 1) + 16 * fq + 8 * (j & 1); }
 
-template <bool NORM, int AL, bool LORA, bool F8>
+// ---- fp4 form: the K loop of one wave.  Ring of D groups with fixed slot roles: the main loop consumes and refills D groups per trip (single
+// exit), the remaining 1 .. 2D-1 groups are a straight-line tail chosen by their count, so every wait count is an immediate.
+template <int AL, bool NORM> struct DecGrp4 { frag wb, xa[AL], gw; unsigned ex; };      // 1 code load = 4 steps, + the 4 exponents of the row
+#ifdef AVLLM_DEC_F4_DEPTH                                                                 // experiment builds: one depth for every form
+template <int AL> constexpr int DEC_D4 = AVLLM_DEC_F4_DEPTH;
+#else
+template <int AL> constexpr int DEC_D4 = AL == 4 ? 3 : 4;                                 // groups in flight (AL = 4: 25 ring registers per group)
+#endif
+
+template <bool NORM, int AL>
+__device__ __forceinline__ void dec_ring_f4(const DecArgs& a, int fr, int fq, int ar, int asub, int wr, long k0, int G, f32x4& acc, float& ss) {
+    constexpr int SPL = 4 / AL, RPL = 16 / SPL, D = DEC_D4<AL>;
+    typedef DecGrp4<AL, NORM> Grp;
+    const bf16* ap = a.A + (long)ar * a.lda + k0 + 32 * fq + 8 * asub;
+    const uint8_t* bp = a.W4 + (long)wr * a.ldw + (k0 >> 1) + fq * 16;
+    const uint8_t* ep = a.E8 + (long)wr * (a.K >> 5) + (k0 >> 5);
+    const bf16* gp = NORM ? a.norm_w + k0 + 32 * fq + 8 * (fr & 3) : a.A;
+    const int esh = 8 * fq;
+    // loads of a group, in issue order: codes, [norm], exponents, activations
+    constexpr int LG = 2 + AL + (NORM ? 1 : 0);
+    Grp s[D];
+    auto issue = [&](Grp& g, int grp) {
+        gld_nt<0>(g.wb, bp + (long)grp * 64);
+        if constexpr (NORM) gld<0>(g.gw, gp + (long)grp * 128);
+        gld_dw<0>(g.ex, ep + (long)grp * 4);
+        static_for<0, AL>([&](auto ic) { gld<16 * SPL * decltype(ic)::value>(g.xa[decltype(ic)::value], ap + (long)grp * 128); });
+    };
+    auto step = [&](Grp& g, auto jc, auto behind) {
+        constexpr int j = decltype(jc)::value;
+        constexpr int through = 2 + (NORM ? 1 : 0) + (j / SPL + 1);
+        constexpr int N = LG - through + decltype(behind)::value * LG;
+        if constexpr (NORM) wait_vm<N>(g.wb, g.xa[j / SPL], g.gw, g.ex);
+        else wait_vm<N>(g.wb, g.xa[j / SPL], g.ex);
+        frag xr = g.xa[j / SPL];
+        if constexpr (j % SPL != 0) xr = row_from_higher<RPL * (j % SPL)>(xr);
+        bf16x8 x = __builtin_bit_cast(bf16x8, xr);
+        if constexpr (NORM) {
+            const bf16x8 gv = __builtin_bit_cast(bf16x8, row_bcast<j>(g.gw));
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float xf = (float)x[e];
+                ss += xf * xf;
+                x[e] = (bf16)(xf * (float)gv[e]);
+            }
+        }
+        // 8 codes of this step = dword j of the load, x 2^(e - 127) of the lane's block
+        const float sc = __uint_as_float(((g.ex >> esh) & 0xffu) << 23);
+        const unsigned c = g.wb[j];
+        const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 1);
+        const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3);
+        const bf16x8 wv = {p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, x, acc, 0, 0, 0);      // D[n][m]
+    };
+    auto consume = [&](Grp& g, auto behind) { static_for<0, 4>([&](auto jc) { step(g, jc, behind); }); };
+    static_for<0, D>([&](auto ic) { if (decltype(ic)::value < G) issue(s[decltype(ic)::value], decltype(ic)::value); });
+    int g = 0;
+    for (; g + 2 * D <= G; g += D)
+        static_for<0, D>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            consume(s[i], std::integral_constant<int, D - 1>{});
+            issue(s[i], g + D + i);
+        });
+    const int rem = G - g;
+    static_for<1, 2 * D>([&](auto tc) {
+        constexpr int T = decltype(tc)::value;
+        if (rem == T)
+            static_for<0, T>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                consume(s[i % D], std::integral_constant<int, (T < i + D ? T : i + D) - 1 - i>{});     // younger groups in flight
+                if constexpr (i + D < T) issue(s[i % D], g + D + i);
+            });
+    });
+}
+
+template <bool NORM, int AL, bool LORA, bool F8, bool F4 = false>
 __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     __shared__ float part[DW][16][17];      // [wave][n][m]
     __shared__ float ssq[DW][16];
@@ -137,14 +220,17 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     const long k0 = ((long)w * ub + (w < ue ? w : ue)) << 7;
     int col;
     const int wr = dec_wrow(a, blockIdx.x, fr, col);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float ss = 0.f;
+    if constexpr (F4) {
+        dec_ring_f4<NORM, AL>(a, fr, fq, ar, asub, wr, k0, G, acc, ss);
+    } else {
     const bf16* ap = F8 ? a.A + (long)ar * a.lda + k0 + dec_koff8(asub, fq) : a.A + (long)ar * a.lda + k0 + asub * 32 + fq * 8;
     const bf16* bp = a.W + (long)wr * a.ldw + k0 + fq * 8;
     const uint8_t* bp8 = a.W8 + (long)wr * a.ldw + k0 + fq * 16;                     // fp8: codes of steps 2p, 2p+1 at byte 64 p
     const uint8_t* ep = a.E8 + (long)wr * (a.K >> 5) + (k0 >> 5);                     // fp8: the row's 4 exponents of a group = one dword
     const int esh = 8 * (fq >> 1);                                                    // fp8: byte of the lane's block within the pair
     const bf16* gp = NORM ? (F8 ? a.norm_w + k0 + dec_koff8(fr & 3, fq) : a.norm_w + k0 + (fr & 3) * 32 + fq * 8) : a.A;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    float ss = 0.f;
     // loads per group, issued as: [norm] then per step: [activation if the step starts a load] weight.  fp8: [norm] exponents, then per step:
     // [activation] [codes if the step starts a pair]
     constexpr int LG = F8 ? 2 + 1 + AL + (NORM ? 1 : 0) : 4 + AL + (NORM ? 1 : 0);
@@ -222,6 +308,7 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
         for (int g = 1; g + 2 < G; g += 2) { consume(gb, one); issue(gb, g + 2); consume(ga, one); issue(ga, g + 3); }
         consume(gb, one);
         consume(ga, none);
+    }
     }
     // adapters: the finishing thread (m, nn) fetches its 16 rank-side products and its B row now (the weight ring has drained; the loads
     // fly while the partial tiles meet in LDS)
@@ -307,6 +394,8 @@ template <bool NORM, int AL, bool LORA>
 __global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, false>(a); }
 template <bool NORM, int AL, bool LORA>
 __global__ __launch_bounds__(DW * 64, 2) void dec_proj_f8_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, true>(a); }
+template <bool NORM, int AL, bool LORA>
+__global__ __launch_bounds__(DW * 64, 2) void dec_proj_f4_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, false, true>(a); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Single-token attention over the cache, ONE pass: a group of G = hd/8 lanes owns cache rows t = g, g + R, ... and carries a running
@@ -411,7 +500,10 @@ static int dec_launch(DecArgs& a, hipStream_t st) {
     const int grid = a.mode == DEC_SWIGLU ? a.N / 8 : a.N / 16;
 #define DEC_LAUNCH(NORMV, ALV)                                                                                                   \
     do {                                                                                                                       \
-        if (a.W8) {                                                                                                            \
+        if (a.W4) {                                                                                                            \
+            if (a.lt) hipLaunchKernelGGL((dec_proj_f4_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
+            else hipLaunchKernelGGL((dec_proj_f4_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);             \
+        } else if (a.W8) {                                                                                                     \
             if (a.lt) hipLaunchKernelGGL((dec_proj_f8_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
             else hipLaunchKernelGGL((dec_proj_f8_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);             \
         } else if (a.lt) hipLaunchKernelGGL((dec_proj_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
@@ -427,16 +519,21 @@ static int dec_launch(DecArgs& a, hipStream_t st) {
 }
 
 int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
-    AV_CHECK_ARG(d && d->A && (d->W || d->W8), "dec_proj: null operand");
+    AV_CHECK_ARG(d && d->A && (d->W || d->W8 || d->W4), "dec_proj: null operand");
+    AV_CHECK_ARG(!(d->W8 && d->W4), "dec_proj: W8 and W4 are two forms of the same weights, give one");
     AV_CHECK_ARG(d->mode >= DEC_PLAIN && d->mode <= DEC_QKV, "dec_proj: mode %d", d->mode);
     AV_CHECK_ARG(av_dec_proj_supported(AV_BF16, d->M, d->K, d->N, d->mode, d->hd),
                  "dec_proj: bf16, 1 <= M <= 16 (M=%d), K %% 128 == 0 (K=%d), N %% 16 == 0 (%% 8 for SwiGLU; N=%d)", d->M, d->K, d->N);
-    AV_CHECK_ARG(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->lda >= d->K && d->ldw >= d->K, "dec_proj: rows must be 16-byte aligned and hold K elements");
+    AV_CHECK_ARG(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->lda >= d->K && d->ldw >= (d->W4 ? d->K / 2 : d->K),
+                 "dec_proj: rows must be 16-byte aligned and hold K elements");
     AV_CHECK_ARG(!d->W8 || (d->E8 && ((uintptr_t)d->W8 & 15) == 0 && d->ldw % 16 == 0 && ((uintptr_t)d->E8 & 3) == 0),
                  "dec_proj(fp8 weights): codes W8 16-byte aligned with rows of ldw %% 16 == 0 bytes (ldw=%ld), exponents E8 [rows, K/32] 4-byte aligned",
                  (long)d->ldw);
+    AV_CHECK_ARG(!d->W4 || (d->E8 && ((uintptr_t)d->W4 & 15) == 0 && d->ldw % 16 == 0 && ((uintptr_t)d->E8 & 3) == 0),
+                 "dec_proj(fp4 weights): codes W4 16-byte aligned with rows of ldw %% 16 == 0 bytes (ldw=%ld), exponents E8 [rows, K/32] 4-byte aligned",
+                 (long)d->ldw);
     DecArgs a = {};
-    a.W8 = (const uint8_t*)d->W8; a.E8 = (const uint8_t*)d->E8;
+    a.W8 = (const uint8_t*)d->W8; a.E8 = (const uint8_t*)d->E8; a.W4 = (const uint8_t*)d->W4;
     if (a.W8) a.W = nullptr;
     a.A = (const bf16*)d->A; a.lda = d->lda; a.W = (const bf16*)d->W; a.ldw = d->ldw; a.norm_w = (const bf16*)d->norm_w; a.eps = d->eps;
     a.M = d->M; a.K = d->K; a.N = d->N; a.mode = d->mode;

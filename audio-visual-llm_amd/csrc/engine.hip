@@ -248,6 +248,16 @@ int check_llama(const avllm_llama* m) {
                          "llama layer %d: decode_fp8 without the fp8 codes and layout-2 exponents", l);
         }
     }
+    if (m->decode_fp4) {
+        AV_CHECK_ARG(!m->decode_fp8, "llama: decode_fp4 and decode_fp8 are two forms of the same token step, set one");
+        AV_CHECK_ARG(m->dtype == AV_BF16 && m->d % 128 == 0 && m->ffn % 128 == 0 && m->vocab % 16 == 0 && m->lm_head8 && m->elm_head8,
+                     "llama: decode_fp4 needs bf16, d and ffn multiples of 128, vocab a multiple of 16 and the e4m3 lm_head codes + exponents");
+        for (int l = 0; l < m->layers; ++l) {
+            const avllm_llama_layer& P = m->layer[l];
+            AV_CHECK_ARG(P.wqkv4 && P.eqkv4 && P.wo4 && P.eo4 && P.wgu4 && P.egu4 && P.wdown4 && P.edown4,
+                         "llama layer %d: decode_fp4 without the MXFP4 codes and exponents", l);
+        }
+    }
     return AV_OK;
 }
 // grouped-query geometry: q is d wide, k and v are dkv = kv_heads*hd wide; the fused row is [q | k | v] = qw columns
@@ -770,6 +780,7 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         p = {};
     }
     const bool f8 = m->decode_fp8 != 0;      // weight-only fp8: the four projections stream codes + exponents (decode.hip, fp8 weight form)
+    const bool f4 = m->decode_fp4 != 0;      // weight-only fp4: MXFP4 codes (two per byte: the row stride halves) + their own exponents
     p.A = w.x; p.lda = d; p.W = P.wqkv; p.ldw = d; p.norm_w = P.ln1_w; p.eps = m->eps; p.M = B; p.K = d; p.N = qw; p.mode = 2;
     p.C = w.qkv; p.ldc = qw; p.dq = d; p.dkv = dkv; p.hd = hd; p.rope = w.rope_tab; p.kc = kcl; p.vc = vcl; p.Tmax = Tmax; p.pos = pos; p.pos_dev = pos_dev;
     if (lora) {
@@ -777,6 +788,7 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         for (int j = 0; j < 3; ++j) p.lora_b[j] = P.lora[j].B_pad;
     }
     if (f8) { p.W8 = P.wqkv8; p.E8 = P.eqkv8; }
+    if (f4) { p.W4 = P.wqkv4; p.E8 = P.eqkv4; p.ldw = d / 2; }
     AV_TRY(av_dec_proj(&p, st));
     AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
     p = {};
@@ -788,14 +800,17 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
     p.A = w.att; p.lda = d; p.W = P.wo; p.ldw = d; p.M = B; p.K = d; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
     if (lora) { p.lora_t = w.lt + 3 * AVLLM_LORA_PAD; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale; p.lora_b[0] = P.lora[3].B_pad; }
     if (f8) { p.W8 = P.wo8; p.E8 = P.eo8; }
+    if (f4) { p.W4 = P.wo4; p.E8 = P.eo4; p.ldw = d / 2; }
     AV_TRY(av_dec_proj(&p, st));
     p = {};
     p.A = w.x; p.lda = d; p.W = P.wgu; p.ldw = d; p.norm_w = P.ln2_w; p.eps = m->eps; p.M = B; p.K = d; p.N = f; p.mode = 1; p.C = w.hmid; p.ldc = f;
     if (f8) { p.W8 = P.wgu8; p.E8 = P.egu8; }
+    if (f4) { p.W4 = P.wgu4; p.E8 = P.egu4; p.ldw = d / 2; }
     AV_TRY(av_dec_proj(&p, st));
     p = {};
     p.A = w.hmid; p.lda = f; p.W = P.wdown; p.ldw = f; p.M = B; p.K = f; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
     if (f8) { p.W8 = P.wdown8; p.E8 = P.edown8; }
+    if (f4) { p.W4 = P.wdown4; p.E8 = P.edown4; p.ldw = f / 2; }
     return av_dec_proj(&p, st);
 }
 
@@ -817,7 +832,7 @@ extern "C" int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* i
             avllm_dec_proj_desc p = {};
             p.A = w.x; p.lda = d; p.W = m->lm_head; p.ldw = d; p.norm_w = m->norm_w; p.eps = m->eps; p.M = B; p.K = d; p.N = m->vocab; p.mode = 0;
             p.C = logits; p.ldc = m->vocab; p.out_f32 = 1;
-            if (m->decode_fp8) { p.W8 = m->lm_head8; p.E8 = m->elm_head8; }
+            if (m->decode_fp8 || m->decode_fp4) { p.W8 = m->lm_head8; p.E8 = m->elm_head8; }      // decode_fp4: lm_head stays e4m3
             return av_dec_proj(&p, st);
         }
     } else {
@@ -835,6 +850,9 @@ extern "C" int avllm_llama_decode_is_fused(const avllm_llama* m, int32_t B) { re
 // disabled fused path read the bf16 matrices
 extern "C" int avllm_llama_decode_streams_fp8(const avllm_llama* m, int32_t B) {
     return m && check_llama(m) == AV_OK && m->decode_fp8 && llama_decode_fused_ok(m, B) ? 1 : 0;
+}
+extern "C" int avllm_llama_decode_streams_fp4(const avllm_llama* m, int32_t B) {
+    return m && check_llama(m) == AV_OK && m->decode_fp4 && llama_decode_fused_ok(m, B) ? 1 : 0;
 }
 
 extern "C" int avllm_llama_decode_step(const avllm_llama* m, const int64_t* ids, int32_t B, int32_t pos, void* kcache,

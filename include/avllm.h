@@ -132,6 +132,11 @@ int avllm_lora_dx_masked(const void* const* T, const int64_t* ldt, const void* c
 size_t avllm_mx_scale_bytes(int32_t R, int32_t K);
 int avllm_mx_quantize(const void* x, int64_t ldx, int32_t R, int32_t K, void* q, int64_t ldq, void* scales, int32_t layout, int32_t dtype,
                       void* stream);
+/* OCP MXFP4 weight images of the token step (avllm_dec_proj's fp4 form): x [R,K] (bf16 or f32, row stride ldx, K % 32 == 0) -> q uint8
+ * [R, K/2] (row stride ldq bytes, ldq % 16 == 0), two e2m1 codes per byte with element 2i in the low nibble, and exps uint8 [R, K/32]
+ * row-major, E8M0 biased by 127.  Rule (OCP MX v1.0, emax = 2): e = floor(log2(amax of the 32-block)) - 2 clamped to [-127, 127] (all-zero
+ * block: -127); codes = x * 2^-e rounded to nearest even onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturated at +-6; bit 3 = sign. */
+int avllm_mx4_quantize(const void* x, int64_t ldx, int32_t R, int32_t K, void* q, int64_t ldq, void* exps, int32_t dtype, void* stream);
 typedef struct avllm_gemm_f8_desc {
     const void* A;  const void* SA;     /* activations: q [M,K] (layout 0 scales) */
     const void* B;  const void* SB;     /* weights:     q [N,K] (layout 1 scales), nn.Linear orientation */
@@ -487,6 +492,10 @@ typedef struct avllm_llama_layer {
     /* fp8 token step (avllm_llama.decode_fp8 != 0): the exponent matrices [rows, K/32] (avllm_mx_quantize layout 2) of the codes wqkv8, wo8,
      * wgu8, wdown8 above, which the token step then streams instead of the bf16 matrices.  Unused otherwise. */
     const void *eqkv8, *eo8, *egu8, *edown8;
+    /* fp4 token step (avllm_llama.decode_fp4 != 0): MXFP4 codes [rows, K/2] and exponent matrices [rows, K/32] of the four frozen matrices
+     * (avllm_mx4_quantize).  The exponents are not those of the fp8 codes: emax differs. */
+    const void *wqkv4, *wo4, *wgu4, *wdown4;
+    const void *eqkv4, *eo4, *egu4, *edown4;
 } avllm_llama_layer;
 
 typedef struct avllm_llama {
@@ -516,6 +525,10 @@ typedef struct avllm_llama {
      * Needs bf16, d, ffn multiples of 128 and vocab a multiple of 16.  B > 16 and prefill stay on the bf16 matrices.  Independent of fp8. */
     int32_t decode_fp8;
     const void* elm_head8;
+    /* 1: weight-only fp4 token step.  As decode_fp8, but the q|k|v, o, gate|up and down projections of the fused step (B <= 16) stream the
+     * MXFP4 codes (wqkv4 .. wdown4, eqkv4 .. edown4); lm_head -- 2 % of the bytes, and the matrix whose rounding moves the argmax most --
+     * streams as e4m3 (lm_head8, elm_head8).  Same shape conditions as decode_fp8; not together with it. */
+    int32_t decode_fp4;
 } avllm_llama;
 
 size_t avllm_llama_train_workspace_bytes(const avllm_llama* m, int32_t B, int32_t S);
@@ -569,6 +582,8 @@ int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* ids, int32_t
 int avllm_llama_decode_is_fused(const avllm_llama* m, int32_t B);
 /* 1 when a token step of B sequences streams the fp8 weight images (decode_fp8 set and the fused path taken), 0 when it reads bf16. */
 int avllm_llama_decode_streams_fp8(const avllm_llama* m, int32_t B);
+/* The same for the fp4 weight images (decode_fp4).  A decode_fp4 model answers 0 to the fp8 query. */
+int avllm_llama_decode_streams_fp4(const avllm_llama* m, int32_t B);
 int avllm_pos_advance(int32_t* pos_dev, int32_t by, void* stream);
 
 /* One projection of a decode token step (bf16, 1 <= M <= 16 rows, K % 128 == 0): C = epilogue(rmsnorm?(A) . W^T).  Every weight row
@@ -602,6 +617,12 @@ typedef struct avllm_dec_proj_desc {
      * the norm fold, residual, outputs and adapters as above: the product is the bf16 form's on the weights codes * 2^(E8 - 127) (exact in
      * bf16), summed in a different fp32 order inside each 64-column pair of K-steps. */
     const void* W8; const void* E8;
+    /* fp4 weight form: W4 != NULL streams the weight rows as OCP MXFP4 codes (e2m1, two per byte: element 2i of a row in the LOW nibble of
+     * byte i, element 2i+1 in the high nibble; bit 3 of a code is the sign) [rows, K/2] (row stride ldw BYTES, ldw % 16 == 0, 16-byte
+     * aligned) with E8 = their E8M0 exponents [rows, K/32] uint8, row-major, biased by 127 (avllm_mx4_quantize); W is then ignored.  Not
+     * together with W8.  Every mode, the norm fold, residual, outputs and adapters as above: the product is the bf16 form's on the weights
+     * code value * 2^(E8 - 127) (exact in bf16), summed in a different fp32 order inside each 128-column group of K-steps. */
+    const void* W4;
 } avllm_dec_proj_desc;
 int avllm_dec_proj(const avllm_dec_proj_desc* d, void* stream);
 /* Single-query attention over the cache rows [0, Tk + *tk_dev) (tk_dev may be NULL) of kc/vc [B][Tmax][(H/kv_group)*hd]: one pass with

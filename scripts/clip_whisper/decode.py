@@ -58,8 +58,9 @@ def parse_args(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=1.0, help="> 1 lowers the score of every token already generated (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size is generated twice (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=0, help="EOS is not generated before this many new tokens")
-    p.add_argument("--decode_weights", type=str, choices=["bf16", "fp8"], default="bf16",
-                   help="fp8: the token steps stream the LLM's frozen projections as block-scaled e4m3 (needs bf16; prefill stays bf16)")
+    p.add_argument("--decode_weights", type=str, choices=["bf16", "fp8", "fp4"], default="bf16",
+                   help="fp8: the token steps stream the LLM's frozen projections as block-scaled e4m3 (needs bf16; prefill stays bf16); "
+                        "fp4: as OCP MXFP4 with lm_head as e4m3 (coarser: about 11.5 %% weight error, effect on WER not measured)")
     p.add_argument("--load_lora", action="store_true")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Weight-streaming rate of the decode-step projections (Llama-2-7B shapes, bf16, B rows): avllm_dec_proj (fused forms) next to the
 round-1 small-M avllm_gemm, each over a rotation of weight copies larger than the 256 MB of L2 + MALL so every launch streams from HBM.
---fp8: the fp8 weight form of the same launches (e4m3 codes + layout-2 exponents) instead of the small-M gemm column."""
+--fp8: the fp8 weight form of the same launches (e4m3 codes + layout-2 exponents) instead of the small-M gemm column; --fp4 (with --fp8):
+the MXFP4 weight form as a third column."""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "audio-visual-llm_amd"))
@@ -10,6 +11,7 @@ from avllm import ops
 
 ap = argparse.ArgumentParser(); ap.add_argument("--batch", type=int, default=8); ap.add_argument("--iters", type=int, default=40)
 ap.add_argument("--fp8", action="store_true")
+ap.add_argument("--fp4", action="store_true")
 a = ap.parse_args()
 dev, BF, M = "cuda:0", torch.bfloat16, a.batch
 d, f, V, hd = 4096, 11008, 32000, 128
@@ -58,12 +60,18 @@ for name, rows, K, mode in (("q|k|v + norm + rope + append", 3 * d, d, 2), ("o +
         if kw is None:
             kw = dict(norm_w=norm, out=o32) if rows == V else dict(R=x, out=x)
         old = lambda i: ops.dec_proj(A, None, W8=W8s[i % ncopy][0], E8=W8s[i % ncopy][1], **kw)
+    t4 = None
+    if a.fp8 and a.fp4:
+        W4s = [ops.mx4_quantize(W) for W in Ws]
+        t4 = timeit(lambda i: ops.dec_proj(A, None, W4=W4s[i % ncopy][0], E8=W4s[i % ncopy][1], **kw), a.iters)
+        del W4s
     tn, to = timeit(new, a.iters), timeit(old, a.iters)
     gb = rows * K * 2 / 1e9
     if a.fp8:
         gb8 = rows * K * (1 + 1 / 32) / 1e9
         print(f"{name:32s} [{rows:6d} x {K:5d}] bf16 {tn * 1e6:7.1f} us = {gb / tn / 1e3:5.2f} TB/s   fp8 {to * 1e6:7.1f} us = {gb8 / to / 1e3:5.2f} TB/s "
-              f"({tn / to:.2f}x)", flush=True)
+              f"({tn / to:.2f}x)" + (f"   fp4 {t4 * 1e6:7.1f} us = {rows * K * (0.5 + 1 / 32) / 1e9 / t4 / 1e3:5.2f} TB/s ({to / t4:.2f}x fp8)" if t4 else ""),
+              flush=True)
         del Ws, W8s
         continue
     print(f"{name:32s} [{rows:6d} x {K:5d}] {gb * 1e3:7.1f} MB  dec_proj {tn * 1e6:7.1f} us = {gb / tn / 1e3:5.2f} TB/s   small-M gemm {to * 1e6:7.1f} us = {gb / to / 1e3:5.2f} TB/s", flush=True)

@@ -9,7 +9,7 @@ from avllm.model import ClipWhisperModel
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8); ap.add_argument("--new", type=int, default=64); ap.add_argument("--frames", type=int, default=125)
-ap.add_argument("--decode_weights", choices=["bf16", "fp8"], default="bf16")
+ap.add_argument("--decode_weights", choices=["bf16", "fp8", "fp4"], default="bf16")
 a = ap.parse_args()
 m = ClipWhisperModel(device="cuda:0", max_seq_len=256, precision="bf16", use_lora=False, synthetic_weights=True, decode_weights=a.decode_weights).eval()
 m.eos_token_id = None                                    # random weights: never stop early
