@@ -14,21 +14,13 @@
 // HBM), its 8 waves split K, each wave keeps a ring of DEPTH 1 KiB weight loads in flight (non-temporal: the stream must not evict
 // the activations from L2) and the 8 partial 16x16 tiles meet in LDS.
 //
-// fp8 weight form (W8 != NULL, dec_proj_f8_kernel): the weight rows are e4m3 codes [*, K] with one E8M0 exponent per 32 elements along K
-// (E8 [*, K/32] row-major, biased by 127: avllm_mx_quantize layout 2).  One 16-byte code load covers TWO K-steps of a lane, so inside each
-// pair of steps the K elements are dealt as  lane (fr, fq), step 2p + s:  elements 64 p + 16 fq + 8 s + [0, 8)  (the bf16 form: 32 j + 8 fq),
-// the activation and norm-weight addresses follow that order, and v_cvt_scalef32_pk_bf16_fp8 turns the codes into the same bf16 MFMA
-// operand (exact: e4m3 x 2^e is a bf16 value).  The wave's K range and the 8-way split are those of the bf16 form; only the grouping of
-// elements into the 32-wide MFMA steps differs, so the result is the bf16 form's on the dequantised weights up to fp32 summation order.
-// A group's loads: [norm] exponent dword, then activation loads as in the bf16 form and 2 code loads instead of 4 weight loads.
-//
-// fp4 weight form (W4 != NULL, dec_proj_f4_kernel): the weight rows are OCP MXFP4 codes (e2m1, two per byte, element 2i in the LOW nibble:
-// the order in which v_cvt_scalef32_pk_bf16_fp4 delivers a byte's two results) with the same kind of exponent matrix (emax = 2;
-// avllm_mx4_quantize).  One 16-byte code load covers all FOUR K-steps of a lane:  lane (fr, fq) holds elements 32 fq + [0, 32) of its weight
-// row -- exactly one MX block, so its scale is byte fq of the row's exponent dword -- and step j multiplies elements 32 fq + 8 j + [0, 8)
-// (dword j of the load, four conversions).  Activation and norm-weight addresses follow that order.  A group is then 1 KiB of weights per
-// wave instead of 4, so the ring is deeper (DEC_D4 groups in flight) to keep a comparable number of bytes on the way.  Depths 2 and 6 were
-// measured against it and not kept (profiles/r08_decode_fp4_bench.txt).
+// Weight forms.  The weight rows are streamed as bf16, as e4m3 codes (fp8: avllm_mx_quantize layout 2) or as OCP MXFP4 codes (fp4: e2m1, two
+// per byte, element 2i in the LOW nibble; avllm_mx4_quantize); both code forms carry one E8M0 exponent per 32 elements along K (E8 [*, K/32]
+// row-major, biased by 127) and become the same bf16 MFMA operand through v_cvt_scalef32_pk_bf16_fp8 / _fp4 (exact: code x 2^e is a bf16
+// value).  A wave's K range, the 8-way split and the 128-column ring group are the same for every form; what a form decides -- 16-byte weight
+// loads per group, which K elements lane (fr, fq) multiplies at step j (the activation and norm-weight addresses follow), which exponent byte
+// scales them, the order in which a group's loads are issued (the wait counts derive from it), the conversion and the ring depth -- is its
+// DecForm below and nowhere else.  So the result is the bf16 form's on the dequantised weights up to fp32 summation order inside a group.
 #include "common.h"
 #include "avllm_internal.h"
 #include <type_traits>
@@ -38,10 +30,12 @@ namespace {
 constexpr int DW = 8;            // waves per workgroup (K split)
 
 enum { DEC_PLAIN = 0, DEC_SWIGLU = 1, DEC_QKV = 2 };
+enum class WForm { bf16 = 0, fp8 = 1, fp4 = 2 };
 
 struct DecArgs {
     const bf16* A; long lda;            // activations [M, K]
-    const bf16* W; long ldw;            // weight rows [*, K]
+    const uint8_t* W; long ldw;         // weight rows [*, K] in the form's elements, ldw BYTES apart
+    const uint8_t* E8; WForm form;      // fp8 / fp4: exponents [*, K/32]
     const bf16* norm_w; float eps;      // NORM: A is RMS-normalised on the fly (x * rstd * w)
     int M, K, N, mode;
     void* C; long ldc; int out_f32;     // PLAIN: C[M,N] (+R); SWIGLU: C[M,N=F] = silu(gate) * up; QKV: q part [M, dq]
@@ -55,8 +49,6 @@ struct DecArgs {
     // (columns 64 j .. 64 j + r of module j; made by a PLAIN launch over the A images), lb[j] the padded B image [rows, 64] of module j
     // (QKV: j = q, k, v; otherwise j = 0).  Added in the epilogue, before RoPE.
     const float* lt; long ldlt; const bf16* lb[3]; float lscale; int lr;
-    const uint8_t* W8; const uint8_t* E8;   // fp8 weight form: codes [*, ldw bytes per row], exponents [*, K/32]
-    const uint8_t* W4;                      // fp4 weight form: codes [*, ldw bytes per row] (two per byte), exponents E8 [*, K/32]
 };
 
 // fragment row fr (0..15) of workgroup b -> weight row, and the logical output column it produces
@@ -78,8 +70,8 @@ __device__ __forceinline__ int dec_wrow(const DecArgs& a, int b, int fr, int& co
     return col;
 }
 
-// 16-byte global loads the compiler's wait-count pass does not see: the ring below keeps 8 K-steps per wave in flight and waits with
-// exact vmcnt values (loads return in issue order), which clang does not do for a register ring (it drains to vmcnt(0) every trip).
+// 16-byte global loads the compiler's wait-count pass does not see: the ring below keeps its groups in flight and waits with exact vmcnt
+// values (loads return in issue order), which clang does not do for a register ring (it drains to vmcnt(0) every trip).
 typedef u32x4 frag;
 template <int OFF> __device__ __forceinline__ void gld(frag& r, const void* p) {
     asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
@@ -87,20 +79,21 @@ template <int OFF> __device__ __forceinline__ void gld(frag& r, const void* p) {
 template <int OFF> __device__ __forceinline__ void gld_nt(frag& r, const void* p) {
     asm volatile("global_load_dwordx4 %0, %1, off offset:%2 nt" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
 }
-template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag& c) {
-    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b) {
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
-}
 template <int OFF> __device__ __forceinline__ void gld_dw(unsigned& r, const void* p) {
     asm volatile("global_load_dword %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
 }
-template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag& c, unsigned& e) {
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(e) : "n"(N));
+// the wait names the registers the step reads, so nothing that uses them moves above it
+template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b) {
+    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag& c) {
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N));
 }
 template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, unsigned& e) {
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(a), "+v"(b), "+v"(e) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void wait_vm(frag& a, frag& b, frag& c, unsigned& e) {
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(e) : "n"(N));
 }
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
@@ -121,47 +114,123 @@ template <int J> __device__ __forceinline__ frag row_bcast(frag v) { return dpp4
 // path is the limiter, so every load that is not a weight load has to go.  AL = activation loads per group:
 //   M > 8: 4 (lane (fr, fq) = row fr of one step);  M <= 8: 2 (lanes fr >= 8 fetch rows 0..7 of the NEXT step and a row rotate brings them
 //   down when that step is consumed; MFMA output columns >= 8 are garbage nobody reads);  M <= 4: 1 (four steps per load).
-// The norm weights of the 4 steps come in ONE load (lane row fr & 3 holds step fr & 3) and reach all rows through a row broadcast.
-template <int AL, bool NORM> struct DecGrp { frag wb[4], xa[AL], gw; };
-template <int AL, bool NORM> struct DecGrp8 { frag wb[2], xa[AL], gw; unsigned ex; };     // fp8: 2 code loads + the 4 exponents of 16 rows
+// The norm weights of the 4 steps come in ONE load (lane row fr & 3 holds step fr & 3) and reach all rows through a row broadcast; the
+// exponents of a weight row's 4 blocks are one dword.
 
-// fp8 form: element offset of step j (0..3) of a 128-column group for lane column fq (the bf16 form's is 32 j + 8 fq)
-__device__ __forceinline__ int dec_koff8(int j, int fq) { return 64 * (j >> 1) + 16 * fq + 8 * (j & 1); }
+// The loads of one group in issue order.  The wait count of a step is read off this list, so it cannot drift from what issue() does.
+enum { LD_W, LD_X, LD_N, LD_E };            // weight load i (16 bytes at byte 64 i of the lane's group), activation load i, norm weights, exponents
+struct DecOrder {
+    int n = 0, kind[10] = {}, idx[10] = {};
+    constexpr void add(int k, int i) { kind[n] = k; idx[n] = i; ++n; }
+    constexpr int upto(int k, int i) const {            // loads issued up to and including load (k, i); 0 if the group has none
+        for (int p = 0; p < n; ++p) if (kind[p] == k && idx[p] == i) return p + 1;
+        return 0;
+    }
+    // loads the step that reads weight load w and activation load x has to see back (they return in issue order)
+    constexpr int through(int w, int x) const {
+        int t = upto(LD_W, w);
+        for (int u : {upto(LD_X, x), upto(LD_N, 0), upto(LD_E, 0)}) t = u > t ? u : t;
+        return t;
+    }
+};
 
-// ---- fp4 form: the K loop of one wave.  Ring of D groups with fixed slot roles: the main loop consumes and refills D groups per trip (single
-// exit), the remaining 1 .. 2D-1 groups are a straight-line tail chosen by their count, so every wait count is an immediate.
-template <int AL, bool NORM> struct DecGrp4 { frag wb, xa[AL], gw; unsigned ex; };      // 1 code load = 4 steps, + the 4 exponents of the row
-#ifdef AVLLM_DEC_F4_DEPTH                                                                 // experiment builds: one depth for every form
-template <int AL> constexpr int DEC_D4 = AVLLM_DEC_F4_DEPTH;
-#else
-template <int AL> constexpr int DEC_D4 = AL == 4 ? 3 : 4;                                 // groups in flight (AL = 4: 25 ring registers per group)
-#endif
+// A weight form's data format, the only place that knows it.  WL: 16-byte weight loads per lane and 128-column group (step j reads load
+// j WL / 4); EXP: the group has an exponent dword; depth: groups in flight, the smaller the group's bytes the deeper; koff: element offset
+// inside the group of step j for lane column fq; ebit: bit offset in the exponent dword of the byte that scales those elements; order: see
+// DecOrder (SPL = steps per activation load; the orders were measured: profiles/r01_decode_bench.txt, r06_decode_fp8_bench.txt,
+// r08_decode_fp4_bench.txt, the last also for depths 2 and 6 of fp4); operand: the step's 8 weights as the bf16 MFMA operand, times sc.
+template <WForm F> struct DecForm;
+template <> struct DecForm<WForm::bf16> {
+    static constexpr int WL = 4;
+    static constexpr bool EXP = false;
+    static constexpr int depth(int) { return 2; }
+    static constexpr int koff(int j, int fq) { return 32 * j + 8 * fq; }
+    static constexpr int ebit(int, int) { return 0; }
+    static constexpr DecOrder order(int SPL, bool NORM) {           // [norm], then per step: [activation if the step starts a load] weight
+        DecOrder o;
+        if (NORM) o.add(LD_N, 0);
+        for (int j = 0; j < 4; ++j) { if (j % SPL == 0) o.add(LD_X, j / SPL); o.add(LD_W, j); }
+        return o;
+    }
+    template <int J> static __device__ __forceinline__ bf16x8 operand(const frag (&wb)[WL], float) { return __builtin_bit_cast(bf16x8, wb[J]); }
+};
+template <> struct DecForm<WForm::fp8> {                            // one code load covers TWO steps of a lane: dwords 2 (j & 1), + 1 are step j's
+    static constexpr int WL = 2;
+    static constexpr bool EXP = true;
+    static constexpr int depth(int) { return 2; }
+    static constexpr int koff(int j, int fq) { return 64 * (j >> 1) + 16 * fq + 8 * (j & 1); }
+    static constexpr int ebit(int j, int fq) { return 16 * (j >> 1) + 8 * (fq >> 1); }
+    static constexpr DecOrder order(int SPL, bool NORM) {           // [norm] exponents, then per step: [activation] [codes if the step starts a pair]
+        DecOrder o;
+        if (NORM) o.add(LD_N, 0);
+        o.add(LD_E, 0);
+        for (int j = 0; j < 4; ++j) { if (j % SPL == 0) o.add(LD_X, j / SPL); if (j % 2 == 0) o.add(LD_W, j / 2); }
+        return o;
+    }
+    template <int J> static __device__ __forceinline__ bf16x8 operand(const frag (&wb)[WL], float sc) {
+        const unsigned c0 = wb[J / 2][2 * (J & 1)], c1 = wb[J / 2][2 * (J & 1) + 1];
+        const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, true);
+        const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, true);
+        return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+    }
+};
+template <> struct DecForm<WForm::fp4> {                            // one code load covers all FOUR steps: the lane's 32 elements are one MX block, dword j is step j's
+    static constexpr int WL = 1;
+    static constexpr bool EXP = true;
+    static constexpr int depth(int AL) { return AL == 4 ? 3 : 4; }  // AL = 4: 25 ring registers per group
+    static constexpr int koff(int j, int fq) { return 32 * fq + 8 * j; }
+    static constexpr int ebit(int, int fq) { return 8 * fq; }
+    static constexpr DecOrder order(int SPL, bool NORM) {           // codes, [norm], exponents, activations
+        DecOrder o;
+        o.add(LD_W, 0);
+        if (NORM) o.add(LD_N, 0);
+        o.add(LD_E, 0);
+        for (int i = 0; i < 4 / SPL; ++i) o.add(LD_X, i);
+        return o;
+    }
+    template <int J> static __device__ __forceinline__ bf16x8 operand(const frag (&wb)[WL], float sc) {
+        const unsigned c = wb[0][J];
+        const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 1);
+        const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3);
+        return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+    }
+};
 
-template <bool NORM, int AL>
-__device__ __forceinline__ void dec_ring_f4(const DecArgs& a, int fr, int fq, int ar, int asub, int wr, long k0, int G, f32x4& acc, float& ss) {
-    constexpr int SPL = 4 / AL, RPL = 16 / SPL, D = DEC_D4<AL>;
-    typedef DecGrp4<AL, NORM> Grp;
-    const bf16* ap = a.A + (long)ar * a.lda + k0 + 32 * fq + 8 * asub;
-    const uint8_t* bp = a.W4 + (long)wr * a.ldw + (k0 >> 1) + fq * 16;
-    const uint8_t* ep = a.E8 + (long)wr * (a.K >> 5) + (k0 >> 5);
-    const bf16* gp = NORM ? a.norm_w + k0 + 32 * fq + 8 * (fr & 3) : a.A;
-    const int esh = 8 * fq;
-    // loads of a group, in issue order: codes, [norm], exponents, activations
-    constexpr int LG = 2 + AL + (NORM ? 1 : 0);
+template <WForm F, int AL> struct DecGrp { frag wb[DecForm<F>::WL], xa[AL], gw; unsigned ex; };
+template <WForm F, int AL, bool NORM> constexpr DecOrder dec_order = DecForm<F>::order(4 / AL, NORM);
+
+// The K loop of one wave: G groups from column k0 on, accumulated in increasing order.  Ring of D groups with fixed slot roles (a loop whose
+// exit alternates between the slots makes the compiler copy ring registers that still have loads in flight): the main loop consumes and
+// refills D groups per trip (single exit), the remaining 1 .. 2D-1 groups are a straight-line tail chosen by their count, so every wait
+// count is an immediate.  A group is refilled in one burst once its 4 steps are consumed.  A wave with G = 0 (K < 1024: fewer groups than waves) issues and consumes nothing.
+template <WForm F, bool NORM, int AL>
+__device__ __forceinline__ void dec_k_loop(const DecArgs& a, int fr, int fq, int ar, int asub, int wr, long k0, int G, f32x4& acc, float& ss) {
+    typedef DecForm<F> Fm;
+    typedef DecGrp<F, AL> Grp;
+    constexpr int SPL = 4 / AL, RPL = 16 / SPL, D = Fm::depth(AL), WL = Fm::WL;        // K-steps, activation rows per activation load
+    constexpr DecOrder ORD = dec_order<F, AL, NORM>;
+    const bf16* ap = a.A + (long)ar * a.lda + k0 + Fm::koff(asub, fq);
+    const uint8_t* bp = a.W + (long)wr * a.ldw + (k0 >> 1) * WL + fq * 16;
+    const uint8_t* ep = Fm::EXP ? a.E8 + (long)wr * (a.K >> 5) + (k0 >> 5) : nullptr;
+    const bf16* gp = NORM ? a.norm_w + k0 + Fm::koff(fr & 3, fq) : a.A;
     Grp s[D];
     auto issue = [&](Grp& g, int grp) {
-        gld_nt<0>(g.wb, bp + (long)grp * 64);
-        if constexpr (NORM) gld<0>(g.gw, gp + (long)grp * 128);
-        gld_dw<0>(g.ex, ep + (long)grp * 4);
-        static_for<0, AL>([&](auto ic) { gld<16 * SPL * decltype(ic)::value>(g.xa[decltype(ic)::value], ap + (long)grp * 128); });
+        static_for<0, ORD.n>([&](auto pc) {
+            constexpr int kind = dec_order<F, AL, NORM>.kind[decltype(pc)::value], i = dec_order<F, AL, NORM>.idx[decltype(pc)::value];
+            if constexpr (kind == LD_W) gld_nt<64 * i>(g.wb[i], bp + (long)grp * (64 * WL));
+            else if constexpr (kind == LD_X) gld<2 * Fm::koff(SPL * i, 0)>(g.xa[i], ap + (long)grp * 128);
+            else if constexpr (kind == LD_N) gld<0>(g.gw, gp + (long)grp * 128);
+            else gld_dw<0>(g.ex, ep + (long)grp * 4);
+        });
     };
-    auto step = [&](Grp& g, auto jc, auto behind) {
-        constexpr int j = decltype(jc)::value;
-        constexpr int through = 2 + (NORM ? 1 : 0) + (j / SPL + 1);
-        constexpr int N = LG - through + decltype(behind)::value * LG;
-        if constexpr (NORM) wait_vm<N>(g.wb, g.xa[j / SPL], g.gw, g.ex);
-        else wait_vm<N>(g.wb, g.xa[j / SPL], g.ex);
-        frag xr = g.xa[j / SPL];
+    auto step = [&](Grp& g, auto jc, auto behind) {      // wait for step j of this group (`behind` younger groups in flight), multiply
+        constexpr int j = decltype(jc)::value, wl = j * WL / 4, xl = j / SPL;
+        constexpr int N = dec_order<F, AL, NORM>.n * (1 + decltype(behind)::value) - dec_order<F, AL, NORM>.through(wl, xl);
+        if constexpr (NORM && Fm::EXP) wait_vm<N>(g.wb[wl], g.xa[xl], g.gw, g.ex);
+        else if constexpr (NORM) wait_vm<N>(g.wb[wl], g.xa[xl], g.gw);
+        else if constexpr (Fm::EXP) wait_vm<N>(g.wb[wl], g.xa[xl], g.ex);
+        else wait_vm<N>(g.wb[wl], g.xa[xl]);
+        frag xr = g.xa[xl];
         if constexpr (j % SPL != 0) xr = row_from_higher<RPL * (j % SPL)>(xr);
         bf16x8 x = __builtin_bit_cast(bf16x8, xr);
         if constexpr (NORM) {
@@ -173,13 +242,9 @@ __device__ __forceinline__ void dec_ring_f4(const DecArgs& a, int fr, int fq, in
                 x[e] = (bf16)(xf * (float)gv[e]);
             }
         }
-        // 8 codes of this step = dword j of the load, x 2^(e - 127) of the lane's block
-        const float sc = __uint_as_float(((g.ex >> esh) & 0xffu) << 23);
-        const unsigned c = g.wb[j];
-        const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 0), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 1);
-        const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 2), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, sc, 3);
-        const bf16x8 wv = {p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, x, acc, 0, 0, 0);      // D[n][m]
+        float sc = 0.f;                                  // 2^(e - 127) of the lane's block
+        if constexpr (Fm::EXP) sc = __uint_as_float(((g.ex >> Fm::ebit(j, fq)) & 0xffu) << 23);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Fm::template operand<j>(g.wb, sc), x, acc, 0, 0, 0);      // D[n][m]
     };
     auto consume = [&](Grp& g, auto behind) { static_for<0, 4>([&](auto jc) { step(g, jc, behind); }); };
     static_for<0, D>([&](auto ic) { if (decltype(ic)::value < G) issue(s[decltype(ic)::value], decltype(ic)::value); });
@@ -202,7 +267,7 @@ __device__ __forceinline__ void dec_ring_f4(const DecArgs& a, int fr, int fq, in
     });
 }
 
-template <bool NORM, int AL, bool LORA, bool F8, bool F4 = false>
+template <WForm F, bool NORM, int AL, bool LORA>
 __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     __shared__ float part[DW][16][17];      // [wave][n][m]
     __shared__ float ssq[DW][16];
@@ -210,8 +275,7 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int fr = lane & 15, fq = lane >> 4;
     const int M = a.M;
-    constexpr int SPL = 4 / AL;              // K-steps per activation load
-    constexpr int RPL = 16 / SPL;            // activation rows per load
+    constexpr int RPL = 4 * AL;              // activation rows per load (16 / K-steps per load)
     const int arow = fr & (RPL - 1), asub = fr / RPL;
     const int ar = arow < M ? arow : M - 1;
     // K in units of 4 steps (128 columns), dealt to the 8 waves as evenly as whole units allow (K = 11008: 11,11,11,11,11,11,10,10)
@@ -222,94 +286,7 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     const int wr = dec_wrow(a, blockIdx.x, fr, col);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float ss = 0.f;
-    if constexpr (F4) {
-        dec_ring_f4<NORM, AL>(a, fr, fq, ar, asub, wr, k0, G, acc, ss);
-    } else {
-    const bf16* ap = F8 ? a.A + (long)ar * a.lda + k0 + dec_koff8(asub, fq) : a.A + (long)ar * a.lda + k0 + asub * 32 + fq * 8;
-    const bf16* bp = a.W + (long)wr * a.ldw + k0 + fq * 8;
-    const uint8_t* bp8 = a.W8 + (long)wr * a.ldw + k0 + fq * 16;                     // fp8: codes of steps 2p, 2p+1 at byte 64 p
-    const uint8_t* ep = a.E8 + (long)wr * (a.K >> 5) + (k0 >> 5);                     // fp8: the row's 4 exponents of a group = one dword
-    const int esh = 8 * (fq >> 1);                                                    // fp8: byte of the lane's block within the pair
-    const bf16* gp = NORM ? (F8 ? a.norm_w + k0 + dec_koff8(fr & 3, fq) : a.norm_w + k0 + (fr & 3) * 32 + fq * 8) : a.A;
-    // loads per group, issued as: [norm] then per step: [activation if the step starts a load] weight.  fp8: [norm] exponents, then per step:
-    // [activation] [codes if the step starts a pair]
-    constexpr int LG = F8 ? 2 + 1 + AL + (NORM ? 1 : 0) : 4 + AL + (NORM ? 1 : 0);
-    typedef std::conditional_t<F8, DecGrp8<AL, NORM>, DecGrp<AL, NORM>> Grp;
-    Grp ga, gb;
-    auto issue = [&](Grp& g, int grp) {
-        if constexpr (NORM) gld<0>(g.gw, gp + (long)grp * 128);
-        if constexpr (F8) gld_dw<0>(g.ex, ep + (long)grp * 4);
-        static_for<0, 4>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            if constexpr (F8) {
-                if constexpr (j % SPL == 0) gld<2 * (64 * (j >> 1) + 8 * (j & 1))>(g.xa[j / SPL], ap + (long)grp * 128);
-                if constexpr (j % 2 == 0) gld_nt<32 * j>(g.wb[j / 2], bp8 + (long)grp * 128);
-            } else {
-                if constexpr (j % SPL == 0) gld<64 * j>(g.xa[j / SPL], ap + (long)grp * 128);
-                gld_nt<64 * j>(g.wb[j], bp + (long)grp * 128);
-            }
-        });
-    };
-    auto step = [&](Grp& g, auto jc, auto behind) {      // wait for step j of this group (`behind` younger groups in flight), multiply
-        constexpr int j = decltype(jc)::value;
-        // loads of this group issued up to and including weight j (fp8: the exponents and the codes of step j's pair)
-        constexpr int through = F8 ? (NORM ? 1 : 0) + 1 + (j / SPL + 1) + (j / 2 + 1) : (NORM ? 1 : 0) + (j / SPL + 1) + (j + 1);
-        constexpr int N = LG - through + decltype(behind)::value * LG;
-        if constexpr (F8) {
-            if constexpr (NORM) wait_vm<N>(g.wb[j / 2], g.xa[j / SPL], g.gw, g.ex);
-            else wait_vm<N>(g.wb[j / 2], g.xa[j / SPL], g.ex);
-        } else {
-            if constexpr (NORM) wait_vm<N>(g.wb[j], g.xa[j / SPL], g.gw);
-            else wait_vm<N>(g.wb[j], g.xa[j / SPL]);
-        }
-        frag xr = g.xa[j / SPL];
-        if constexpr (j % SPL != 0) xr = row_from_higher<RPL * (j % SPL)>(xr);
-        bf16x8 x = __builtin_bit_cast(bf16x8, xr);
-        if constexpr (NORM) {
-            const bf16x8 gv = __builtin_bit_cast(bf16x8, row_bcast<j>(g.gw));
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float xf = (float)x[e];
-                ss += xf * xf;
-                x[e] = (bf16)(xf * (float)gv[e]);
-            }
-        }
-        bf16x8 wv;
-        if constexpr (F8) {         // 8 codes of this step (dwords 2 (j & 1), +1 of the pair's load) x 2^(e - 127) of the lane's block
-            const float sc = __uint_as_float(((g.ex >> (16 * (j >> 1) + esh)) & 0xffu) << 23);
-            const unsigned c0 = g.wb[j / 2][2 * (j & 1)], c1 = g.wb[j / 2][2 * (j & 1) + 1];
-            const bf16x2 p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, false), p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c0, sc, true);
-            const bf16x2 p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, false), p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c1, sc, true);
-            wv = (bf16x8){p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
-        } else {
-            wv = __builtin_bit_cast(bf16x8, g.wb[j]);
-        }
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, x, acc, 0, 0, 0);      // D[n][m]
-    };
-    auto consume = [&](Grp& g, auto behind) { static_for<0, 4>([&](auto jc) { step(g, jc, behind); }); };
-    const std::integral_constant<int, 0> none{};
-    const std::integral_constant<int, 1> one{};
-    // Two groups in flight; a group is refilled in one burst once its 4 steps are consumed.  Single-exit loops with fixed slot roles (a loop
-    // whose exit alternates between the groups makes the compiler copy ring registers that still have loads in flight): an odd group count
-    // peels one refill first, which swaps the roles for the rest of the wave's life.
-    if (G == 1) {
-        issue(ga, 0);
-        consume(ga, none);
-    } else if (G >= 2 && !(G & 1)) {
-        issue(ga, 0);
-        issue(gb, 1);
-        for (int g = 0; g + 2 < G; g += 2) { consume(ga, one); issue(ga, g + 2); consume(gb, one); issue(gb, g + 3); }
-        consume(ga, one);
-        consume(gb, none);
-    } else if (G >= 3) {
-        issue(ga, 0);
-        issue(gb, 1);
-        consume(ga, one); issue(ga, 2);
-        for (int g = 1; g + 2 < G; g += 2) { consume(gb, one); issue(gb, g + 2); consume(ga, one); issue(ga, g + 3); }
-        consume(gb, one);
-        consume(ga, none);
-    }
-    }
+    dec_k_loop<F, NORM, AL>(a, fr, fq, ar, asub, wr, k0, G, acc, ss);
     // adapters: the finishing thread (m, nn) fetches its 16 rank-side products and its B row now (the weight ring has drained; the loads
     // fly while the partial tiles meet in LDS)
     f32x4 ltv[4] = {};
@@ -391,11 +368,11 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
 }
 
 template <bool NORM, int AL, bool LORA>
-__global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, false>(a); }
+__global__ __launch_bounds__(DW * 64, 2) void dec_proj_kernel(DecArgs a) { dec_proj_body<WForm::bf16, NORM, AL, LORA>(a); }
 template <bool NORM, int AL, bool LORA>
-__global__ __launch_bounds__(DW * 64, 2) void dec_proj_f8_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, true>(a); }
+__global__ __launch_bounds__(DW * 64, 2) void dec_proj_f8_kernel(DecArgs a) { dec_proj_body<WForm::fp8, NORM, AL, LORA>(a); }
 template <bool NORM, int AL, bool LORA>
-__global__ __launch_bounds__(DW * 64, 2) void dec_proj_f4_kernel(DecArgs a) { dec_proj_body<NORM, AL, LORA, false, true>(a); }
+__global__ __launch_bounds__(DW * 64, 2) void dec_proj_f4_kernel(DecArgs a) { dec_proj_body<WForm::fp4, NORM, AL, LORA>(a); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Single-token attention over the cache, ONE pass: a group of G = hd/8 lanes owns cache rows t = g, g + R, ... and carries a running
@@ -497,23 +474,25 @@ bool av_dec_proj_supported(int dtype, int M, int K, int N, int mode, int hd) {
 }
 
 static int dec_launch(DecArgs& a, hipStream_t st) {
+    // [form][norm][al: 1, 2, 4][adapters]
+    static const decltype(&dec_proj_kernel<false, 1, false>) kernel[3][2][3][2] = {
+        {{{dec_proj_kernel<false, 1, false>, dec_proj_kernel<false, 1, true>}, {dec_proj_kernel<false, 2, false>, dec_proj_kernel<false, 2, true>},
+          {dec_proj_kernel<false, 4, false>, dec_proj_kernel<false, 4, true>}},
+         {{dec_proj_kernel<true, 1, false>, dec_proj_kernel<true, 1, true>}, {dec_proj_kernel<true, 2, false>, dec_proj_kernel<true, 2, true>},
+          {dec_proj_kernel<true, 4, false>, dec_proj_kernel<true, 4, true>}}},
+        {{{dec_proj_f8_kernel<false, 1, false>, dec_proj_f8_kernel<false, 1, true>}, {dec_proj_f8_kernel<false, 2, false>, dec_proj_f8_kernel<false, 2, true>},
+          {dec_proj_f8_kernel<false, 4, false>, dec_proj_f8_kernel<false, 4, true>}},
+         {{dec_proj_f8_kernel<true, 1, false>, dec_proj_f8_kernel<true, 1, true>}, {dec_proj_f8_kernel<true, 2, false>, dec_proj_f8_kernel<true, 2, true>},
+          {dec_proj_f8_kernel<true, 4, false>, dec_proj_f8_kernel<true, 4, true>}}},
+        {{{dec_proj_f4_kernel<false, 1, false>, dec_proj_f4_kernel<false, 1, true>}, {dec_proj_f4_kernel<false, 2, false>, dec_proj_f4_kernel<false, 2, true>},
+          {dec_proj_f4_kernel<false, 4, false>, dec_proj_f4_kernel<false, 4, true>}},
+         {{dec_proj_f4_kernel<true, 1, false>, dec_proj_f4_kernel<true, 1, true>}, {dec_proj_f4_kernel<true, 2, false>, dec_proj_f4_kernel<true, 2, true>},
+          {dec_proj_f4_kernel<true, 4, false>, dec_proj_f4_kernel<true, 4, true>}}}};
     const int grid = a.mode == DEC_SWIGLU ? a.N / 8 : a.N / 16;
-#define DEC_LAUNCH(NORMV, ALV)                                                                                                   \
-    do {                                                                                                                       \
-        if (a.W4) {                                                                                                            \
-            if (a.lt) hipLaunchKernelGGL((dec_proj_f4_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
-            else hipLaunchKernelGGL((dec_proj_f4_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);             \
-        } else if (a.W8) {                                                                                                     \
-            if (a.lt) hipLaunchKernelGGL((dec_proj_f8_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
-            else hipLaunchKernelGGL((dec_proj_f8_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);             \
-        } else if (a.lt) hipLaunchKernelGGL((dec_proj_kernel<NORMV, ALV, true>), dim3(grid), dim3(DW * 64), 0, st, a);        \
-        else hipLaunchKernelGGL((dec_proj_kernel<NORMV, ALV, false>), dim3(grid), dim3(DW * 64), 0, st, a);                    \
-    } while (0)
     const int ev = av_knob(AV_KNOB_DEC_AL);       // experiment knob: force the activation-load form (4 = one load per step)
     const int al = ev ? ev : (a.M <= 4 ? 1 : a.M <= 8 ? 2 : 4);
-    if (a.norm_w) { if (al == 1 && a.M <= 4) DEC_LAUNCH(true, 1); else if (al <= 2 && a.M <= 8) DEC_LAUNCH(true, 2); else DEC_LAUNCH(true, 4); }
-    else { if (al == 1 && a.M <= 4) DEC_LAUNCH(false, 1); else if (al <= 2 && a.M <= 8) DEC_LAUNCH(false, 2); else DEC_LAUNCH(false, 4); }
-#undef DEC_LAUNCH
+    const int ali = al == 1 && a.M <= 4 ? 0 : al <= 2 && a.M <= 8 ? 1 : 2;
+    hipLaunchKernelGGL(kernel[(int)a.form][a.norm_w != nullptr][ali][a.lt != nullptr], dim3(grid), dim3(DW * 64), 0, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -526,16 +505,15 @@ int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
                  "dec_proj: bf16, 1 <= M <= 16 (M=%d), K %% 128 == 0 (K=%d), N %% 16 == 0 (%% 8 for SwiGLU; N=%d)", d->M, d->K, d->N);
     AV_CHECK_ARG(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->lda >= d->K && d->ldw >= (d->W4 ? d->K / 2 : d->K),
                  "dec_proj: rows must be 16-byte aligned and hold K elements");
-    AV_CHECK_ARG(!d->W8 || (d->E8 && ((uintptr_t)d->W8 & 15) == 0 && d->ldw % 16 == 0 && ((uintptr_t)d->E8 & 3) == 0),
-                 "dec_proj(fp8 weights): codes W8 16-byte aligned with rows of ldw %% 16 == 0 bytes (ldw=%ld), exponents E8 [rows, K/32] 4-byte aligned",
-                 (long)d->ldw);
-    AV_CHECK_ARG(!d->W4 || (d->E8 && ((uintptr_t)d->W4 & 15) == 0 && d->ldw % 16 == 0 && ((uintptr_t)d->E8 & 3) == 0),
-                 "dec_proj(fp4 weights): codes W4 16-byte aligned with rows of ldw %% 16 == 0 bytes (ldw=%ld), exponents E8 [rows, K/32] 4-byte aligned",
-                 (long)d->ldw);
+    // the public descriptor names the form by the pointer that is set (ldw: bf16 elements, or bytes of codes); the kernels take one pointer
+    const WForm form = d->W4 ? WForm::fp4 : d->W8 ? WForm::fp8 : WForm::bf16;
+    const void* W = d->W4 ? d->W4 : d->W8 ? d->W8 : d->W;
+    AV_CHECK_ARG(form == WForm::bf16 || (d->E8 && ((uintptr_t)W & 15) == 0 && d->ldw % 16 == 0 && ((uintptr_t)d->E8 & 3) == 0),
+                 "dec_proj(%s weights): codes 16-byte aligned with rows of ldw %% 16 == 0 bytes (ldw=%ld), exponents E8 [rows, K/32] 4-byte aligned",
+                 form == WForm::fp4 ? "fp4" : "fp8", (long)d->ldw);
     DecArgs a = {};
-    a.W8 = (const uint8_t*)d->W8; a.E8 = (const uint8_t*)d->E8; a.W4 = (const uint8_t*)d->W4;
-    if (a.W8) a.W = nullptr;
-    a.A = (const bf16*)d->A; a.lda = d->lda; a.W = (const bf16*)d->W; a.ldw = d->ldw; a.norm_w = (const bf16*)d->norm_w; a.eps = d->eps;
+    a.W = (const uint8_t*)W; a.ldw = form == WForm::bf16 ? 2 * d->ldw : d->ldw; a.E8 = (const uint8_t*)d->E8; a.form = form;
+    a.A = (const bf16*)d->A; a.lda = d->lda; a.norm_w = (const bf16*)d->norm_w; a.eps = d->eps;
     a.M = d->M; a.K = d->K; a.N = d->N; a.mode = d->mode;
     a.C = d->C; a.ldc = d->ldc; a.out_f32 = d->out_f32; a.R = (const bf16*)d->R; a.ldr = d->ldr;
     if (d->mode == DEC_PLAIN) {

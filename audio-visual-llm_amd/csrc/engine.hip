@@ -239,23 +239,17 @@ int check_llama(const avllm_llama* m) {
     AV_CHECK_ARG(m->d % m->heads == 0 && m->d % 64 == 0 && m->ffn % 64 == 0, "llama: d=%d ffn=%d must be multiples of 64", m->d, m->ffn);
     AV_CHECK_ARG(m->layers > 0 && m->layers <= 256, "llama: layers=%d", m->layers);
     AV_CHECK_ARG(m->kv_heads >= 0 && (m->kv_heads == 0 || m->heads % m->kv_heads == 0), "llama: heads=%d kv_heads=%d", m->heads, m->kv_heads);
-    if (m->decode_fp8) {
+    if (m->decode_fp8 || m->decode_fp4) {
+        AV_CHECK_ARG(!(m->decode_fp8 && m->decode_fp4), "llama: decode_fp4 and decode_fp8 are two forms of the same token step, set one");
+        const bool f4 = m->decode_fp4 != 0;
+        const char* mode = f4 ? "decode_fp4" : "decode_fp8";
         AV_CHECK_ARG(m->dtype == AV_BF16 && m->d % 128 == 0 && m->ffn % 128 == 0 && m->vocab % 16 == 0 && m->lm_head8 && m->elm_head8,
-                     "llama: decode_fp8 needs bf16, d and ffn multiples of 128, vocab a multiple of 16 and the lm_head codes + exponents");
+                     "llama: %s needs bf16, d and ffn multiples of 128, vocab a multiple of 16 and the e4m3 lm_head codes + exponents", mode);
         for (int l = 0; l < m->layers; ++l) {
             const avllm_llama_layer& P = m->layer[l];
-            AV_CHECK_ARG(P.wqkv8 && P.eqkv8 && P.wo8 && P.eo8 && P.wgu8 && P.egu8 && P.wdown8 && P.edown8,
-                         "llama layer %d: decode_fp8 without the fp8 codes and layout-2 exponents", l);
-        }
-    }
-    if (m->decode_fp4) {
-        AV_CHECK_ARG(!m->decode_fp8, "llama: decode_fp4 and decode_fp8 are two forms of the same token step, set one");
-        AV_CHECK_ARG(m->dtype == AV_BF16 && m->d % 128 == 0 && m->ffn % 128 == 0 && m->vocab % 16 == 0 && m->lm_head8 && m->elm_head8,
-                     "llama: decode_fp4 needs bf16, d and ffn multiples of 128, vocab a multiple of 16 and the e4m3 lm_head codes + exponents");
-        for (int l = 0; l < m->layers; ++l) {
-            const avllm_llama_layer& P = m->layer[l];
-            AV_CHECK_ARG(P.wqkv4 && P.eqkv4 && P.wo4 && P.eo4 && P.wgu4 && P.egu4 && P.wdown4 && P.edown4,
-                         "llama layer %d: decode_fp4 without the MXFP4 codes and exponents", l);
+            AV_CHECK_ARG(f4 ? P.wqkv4 && P.eqkv4 && P.wo4 && P.eo4 && P.wgu4 && P.egu4 && P.wdown4 && P.edown4
+                            : P.wqkv8 && P.eqkv8 && P.wo8 && P.eo8 && P.wgu8 && P.egu8 && P.wdown8 && P.edown8,
+                         "llama layer %d: %s without the %s codes and their exponents", l, mode, f4 ? "MXFP4" : "fp8");
         }
     }
     return AV_OK;
@@ -763,6 +757,14 @@ static bool llama_decode_fused_ok(const avllm_llama* m, int B) {
     return true;
 }
 
+// The weights one projection of the token step streams, in the model's form: bf16 rows of K, or with decode_fp8 / decode_fp4 the e4m3 / MXFP4
+// codes (two per byte: the row stride halves) with their exponents (decode.hip)
+static void dec_weights(const avllm_llama* m, avllm_dec_proj_desc& p, int K, const void* W, const void* W8, const void* E8, const void* W4, const void* E4) {
+    p.W = W; p.ldw = K;
+    if (m->decode_fp8) { p.W8 = W8; p.E8 = E8; }
+    if (m->decode_fp4) { p.W4 = W4; p.E8 = E4; p.ldw = K / 2; }
+}
+
 static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w, int B, int pos, const int* pos_dev, void* kc, void* vc, int Tmax,
                                     hipStream_t st) {
     const avllm_llama_layer& P = m->layer[l];
@@ -779,16 +781,13 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         AV_TRY(av_dec_proj(&p, st));
         p = {};
     }
-    const bool f8 = m->decode_fp8 != 0;      // weight-only fp8: the four projections stream codes + exponents (decode.hip, fp8 weight form)
-    const bool f4 = m->decode_fp4 != 0;      // weight-only fp4: MXFP4 codes (two per byte: the row stride halves) + their own exponents
-    p.A = w.x; p.lda = d; p.W = P.wqkv; p.ldw = d; p.norm_w = P.ln1_w; p.eps = m->eps; p.M = B; p.K = d; p.N = qw; p.mode = 2;
+    dec_weights(m, p, d, P.wqkv, P.wqkv8, P.eqkv8, P.wqkv4, P.eqkv4);
+    p.A = w.x; p.lda = d; p.norm_w = P.ln1_w; p.eps = m->eps; p.M = B; p.K = d; p.N = qw; p.mode = 2;
     p.C = w.qkv; p.ldc = qw; p.dq = d; p.dkv = dkv; p.hd = hd; p.rope = w.rope_tab; p.kc = kcl; p.vc = vcl; p.Tmax = Tmax; p.pos = pos; p.pos_dev = pos_dev;
     if (lora) {
         p.lora_t = w.lt; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale;
         for (int j = 0; j < 3; ++j) p.lora_b[j] = P.lora[j].B_pad;
     }
-    if (f8) { p.W8 = P.wqkv8; p.E8 = P.eqkv8; }
-    if (f4) { p.W4 = P.wqkv4; p.E8 = P.eqkv4; p.ldw = d / 2; }
     AV_TRY(av_dec_proj(&p, st));
     AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
     p = {};
@@ -797,20 +796,17 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         AV_TRY(av_dec_proj(&p, st));
         p = {};
     }
-    p.A = w.att; p.lda = d; p.W = P.wo; p.ldw = d; p.M = B; p.K = d; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
+    dec_weights(m, p, d, P.wo, P.wo8, P.eo8, P.wo4, P.eo4);
+    p.A = w.att; p.lda = d; p.M = B; p.K = d; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
     if (lora) { p.lora_t = w.lt + 3 * AVLLM_LORA_PAD; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale; p.lora_b[0] = P.lora[3].B_pad; }
-    if (f8) { p.W8 = P.wo8; p.E8 = P.eo8; }
-    if (f4) { p.W4 = P.wo4; p.E8 = P.eo4; p.ldw = d / 2; }
     AV_TRY(av_dec_proj(&p, st));
     p = {};
-    p.A = w.x; p.lda = d; p.W = P.wgu; p.ldw = d; p.norm_w = P.ln2_w; p.eps = m->eps; p.M = B; p.K = d; p.N = f; p.mode = 1; p.C = w.hmid; p.ldc = f;
-    if (f8) { p.W8 = P.wgu8; p.E8 = P.egu8; }
-    if (f4) { p.W4 = P.wgu4; p.E8 = P.egu4; p.ldw = d / 2; }
+    dec_weights(m, p, d, P.wgu, P.wgu8, P.egu8, P.wgu4, P.egu4);
+    p.A = w.x; p.lda = d; p.norm_w = P.ln2_w; p.eps = m->eps; p.M = B; p.K = d; p.N = f; p.mode = 1; p.C = w.hmid; p.ldc = f;
     AV_TRY(av_dec_proj(&p, st));
     p = {};
-    p.A = w.hmid; p.lda = f; p.W = P.wdown; p.ldw = f; p.M = B; p.K = f; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
-    if (f8) { p.W8 = P.wdown8; p.E8 = P.edown8; }
-    if (f4) { p.W4 = P.wdown4; p.E8 = P.edown4; p.ldw = f / 2; }
+    dec_weights(m, p, f, P.wdown, P.wdown8, P.edown8, P.wdown4, P.edown4);
+    p.A = w.hmid; p.lda = f; p.M = B; p.K = f; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
     return av_dec_proj(&p, st);
 }
 

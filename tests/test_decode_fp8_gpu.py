@@ -51,7 +51,9 @@ def test_layout2_exponents_and_codes_match_the_oracle(dev, R, K):
 
 
 # ------------------------------------------------------------------------------------------------ 2. dec_proj fp8 vs torch on W~
-@pytest.mark.parametrize("K", [128, 4096, 11008])
+# K: groups per wave 0 / 1 (128), 2 / 1 (1152), 3 / 2 (2944), 4 (4096), 5 (5120), 11 / 10 (11008): with the ring of 2 groups these reach every
+# length of the straight-line tail, 1 .. 3, with and without a trip of the main loop before it
+@pytest.mark.parametrize("K", [128, 1152, 2944, 4096, 5120, 11008])
 @pytest.mark.parametrize("M", [1, 4, 5, 8, 16])
 def test_dec_proj_fp8_plain_norm_residual(dev, M, K):
     N = 528

@@ -21,8 +21,8 @@ def rms(x, w, eps):
 
 
 # K / 128 units dealt to the 8 waves: 1 (one wave works), 3, 9 (two groups on one wave), 23 (odd / even group counts mixed: 3,3,3,3,3,3,3,2),
-# 32 (4096: four groups each), 86 (11008: 11 / 10)
-@pytest.mark.parametrize("K", [128, 384, 1152, 2944, 4096, 11008])
+# 32 (4096: four groups each), 40 (5120: five, a trip of the main loop and a tail of 3), 86 (11008: 11 / 10)
+@pytest.mark.parametrize("K", [128, 384, 1152, 2944, 4096, 5120, 11008])
 @pytest.mark.parametrize("M", [1, 3, 4, 5, 8, 9, 16])
 def test_dec_proj_plain_norm_residual(dev, M, K):
     N = 528
