@@ -52,6 +52,8 @@ class LlamaCfg:
     theta: float = 10000.0
     kv_heads: int = 0           # grouped-query attention: key/value heads (0 = heads)
     rope_scaling: tuple = ()    # () = plain RoPE; (factor, low_freq_factor, high_freq_factor, original_max_position_embeddings) = "llama3" scaling
+    qkv_bias: bool = False      # q_proj / k_proj / v_proj carry a (frozen) bias: Qwen2 / Qwen2.5, or a Llama config with attention_bias
+    o_bias: bool = False        # o_proj carries one too: attention_bias only
 
     @property
     def head_dim(self):
@@ -97,6 +99,13 @@ LLAMA = {
     "llama-3-8b": LlamaCfg(4096, 32, 32, 14336, 128256, 1e-5, 500000.0, 8),
     "tinyllama": LlamaCfg(2048, 32, 22, 5632, 32000, 1e-5, 10000.0, 4),
     "mistral-7b": LlamaCfg(4096, 32, 32, 14336, 32000, 1e-5, 10000.0, 8),     # sliding window 4096 >= every sequence of this path
+    # Qwen2.5: the same architecture with a bias on q, k and v.  hidden / heads / kv_heads / ffn / layers / eps of the 0.5B and 7B rows are the
+    # defaults and docstring example of transformers' Qwen2Config / the published config.json; vocab (151936, 152064 for 7B), theta 1e6 and
+    # the 1.5B / 3B rows are from the published config.json files as remembered: no copy of them was at hand to check against.
+    "qwen2.5-0.5b": LlamaCfg(896, 14, 24, 4864, 151936, 1e-6, 1e6, 2, qkv_bias=True),
+    "qwen2.5-1.5b": LlamaCfg(1536, 12, 28, 8960, 151936, 1e-6, 1e6, 2, qkv_bias=True),
+    "qwen2.5-3b": LlamaCfg(2048, 16, 36, 11008, 151936, 1e-6, 1e6, 2, qkv_bias=True),
+    "qwen2.5-7b": LlamaCfg(3584, 28, 28, 18944, 152064, 1e-6, 1e6, 4, qkv_bias=True),
 }
 
 
@@ -176,14 +185,19 @@ def synth_llama(c, device, dtype, seed):
     d, f = c.hidden, c.ffn
     sd = {"model.embed_tokens.weight": g.n((c.vocab, d), 0.5), "model.norm.weight": g.n((d,), 0.1, 1.0),
           "lm_head.weight": g.n((c.vocab, d), 1 / math.sqrt(d))}
+    dkv = (c.kv_heads or c.heads) * c.head_dim               # grouped-query attention: k/v project to kv_heads*head_dim
     for i in range(c.layers):
         p = f"model.layers.{i}."
-        dkv = (c.kv_heads or c.heads) * c.head_dim           # grouped-query attention: k/v project to kv_heads*head_dim
         for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
             sd[p + f"self_attn.{nm}.weight"] = g.n((dkv if nm in ("k_proj", "v_proj") else d, d), 1 / math.sqrt(d))
         sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"] = g.n((f, d), 1 / math.sqrt(d)), g.n((f, d), 1 / math.sqrt(d))
         sd[p + "mlp.down_proj.weight"] = g.n((d, f), 1 / math.sqrt(f))
         sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = g.n((d,), 0.1, 1.0), g.n((d,), 0.1, 1.0)
+    # biases are drawn after everything else: a model without them keeps the tensors it always had
+    for i in range(c.layers):
+        for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
+            if getattr(c, "o_bias" if nm == "o_proj" else "qkv_bias", False):
+                sd[f"model.layers.{i}.self_attn.{nm}.bias"] = g.n((dkv if nm in ("k_proj", "v_proj") else d,), 0.3)
     return sd
 
 
@@ -213,8 +227,35 @@ def _cfg_from_hf_dir(path, kind):
         raise NotImplementedError("head_dim != hidden_size / num_attention_heads is not implemented")
     rope = c.get("rope_theta", (c.get("rope_parameters") or {}).get("rope_theta", 10000.0))
     kvh = c.get("num_key_value_heads", c["num_attention_heads"])
+    qkv_bias, o_bias = _attn_biases(c.get)
     return LlamaCfg(c["hidden_size"], c["num_attention_heads"], c["num_hidden_layers"], c["intermediate_size"], c["vocab_size"],
-                    c.get("rms_norm_eps", 1e-5), rope, 0 if kvh == c["num_attention_heads"] else kvh, rs)
+                    c.get("rms_norm_eps", 1e-5), rope, 0 if kvh == c["num_attention_heads"] else kvh, rs, qkv_bias, o_bias)
+
+
+def _attn_biases(get):
+    """(qkv_bias, o_bias) of a HuggingFace config read through `get(name, default)`: Qwen2 / Qwen2.5 put a bias on q, k and v, a Llama
+    config with attention_bias on all four.  What the Qwen2 config can switch on beyond that is refused, not ignored."""
+    if get("use_sliding_window", False):
+        raise NotImplementedError("use_sliding_window: true (sliding-window attention) is not implemented")
+    ab = bool(get("attention_bias", False))
+    return ab or get("model_type", None) == "qwen2", ab
+
+
+def check_llama_keys(sd, cfg):
+    """The attention-bias keys of a Llama-architecture state dict agree with the config, and tensors of other architectures that would
+    otherwise be skipped in silence (the model computed would be a different one) are refused by name."""
+    for k in sd:
+        if k.endswith(("mlp.gate_proj.bias", "mlp.up_proj.bias", "mlp.down_proj.bias")):
+            raise NotImplementedError(f"{k}: MLP biases are not implemented")
+        if k.endswith(("self_attn.q_norm.weight", "self_attn.k_norm.weight")):
+            raise NotImplementedError(f"{k}: q/k norms (Qwen3) are not implemented")
+    for i in range(cfg.layers):
+        for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
+            key = f"model.layers.{i}.self_attn.{nm}.bias"
+            want = bool(getattr(cfg, "o_bias" if nm == "o_proj" else "qkv_bias", False))
+            if (key in sd) != want:
+                raise ValueError(f"{key} is {'present' if key in sd else 'missing'} but the config says "
+                                 f"{'qkv' if nm != 'o_proj' else 'o'}_bias={want} (model_type qwen2 / attention_bias decide it)")
 
 
 def _rope_scaling(scaling):
@@ -280,9 +321,10 @@ def resolve_arch(llm_path, whisper_model, clip_model, config, weights, seed, lor
                 else:
                     kvh = getattr(hc, "num_key_value_heads", None) or hc.num_attention_heads
                     rope = getattr(hc, "rope_theta", None) or (getattr(hc, "rope_parameters", None) or {}).get("rope_theta", 10000.0)
+                    qkv_bias, o_bias = _attn_biases(lambda name, default, hc=hc: getattr(hc, name, default))
                     parts[kind] = LlamaCfg(hc.hidden_size, hc.num_attention_heads, hc.num_hidden_layers, hc.intermediate_size,
                                            hc.vocab_size, hc.rms_norm_eps, rope, 0 if kvh == hc.num_attention_heads else kvh,
-                                           _rope_scaling(getattr(hc, "rope_scaling", None) or {}))
+                                           _rope_scaling(getattr(hc, "rope_scaling", None) or {}), qkv_bias, o_bias)
             elif isinstance(path, str) and os.path.isdir(path) and os.path.exists(os.path.join(path, "config.json")):
                 parts[kind] = _cfg_from_hf_dir(path, kind)
             else:

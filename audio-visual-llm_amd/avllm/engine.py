@@ -13,6 +13,7 @@ import torch
 
 from . import lib as L
 from . import ops
+from .arch import check_llama_keys
 
 
 class Workspace:
@@ -251,6 +252,7 @@ class LlamaEngine:
         if self.fp8 or self.decode_fp8 or self.decode_fp4:
             m.lm_head8, m.slm_head8, m.elm_head8 = images(head, self.decode_fp8 or self.decode_fp4)
         self.layers = (L.LlamaLayer * cfg.layers)()
+        check_llama_keys(sd, cfg)
         # ---- LoRA masters / grads / padded operand images
         self.per_layer = sum(r * (d + do) for do in self.douts)
         n = cfg.layers * self.per_layer
@@ -276,6 +278,11 @@ class LlamaEngine:
             ly.ln1_w = put(sd[p + "input_layernorm.weight"]).data_ptr()
             ly.ln2_w = put(sd[p + "post_attention_layernorm.weight"]).data_ptr()
             ly.wqkv, ly.wo, ly.wgu, ly.wdown = wqkv.data_ptr(), wo.data_ptr(), wgu.data_ptr(), wdown.data_ptr()
+            # frozen attention biases (Qwen2: q|k|v; attention_bias: o as well), in the model dtype, one [d + 2 dkv] vector like wqkv's rows
+            if getattr(cfg, "qkv_bias", False):
+                ly.bqkv = put(torch.cat([sd[p + f"self_attn.{nm}.bias"] for nm in LORA_TARGETS[:3]], 0)).data_ptr()
+            if getattr(cfg, "o_bias", False):
+                ly.bo = put(sd[p + "self_attn.o_proj.bias"]).data_ptr()
             if training:
                 ly.wqkv_t, ly.wo_t = put(wqkv.t()).data_ptr(), put(wo.t()).data_ptr()
                 ly.wgu_t, ly.wdown_t = put(wgu.t()).data_ptr(), put(wdown.t()).data_ptr()

@@ -55,7 +55,8 @@ class LlamaLayer(C.Structure):
     _fields_ = [(n, vp) for n in ("ln1_w", "ln2_w", "wqkv", "wo", "wgu", "wdown", "wqkv_t", "wo_t", "wgu_t", "wdown_t")] + \
                [("lora", LoraMod * 4)] + [(n, vp) for n in ("wqkv8", "sqkv8", "wo8", "so8", "wgu8", "sgu8", "wdown8", "sdown8")] + \
                [(n, vp) for n in ("eqkv8", "eo8", "egu8", "edown8")] + \
-               [(n, vp) for n in ("wqkv4", "wo4", "wgu4", "wdown4", "eqkv4", "eo4", "egu4", "edown4")]
+               [(n, vp) for n in ("wqkv4", "wo4", "wgu4", "wdown4", "eqkv4", "eo4", "egu4", "edown4")] + \
+               [(n, vp) for n in ("bqkv", "bo")]
 
 
 class Llama(C.Structure):
@@ -77,7 +78,8 @@ class DecProjDesc(C.Structure):
     _fields_ = [("A", vp), ("lda", i64), ("W", vp), ("ldw", i64), ("norm_w", vp), ("eps", f32), ("M", i32), ("K", i32), ("N", i32), ("mode", i32),
                 ("C", vp), ("ldc", i64), ("out_f32", i32), ("R", vp), ("ldr", i64), ("dq", i32), ("dkv", i32), ("hd", i32), ("rope", vp),
                 ("kc", vp), ("vc", vp), ("Tmax", i32), ("pos", i32), ("pos_dev", vp),
-                ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32), ("W8", vp), ("E8", vp), ("W4", vp)]
+                ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32), ("W8", vp), ("E8", vp), ("W4", vp),
+                ("bias", vp)]
 
 
 class StepState(C.Structure):

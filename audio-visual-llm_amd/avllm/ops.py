@@ -622,12 +622,13 @@ def norm_mxq(x, w, b=None, eps=1e-5, want_y=False, want_rstd=False):
 
 
 def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=False, rope=None, kc=None, vc=None, pos=0, pos_dev=None, dq=0, dkv=0, hd=0,
-             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None, W4=None):
+             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None, W4=None, bias=None):
     """One projection of a decode token step (avllm_dec_proj): A [M<=16, K] bf16, W [rows, K] bf16.
     mode 0: out[M, rows] = rmsnorm?(A) . W^T (+ R);  mode 1: W = [gate; up], out[M, rows/2] = silu(gate) * up;
     mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev).
     fp8 weight form: W8 = e4m3 codes uint8 [rows, K], E8 = exponents uint8 [rows, K/32] (mx_quantize(w, 2)); W may then be None.
-    fp4 weight form: W4 = MXFP4 codes uint8 [rows, K/2], E8 = their exponents uint8 [rows, K/32] (mx4_quantize(w)); not together with W8."""
+    fp4 weight form: W4 = MXFP4 codes uint8 [rows, K/2], E8 = their exponents uint8 [rows, K/32] (mx4_quantize(w)); not together with W8.
+    bias: bf16 [rows] in W's row order, added before adapters, residual and RoPE (modes 0 and 2)."""
     M, K = A.shape
     d = L.DecProjDesc()
     Wr = W4 if W4 is not None else (W8 if W8 is not None else W)
@@ -653,6 +654,10 @@ def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=Fals
         d.lora_t, d.ld_lora_t, d.lora_r, d.lora_scale = L.ptr(lora_t), _ld(lora_t), lora_r, lora_scale
         for j, b in enumerate(lora_b):
             d.lora_b[j] = L.ptr(b)
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or bias.numel() != N or not bias.is_contiguous():
+            raise ValueError(f"dec_proj: bias must be a contiguous bf16 [{N}] tensor")
+        d.bias = L.ptr(bias)
     L.check(L.load().avllm_dec_proj(C.byref(d), L.stream_ptr()))
     return out
 

@@ -49,6 +49,9 @@ struct DecArgs {
     // (columns 64 j .. 64 j + r of module j; made by a PLAIN launch over the A images), lb[j] the padded B image [rows, 64] of module j
     // (QKV: j = q, k, v; otherwise j = 0).  Added in the epilogue, before RoPE.
     const float* lt; long ldlt; const bf16* lb[3]; float lscale; int lr;
+    // frozen projection bias (Qwen2 q|k|v, attention_bias o): [N] in logical output column order, added to the fp32 sum after the RMS scale,
+    // before the adapter term, the residual and RoPE (peft: base_layer(x) with its bias, + adapter).  PLAIN and QKV only.
+    const bf16* bias;
 };
 
 // fragment row fr (0..15) of workgroup b -> weight row, and the logical output column it produces
@@ -267,7 +270,7 @@ __device__ __forceinline__ void dec_k_loop(const DecArgs& a, int fr, int fq, int
     });
 }
 
-template <WForm F, bool NORM, int AL, bool LORA>
+template <WForm F, bool NORM, int AL, bool LORA, bool BIAS = false>
 __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     __shared__ float part[DW][16][17];      // [wave][n][m]
     __shared__ float ssq[DW][16];
@@ -307,6 +310,18 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
             }
         }
     }
+    // bias of the finishing thread's column, fetched with the adapter operands.  BIAS is a template parameter, not a run-time test: a
+    // wave-uniform `if (a.bias)` in the one kernel measured slower or equal in all nine cells of the bias-free Llama-2-7B token step (mean
+    // +5 us, 0.15 %; three cells beyond the round-to-round spread: profiles/r09_decode_bias_bench.txt), so a launch without a bias (every
+    // Llama checkpoint) runs the kernels it always ran
+    float bv = 0.f;
+    if constexpr (BIAS) {
+        if (threadIdx.x < 256) {
+            int oc;
+            dec_wrow(a, blockIdx.x, threadIdx.x & 15, oc);
+            if (oc < a.N) bv = (float)a.bias[oc];
+        }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) part[w][fq * 4 + i][fr] = acc[i];
     if (NORM) {
@@ -326,6 +341,7 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
         for (int x = 0; x < DW; ++x) t += ssq[x][m];
         s *= rsqrtf(t / (float)a.K + a.eps);
     }
+    if constexpr (BIAS) s += bv;
     if constexpr (LORA) {
         float u = 0.f;
 #pragma unroll
@@ -373,6 +389,14 @@ template <bool NORM, int AL, bool LORA>
 __global__ __launch_bounds__(DW * 64, 2) void dec_proj_f8_kernel(DecArgs a) { dec_proj_body<WForm::fp8, NORM, AL, LORA>(a); }
 template <bool NORM, int AL, bool LORA>
 __global__ __launch_bounds__(DW * 64, 2) void dec_proj_f4_kernel(DecArgs a) { dec_proj_body<WForm::fp4, NORM, AL, LORA>(a); }
+
+// the same with a bias (modes 0 and 2 only)
+template <bool NORM, int AL, bool LORA>
+__global__ __launch_bounds__(DW * 64, 2) void dec_bias_kernel(DecArgs a) { dec_proj_body<WForm::bf16, NORM, AL, LORA, true>(a); }
+template <bool NORM, int AL, bool LORA>
+__global__ __launch_bounds__(DW * 64, 2) void dec_bias_f8_kernel(DecArgs a) { dec_proj_body<WForm::fp8, NORM, AL, LORA, true>(a); }
+template <bool NORM, int AL, bool LORA>
+__global__ __launch_bounds__(DW * 64, 2) void dec_bias_f4_kernel(DecArgs a) { dec_proj_body<WForm::fp4, NORM, AL, LORA, true>(a); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Single-token attention over the cache, ONE pass: a group of G = hd/8 lanes owns cache rows t = g, g + R, ... and carries a running
@@ -488,11 +512,16 @@ static int dec_launch(DecArgs& a, hipStream_t st) {
           {dec_proj_f4_kernel<false, 4, false>, dec_proj_f4_kernel<false, 4, true>}},
          {{dec_proj_f4_kernel<true, 1, false>, dec_proj_f4_kernel<true, 1, true>}, {dec_proj_f4_kernel<true, 2, false>, dec_proj_f4_kernel<true, 2, true>},
           {dec_proj_f4_kernel<true, 4, false>, dec_proj_f4_kernel<true, 4, true>}}}};
+#define DEC_FORM_TABLE(K) {{{K<false, 1, false>, K<false, 1, true>}, {K<false, 2, false>, K<false, 2, true>}, {K<false, 4, false>, K<false, 4, true>}}, \
+                           {{K<true, 1, false>, K<true, 1, true>}, {K<true, 2, false>, K<true, 2, true>}, {K<true, 4, false>, K<true, 4, true>}}}
+    static const decltype(&dec_proj_kernel<false, 1, false>) kernel_bias[3][2][3][2] = {DEC_FORM_TABLE(dec_bias_kernel), DEC_FORM_TABLE(dec_bias_f8_kernel),
+                                                                                        DEC_FORM_TABLE(dec_bias_f4_kernel)};
+#undef DEC_FORM_TABLE
     const int grid = a.mode == DEC_SWIGLU ? a.N / 8 : a.N / 16;
     const int ev = av_knob(AV_KNOB_DEC_AL);       // experiment knob: force the activation-load form (4 = one load per step)
     const int al = ev ? ev : (a.M <= 4 ? 1 : a.M <= 8 ? 2 : 4);
     const int ali = al == 1 && a.M <= 4 ? 0 : al <= 2 && a.M <= 8 ? 1 : 2;
-    hipLaunchKernelGGL(kernel[(int)a.form][a.norm_w != nullptr][ali][a.lt != nullptr], dim3(grid), dim3(DW * 64), 0, st, a);
+    hipLaunchKernelGGL((a.bias ? kernel_bias : kernel)[(int)a.form][a.norm_w != nullptr][ali][a.lt != nullptr], dim3(grid), dim3(DW * 64), 0, st, a);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -536,6 +565,11 @@ int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
         for (int j = 0; j < nmod; ++j) AV_CHECK_ARG(d->lora_b[j], "dec_proj: adapter B image %d missing", j);
         a.lt = d->lora_t; a.ldlt = d->ld_lora_t; a.lscale = d->lora_scale; a.lr = d->lora_r;
         for (int j = 0; j < nmod; ++j) a.lb[j] = (const bf16*)d->lora_b[j];
+    }
+    if (d->bias) {
+        AV_CHECK_ARG(d->mode != DEC_SWIGLU && ((uintptr_t)d->bias & 1) == 0, "dec_proj: a bias [N] (bf16, 2-byte aligned) goes with modes 0 and 2, not SwiGLU (mode=%d)",
+                     d->mode);
+        a.bias = (const bf16*)d->bias;
     }
     return dec_launch(a, st);
 }

@@ -260,11 +260,15 @@ inline int llama_dkv(const avllm_llama* m) { return llama_kv_heads(m) * (m->d / 
 inline int llama_qw(const avllm_llama* m) { return m->d + 2 * llama_dkv(m); }
 inline int llama_off(const avllm_llama* m, int j) { return j == 0 ? 0 : (j == 1 ? m->d : m->d + llama_dkv(m)); }     // column (= wqkv row) of slice j
 inline int llama_wid(const avllm_llama* m, int j) { return j == 0 ? m->d : llama_dkv(m); }
+// slice j of a layer's q|k|v bias (NULL without one)
+inline const void* llama_bias(const avllm_llama* m, const avllm_llama_layer& P, int j) {
+    return P.bqkv ? (const char*)P.bqkv + (size_t)llama_off(m, j) * av_dtype_size(m->dtype) : nullptr;
+}
 
-// y[:, slice j] = x W_j^T (+ t_j B_j^T)
+// y[:, slice j] = x W_j^T + bias_j (+ t_j B_j^T)
 int lora_proj(const avllm_llama* m, const void* x, long ldx, const void* W, long ldw, int K, int N, const avllm_lora_mod& lm,
               void* t, long ldt, void* y, long ldy, const void* R, long ldr, int M, hipStream_t st, const void* xl = nullptr,
-              uint32_t a_seed = 0, float a_p = 0.f) {
+              uint32_t a_seed = 0, float a_p = 0.f, const void* bias = nullptr) {
     // (the step's base seed may live in device memory: m->dropout_seed_dev, see avllm_step_state)
     avllm_gemm_desc g;
     const bool has = lm.A_pad != nullptr;
@@ -278,7 +282,7 @@ int lora_proj(const avllm_llama* m, const void* x, long ldx, const void* W, long
     }
     g = gemm_desc(m->dtype, x, ldx, W, ldw, y, ldy, M, N, K);
     if (has) { g.A2 = t; g.lda2 = ldt; g.B2 = lm.B_pad; g.ldb2 = AVLLM_LORA_PAD; g.K2 = AVLLM_LORA_PAD; }
-    g.R = R; g.ldr = ldr;
+    g.R = R; g.ldr = ldr; g.bias = bias;
     return av_gemm(&g, st);
 }
 
@@ -404,7 +408,7 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
         if (fp8) {      // one fp8 product for q|k|v (one quantisation of the normed input), adapters added on top
             AV_CHECK_ARG(P.wqkv8 && P.sqkv8 && P.wo8 && P.so8 && P.wgu8 && P.sgu8 && P.wdown8 && P.sdown8, "llama layer %d: fp8 mode without fp8 weight images", l);
             AV_TRY(f8_quant(w.f8, a.xn1, d, M, d, st));
-            AV_TRY(f8_proj(w.f8, M, d, P.wqkv8, P.sqkv8, qw, a.qkv, qw, nullptr, AV_ACT_NONE, nullptr, 0, st));
+            AV_TRY(f8_proj(w.f8, M, d, P.wqkv8, P.sqkv8, qw, a.qkv, qw, P.bqkv, AV_ACT_NONE, nullptr, 0, st));
         }
         // all three rank-side products t_j = s * dropout_j(xn1) A_j^T in one launch (xn1 read once): csrc/lora_batch.hip
         const bool batch_qkv = !fp8 && dt == AV_BF16 && P.lora[0].A_pad && P.lora[1].A_pad && P.lora[2].A_pad && (!drop || fuse_drop) &&
@@ -424,6 +428,7 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
                 avllm_gemm_desc gp = gemm_desc(dt, a.xn1, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, d,
                                                (char*)a.qkv + (size_t)llama_off(m, j) * es, qw, M, llama_wid(m, j), d);
                 gp.A2 = (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es; gp.lda2 = 3 * AVLLM_LORA_PAD; gp.B2 = P.lora[j].B_pad; gp.ldb2 = AVLLM_LORA_PAD; gp.K2 = AVLLM_LORA_PAD;
+                gp.bias = llama_bias(m, P, j);
                 AV_TRY(av_gemm(&gp, st));
                 continue;
             }
@@ -434,7 +439,8 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
             }
             AV_TRY(lora_proj(m, a.xn1, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, d, d, llama_wid(m, j), P.lora[j],
                              (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es, 3 * AVLLM_LORA_PAD,
-                             (char*)a.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st, xl, sj, fuse_drop ? m->lora_dropout : 0.f));
+                             (char*)a.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st, xl, sj, fuse_drop ? m->lora_dropout : 0.f,
+                             llama_bias(m, P, j)));
         }
         AV_TRY(av_rope_tab(a.qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));      // q and k slices are adjacent: H + Hkv heads
         const char* qkv = (const char*)a.qkv;
@@ -446,11 +452,11 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
             if (drop && !fuse_drop && P.lora[3].A_pad) { AV_TRY(av_dropout(a.att, w.xd, M, d, so, m->lora_dropout, dt, st, m->dropout_seed_dev)); xl = w.xd; }
             if (fp8) {
                 AV_TRY(f8_quant(w.f8, a.att, d, M, d, st));
-                AV_TRY(f8_proj(w.f8, M, d, P.wo8, P.so8, d, a.h1, d, nullptr, AV_ACT_NONE, resid[l], d, st));
+                AV_TRY(f8_proj(w.f8, M, d, P.wo8, P.so8, d, a.h1, d, P.bo, AV_ACT_NONE, resid[l], d, st));
                 AV_TRY(lora_add(m, a.att, d, d, d, P.lora[3], a.to, AVLLM_LORA_PAD, a.h1, d, M, st, xl, so, fuse_drop ? m->lora_dropout : 0.f));
             } else
             AV_TRY(lora_proj(m, a.att, d, P.wo, d, d, d, P.lora[3], a.to, AVLLM_LORA_PAD, a.h1, d, resid[l], d, M, st, xl, so,
-                             fuse_drop ? m->lora_dropout : 0.f));
+                             fuse_drop ? m->lora_dropout : 0.f, P.bo));
         }
         AV_TRY(av_rmsnorm_fwd(a.h1, P.ln2_w, w.xn2, a.rstd2, M, d, m->eps, dt, st));
         if (fp8) {
@@ -670,11 +676,12 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
     AV_TRY(av_rmsnorm_fwd(w.x, P.ln1_w, w.xn, nullptr, M, d, m->eps, dt, st));
     if (!P.lora[0].A_pad && !P.lora[1].A_pad && !P.lora[2].A_pad) {      // no adapters (decode.py path): one fused q|k|v projection
         avllm_gemm_desc gq = gemm_desc(dt, w.xn, d, P.wqkv, d, w.qkv, qw, M, qw, d);
+        gq.bias = P.bqkv;
         AV_TRY(av_gemm(&gq, st));
     } else
     for (int j = 0; j < 3; ++j)
         AV_TRY(lora_proj(m, w.xn, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, d, d, llama_wid(m, j), P.lora[j], w.t, AVLLM_LORA_PAD,
-                         (char*)w.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st));
+                         (char*)w.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st, nullptr, 0, 0.f, llama_bias(m, P, j)));
     char* qkv = (char*)w.qkv;
     if (l == 0) AV_TRY(av_rope_table(w.rope_tab, S, hd, pos0, m->theta, st, nullptr, llama_rope_scale(m)));
     AV_TRY(av_rope_tab(qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));
@@ -687,7 +694,7 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
         AV_TRY(av_attention_fwd(qkv, qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, w.att, nullptr, B, S, S, H, hd, qw, qw, qw,
                                 d, scale, 1, dt, 0, st, Hkv));
     }
-    AV_TRY(lora_proj(m, w.att, d, P.wo, d, d, d, P.lora[3], w.t, AVLLM_LORA_PAD, w.x, d, w.x, d, M, st));
+    AV_TRY(lora_proj(m, w.att, d, P.wo, d, d, d, P.lora[3], w.t, AVLLM_LORA_PAD, w.x, d, w.x, d, M, st, nullptr, 0, 0.f, P.bo));
     AV_TRY(av_rmsnorm_fwd(w.x, P.ln2_w, w.xn, nullptr, M, d, m->eps, dt, st));
     avllm_gemm_desc g = gemm_desc(dt, w.xn, d, P.wgu, d, w.gu, 2 * f, M, 2 * f, d);
     AV_TRY(av_gemm(&g, st));
@@ -784,6 +791,7 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
     dec_weights(m, p, d, P.wqkv, P.wqkv8, P.eqkv8, P.wqkv4, P.eqkv4);
     p.A = w.x; p.lda = d; p.norm_w = P.ln1_w; p.eps = m->eps; p.M = B; p.K = d; p.N = qw; p.mode = 2;
     p.C = w.qkv; p.ldc = qw; p.dq = d; p.dkv = dkv; p.hd = hd; p.rope = w.rope_tab; p.kc = kcl; p.vc = vcl; p.Tmax = Tmax; p.pos = pos; p.pos_dev = pos_dev;
+    p.bias = P.bqkv;
     if (lora) {
         p.lora_t = w.lt; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale;
         for (int j = 0; j < 3; ++j) p.lora_b[j] = P.lora[j].B_pad;
@@ -797,7 +805,7 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         p = {};
     }
     dec_weights(m, p, d, P.wo, P.wo8, P.eo8, P.wo4, P.eo4);
-    p.A = w.att; p.lda = d; p.M = B; p.K = d; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d;
+    p.A = w.att; p.lda = d; p.M = B; p.K = d; p.N = d; p.mode = 0; p.C = w.x; p.ldc = d; p.R = w.x; p.ldr = d; p.bias = P.bo;
     if (lora) { p.lora_t = w.lt + 3 * AVLLM_LORA_PAD; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale; p.lora_b[0] = P.lora[3].B_pad; }
     AV_TRY(av_dec_proj(&p, st));
     p = {};

@@ -496,6 +496,11 @@ typedef struct avllm_llama_layer {
      * (avllm_mx4_quantize).  The exponents are not those of the fp8 codes: emax differs. */
     const void *wqkv4, *wo4, *wgu4, *wdown4;
     const void *eqkv4, *eo4, *egu4, *edown4;
+    /* frozen attention projection biases in the model dtype, NULL = none: bqkv [d+2*dkv] = [q;k;v] (Qwen2 / Qwen2.5, or a Llama checkpoint
+     * saved with attention_bias), bo [d] (attention_bias only).  Added to the fp32 accumulator of the base product before its one rounding, on
+     * every path (training forward in bf16 / fp32 / fp8, prefill, token step in every weight form); peft's order: base_layer(x) with its bias,
+     * plus the adapter term, then RoPE.  No gradient is formed for them. */
+    const void *bqkv, *bo;
 } avllm_llama_layer;
 
 typedef struct avllm_llama {
@@ -623,6 +628,10 @@ typedef struct avllm_dec_proj_desc {
      * together with W8.  Every mode, the norm fold, residual, outputs and adapters as above: the product is the bf16 form's on the weights
      * code value * 2^(E8 - 127) (exact in bf16), summed in a different fp32 order inside each 128-column group of K-steps. */
     const void* W4;
+    /* bias != NULL: bf16 [N] in the logical output column order of W's rows (mode 2: [q;k;v], not the kernel's rotary pairing), added to the
+     * fp32 sum after the norm fold's scale and before the adapter term, the residual and RoPE.  Modes 0 and 2; refused in mode 1.  NULL: the
+     * launch is the bias-free kernel (the epilogue is templated on the bias). */
+    const void* bias;
 } avllm_dec_proj_desc;
 int avllm_dec_proj(const avllm_dec_proj_desc* d, void* stream);
 /* Single-query attention over the cache rows [0, Tk + *tk_dev) (tk_dev may be NULL) of kc/vc [B][Tmax][(H/kv_group)*hd]: one pass with

@@ -2,30 +2,34 @@
 """Token-step time of the fused decode path at 7B shapes: bf16 weights against the weight-only fp8 stream (decode_fp8) and the weight-only fp4
 stream (decode_fp4), alternated in one process: one engine holds all three weight forms and the descriptor's decode_fp8 / decode_fp4 flags
 select the one a step reads.  Each step is a captured hipGraph replayed with the position in device memory (what generate() amortises), at a
-cache position of 300 (bench.py's decode shape).  Synthetic weights; adapters (rank 16 on q, k, v, o) optional.  Per form: the median over
+cache position of 300 (bench.py's decode shape).  Synthetic weights; adapters (rank 16 on q, k, v, o) optional.  --model qwen2.5-7b runs
+Qwen2.5-7B's shapes (d 3584, 28 heads over 4 kv heads, ffn 18944, vocab 152064, 28 layers) with its q|k|v biases.  Per form: the median over
 the rounds and their spread (max - min); a difference between two forms counts only when it exceeds the spreads."""
-import argparse, os, statistics, sys
+import argparse, dataclasses, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "audio-visual-llm_amd"))
 import torch
 from avllm import lib as L
 from avllm import ops
-from avllm.arch import LlamaCfg, LoraCfg
+from avllm.arch import LLAMA, LlamaCfg, LoraCfg
 from avllm.engine import LlamaEngine
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--model", choices=["llama2-7b", "mistral-7b"], default="llama2-7b")
+ap.add_argument("--model", choices=["llama2-7b", "mistral-7b", "qwen2.5-7b"], default="llama2-7b")
 ap.add_argument("--batches", type=str, default="1,8,16")
 ap.add_argument("--forms", type=str, default="bf16,fp8,fp4")
 ap.add_argument("--lora", action="store_true")
 ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--layers", type=int, default=32, help="fewer layers: a rehearsal, not a measurement")
+ap.add_argument("--layers", type=int, default=0, help="fewer layers than the model's (32; Qwen2.5-7B: 28): a rehearsal, not a measurement")
 a = ap.parse_args()
 forms = a.forms.split(",")
 assert forms and all(f in ("bf16", "fp8", "fp4") for f in forms), forms
 dev, BF = "cuda:0", torch.bfloat16
-cfg = LlamaCfg(4096, 32, a.layers, 11008, 32000) if a.model == "llama2-7b" else LlamaCfg(4096, 32, a.layers, 14336, 32000, kv_heads=8)
+if a.model == "qwen2.5-7b":
+    cfg = dataclasses.replace(LLAMA["qwen2.5-7b"], layers=a.layers or LLAMA["qwen2.5-7b"].layers)
+else:
+    cfg = LlamaCfg(4096, 32, a.layers or 32, 11008, 32000) if a.model == "llama2-7b" else LlamaCfg(4096, 32, a.layers or 32, 14336, 32000, kv_heads=8)
 g = torch.Generator(device=dev).manual_seed(0)
 hd = cfg.hidden // cfg.heads
 dkv = (cfg.kv_heads or cfg.heads) * hd
@@ -43,6 +47,8 @@ for i in range(cfg.layers):
                        "self_attn.o_proj": (cfg.hidden, cfg.hidden), "mlp.gate_proj": (cfg.ffn, cfg.hidden), "mlp.up_proj": (cfg.ffn, cfg.hidden),
                        "mlp.down_proj": (cfg.hidden, cfg.ffn)}.items():
         sd[p + nm + ".weight"] = w(o, k)
+        if nm.startswith("self_attn.") and (cfg.o_bias if nm.endswith("o_proj") else cfg.qkv_bias):
+            sd[p + nm + ".bias"] = torch.randn(o, device=dev, generator=g, dtype=BF) * 0.3
     sd[p + "input_layernorm.weight"] = torch.ones(cfg.hidden, device=dev, dtype=BF)
     sd[p + "post_attention_layernorm.weight"] = torch.ones(cfg.hidden, device=dev, dtype=BF)
 eng = LlamaEngine(sd, cfg, LoraCfg(16, 32.0) if a.lora else None, None, dtype=BF, device=dev, training=False, decode_fp8=True)
