@@ -625,7 +625,8 @@ def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=Fals
              lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None, W4=None, bias=None):
     """One projection of a decode token step (avllm_dec_proj): A [M<=16, K] bf16, W [rows, K] bf16.
     mode 0: out[M, rows] = rmsnorm?(A) . W^T (+ R);  mode 1: W = [gate; up], out[M, rows/2] = silu(gate) * up;
-    mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev).
+    mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev);
+    hd must be a power of two >= 32 (any other head dim raises ValueError).
     fp8 weight form: W8 = e4m3 codes uint8 [rows, K], E8 = exponents uint8 [rows, K/32] (mx_quantize(w, 2)); W may then be None.
     fp4 weight form: W4 = MXFP4 codes uint8 [rows, K/2], E8 = their exponents uint8 [rows, K/32] (mx4_quantize(w)); not together with W8.
     bias: bf16 [rows] in W's row order, added before adapters, residual and RoPE (modes 0 and 2)."""

@@ -493,7 +493,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode1_kernel(const T* __restri
 bool av_dec_proj_supported(int dtype, int M, int K, int N, int mode, int hd) {
     if (dtype != AV_BF16 || M < 1 || M > 16 || K % 128 != 0) return false;
     if (mode == DEC_SWIGLU) return N % 8 == 0;
-    if (mode == DEC_QKV) return N % 16 == 0 && hd % 16 == 0 && hd >= 32;
+    // the rotary index of a column is (col % hd) & (hd / 2 - 1): a mask, so hd has to be a power of two (32, 64, 128, ...)
+    if (mode == DEC_QKV) return N % 16 == 0 && hd >= 32 && (hd & (hd - 1)) == 0;
     return N % 16 == 0;
 }
 
@@ -531,7 +532,8 @@ int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
     AV_CHECK_ARG(!(d->W8 && d->W4), "dec_proj: W8 and W4 are two forms of the same weights, give one");
     AV_CHECK_ARG(d->mode >= DEC_PLAIN && d->mode <= DEC_QKV, "dec_proj: mode %d", d->mode);
     AV_CHECK_ARG(av_dec_proj_supported(AV_BF16, d->M, d->K, d->N, d->mode, d->hd),
-                 "dec_proj: bf16, 1 <= M <= 16 (M=%d), K %% 128 == 0 (K=%d), N %% 16 == 0 (%% 8 for SwiGLU; N=%d)", d->M, d->K, d->N);
+                 "dec_proj: bf16, 1 <= M <= 16 (M=%d), K %% 128 == 0 (K=%d), N %% 16 == 0 (%% 8 for SwiGLU; N=%d), q|k|v: head dim a power of two >= 32 (hd=%d)",
+                 d->M, d->K, d->N, d->hd);
     AV_CHECK_ARG(d->lda % 8 == 0 && d->ldw % 8 == 0 && d->lda >= d->K && d->ldw >= (d->W4 ? d->K / 2 : d->K),
                  "dec_proj: rows must be 16-byte aligned and hold K elements");
     // the public descriptor names the form by the pointer that is set (ldw: bf16 elements, or bytes of codes); the kernels take one pointer

@@ -596,7 +596,8 @@ int avllm_pos_advance(int32_t* pos_dev, int32_t by, void* stream);
  *   mode 0  plain: C[M,N] (+ R), bf16 or f32 out                                    (o_proj / down_proj + residual, lm_head)
  *   mode 1  SwiGLU: W = [gate; up] rows [2N, K]; C[M,N] = silu(A.gate^T) * (A.up^T)  (LlamaMLP.forward's act_fn(gate) * up)
  *   mode 2  q|k|v: W rows [dq + 2 dkv, K]; rotary embedding on q and k (pairs (i, i + hd/2), table rope[hd/2][2] = cos,sin of the
- *           position); q -> C[M,dq]; k, v -> cache rows kc/vc[m][pos + *pos_dev][dkv]  (apply_rotary_pos_emb + DynamicCache.update)
+ *           position); q -> C[M,dq]; k, v -> cache rows kc/vc[m][pos + *pos_dev][dkv]  (apply_rotary_pos_emb + DynamicCache.update).
+ *           hd must be a power of two >= 32 (32, 64, 128, 256, ...): any other head dim is an argument error.
  * norm_w != NULL folds the preceding RMSNorm in: x * rsqrt(mean(x^2) + eps) * norm_w is applied to A on the fly. */
 typedef struct avllm_dec_proj_desc {
     const void* A; int64_t lda;

@@ -432,3 +432,64 @@ def lora_dx_bar(ref):
         e = e + kept * (ref.scale * GEMM_MFMA_ALLOW * 32.0 * U32 * sj + U32 * (ref.scale * pj).abs())
         total = total + kept * (ref.scale * pj).abs()
     return e + (len(ref.prods) + 1) * U32 * total + FP32_DENORM + BF16_OUT_REL * ref.out.abs()
+
+
+# ---- the fused token-step projection against float64 (tests/test_decode_pin_gpu.py; restatement, host emulation and cases in tests/refs64_decode.py).
+# No number here comes from a kernel's output.  The chain, in the kernel's order, each term elementwise on the float64 quantities of
+# refs64_decode.dec_proj64 (`ref`):
+#   accumulator: gemm_acc_bar(sum_abs, K, "split8") -- bf16 x bf16 products are exact, the MFMA's internal order is not documented (any-order bound
+#                with the allowance), the 8 wave partials meet in LDS order.  The fold xg = bf16(x g) is an exact fp32 product rounded once, in
+#                the reference too, so it adds nothing.  exact / locate: 0 (every partial sum is held by fp32; the tests check that premise).
+#   norm:        s = acc * rstd.  t = sum x^2 is K positive fp32 additions of exact squares (a lane's chain, 2 butterfly additions over the
+#                lane columns, 8 wave partials): any order of n additions of positive terms stays under n 2^-24 relative, n = K + 10; the division
+#                by K and the sum with eps round once each; the power -1/2 halves the relative error: (K + 12) / 2 half-ulps.  rsqrtf: the HIP
+#                programming guide's table of device math functions lists rsqrtf with a maximum error of 1 ulp (it is v_rsq_f32); DEC_RSQRT_ULP = 2
+#                is taken, the second ulp for the denormal-input scaling sequence around the instruction, = 4 half-ulps.  Then the product rounds once.
+#   bias:        one rounded sum.
+#   adapters:    u = a 16-term fmaf chain: 16 2^-24 sum |lt| |lb|, times |scale|; the product scale * u and the sum round once each (two roundings;
+#                a contracted fma rounds once and is covered).
+#   residual:    one rounded sum.
+#   SwiGLU:      silu(g) * up with the errors e_g, e_up of both columns: |up| (|silu'(g)| e_g + silu_bar(g)) + |silu(g)| e_up + the cross term, the
+#                second-order term of silu (|silu''| <= 1/2) and the rounded product.  silu_bar carries __expf (expf_rel), the sum and the division.
+#   rotation:    o = z c -+ z' s with the fp32 table the reference reads too: |c| e_z + |s| e_z' + the two rounded products and the rounded sum.
+#                The compiler may contract one product into an fma, which rounds less: the bound of the uncontracted form covers both.
+#   output:      BF16_OUT_REL |out| ONCE for a bf16 output (the single-rounding statement the offset family, R = -z + noise, holds the kernel to),
+#                and FP32_DENORM.
+DEC_RSQRT_ULP = 2.0
+
+
+def dec_rstd_rel(K):
+    """Relative error of the kernel's fp32 rstd = rsqrtf(sum x^2 / K + eps) (derivation above)."""
+    return (0.5 * (K + 12) + 2.0 * DEC_RSQRT_ULP) * U32
+
+
+def dec_proj_bar(ref, exact=False):
+    """Elementwise bar [M, N out] of one avllm_dec_proj launch from refs64_decode.dec_proj64's namespace.  exact: the accumulator (and the adapter
+    chain, whose operands are then small integers too) carries 0."""
+    import torch
+    K = ref.K
+    e = torch.zeros_like(ref.acc) if exact else gemm_acc_bar(ref.sum_abs, K, "split8")
+    if ref.rstd is not None:
+        e = ref.rstd * e + ref.y.abs() * dec_rstd_rel(K) + U32 * ref.y.abs()
+    if ref.bias:
+        e = e + U32 * ref.zb.abs()
+    if ref.u is not None:
+        chain = 0.0 if exact else 16.0 * U32 * ref.u_abs
+        e = e + abs(ref.scale) * chain + U32 * ((ref.scale * ref.u).abs() + ref.z.abs())
+    if ref.mode == 0:
+        if ref.R is not None:
+            e = e + U32 * ref.out.abs()
+    elif ref.mode == 1:
+        F = ref.F
+        g, up, eg, eu = ref.z[:, :F], ref.z[:, F:], e[:, :F], e[:, F:]
+        s = torch.sigmoid(g)
+        d_silu = (s + g * s * (1 - s)).abs()
+        e_silu = d_silu * eg + 0.5 * eg * eg + silu_bar(g)
+        e = up.abs() * e_silu + (g * s).abs() * eu + e_silu * eu + U32 * ref.out.abs()
+    else:
+        c, sn, p = ref.cosv[None, :], ref.sinv[None, :], ref.partner
+        rotary = (sn != 0) | (c != 1)
+        zp = ref.z[:, p]
+        e = torch.where(rotary, c.abs() * e + sn.abs() * e[:, p] + U32 * ((ref.z * c).abs() + (zp * sn).abs() + ref.out.abs()), e)
+    e = e + FP32_DENORM
+    return e if ref.out_f32 else e + BF16_OUT_REL * ref.out.abs()

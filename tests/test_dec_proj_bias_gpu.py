@@ -3,8 +3,6 @@ test_gemm_pin_gpu.py: `locate` (zero weights, bias[n] = a distinct small integer
 the permuted column order of the rotary region invites, is a wrong integer) and `exact` (operands on grids where every partial sum is exact)
 carry the bar 0; `offset` (bias +-64 on products of size 1: the Qwen case, k biases are large) is held to ONE rounding of the exact sum by
 bars.gemm_bar.  Bars come from tests/bars.py unchanged."""
-import zlib
-
 import pytest
 import torch
 
@@ -14,52 +12,10 @@ import bars  # noqa: E402
 import mxfp4_ref as mx4  # noqa: E402
 import refs64_gemm as G  # noqa: E402
 from avllm import ops  # noqa: E402
-from oracle import mxfp8  # noqa: E402
+from refs64_decode import distinct_bias, gen, grid_weights, ints, rope_table, rot, wargs  # noqa: E402
 
 BF, F64 = torch.bfloat16, torch.float64
 FORMS = ("bf16", "fp8", "fp4")
-
-
-def gen(*key):
-    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def ints(shape, lo, hi, *key):
-    return torch.randint(lo, hi + 1, shape, generator=gen(*key)).float()
-
-
-def wargs(W, form):
-    """dec_proj's weight arguments for the host matrix W (values every form holds exactly) in one of the three forms."""
-    if form == "bf16":
-        assert torch.equal(W.to(BF).float(), W)
-        return dict(W=W.to(BF).cuda())
-    if form == "fp8":
-        q, e = ops.mx_quantize(W.to(BF).cuda(), 2)
-        assert torch.equal(mxfp8.dequantize(q.cpu(), e.cpu().to(torch.int32) - 127), W)
-        return dict(W=None, W8=q, E8=e)
-    codes, e = mx4.quantize(W)
-    assert torch.equal(mx4.dequantize(codes, e), W)
-    return dict(W=None, W4=mx4.pack(codes).cuda(), E8=(e + 127).to(torch.uint8).cuda())
-
-
-def distinct_bias(N):
-    """bias[n] = n - N/2: distinct integers of magnitude <= 256, each a bf16 value."""
-    assert N <= 512
-    b = (torch.arange(N) - N // 2).float()
-    assert torch.equal(b.to(BF).float(), b)
-    return b
-
-
-def rope_table(hd, cos, sin):
-    return torch.tensor([cos, sin], dtype=torch.float32).repeat(hd // 2, 1).contiguous().cuda()
-
-
-def rot(t, nh, hd, cos, sin):
-    """apply_rotary_pos_emb with one (cos, sin) for every frequency: pairs (i, i + hd/2) inside each head."""
-    M = t.shape[0]
-    t = t.view(M, nh, hd)
-    a, b = t[..., : hd // 2], t[..., hd // 2:]
-    return torch.cat([a * cos - b * sin, b * cos + a * sin], -1).reshape(M, nh * hd)
 
 
 # ------------------------------------------------------------------------------------------------ locate, bar 0
@@ -132,16 +88,6 @@ def test_locate_qkv(dev, M, K, hd, heads, kvh):
 
 
 # ------------------------------------------------------------------------------------------------ exact, bar 0, three weight forms
-def grid_weights(N, K):
-    """Weights on the MXFP4 grid, every 32-block of a row with its own exponent (test_decode_fp4_gpu.py's construction; the exponents cycle
-    over 8 values so that any K fits fp32's 24 bits): e4m3 and bf16 hold them too."""
-    W = torch.zeros(N, K)
-    for b in range(K // 32):
-        W[:, 32 * b:32 * b + 32] = (torch.arange(32) % 7 - 3).float() * 2.0 ** (b % 8 - 3) * (1.0 - 2.0 * (torch.arange(N) % 2)).float()[:, None]
-    W[:, 1::2] *= 0.5
-    return W
-
-
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("K", [128, 896, 1152])
 @pytest.mark.parametrize("M", [1, 5, 16])
