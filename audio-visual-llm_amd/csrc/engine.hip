@@ -57,88 +57,90 @@ inline int f8_proj(const F8Buf& f, int M, int K, const void* W8, const void* S8,
     return av_gemm_f8(&d, st);
 }
 
+// One frozen linear layer, y = act(x W^T + bias) + R, on the matrix in the mode's form.  f8 == nullptr: W in the activation dtype (av_gemm).
+// Otherwise the e4m3 image W8 with its scales S8 times the block-scaled codes of x in *f8; x is quantised here unless the caller says the
+// codes are already there (after av_norm_mxq, after av_attention_fwd_mxq, for a second projection of the same input).
+struct Frozen { const void *W, *W8, *S8, *bias; };
+int linear(int dtype, const F8Buf* f8, bool quantised, const Frozen& w, const void* x, long ldx, int M, int K, int N, void* y, long ldy, int act,
+           const void* R, long ldr, hipStream_t st) {
+    if (f8) {
+        if (!quantised) AV_TRY(f8_quant(*f8, x, ldx, M, K, st));
+        return f8_proj(*f8, M, K, w.W8, w.S8, N, y, ldy, w.bias, act, R, ldr, st);
+    }
+    avllm_gemm_desc g = gemm_desc(dtype, x, ldx, w.W, K, y, ldy, M, N, K);
+    g.bias = w.bias; g.act = act; g.R = R; g.ldr = ldr;
+    return av_gemm(&g, st);
+}
+
 // ------------------------------------------------------------------ encoders
-struct EncBuf { void *x, *xn, *qkv, *att, *ff; F8Buf f8; };
+// xc / xcn: the CLS rows of the last block (CLIP only)
+struct EncBuf { void *x, *xn, *qkv, *att, *ff, *xc, *xcn; F8Buf f8; };
+void carve_enc(Bump& b, EncBuf& e, long M, long cls_rows, int d, int ffn, size_t es, bool fp8) {
+    e.x = b.take((size_t)M * d * es);
+    e.xn = b.take((size_t)M * d * es);
+    e.qkv = b.take((size_t)M * 3 * d * es);
+    e.att = b.take((size_t)M * d * es);
+    e.ff = b.take((size_t)M * ffn * es);
+    if (cls_rows) {
+        e.xc = b.take((size_t)cls_rows * d * es);
+        e.xcn = b.take((size_t)cls_rows * d * es);
+    }
+    if (fp8) carve_f8(b, e.f8, M, ffn > d ? ffn : d);
+}
 
 int encoder_layers(int dtype, const avllm_enc_layer* L, int layers, int d, int heads, int ffn, int tokens, long items,
-                   float eps, int act, const EncBuf& b, bool cls_only_last, void* cls_out, void* xc, void* xcn, hipStream_t st, bool fp8 = false) {
+                   float eps, int act, const EncBuf& b, bool cls_only_last, void* cls_out, hipStream_t st, bool fp8 = false) {
     const long M = items * tokens;
     const int hd = d / heads;
     const size_t es = av_dtype_size(dtype);
     for (int l = 0; l < layers; ++l) {
         const avllm_enc_layer& P = L[l];
         AV_CHECK_ARG(!fp8 || (P.wqkv8 && P.sqkv8 && P.wo8 && P.so8 && P.w18 && P.s18 && P.w28 && P.s28), "encoder layer %d: fp8 mode without fp8 weight images", l);
+        const F8Buf* fq = fp8 ? &b.f8 : nullptr;
         const bool nq = fp8 && d % 128 == 0 && d <= 8192 && !av_knob(AV_KNOB_F8_UNFUSED_QUANT);      // LayerNorm straight to e4m3 + scales (fp8.hip norm_mxq_kernel)
         if (nq) AV_TRY(av_norm_mxq(b.x, P.ln1_w, P.ln1_b, nullptr, nullptr, b.f8.q, d, b.f8.s, M, d, eps, st));
         else AV_TRY(av_layernorm(b.x, P.ln1_w, P.ln1_b, b.xn, M, d, eps, dtype, st));
-        avllm_gemm_desc g;
-        if (fp8) {
-            if (!nq) AV_TRY(f8_quant(b.f8, b.xn, d, (int)M, d, st));
-            AV_TRY(f8_proj(b.f8, (int)M, d, P.wqkv8, P.sqkv8, 3 * d, b.qkv, 3 * d, P.bqkv, AV_ACT_NONE, nullptr, 0, st));
-        } else {
-            g = gemm_desc(dtype, b.xn, d, P.wqkv, d, b.qkv, 3 * d, (int)M, 3 * d, d);
-            g.bias = P.bqkv;
-            AV_TRY(av_gemm(&g, st));
-        }
+        AV_TRY(linear(dtype, fq, nq, {P.wqkv, P.wqkv8, P.sqkv8, P.bqkv}, b.xn, d, (int)M, d, 3 * d, b.qkv, 3 * d, AV_ACT_NONE, nullptr, 0, st));
         const char* qkv = (const char*)b.qkv;
+        // only token 0 of the last block is consumed (clip_whisper_model.py:1141): the block is finished on the CLS rows, a handful, in the
+        // activation dtype also in fp8 mode
+        const bool cls = cls_only_last && l == layers - 1;
         // fp8: the attention output is only ever the out-projection's A operand -- the one-pass kernel (CLIP: <= 272 tokens) block-scales it in its
         // epilogue; the bf16 tensor is not written (the CLS-only last block keeps the bf16 form)
-        const bool att_q = fp8 && !(cls_only_last && l == layers - 1) && av_attention_fwd_mxq_ok((int)items, tokens, heads, hd, dtype, heads);
+        const bool att_q = fp8 && !cls && av_attention_fwd_mxq_ok((int)items, tokens, heads, hd, dtype, heads);
         if (att_q) AV_TRY(av_attention_fwd_mxq(qkv, qkv + (size_t)d * es, qkv + (size_t)2 * d * es, b.f8.q, d, b.f8.s, (int)items, tokens, heads, hd,
                                                3 * d, 3 * d, 3 * d, 1.0f / sqrtf((float)hd), st));
         else
         AV_TRY(av_attention_fwd(qkv, qkv + (size_t)d * es, qkv + (size_t)2 * d * es, b.att, nullptr, (int)items, tokens, tokens,
                                 heads, hd, 3 * d, 3 * d, 3 * d, d, 1.0f / sqrtf((float)hd), 0, dtype, 0, st));
-        if (cls_only_last && l == layers - 1) {
-            // only token 0 of the last block is consumed (clip_whisper_model.py:1141): finish the block on CLS rows
-            g = gemm_desc(dtype, b.att, (long)tokens * d, P.wo, d, xc, d, (int)items, d, d);
-            g.bias = P.bo; g.R = b.x; g.ldr = (long)tokens * d;
-            AV_TRY(av_gemm(&g, st));
-            AV_TRY(av_layernorm(xc, P.ln2_w, P.ln2_b, xcn, items, d, eps, dtype, st));
-            g = gemm_desc(dtype, xcn, d, P.w1, d, b.ff, ffn, (int)items, ffn, d);
-            g.bias = P.b1; g.act = act;
-            AV_TRY(av_gemm(&g, st));
-            g = gemm_desc(dtype, b.ff, ffn, P.w2, ffn, cls_out, d, (int)items, d, ffn);
-            g.bias = P.b2; g.R = xc; g.ldr = d;
-            AV_TRY(av_gemm(&g, st));
-            return AV_OK;
-        }
-        if (fp8) {      // the CLS-only last block above stays bf16: a handful of rows
-            if (!att_q) AV_TRY(f8_quant(b.f8, b.att, d, (int)M, d, st));
-            AV_TRY(f8_proj(b.f8, (int)M, d, P.wo8, P.so8, d, b.x, d, P.bo, AV_ACT_NONE, b.x, d, st));
-            if (nq) AV_TRY(av_norm_mxq(b.x, P.ln2_w, P.ln2_b, nullptr, nullptr, b.f8.q, d, b.f8.s, M, d, eps, st));
-            else {
-                AV_TRY(av_layernorm(b.x, P.ln2_w, P.ln2_b, b.xn, M, d, eps, dtype, st));
-                AV_TRY(f8_quant(b.f8, b.xn, d, (int)M, d, st));
+        // the block tail: rows of the token-major buffers (row stride d), or their CLS rows (stride tokens * d) into xc -> xcn -> cls_out
+        if (cls) fq = nullptr;
+        const int rows = cls ? (int)items : (int)M;
+        const long ldx = cls ? (long)tokens * d : d;
+        void* x1 = cls ? b.xc : b.x;
+        void* xn = cls ? b.xcn : b.xn;
+        void* out = cls ? cls_out : b.x;
+        AV_TRY(linear(dtype, fq, att_q, {P.wo, P.wo8, P.so8, P.bo}, b.att, ldx, rows, d, d, x1, d, AV_ACT_NONE, b.x, ldx, st));
+        const bool nq2 = nq && !cls;
+        if (nq2) AV_TRY(av_norm_mxq(x1, P.ln2_w, P.ln2_b, nullptr, nullptr, b.f8.q, d, b.f8.s, rows, d, eps, st));
+        else AV_TRY(av_layernorm(x1, P.ln2_w, P.ln2_b, xn, rows, d, eps, dtype, st));
+        if (fq) {
+            if (!nq2) AV_TRY(f8_quant(*fq, xn, d, rows, d, st));      // fc1's input: in the F8Buf from here on, either way
+            // fc1 with its output quantised in the epilogue (codes + scale image live in the bf16 ff buffer's memory: 1 + 1/32 of its 2 bytes
+            // per element), so fc2 reads them directly: no bf16 copy of the [M, ffn] activation, no quantiser pass over it
+            avllm_gemm_f8_desc q1 = {};
+            q1.A = b.f8.q; q1.SA = b.f8.s; q1.B = P.w18; q1.SB = P.s18; q1.bias = P.b1; q1.lda = d; q1.ldb = d; q1.M = rows; q1.N = ffn; q1.K = d; q1.act = act;
+            F8Buf ffq;
+            ffq.q = b.ff; ffq.s = (char*)b.ff + (((size_t)M * ffn + 255) & ~(size_t)255);
+            q1.Cq = ffq.q; q1.SCq = ffq.s; q1.ldcq = ffn;
+            if (!av_knob(AV_KNOB_F8_UNFUSED_QUANT) && avllm_gemm_f8_takes_quantised_output(&q1) && (size_t)M * ffn + 256 + avllm_mx_scale_bytes((int)M, ffn) <= (size_t)M * ffn * es) {
+                AV_TRY(av_gemm_f8(&q1, st));
+                AV_TRY(linear(dtype, &ffq, true, {P.w2, P.w28, P.s28, P.b2}, b.ff, ffn, rows, ffn, d, out, d, AV_ACT_NONE, x1, d, st));
+                continue;
             }
-            {   // fc1 with its output quantised in the epilogue (codes + scale image live in the bf16 ff buffer's memory: 1 + 1/32 of its 2 bytes
-                // per element), so fc2 reads them directly: no bf16 copy of the [M, ffn] activation, no quantiser pass over it
-                avllm_gemm_f8_desc q1 = {};
-                q1.A = b.f8.q; q1.SA = b.f8.s; q1.B = P.w18; q1.SB = P.s18; q1.bias = P.b1; q1.lda = d; q1.ldb = d; q1.M = (int)M; q1.N = ffn; q1.K = d; q1.act = act;
-                F8Buf ffq;
-                ffq.q = b.ff; ffq.s = (char*)b.ff + (((size_t)M * ffn + 255) & ~(size_t)255);
-                q1.Cq = ffq.q; q1.SCq = ffq.s; q1.ldcq = ffn;
-                if (!av_knob(AV_KNOB_F8_UNFUSED_QUANT) && avllm_gemm_f8_takes_quantised_output(&q1) && (size_t)M * ffn + 256 + avllm_mx_scale_bytes((int)M, ffn) <= (size_t)M * ffn * es) {
-                    AV_TRY(av_gemm_f8(&q1, st));
-                    AV_TRY(f8_proj(ffq, (int)M, ffn, P.w28, P.s28, d, b.x, d, P.b2, AV_ACT_NONE, b.x, d, st));
-                    continue;
-                }
-            }
-            AV_TRY(f8_proj(b.f8, (int)M, d, P.w18, P.s18, ffn, b.ff, ffn, P.b1, act, nullptr, 0, st));
-            AV_TRY(f8_quant(b.f8, b.ff, ffn, (int)M, ffn, st));
-            AV_TRY(f8_proj(b.f8, (int)M, ffn, P.w28, P.s28, d, b.x, d, P.b2, AV_ACT_NONE, b.x, d, st));
-            continue;
         }
-        g = gemm_desc(dtype, b.att, d, P.wo, d, b.x, d, (int)M, d, d);
-        g.bias = P.bo; g.R = b.x; g.ldr = d;
-        AV_TRY(av_gemm(&g, st));
-        AV_TRY(av_layernorm(b.x, P.ln2_w, P.ln2_b, b.xn, M, d, eps, dtype, st));
-        g = gemm_desc(dtype, b.xn, d, P.w1, d, b.ff, ffn, (int)M, ffn, d);
-        g.bias = P.b1; g.act = act;
-        AV_TRY(av_gemm(&g, st));
-        g = gemm_desc(dtype, b.ff, ffn, P.w2, ffn, b.x, d, (int)M, d, ffn);
-        g.bias = P.b2; g.R = b.x; g.ldr = d;
-        AV_TRY(av_gemm(&g, st));
+        AV_TRY(linear(dtype, fq, true, {P.w1, P.w18, P.s18, P.b1}, xn, d, rows, d, ffn, b.ff, ffn, act, nullptr, 0, st));
+        AV_TRY(linear(dtype, fq, false, {P.w2, P.w28, P.s28, P.b2}, b.ff, ffn, rows, ffn, d, out, d, AV_ACT_NONE, x1, d, st));
     }
     return AV_OK;
 }
@@ -150,43 +152,36 @@ void carve_whisper(const avllm_whisper* w, int B, Bump& b, WhisperWs& s) {
     s.cols1 = b.take((size_t)B * T2 * w->k1pad * es);
     s.h1 = b.take((size_t)B * T2 * w->d * es);
     s.cols2 = b.take((size_t)M * 3 * w->d * es);
-    s.e.x = b.take((size_t)M * w->d * es);
-    s.e.xn = b.take((size_t)M * w->d * es);
-    s.e.qkv = b.take((size_t)M * 3 * w->d * es);
-    s.e.att = b.take((size_t)M * w->d * es);
-    s.e.ff = b.take((size_t)M * w->ffn * es);
-    if (w->fp8) carve_f8(b, s.e.f8, M, w->ffn > w->d ? w->ffn : w->d);
+    carve_enc(b, s.e, M, 0, w->d, w->ffn, es, w->fp8 != 0);
 }
 
-struct ClipWs { void* cols; EncBuf e; void *xc, *xcn; };
+struct ClipWs { void* cols; EncBuf e; };
 void carve_clip(const avllm_clip* c, int N, Bump& b, ClipWs& s, int& kpad) {
     const size_t es = av_dtype_size(c->dtype);
     const int g = c->image / c->patch;
     kpad = (3 * c->patch * c->patch + 63) / 64 * 64;
-    const long M = (long)N * c->tokens;
     s.cols = b.take((size_t)N * g * g * kpad * es);
-    s.e.x = b.take((size_t)M * c->d * es);
-    s.e.xn = b.take((size_t)M * c->d * es);
-    s.e.qkv = b.take((size_t)M * 3 * c->d * es);
-    s.e.att = b.take((size_t)M * c->d * es);
-    s.e.ff = b.take((size_t)M * c->ffn * es);
-    s.xc = b.take((size_t)N * c->d * es);
-    s.xcn = b.take((size_t)N * c->d * es);
-    if (c->fp8) carve_f8(b, s.e.f8, M, c->ffn > c->d ? c->ffn : c->d);
+    carve_enc(b, s.e, (long)N * c->tokens, N, c->d, c->ffn, es, c->fp8 != 0);
 }
 
 // ------------------------------------------------------------------ llama
-inline int llama_kv_heads(const avllm_llama* m);
-inline int llama_dkv(const avllm_llama* m);
-inline int llama_qw(const avllm_llama* m);
-inline int llama_off(const avllm_llama* m, int j);
-inline int llama_wid(const avllm_llama* m, int j);
+// grouped-query geometry: q is d wide, k and v are dkv = kv_heads*hd wide; the fused row is [q | k | v] = qw columns
+inline int llama_kv_heads(const avllm_llama* m) { return m->kv_heads > 0 ? m->kv_heads : m->heads; }
+inline int llama_dkv(const avllm_llama* m) { return llama_kv_heads(m) * (m->d / m->heads); }
+inline int llama_qw(const avllm_llama* m) { return m->d + 2 * llama_dkv(m); }
+inline int llama_off(const avllm_llama* m, int j) { return j == 0 ? 0 : (j == 1 ? m->d : m->d + llama_dkv(m)); }     // column (= wqkv row) of slice j
+inline int llama_wid(const avllm_llama* m, int j) { return j == 0 ? m->d : llama_dkv(m); }
+// slice j of a layer's q|k|v bias (NULL without one)
+inline const void* llama_bias(const avllm_llama* m, const avllm_llama_layer& P, int j) {
+    return P.bqkv ? (const char*)P.bqkv + (size_t)llama_off(m, j) * av_dtype_size(m->dtype) : nullptr;
+}
+
 struct LlamaLayerAct {
     void *xn1, *qkv, *att, *tqkv, *to, *h1, *gu;
     float *rstd1, *rstd2, *lse;
 };
 struct LlamaTrainWs {
-    void** resid;            // host array [layers+1] (lives in a std::vector owned by the caller frame)
+    void** resid;            // host array [layers+1]
     LlamaLayerAct* act;      // host array [layers]
     void *xn2, *hmid, *xf, *logits, *xd;
     float *rstd_f, *row_lse, *delta, *rope_tab;
@@ -233,12 +228,22 @@ void carve_llama_train(const avllm_llama* m, int B, int S, Bump& b, LlamaTrainWs
     w.dto = b.take((size_t)M * AVLLM_LORA_PAD * es);
     if (m->fp8) carve_f8(b, w.f8, M, f > d ? f : d);
 }
+// The training workspace laid out in ws (null with an unlimited size: the dry run that sizes it), with the host arrays its layout points into
+struct LlamaTrainFrame {
+    Bump b; LlamaTrainWs w; void* resid[257]; LlamaLayerAct act[256];
+    LlamaTrainFrame(const avllm_llama* m, int B, int S, void* ws, size_t ws_bytes) : b(ws, ws_bytes) { carve_llama_train(m, B, S, b, w, resid, act); }
+};
 
 int check_llama(const avllm_llama* m) {
     AV_CHECK_ARG(m && m->layer && m->embed && m->norm_w && m->lm_head, "llama: null model fields");
     AV_CHECK_ARG(m->d % m->heads == 0 && m->d % 64 == 0 && m->ffn % 64 == 0, "llama: d=%d ffn=%d must be multiples of 64", m->d, m->ffn);
     AV_CHECK_ARG(m->layers > 0 && m->layers <= 256, "llama: layers=%d", m->layers);
     AV_CHECK_ARG(m->kv_heads >= 0 && (m->kv_heads == 0 || m->heads % m->kv_heads == 0), "llama: heads=%d kv_heads=%d", m->heads, m->kv_heads);
+    if (m->fp8)
+        for (int l = 0; l < m->layers; ++l) {
+            const avllm_llama_layer& P = m->layer[l];
+            AV_CHECK_ARG(P.wqkv8 && P.sqkv8 && P.wo8 && P.so8 && P.wgu8 && P.sgu8 && P.wdown8 && P.sdown8, "llama layer %d: fp8 mode without fp8 weight images", l);
+        }
     if (m->decode_fp8 || m->decode_fp4) {
         AV_CHECK_ARG(!(m->decode_fp8 && m->decode_fp4), "llama: decode_fp4 and decode_fp8 are two forms of the same token step, set one");
         const bool f4 = m->decode_fp4 != 0;
@@ -254,48 +259,105 @@ int check_llama(const avllm_llama* m) {
     }
     return AV_OK;
 }
-// grouped-query geometry: q is d wide, k and v are dkv = kv_heads*hd wide; the fused row is [q | k | v] = qw columns
-inline int llama_kv_heads(const avllm_llama* m) { return m->kv_heads > 0 ? m->kv_heads : m->heads; }
-inline int llama_dkv(const avllm_llama* m) { return llama_kv_heads(m) * (m->d / m->heads); }
-inline int llama_qw(const avllm_llama* m) { return m->d + 2 * llama_dkv(m); }
-inline int llama_off(const avllm_llama* m, int j) { return j == 0 ? 0 : (j == 1 ? m->d : m->d + llama_dkv(m)); }     // column (= wqkv row) of slice j
-inline int llama_wid(const avllm_llama* m, int j) { return j == 0 ? m->d : llama_dkv(m); }
-// slice j of a layer's q|k|v bias (NULL without one)
-inline const void* llama_bias(const avllm_llama* m, const avllm_llama_layer& P, int j) {
-    return P.bqkv ? (const char*)P.bqkv + (size_t)llama_off(m, j) * av_dtype_size(m->dtype) : nullptr;
+
+// ------------------------------------------------------------------ LoRA adapters
+// The step's adapter dropout (peft: lora_B(lora_A(dropout(x))), one mask per wrapped module).  p = 0: none.  fused: the kernels that read the
+// adapter's input generate its mask themselves (bf16 MFMA kernels); otherwise (fp32 parity mode, narrow models) dropout(x) is materialised.
+// The backward pass regenerates the forward's masks from the same seeds, so both take this rule from here.
+struct LoraDrop {
+    float p; bool fused;
+    float fused_p() const { return fused ? p : 0.f; }
+};
+inline LoraDrop lora_drop(const avllm_llama* m) {
+    const float p = m->lora_dropout > 0.f ? m->lora_dropout : 0.f;
+    return {p, p > 0.f && m->dtype == AV_BF16 && m->d % 256 == 0 && m->lora_r <= 16};
+}
+// the mask of layer l, module j (q, k, v, o); the step's base seed may live in device memory instead (m->dropout_seed_dev, see avllm_step_state)
+inline uint32_t lora_seed(const avllm_llama* m, int l, int j) { return m->dropout_seed + 4u * l + j; }
+// the adapter branch's input: x itself, or dropout(x) in xd after an av_dropout launch when masks are materialised
+int lora_input(const avllm_llama* m, const LoraDrop& dr, const void* x, void* xd, int M, uint32_t seed, const void*& xl, hipStream_t st) {
+    xl = x;
+    if (dr.p > 0.f && !dr.fused) { AV_TRY(av_dropout(x, xd, M, m->d, seed, dr.p, m->dtype, st, m->dropout_seed_dev)); xl = xd; }
+    return AV_OK;
 }
 
-// y[:, slice j] = x W_j^T + bias_j (+ t_j B_j^T)
-int lora_proj(const avllm_llama* m, const void* x, long ldx, const void* W, long ldw, int K, int N, const avllm_lora_mod& lm,
-              void* t, long ldt, void* y, long ldy, const void* R, long ldr, int M, hipStream_t st, const void* xl = nullptr,
-              uint32_t a_seed = 0, float a_p = 0.f, const void* bias = nullptr) {
-    // (the step's base seed may live in device memory: m->dropout_seed_dev, see avllm_step_state)
+// Adapter j of layer l in the training workspace: q, k, v (j = 0..2) share the [M, 3*64] buffers tqkv / dtqkv, o (j = 3) has to / dto
+struct LoraView {
+    const avllm_lora_mod* mod;
+    uint32_t seed;
+    void *t, *dt; long ldt;      // forward t_j = s dropout_j(x) A_j^T, backward d t_j, and the row stride of both
+    int off, wid;                // its columns of the fused q|k|v row (o: its own d columns)
+    bool at_slice;               // AT_pad is the j-th 64-column slice of one [d, 3*64] matrix that starts at q's
+};
+inline LoraView lora_view(const avllm_llama* m, int l, int j, const LlamaLayerAct& a, const LlamaTrainWs& w) {
+    const avllm_lora_mod* lora = m->layer[l].lora;
+    LoraView v = {&lora[j], lora_seed(m, l, j), a.to, w.dto, AVLLM_LORA_PAD, 0, m->d, false};
+    if (j < 3) {
+        const size_t es = av_dtype_size(m->dtype), slot = (size_t)j * AVLLM_LORA_PAD * es;
+        v.t = (char*)a.tqkv + slot; v.dt = (char*)w.dtqkv + slot; v.ldt = 3 * AVLLM_LORA_PAD;
+        v.off = llama_off(m, j); v.wid = llama_wid(m, j);
+        v.at_slice = lora[j].ld_at == 3 * AVLLM_LORA_PAD && (const char*)lora[j].AT_pad == (const char*)lora[0].AT_pad + slot;
+    }
+    return v;
+}
+
+// One adapted projection of x [M, K]: y = x W^T + bias + R + t B^T with t = s * dropout(x) A^T, the rank-side product of xl (lora_input),
+// made here unless have_t.  W is the frozen matrix for the base product with the adapter as its second K segment (bf16 / fp32); W == nullptr
+// (fp8 mode) means y already holds the base product with its bias and residual, and the adapter term is added by a K = 64 GEMM.
+int lora_linear(const avllm_llama* m, const void* x, int K, const void* W, const void* bias, int N, const avllm_lora_mod& lm, const void* xl,
+                uint32_t a_seed, float a_p, void* t, long ldt, bool have_t, void* y, long ldy, const void* R, long ldr, int M, hipStream_t st) {
     avllm_gemm_desc g;
     const bool has = lm.A_pad != nullptr;
-    if (has) {
-        // xl = dropout(x) for the adapter branch when lora_dropout is active (peft: lora_B(lora_A(dropout(x))))
-        g = gemm_desc(m->dtype, xl ? xl : x, xl ? (long)K : ldx, lm.A_pad, K, t, ldt, M, AVLLM_LORA_PAD, K);
+    if (has && !have_t) {
+        g = gemm_desc(m->dtype, xl, K, lm.A_pad, K, t, ldt, M, AVLLM_LORA_PAD, K);
         g.alpha = m->lora_scale;
         g.a_drop_seed = a_seed; g.a_drop_p = a_p; g.seed_dev = m->dropout_seed_dev;      // bf16: dropout generated inside the rank-side GEMM
         g.n_valid = m->lora_r;                         // rank padded to 64: the padding columns are written as zeros, not computed
         AV_TRY(av_gemm(&g, st));
     }
-    g = gemm_desc(m->dtype, x, ldx, W, ldw, y, ldy, M, N, K);
-    if (has) { g.A2 = t; g.lda2 = ldt; g.B2 = lm.B_pad; g.ldb2 = AVLLM_LORA_PAD; g.K2 = AVLLM_LORA_PAD; }
-    g.R = R; g.ldr = ldr; g.bias = bias;
+    if (W) {
+        g = gemm_desc(m->dtype, x, K, W, K, y, ldy, M, N, K);
+        if (has) { g.A2 = t; g.lda2 = ldt; g.B2 = lm.B_pad; g.ldb2 = AVLLM_LORA_PAD; g.K2 = AVLLM_LORA_PAD; }
+        g.R = R; g.ldr = ldr; g.bias = bias;
+    } else {
+        if (!has) return AV_OK;
+        g = gemm_desc(m->dtype, t, ldt, lm.B_pad, AVLLM_LORA_PAD, y, ldy, M, N, AVLLM_LORA_PAD);
+        g.R = y; g.ldr = ldy;
+    }
     return av_gemm(&g, st);
 }
 
-// fp8 mode: the adapter term alone, y += scale * (dropout(x) A^T) B^T on top of a base product already in y (bf16, rank-side GEMM + K=64 GEMM)
-int lora_add(const avllm_llama* m, const void* x, long ldx, int K, int N, const avllm_lora_mod& lm, void* t, long ldt, void* y, long ldy, int M,
-             hipStream_t st, const void* xl, uint32_t a_seed, float a_p) {
-    if (!lm.A_pad) return AV_OK;
-    avllm_gemm_desc g = gemm_desc(m->dtype, xl ? xl : x, xl ? (long)K : ldx, lm.A_pad, K, t, ldt, M, AVLLM_LORA_PAD, K);
-    g.alpha = m->lora_scale; g.a_drop_seed = a_seed; g.a_drop_p = a_p; g.seed_dev = m->dropout_seed_dev; g.n_valid = m->lora_r;
-    AV_TRY(av_gemm(&g, st));
-    g = gemm_desc(m->dtype, t, ldt, lm.B_pad, AVLLM_LORA_PAD, y, ldy, M, N, AVLLM_LORA_PAD);
-    g.R = y; g.ldr = ldy;
-    return av_gemm(&g, st);
+// One adapter's weight gradients and d t from dy, its columns of the projection's output gradient: dB += dy^T t, dt = s dy B,
+// dA += dt^T dropout(x)
+int lora_wgrad(const avllm_llama* m, const LoraDrop& dr, const LoraView& v, const void* dy, long ldy, const void* x, void* xd, int M, hipStream_t st) {
+    const avllm_lora_mod& lm = *v.mod;
+    const int dt = m->dtype, d = m->d, R = m->lora_r;
+    AV_TRY(av_gemm_tn(dy, ldy, v.wid, v.t, v.ldt, R, M, lm.gB, R, 1.0f, dt, st));
+    avllm_gemm_desc gt = gemm_desc(dt, dy, ldy, lm.BT_pad, v.wid, v.dt, v.ldt, M, AVLLM_LORA_PAD, v.wid);
+    gt.alpha = m->lora_scale; gt.n_valid = R;
+    AV_TRY(av_gemm(&gt, st));
+    const void* xin;
+    AV_TRY(lora_input(m, dr, x, xd, M, v.seed, xin, st));
+    return av_gemm_tn(v.dt, v.ldt, R, xin, d, d, M, lm.gA, d, 1.0f, dt, st, v.seed, dr.fused_p(), m->dropout_seed_dev);
+}
+
+// dx += sum_j mask_j * (dt_j . A_j) / (1-p) over the adapters present among v[0..n): their input gradients pass back through their dropout.
+// One pass over dx for all of them when the fused kernel applies (csrc/lora_dx.hip), a masked K = 64 GEMM each otherwise.
+int lora_dx_dropped(const avllm_llama* m, const LoraDrop& dr, const LoraView* v, int n, void* dx, int M, hipStream_t st) {
+    const int dt = m->dtype, d = m->d;
+    const void* Tp[3]; const void* Ap[3]; long lt[3], la[3]; uint32_t sd[3]; int nj = 0;
+    for (int j = 0; j < n; ++j) {
+        if (!v[j].mod->A_pad) continue;
+        Tp[nj] = v[j].dt; lt[nj] = v[j].ldt; Ap[nj] = v[j].mod->AT_pad; la[nj] = v[j].mod->ld_at; sd[nj] = v[j].seed; ++nj;
+    }
+    if (dr.fused && av_lora_dx_masked_supported(dt, d, m->lora_r, lt, la, nj, d, d))
+        return av_lora_dx_masked(Tp, lt, Ap, la, sd, nj, m->lora_r, dx, d, dx, d, M, d, dr.p, m->dropout_seed_dev, dt, st);
+    for (int k = 0; k < nj; ++k) {
+        avllm_gemm_desc gm = gemm_desc(dt, Tp[k], lt[k], Ap[k], la[k], dx, d, M, d, AVLLM_LORA_PAD);
+        gm.R = dx; gm.ldr = d; gm.drop_seed = sd[k]; gm.drop_p = dr.p; gm.seed_dev = m->dropout_seed_dev;
+        AV_TRY(av_gemm(&gm, st));
+    }
+    return AV_OK;
 }
 
 }  // namespace
@@ -330,7 +392,7 @@ extern "C" int avllm_whisper_encoder_fwd(const avllm_whisper* w, const float* me
     AV_TRY(av_gemm(&g, st));
     AV_CHECK_ARG(!w->fp8 || (dt == AV_BF16 && d % 128 == 0 && w->ffn % 128 == 0), "whisper: fp8 needs bf16 activations and widths that are multiples of 128");
     AV_TRY(encoder_layers(dt, w->layer, w->layers, d, w->heads, w->ffn, w->n_ctx, B, 1e-5f, AV_ACT_GELU, s.e, false, nullptr,
-                          nullptr, nullptr, st, w->fp8 != 0));
+                          st, w->fp8 != 0));
     return av_layernorm(s.e.x, w->lnf_w, w->lnf_b, out, M, d, 1e-5f, dt, st);
 }
 
@@ -365,17 +427,13 @@ extern "C" int avllm_clip_vision_cls_fwd(const avllm_clip* c, const void* frames
     AV_TRY(av_layernorm(s.e.xn, c->pre_ln_w, c->pre_ln_b, s.e.x, (long)N * c->tokens, d, c->eps, dt, st));
     AV_CHECK_ARG(!c->fp8 || (dt == AV_BF16 && d % 128 == 0 && c->ffn % 128 == 0), "clip: fp8 needs bf16 activations and widths that are multiples of 128");
     return encoder_layers(dt, c->layer, c->layers, d, c->heads, c->ffn, c->tokens, N, c->eps, AV_ACT_QUICK_GELU, s.e, true, cls,
-                          s.xc, s.xcn, st, c->fp8 != 0);
+                          st, c->fp8 != 0);
 }
 
 // =============================================================================================== Llama train
 extern "C" size_t avllm_llama_train_workspace_bytes(const avllm_llama* m, int32_t B, int32_t S) {
-    Bump b(nullptr, (size_t)-1);
-    LlamaTrainWs w;
-    void* resid[257]; LlamaLayerAct act[256];
     if (!m || m->layers > 256) return 0;
-    carve_llama_train(m, B, S, b, w, resid, act);
-    return bump_size(b);
+    return bump_size(LlamaTrainFrame(m, B, S, nullptr, (size_t)-1).b);
 }
 
 extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, const int64_t* labels, int32_t B, int32_t S,
@@ -384,103 +442,58 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
     AV_TRY(check_llama(m));
     AV_CHECK_ARG(x && ws && B > 0 && S > 0, "llama_lora_fwd_loss: null/empty");
     AV_CHECK_ARG(!labels || (loss_sum && count), "llama_lora_fwd_loss: labels need loss_sum/count");
-    Bump b(ws, ws_bytes);
-    LlamaTrainWs w;
-    void* resid[257]; LlamaLayerAct act[256];
-    carve_llama_train(m, B, S, b, w, resid, act);
-    if (!b.ok) return av_set_error(AV_ERR_WORKSPACE, "llama_lora_fwd_loss: workspace %zu < %zu bytes", ws_bytes, bump_size(b));
+    LlamaTrainFrame fr(m, B, S, ws, ws_bytes);
+    if (!fr.b.ok) return av_set_error(AV_ERR_WORKSPACE, "llama_lora_fwd_loss: workspace %zu < %zu bytes", ws_bytes, bump_size(fr.b));
+    LlamaTrainWs& w = fr.w;
     const int dt = m->dtype, d = m->d, f = m->ffn, H = m->heads, hd = d / H;
     const int Hkv = llama_kv_heads(m), dkv = llama_dkv(m), qw = llama_qw(m);
     const size_t es = av_dtype_size(dt);
     const int M = B * S;
-    AV_HIP(hipMemcpyAsync(resid[0], x, (size_t)M * d * es, hipMemcpyDeviceToDevice, st));
+    AV_HIP(hipMemcpyAsync(w.resid[0], x, (size_t)M * d * es, hipMemcpyDeviceToDevice, st));
     AV_TRY(av_rope_table(w.rope_tab, S, hd, 0, m->theta, st, nullptr, llama_rope_scale(m)));
-    const bool drop = m->lora_dropout > 0.f;
-    // bf16 (MFMA kernels): masks are generated inside the rank-side GEMMs; fp32 parity mode materialises dropout(x)
-    const bool fuse_drop = drop && m->dtype == AV_BF16 && d % 256 == 0 && m->lora_r <= 16;
-    const bool fp8 = m->fp8 != 0;
-    AV_CHECK_ARG(!fp8 || (dt == AV_BF16 && d % 128 == 0 && f % 128 == 0 && m->vocab % 8 == 0 && m->lm_head8 && m->slm_head8),
+    const LoraDrop dr = lora_drop(m);
+    AV_CHECK_ARG(!m->fp8 || (dt == AV_BF16 && d % 128 == 0 && f % 128 == 0 && m->vocab % 8 == 0 && m->lm_head8 && m->slm_head8),
                  "llama: fp8 needs bf16 activations, d and ffn multiples of 128 and the fp8 weight images");
+    const F8Buf* fq = m->fp8 ? &w.f8 : nullptr;      // fp8 mode: frozen products on the e4m3 images, the adapters' terms added on top in bf16
     for (int l = 0; l < m->layers; ++l) {
         const avllm_llama_layer& P = m->layer[l];
-        LlamaLayerAct& a = act[l];
-        AV_TRY(av_rmsnorm_fwd(resid[l], P.ln1_w, a.xn1, a.rstd1, M, d, m->eps, dt, st));
-        if (fp8) {      // one fp8 product for q|k|v (one quantisation of the normed input), adapters added on top
-            AV_CHECK_ARG(P.wqkv8 && P.sqkv8 && P.wo8 && P.so8 && P.wgu8 && P.sgu8 && P.wdown8 && P.sdown8, "llama layer %d: fp8 mode without fp8 weight images", l);
-            AV_TRY(f8_quant(w.f8, a.xn1, d, M, d, st));
-            AV_TRY(f8_proj(w.f8, M, d, P.wqkv8, P.sqkv8, qw, a.qkv, qw, P.bqkv, AV_ACT_NONE, nullptr, 0, st));
-        }
+        LlamaLayerAct& a = w.act[l];
+        const LoraView v[4] = {lora_view(m, l, 0, a, w), lora_view(m, l, 1, a, w), lora_view(m, l, 2, a, w), lora_view(m, l, 3, a, w)};
+        AV_TRY(av_rmsnorm_fwd(w.resid[l], P.ln1_w, a.xn1, a.rstd1, M, d, m->eps, dt, st));
+        // fp8: one product for q|k|v (one quantisation of the normed input)
+        if (fq) AV_TRY(linear(dt, fq, false, {nullptr, P.wqkv8, P.sqkv8, P.bqkv}, a.xn1, d, M, d, qw, a.qkv, qw, AV_ACT_NONE, nullptr, 0, st));
         // all three rank-side products t_j = s * dropout_j(xn1) A_j^T in one launch (xn1 read once): csrc/lora_batch.hip
-        const bool batch_qkv = !fp8 && dt == AV_BF16 && P.lora[0].A_pad && P.lora[1].A_pad && P.lora[2].A_pad && (!drop || fuse_drop) &&
+        const bool batch_qkv = !fq && dt == AV_BF16 && P.lora[0].A_pad && P.lora[1].A_pad && P.lora[2].A_pad && (dr.p == 0.f || dr.fused) &&
                                d % 256 == 0 && av_lora_batch_supported(dt, m->lora_r, 3) && !av_knob(AV_KNOB_LORA_UNBATCHED);
         if (batch_qkv) {
             const void* Ap[3] = {a.xn1, a.xn1, a.xn1}; const long la[3] = {d, d, d}; const int Kk[3] = {d, d, d};
             const void* Bp[3] = {P.lora[0].A_pad, P.lora[1].A_pad, P.lora[2].A_pad}; const long lb[3] = {d, d, d};
             void* Cp[3]; long lc[3]; uint32_t sd[3];
-            for (int j = 0; j < 3; ++j) { Cp[j] = (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es; lc[j] = 3 * AVLLM_LORA_PAD; sd[j] = m->dropout_seed + 4u * l + j; }
-            AV_TRY(av_lora_rank3(Ap, la, Kk, Bp, lb, Cp, lc, sd, 3, M, m->lora_r, m->lora_scale, drop ? m->lora_dropout : 0.f, m->dropout_seed_dev, 1, dt, st));
+            for (int j = 0; j < 3; ++j) { Cp[j] = v[j].t; lc[j] = v[j].ldt; sd[j] = v[j].seed; }
+            AV_TRY(av_lora_rank3(Ap, la, Kk, Bp, lb, Cp, lc, sd, 3, M, m->lora_r, m->lora_scale, dr.p, m->dropout_seed_dev, 1, dt, st));
         }
         for (int j = 0; j < 3; ++j) {
-            const void* xl = nullptr;
-            const uint32_t sj = m->dropout_seed + 4u * l + j;
-            if (drop && !fuse_drop && P.lora[j].A_pad) { AV_TRY(av_dropout(a.xn1, w.xd, M, d, sj, m->lora_dropout, dt, st, m->dropout_seed_dev)); xl = w.xd; }
-            if (batch_qkv) {      // the projection with the adapter term as its second K segment; t_j is already there
-                avllm_gemm_desc gp = gemm_desc(dt, a.xn1, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, d,
-                                               (char*)a.qkv + (size_t)llama_off(m, j) * es, qw, M, llama_wid(m, j), d);
-                gp.A2 = (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es; gp.lda2 = 3 * AVLLM_LORA_PAD; gp.B2 = P.lora[j].B_pad; gp.ldb2 = AVLLM_LORA_PAD; gp.K2 = AVLLM_LORA_PAD;
-                gp.bias = llama_bias(m, P, j);
-                AV_TRY(av_gemm(&gp, st));
-                continue;
-            }
-            if (fp8) {
-                AV_TRY(lora_add(m, a.xn1, d, d, llama_wid(m, j), P.lora[j], (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es, 3 * AVLLM_LORA_PAD,
-                                (char*)a.qkv + (size_t)llama_off(m, j) * es, qw, M, st, xl, sj, fuse_drop ? m->lora_dropout : 0.f));
-                continue;
-            }
-            AV_TRY(lora_proj(m, a.xn1, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, d, d, llama_wid(m, j), P.lora[j],
-                             (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es, 3 * AVLLM_LORA_PAD,
-                             (char*)a.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st, xl, sj, fuse_drop ? m->lora_dropout : 0.f,
-                             llama_bias(m, P, j)));
+            const void* xl = a.xn1;
+            if (v[j].mod->A_pad) AV_TRY(lora_input(m, dr, a.xn1, w.xd, M, v[j].seed, xl, st));
+            AV_TRY(lora_linear(m, a.xn1, d, fq ? nullptr : (const char*)P.wqkv + (size_t)v[j].off * d * es, llama_bias(m, P, j), v[j].wid, *v[j].mod,
+                               xl, v[j].seed, dr.fused_p(), v[j].t, v[j].ldt, batch_qkv, (char*)a.qkv + (size_t)v[j].off * es, qw, nullptr, 0, M, st));
         }
         AV_TRY(av_rope_tab(a.qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));      // q and k slices are adjacent: H + Hkv heads
         const char* qkv = (const char*)a.qkv;
         AV_TRY(av_attention_fwd(qkv, qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, a.att, a.lse, B, S, S, H, hd, qw, qw,
                                 qw, d, 1.0f / sqrtf((float)hd), 1, dt, 0, st, Hkv));
-        {
-            const void* xl = nullptr;
-            const uint32_t so = m->dropout_seed + 4u * l + 3;
-            if (drop && !fuse_drop && P.lora[3].A_pad) { AV_TRY(av_dropout(a.att, w.xd, M, d, so, m->lora_dropout, dt, st, m->dropout_seed_dev)); xl = w.xd; }
-            if (fp8) {
-                AV_TRY(f8_quant(w.f8, a.att, d, M, d, st));
-                AV_TRY(f8_proj(w.f8, M, d, P.wo8, P.so8, d, a.h1, d, P.bo, AV_ACT_NONE, resid[l], d, st));
-                AV_TRY(lora_add(m, a.att, d, d, d, P.lora[3], a.to, AVLLM_LORA_PAD, a.h1, d, M, st, xl, so, fuse_drop ? m->lora_dropout : 0.f));
-            } else
-            AV_TRY(lora_proj(m, a.att, d, P.wo, d, d, d, P.lora[3], a.to, AVLLM_LORA_PAD, a.h1, d, resid[l], d, M, st, xl, so,
-                             fuse_drop ? m->lora_dropout : 0.f, P.bo));
-        }
+        const void* xl = a.att;
+        if (v[3].mod->A_pad) AV_TRY(lora_input(m, dr, a.att, w.xd, M, v[3].seed, xl, st));
+        if (fq) AV_TRY(linear(dt, fq, false, {nullptr, P.wo8, P.so8, P.bo}, a.att, d, M, d, d, a.h1, d, AV_ACT_NONE, w.resid[l], d, st));
+        AV_TRY(lora_linear(m, a.att, d, fq ? nullptr : P.wo, P.bo, d, *v[3].mod, xl, v[3].seed, dr.fused_p(), v[3].t, v[3].ldt, false, a.h1, d,
+                           w.resid[l], d, M, st));
         AV_TRY(av_rmsnorm_fwd(a.h1, P.ln2_w, w.xn2, a.rstd2, M, d, m->eps, dt, st));
-        if (fp8) {
-            AV_TRY(f8_quant(w.f8, w.xn2, d, M, d, st));
-            AV_TRY(f8_proj(w.f8, M, d, P.wgu8, P.sgu8, 2 * f, a.gu, 2 * f, nullptr, AV_ACT_NONE, nullptr, 0, st));
-            AV_TRY(av_swiglu_fwd(a.gu, w.hmid, M, f, dt, st));
-            AV_TRY(f8_quant(w.f8, w.hmid, f, M, f, st));
-            AV_TRY(f8_proj(w.f8, M, f, P.wdown8, P.sdown8, d, resid[l + 1], d, nullptr, AV_ACT_NONE, a.h1, d, st));
-            continue;
-        }
-        avllm_gemm_desc g = gemm_desc(dt, w.xn2, d, P.wgu, d, a.gu, 2 * f, M, 2 * f, d);
-        AV_TRY(av_gemm(&g, st));
+        AV_TRY(linear(dt, fq, false, {P.wgu, P.wgu8, P.sgu8, nullptr}, w.xn2, d, M, d, 2 * f, a.gu, 2 * f, AV_ACT_NONE, nullptr, 0, st));
         AV_TRY(av_swiglu_fwd(a.gu, w.hmid, M, f, dt, st));
-        g = gemm_desc(dt, w.hmid, f, P.wdown, f, resid[l + 1], d, M, d, f);
-        g.R = a.h1; g.ldr = d;
-        AV_TRY(av_gemm(&g, st));
+        AV_TRY(linear(dt, fq, false, {P.wdown, P.wdown8, P.sdown8, nullptr}, w.hmid, f, M, f, d, w.resid[l + 1], d, AV_ACT_NONE, a.h1, d, st));
     }
-    AV_TRY(av_rmsnorm_fwd(resid[m->layers], m->norm_w, w.xf, w.rstd_f, M, d, m->eps, dt, st));
-    avllm_gemm_desc g = gemm_desc(dt, w.xf, d, m->lm_head, d, w.logits, m->vocab, M, m->vocab, d);
-    if (fp8) {
-        AV_TRY(f8_quant(w.f8, w.xf, d, M, d, st));
-        AV_TRY(f8_proj(w.f8, M, d, m->lm_head8, m->slm_head8, m->vocab, w.logits, m->vocab, nullptr, AV_ACT_NONE, nullptr, 0, st));
-    } else
-    AV_TRY(av_gemm(&g, st));
+    AV_TRY(av_rmsnorm_fwd(w.resid[m->layers], m->norm_w, w.xf, w.rstd_f, M, d, m->eps, dt, st));
+    AV_TRY(linear(dt, fq, false, {m->lm_head, m->lm_head8, m->slm_head8, nullptr}, w.xf, d, M, d, m->vocab, w.logits, m->vocab, AV_ACT_NONE, nullptr, 0, st));
     if (logits_out) AV_HIP(hipMemcpyAsync(logits_out, w.logits, (size_t)M * m->vocab * es, hipMemcpyDeviceToDevice, st));
     if (labels) AV_TRY(av_ce_fwd(w.logits, m->vocab, labels, B, S, m->vocab, w.row_lse, loss_sum, count, dt, st));
     return AV_OK;
@@ -506,30 +519,27 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
     AV_TRY(check_llama(m));
     AV_CHECK_ARG(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi < m->layers, "llama_lora_bwd_layers: bad layer range [%d, %d]", layer_lo, layer_hi);
     AV_CHECK_ARG(labels && count && ws && m->lm_head_t, "llama_lora_bwd: null (training needs the transposed weight images)");
-    Bump b(ws, ws_bytes);
-    LlamaTrainWs w;
-    void* resid[257]; LlamaLayerAct act[256];
-    carve_llama_train(m, B, S, b, w, resid, act);
-    if (!b.ok) return av_set_error(AV_ERR_WORKSPACE, "llama_lora_bwd: workspace %zu < %zu bytes", ws_bytes, bump_size(b));
+    LlamaTrainFrame fr(m, B, S, ws, ws_bytes);
+    if (!fr.b.ok) return av_set_error(AV_ERR_WORKSPACE, "llama_lora_bwd: workspace %zu < %zu bytes", ws_bytes, bump_size(fr.b));
+    LlamaTrainWs& w = fr.w;
     const int dt = m->dtype, d = m->d, f = m->ffn, H = m->heads, hd = d / H, V = m->vocab;
     const int Hkv = llama_kv_heads(m), dkv = llama_dkv(m), qw = llama_qw(m);
     const size_t es = av_dtype_size(dt);
     const int M = B * S, R = m->lora_r;
-    const float sc = m->lora_scale;
-    const bool drop = m->lora_dropout > 0.f;
-    // bf16 (MFMA kernels): masks are generated inside the rank-side GEMMs; fp32 parity mode materialises dropout(x)
-    const bool fuse_drop = drop && m->dtype == AV_BF16 && d % 256 == 0 && m->lora_r <= 16;
+    const LoraDrop dr = lora_drop(m);      // the forward's rule and seeds: the masks are regenerated, not stored
+    const bool drop = dr.p > 0.f;
     avllm_gemm_desc g;
     if (layer_hi == m->layers - 1) {      // the piece that starts at the top also runs loss -> lm_head -> final norm
         AV_TRY(av_ce_bwd(w.logits, V, labels, w.row_lse, count, grad_scale, w.logits, B, S, V, dt, st));
         g = gemm_desc(dt, w.logits, V, m->lm_head_t, V, w.dxn, d, M, d, V);
         AV_CHECK_ARG(V % 64 == 0, "llama_lora_bwd: vocab %d must be a multiple of 64", V);
         AV_TRY(av_gemm(&g, st));
-        AV_TRY(av_rmsnorm_bwd(w.dxn, resid[m->layers], m->norm_w, w.rstd_f, nullptr, w.dres, M, d, dt, st));
+        AV_TRY(av_rmsnorm_bwd(w.dxn, w.resid[m->layers], m->norm_w, w.rstd_f, nullptr, w.dres, M, d, dt, st));
     }
     for (int l = layer_hi; l >= layer_lo; --l) {
         const avllm_llama_layer& P = m->layer[l];
-        LlamaLayerAct& a = act[l];
+        LlamaLayerAct& a = w.act[l];
+        const LoraView v[4] = {lora_view(m, l, 0, a, w), lora_view(m, l, 1, a, w), lora_view(m, l, 2, a, w), lora_view(m, l, 3, a, w)};
         AV_CHECK_ARG(P.wqkv_t && P.wo_t && P.wgu_t && P.wdown_t, "llama_lora_bwd: layer %d has no transposed weights", l);
         // ---- MLP: resid[l+1] = h1 + down(silu(g)*u)
         g = gemm_desc(dt, w.dres, d, P.wdown_t, d, w.dhmid, f, M, f, d);
@@ -539,32 +549,15 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
         AV_TRY(av_gemm(&g, st));
         AV_TRY(av_rmsnorm_bwd(w.dxn, a.h1, P.ln2_w, a.rstd2, w.dres, w.dres, M, d, dt, st));      // dres = d h1
         // ---- o_proj (+LoRA): h1 = resid[l] + att Wo^T + to Bo^T
-        const avllm_lora_mod& lo = P.lora[3];
+        const avllm_lora_mod& lo = *v[3].mod;
         g = gemm_desc(dt, w.dres, d, P.wo_t, d, w.datt, d, M, d, d);
         if (lo.A_pad) {
-            AV_TRY(av_gemm_tn(w.dres, d, d, a.to, AVLLM_LORA_PAD, R, M, lo.gB, R, 1.0f, dt, st));
-            avllm_gemm_desc gt = gemm_desc(dt, w.dres, d, lo.BT_pad, d, w.dto, AVLLM_LORA_PAD, M, AVLLM_LORA_PAD, d);
-            gt.alpha = sc; gt.n_valid = R;
-            AV_TRY(av_gemm(&gt, st));
-            const void* xin = a.att;
-            if (drop && !fuse_drop) { AV_TRY(av_dropout(a.att, w.xd, M, d, m->dropout_seed + 4u * l + 3, m->lora_dropout, dt, st, m->dropout_seed_dev)); xin = w.xd; }
-            AV_TRY(av_gemm_tn(w.dto, AVLLM_LORA_PAD, R, xin, d, d, M, lo.gA, d, 1.0f, dt, st, m->dropout_seed + 4u * l + 3,
-                              fuse_drop ? m->lora_dropout : 0.f, m->dropout_seed_dev));
-            if (!drop) { g.A2 = w.dto; g.lda2 = AVLLM_LORA_PAD; g.B2 = lo.AT_pad; g.ldb2 = lo.ld_at; g.K2 = AVLLM_LORA_PAD; }
+            AV_TRY(lora_wgrad(m, dr, v[3], w.dres, d, a.att, w.xd, M, st));
+            // without dropout the adapter's input gradient rides in the frozen product as its second K segment
+            if (!drop) { g.A2 = v[3].dt; g.lda2 = v[3].ldt; g.B2 = lo.AT_pad; g.ldb2 = lo.ld_at; g.K2 = AVLLM_LORA_PAD; }
         }
         AV_TRY(av_gemm(&g, st));
-        if (lo.A_pad && drop) {       // d att += mask_o * (dto . A_o) / (1-p): the adapter's input gradient passes back through its dropout
-            const void* Tp[1] = {w.dto}; const void* Ap[1] = {lo.AT_pad};
-            const long lt[1] = {AVLLM_LORA_PAD}, la[1] = {lo.ld_at};
-            const uint32_t sd[1] = {m->dropout_seed + 4u * l + 3};
-            if (fuse_drop && av_lora_dx_masked_supported(dt, d, R, lt, la, 1, d, d)) {
-                AV_TRY(av_lora_dx_masked(Tp, lt, Ap, la, sd, 1, R, w.datt, d, w.datt, d, M, d, m->lora_dropout, m->dropout_seed_dev, dt, st));
-            } else {
-            avllm_gemm_desc gm = gemm_desc(dt, w.dto, AVLLM_LORA_PAD, lo.AT_pad, lo.ld_at, w.datt, d, M, d, AVLLM_LORA_PAD);
-            gm.R = w.datt; gm.ldr = d; gm.drop_seed = m->dropout_seed + 4u * l + 3; gm.drop_p = m->lora_dropout; gm.seed_dev = m->dropout_seed_dev;
-            AV_TRY(av_gemm(&gm, st));
-            }
-        }
+        if (lo.A_pad && drop) AV_TRY(lora_dx_dropped(m, dr, &v[3], 1, w.datt, M, st));
         // ---- attention
         const char* qkv = (const char*)a.qkv;
         char* dqkv = (char*)w.dqkv;
@@ -574,73 +567,35 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
                                 1.0f / sqrtf((float)hd), 1, dt, 0, st, Hkv, fuse_rope ? w.rope_tab : nullptr));
         if (!fuse_rope) AV_TRY(av_rope_tab(dqkv, qw, M, S, H + Hkv, hd, w.rope_tab, 1, dt, st));
         // ---- q,k,v projections (+LoRA)
-        bool any = false, contiguous = true;
-        const bool batch_bwd = dt == AV_BF16 && P.lora[0].A_pad && P.lora[1].A_pad && P.lora[2].A_pad && (!drop || fuse_drop) && d % 256 == 0 &&
+        bool any = false, contiguous = true;      // contiguous: all three present, their AT_pad images the slices of one [d,192] matrix
+        for (int j = 0; j < 3; ++j) { any |= v[j].mod->A_pad != nullptr; contiguous &= v[j].mod->A_pad && v[j].at_slice; }
+        const bool batch_bwd = dt == AV_BF16 && P.lora[0].A_pad && P.lora[1].A_pad && P.lora[2].A_pad && (!drop || dr.fused) && d % 256 == 0 &&
                                dkv % 256 == 0 && av_lora_batch_supported(dt, R, 3) && !av_knob(AV_KNOB_LORA_UNBATCHED);
         if (batch_bwd) {      // three launches for the three adapters' dB, dt and dA (csrc/lora_batch.hip) instead of nine
-            any = true;
-            const void* Tq[3]; long ltq[3]; float* gBp[3]; long lgb[3]; int c0[3], nc[3];
-            const void* dyp[3]; long ldy[3]; int Kd[3]; const void* BTp[3]; long lbt[3]; void* dtp[3]; long ldt3[3];
+            const void* Tq[3]; long ldt3[3]; float* gBp[3]; long lgb[3]; int c0[3], nc[3];
+            const void* dyp[3]; long ldy[3]; const void* BTp[3]; long lbt[3]; void* dtp[3];
             const void* dtc[3]; float* gAp[3]; long lga[3]; uint32_t sd[3];
             for (int j = 0; j < 3; ++j) {
-                const avllm_lora_mod& lj = P.lora[j];
-                Tq[j] = (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es; ltq[j] = 3 * AVLLM_LORA_PAD; gBp[j] = lj.gB; lgb[j] = R;
-                c0[j] = llama_off(m, j); nc[j] = llama_wid(m, j);
-                dyp[j] = dqkv + (size_t)llama_off(m, j) * es; ldy[j] = qw; Kd[j] = llama_wid(m, j); BTp[j] = lj.BT_pad; lbt[j] = llama_wid(m, j);
-                dtp[j] = (char*)w.dtqkv + (size_t)j * AVLLM_LORA_PAD * es; ldt3[j] = 3 * AVLLM_LORA_PAD; dtc[j] = dtp[j];
-                gAp[j] = lj.gA; lga[j] = d; sd[j] = m->dropout_seed + 4u * l + j;
-                if (lj.ld_at != 3 * AVLLM_LORA_PAD ||
-                    (const char*)lj.AT_pad != (const char*)P.lora[0].AT_pad + (size_t)j * AVLLM_LORA_PAD * es) contiguous = false;
+                const avllm_lora_mod& lj = *v[j].mod;
+                Tq[j] = v[j].t; dtp[j] = v[j].dt; dtc[j] = v[j].dt; ldt3[j] = v[j].ldt; sd[j] = v[j].seed;
+                c0[j] = v[j].off; nc[j] = v[j].wid; lbt[j] = v[j].wid;
+                dyp[j] = dqkv + (size_t)v[j].off * es; ldy[j] = qw; BTp[j] = lj.BT_pad;
+                gBp[j] = lj.gB; lgb[j] = R; gAp[j] = lj.gA; lga[j] = d;
             }
-            AV_TRY(av_gemm_tn_multi(dqkv, qw, qw, Tq, ltq, gBp, lgb, c0, nc, nullptr, 3, R, M, 1.0f, 0.f, nullptr, 0, dt, st));          // dB_j = dy_j^T t_j
-            AV_TRY(av_lora_rank3(dyp, ldy, Kd, BTp, lbt, dtp, ldt3, nullptr, 3, M, R, sc, 0.f, nullptr, 0, dt, st));                     // dt_j = s dy_j B_j
-            AV_TRY(av_gemm_tn_multi(a.xn1, d, d, dtc, ldt3, gAp, lga, nullptr, nullptr, sd, 3, R, M, 1.0f, drop ? m->lora_dropout : 0.f,   // dA_j = dt_j^T dropout_j(xn1)
-                                    m->dropout_seed_dev, 1, dt, st));
+            AV_TRY(av_gemm_tn_multi(dqkv, qw, qw, Tq, ldt3, gBp, lgb, c0, nc, nullptr, 3, R, M, 1.0f, 0.f, nullptr, 0, dt, st));           // dB_j = dy_j^T t_j
+            AV_TRY(av_lora_rank3(dyp, ldy, nc, BTp, lbt, dtp, ldt3, nullptr, 3, M, R, m->lora_scale, 0.f, nullptr, 0, dt, st));            // dt_j = s dy_j B_j
+            AV_TRY(av_gemm_tn_multi(a.xn1, d, d, dtc, ldt3, gAp, lga, nullptr, nullptr, sd, 3, R, M, 1.0f, dr.p, m->dropout_seed_dev, 1,   // dA_j = dt_j^T dropout_j(xn1)
+                                    dt, st));
         } else
-        for (int j = 0; j < 3; ++j) {
-            const avllm_lora_mod& lj = P.lora[j];
-            if (!lj.A_pad) { contiguous = false; continue; }
-            any = true;
-            const char* dy = dqkv + (size_t)llama_off(m, j) * es;
-            const int wj = llama_wid(m, j);
-            char* dtj = (char*)w.dtqkv + (size_t)j * AVLLM_LORA_PAD * es;
-            AV_TRY(av_gemm_tn(dy, qw, wj, (char*)a.tqkv + (size_t)j * AVLLM_LORA_PAD * es, 3 * AVLLM_LORA_PAD, R, M, lj.gB, R, 1.0f, dt, st));
-            avllm_gemm_desc gt = gemm_desc(dt, dy, qw, lj.BT_pad, wj, dtj, 3 * AVLLM_LORA_PAD, M, AVLLM_LORA_PAD, wj);
-            gt.alpha = sc; gt.n_valid = R;
-            AV_TRY(av_gemm(&gt, st));
-            const void* xin = a.xn1;
-            if (drop && !fuse_drop) { AV_TRY(av_dropout(a.xn1, w.xd, M, d, m->dropout_seed + 4u * l + j, m->lora_dropout, dt, st, m->dropout_seed_dev)); xin = w.xd; }
-            AV_TRY(av_gemm_tn(dtj, 3 * AVLLM_LORA_PAD, R, xin, d, d, M, lj.gA, d, 1.0f, dt, st, m->dropout_seed + 4u * l + j,
-                              fuse_drop ? m->lora_dropout : 0.f, m->dropout_seed_dev));
-            if (lj.ld_at != 3 * AVLLM_LORA_PAD ||
-                (const char*)lj.AT_pad != (const char*)P.lora[0].AT_pad + (size_t)j * AVLLM_LORA_PAD * es) contiguous = false;
-        }
+        for (int j = 0; j < 3; ++j)
+            if (v[j].mod->A_pad) AV_TRY(lora_wgrad(m, dr, v[j], dqkv + (size_t)v[j].off * es, qw, a.xn1, w.xd, M, st));
         if (l > 0 || dx_embeds) {      // layer 0: d(inputs_embeds) only when the caller trains the connectors (frozen otherwise: SURVEY.md fact 4)
             AV_CHECK_ARG(!any || contiguous || drop, "llama_lora_bwd: q/k/v AT_pad images must be the three 64-column slices of one [d,192] matrix");
             g = gemm_desc(dt, w.dqkv, qw, P.wqkv_t, qw, w.dxn, d, M, d, qw);
             if (any && !drop) { g.A2 = w.dtqkv; g.lda2 = 3 * AVLLM_LORA_PAD; g.B2 = P.lora[0].AT_pad; g.ldb2 = 3 * AVLLM_LORA_PAD; g.K2 = 3 * AVLLM_LORA_PAD; }
             AV_TRY(av_gemm(&g, st));
-            if (any && drop) {
-                // all three adapters' input gradients in one pass over dX when the fused kernel applies (csrc/lora_dx.hip)
-                const void* Tp[3]; const void* Ap[3]; long lt[3], la[3]; uint32_t sd[3]; int nj = 0;
-                for (int j = 0; j < 3; ++j) {
-                    if (!P.lora[j].A_pad) continue;
-                    Tp[nj] = (char*)w.dtqkv + (size_t)j * AVLLM_LORA_PAD * es; lt[nj] = 3 * AVLLM_LORA_PAD;
-                    Ap[nj] = P.lora[j].AT_pad; la[nj] = P.lora[j].ld_at; sd[nj] = m->dropout_seed + 4u * l + j; ++nj;
-                }
-                if (fuse_drop && av_lora_dx_masked_supported(dt, d, R, lt, la, nj, d, d)) {
-                    AV_TRY(av_lora_dx_masked(Tp, lt, Ap, la, sd, nj, R, w.dxn, d, w.dxn, d, M, d, m->lora_dropout, m->dropout_seed_dev, dt, st));
-                } else
-                for (int j = 0; j < 3; ++j) {
-                    const avllm_lora_mod& lj = P.lora[j];
-                    if (!lj.A_pad) continue;
-                    avllm_gemm_desc gm = gemm_desc(dt, (char*)w.dtqkv + (size_t)j * AVLLM_LORA_PAD * es, 3 * AVLLM_LORA_PAD, lj.AT_pad, lj.ld_at,
-                                                   w.dxn, d, M, d, AVLLM_LORA_PAD);
-                    gm.R = w.dxn; gm.ldr = d; gm.drop_seed = m->dropout_seed + 4u * l + j; gm.drop_p = m->lora_dropout; gm.seed_dev = m->dropout_seed_dev;
-                    AV_TRY(av_gemm(&gm, st));
-                }
-            }
-            AV_TRY(av_rmsnorm_bwd(w.dxn, resid[l], P.ln1_w, a.rstd1, w.dres, l > 0 ? w.dres : dx_embeds, M, d, dt, st));      // layer 0: d resid[0]
+            if (any && drop) AV_TRY(lora_dx_dropped(m, dr, v, 3, w.dxn, M, st));
+            AV_TRY(av_rmsnorm_bwd(w.dxn, w.resid[l], P.ln1_w, a.rstd1, w.dres, l > 0 ? w.dres : dx_embeds, M, d, dt, st));      // layer 0: d resid[0]
         }
         if (after_layer) after_layer(l, user);
     }
@@ -680,8 +635,8 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
         AV_TRY(av_gemm(&gq, st));
     } else
     for (int j = 0; j < 3; ++j)
-        AV_TRY(lora_proj(m, w.xn, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, d, d, llama_wid(m, j), P.lora[j], w.t, AVLLM_LORA_PAD,
-                         (char*)w.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st, nullptr, 0, 0.f, llama_bias(m, P, j)));
+        AV_TRY(lora_linear(m, w.xn, d, (const char*)P.wqkv + (size_t)llama_off(m, j) * d * es, llama_bias(m, P, j), llama_wid(m, j), P.lora[j], w.xn, 0, 0.f,
+                           w.t, AVLLM_LORA_PAD, false, (char*)w.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st));
     char* qkv = (char*)w.qkv;
     if (l == 0) AV_TRY(av_rope_table(w.rope_tab, S, hd, pos0, m->theta, st, nullptr, llama_rope_scale(m)));
     AV_TRY(av_rope_tab(qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));
@@ -694,7 +649,7 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
         AV_TRY(av_attention_fwd(qkv, qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, w.att, nullptr, B, S, S, H, hd, qw, qw, qw,
                                 d, scale, 1, dt, 0, st, Hkv));
     }
-    AV_TRY(lora_proj(m, w.att, d, P.wo, d, d, d, P.lora[3], w.t, AVLLM_LORA_PAD, w.x, d, w.x, d, M, st, nullptr, 0, 0.f, P.bo));
+    AV_TRY(lora_linear(m, w.att, d, P.wo, P.bo, d, P.lora[3], w.att, 0, 0.f, w.t, AVLLM_LORA_PAD, false, w.x, d, w.x, d, M, st));
     AV_TRY(av_rmsnorm_fwd(w.x, P.ln2_w, w.xn, nullptr, M, d, m->eps, dt, st));
     avllm_gemm_desc g = gemm_desc(dt, w.xn, d, P.wgu, d, w.gu, 2 * f, M, 2 * f, d);
     AV_TRY(av_gemm(&g, st));
@@ -760,7 +715,7 @@ static bool llama_decode_fused_ok(const avllm_llama* m, int B) {
         !av_dec_proj_supported(AV_BF16, B, m->ffn, m->d, 0, hd) || !av_dec_proj_supported(AV_BF16, B, m->d, m->d, 0, hd)) return false;
     bool any;
     for (int l = 0; l < m->layers; ++l)
-        if (!llama_decode_lora_ok(m, m->layer[l], any)) return false;      // adapters the epilogue form does not cover: the general path (lora_proj)
+        if (!llama_decode_lora_ok(m, m->layer[l], any)) return false;      // adapters the epilogue form does not cover: the general path (lora_linear)
     return true;
 }
 
