@@ -4,7 +4,7 @@
 // one per SIMD, each owns a 128x128 quadrant (256 accumulator AGPRs); operands travel global -> LDS by global_load_lds_dwordx4 into two
 // 64-KiB stage buffers (256 A rows + 256 B rows of 128 BYTES = one K-step of 128 fp8 elements: byte for byte the bf16 kernel's K-step,
 // at twice the K); the pipeline never drains between tiles; the epilogue stores 16-byte bf16 chunks straight from the accumulators
-// (column-interleaved weight fragments, gemm.hip WP_BOFF).
+// (column-interleaved weight fragments, gemm_shared.h WP_BOFF and acc_store_*).
 //
 // What differs: one v_mfma_scale_f32_16x16x128_f8f6f4 consumes a whole 128-element row slice of each operand (8 VGPRs = the 16-byte chunks
 // fq and 4 + fq of the lane's row, two ds_read_b128 -- the same two chunks the bf16 kernel reads as its k-halves), so a K-step is 64 MFMAs of 32 cycles instead of 128 of 16, and a fragment cannot be
@@ -26,7 +26,7 @@
 
 namespace {
 
-using avg::epilogue_fast8; using avg::xcd_remap; using avg::tile_coords;
+using avg::xcd_remap; using avg::tile_coords;
 __device__ __forceinline__ int f8_groups_dev(int R) { return (R + 255) / 256 * 4; }
 
 typedef __attribute__((ext_vector_type(8))) int v8i;
@@ -44,9 +44,6 @@ struct F8Args {
     uint8_t* Cq; uint32_t* SCq; long ldcq;                             // quantised output (see include/avllm.h)
 };
 
-#define F8_BOFF(j) ((((j) >> 1) * 32 + ((j) & 1) * 4) * 128)
-#define F8_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define F8_LD(voff, base, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(m0v), "v"(voff), "s"(base) : "memory")
 #define F8_LDS32(dst, voff, base) asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base) : "memory")
 
 // opsel of the weight-side scale (first MFMA operand) = J & 3, of the activation-side scale = I & 3
@@ -76,14 +73,10 @@ __device__ __forceinline__ void f8_mfma(f32x4& acc, const v8i fb, const v8i fa, 
 
 struct F8Frag { v4i lo, hi; };
 
-template <int I, int N, class F> __device__ __forceinline__ void f8_static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); f8_static_for<I + 1, N>(f); }
-}
-
 // Slot N of a K-step.  ONE instantiation serves every K-step of every tile (the tile boundary is a cold block inside the K-step loop: a
 // separate copy of this 64-MFMA body for "first K-step of a tile" made the register allocator permute the 128 fragment registers through
-// scratch at every tile boundary).  `relaxed`: this is the first K-step after a full epilogue, whose stores may stay in flight (gemm.hip
-// wpgemm_step MODE 2).  ad[] = this lane's fragment addresses in the OTHER buffer (next K-step): A lo / A hi /
+// scratch at every tile boundary).  `relaxed`: this is the first K-step after a full epilogue, whose stores may stay in flight (gemm_shared.h
+// wgemm_step MODE 2).  ad[] = this lane's fragment addresses in the OTHER buffer (next K-step): A lo / A hi /
 // B lo / B hi (the two 16-byte halves of a lane's 32 bytes are swizzled apart, hence two bases per operand).
 template <int N>
 __device__ __forceinline__ void f8_step(f32x4 (&acc)[8][8], F8Frag (&FA)[8], F8Frag (&FB)[8], int (&sCur)[4], int (&sNext)[4],
@@ -109,14 +102,14 @@ __device__ __forceinline__ void f8_step(f32x4 (&acc)[8][8], F8Frag (&FA)[8], F8F
     }
     if constexpr (N >= 16 && N < 48 && !(N & 1)) {            // DMA of K-step t+2 into the CURRENT buffer: 8 A loads, then 8 B loads
         constexpr int k = (N - 16) >> 1;
-        if constexpr (k < 8) F8_LD(vA[k], pA, m0A + k * 1024); else F8_LD(vB[k - 8], pB, m0B + (k - 8) * 1024);
+        if constexpr (k < 8) AV_W_LD(vA[k], pA, m0A + k * 1024); else AV_W_LD(vB[k - 8], pB, m0B + (k - 8) * 1024);
     }
     // ---- fragment reloads for the next K-step, in place: weight fragment j after its column (slots 8j+9, 8j+10), activation fragment i after
     // its two last products (slots 50+2i, 51+2i)
-    if constexpr (N >= 9 && N < 50 && ((N - 9) & 7) == 0) { constexpr int j = (N - 9) >> 3; F8_RD(FB[j].lo, ad[2], F8_BOFF(j)); }
-    if constexpr (N >= 10 && N < 51 && ((N - 10) & 7) == 0) { constexpr int j = (N - 10) >> 3; F8_RD(FB[j].hi, ad[3], F8_BOFF(j)); }
-    if constexpr (N >= 50 && !(N & 1)) { constexpr int i = (N - 50) >> 1; F8_RD(FA[i].lo, ad[0], i * 2048); }
-    if constexpr (N >= 51 && (N & 1)) { constexpr int i = (N - 51) >> 1; F8_RD(FA[i].hi, ad[1], i * 2048); }
+    if constexpr (N >= 9 && N < 50 && ((N - 9) & 7) == 0) { constexpr int j = (N - 9) >> 3; AV_W_RD(FB[j].lo, ad[2], WP_BOFF(j, 128)); }
+    if constexpr (N >= 10 && N < 51 && ((N - 10) & 7) == 0) { constexpr int j = (N - 10) >> 3; AV_W_RD(FB[j].hi, ad[3], WP_BOFF(j, 128)); }
+    if constexpr (N >= 50 && !(N & 1)) { constexpr int i = (N - 50) >> 1; AV_W_RD(FA[i].lo, ad[0], i * 2048); }
+    if constexpr (N >= 51 && (N & 1)) { constexpr int i = (N - 51) >> 1; AV_W_RD(FA[i].hi, ad[1], i * 2048); }
 }
 
 template <int... Ns>
@@ -126,9 +119,9 @@ __device__ __forceinline__ void f8_kstep(std::integer_sequence<int, Ns...>, f32x
                                          const uint32_t* pSB, bool relaxed) {
     (f8_step<Ns>(acc, FA, FB, sCur, sNext, sN2, ad, vA, vB, pA, pB, m0A, m0B, vS, pSA, pSB, relaxed), ...);
     // the reads that could not be placed: FA[7] (died at slot 63), FB[6] (62), FB[7] (63)
-    F8_RD(FA[7].lo, ad[0], 7 * 2048); F8_RD(FA[7].hi, ad[1], 7 * 2048);
-    F8_RD(FB[6].lo, ad[2], F8_BOFF(6)); F8_RD(FB[6].hi, ad[3], F8_BOFF(6));
-    F8_RD(FB[7].lo, ad[2], F8_BOFF(7)); F8_RD(FB[7].hi, ad[3], F8_BOFF(7));
+    AV_W_RD(FA[7].lo, ad[0], 7 * 2048); AV_W_RD(FA[7].hi, ad[1], 7 * 2048);
+    AV_W_RD(FB[6].lo, ad[2], WP_BOFF(6, 128)); AV_W_RD(FB[6].hi, ad[3], WP_BOFF(6, 128));
+    AV_W_RD(FB[7].lo, ad[2], WP_BOFF(7, 128)); AV_W_RD(FB[7].hi, ad[3], WP_BOFF(7, 128));
 #pragma unroll
     for (int k = 0; k < 4; ++k) sCur[k] = sNext[k];
     asm volatile("s_nop 1" ::: "memory");
@@ -198,8 +191,8 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
         else { F8_LDS32(sN2[0], vS[0], psa); F8_LDS32(sN2[1], vS[1], psa); F8_LDS32(sN2[2], vS[2], psb); F8_LDS32(sN2[3], vS[3], psb); }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            F8_LD(vA1[q], pa, mw + s * STAGE + q * 1024);
-            F8_LD(vB1[q], pb, mw + s * STAGE + TM * 128 + q * 1024);
+            AV_W_LD(vA1[q], pa, mw + s * STAGE + q * 1024);
+            AV_W_LD(vB1[q], pb, mw + s * STAGE + TM * 128 + q * 1024);
         }
         advance();
     }
@@ -207,8 +200,8 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
     F8Frag FA[8], FB[8];                                             // a lane's 32 operand bytes as the two 16-byte halves it reads
     asm volatile("s_waitcnt vmcnt(20)" ::: "memory");               // K-step 0 (and its scale words) have landed; K-step 1's 20 loads may be in flight
     __builtin_amdgcn_s_barrier();
-#define F8_PRO_A(I) F8_RD(FA[I].lo, base[0], (I) * 2048); F8_RD(FA[I].hi, base[1], (I) * 2048)
-#define F8_PRO_B(J) F8_RD(FB[J].lo, base[2], F8_BOFF(J)); F8_RD(FB[J].hi, base[3], F8_BOFF(J))
+#define F8_PRO_A(I) AV_W_RD(FA[I].lo, base[0], (I) * 2048); AV_W_RD(FA[I].hi, base[1], (I) * 2048)
+#define F8_PRO_B(J) AV_W_RD(FB[J].lo, base[2], WP_BOFF(J, 128)); AV_W_RD(FB[J].hi, base[3], WP_BOFF(J, 128))
     F8_PRO_B(0); F8_PRO_B(1); F8_PRO_B(2); F8_PRO_B(3); F8_PRO_B(4); F8_PRO_B(5); F8_PRO_B(6); F8_PRO_B(7);
     F8_PRO_A(0); F8_PRO_A(1); F8_PRO_A(2); F8_PRO_A(3); F8_PRO_A(4); F8_PRO_A(5); F8_PRO_A(6); F8_PRO_A(7);
 #undef F8_PRO_A
@@ -241,9 +234,8 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
         // ---- tile boundary.  Result latency of the last MFMAs (invisible to the compiler's hazard recogniser): nops, and every accumulator
         // named as an in/out operand so that compiler-generated readers stay behind them
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-#define F8_PIN8(I) asm volatile("" : "+a"(acc[I][0]), "+a"(acc[I][1]), "+a"(acc[I][2]), "+a"(acc[I][3]), "+a"(acc[I][4]), "+a"(acc[I][5]), "+a"(acc[I][6]), "+a"(acc[I][7]))
-        F8_PIN8(0); F8_PIN8(1); F8_PIN8(2); F8_PIN8(3); F8_PIN8(4); F8_PIN8(5); F8_PIN8(6); F8_PIN8(7);
-        // epilogue straight from the accumulators (as gemm_bf16_wp_kernel): lane (fr, fq), row block i, column pair p -> 8 consecutive columns
+        AV_W_PIN8(0); AV_W_PIN8(1); AV_W_PIN8(2); AV_W_PIN8(3); AV_W_PIN8(4); AV_W_PIN8(5); AV_W_PIN8(6); AV_W_PIN8(7);
+        // epilogue straight from the accumulators (avg::acc_store_general / _full / _full_res): lane (fr, fq), row block i, column pair p -> 8 consecutive columns
         int tm, tn;
         tile_coords(xcd_remap(vid, ntiles), tiles_m, tiles_n, tm, tn);
         const int m0 = tm * TM + wr * 128 + fr, n = tn * TN + wc * 128 + fq * 8;
@@ -258,22 +250,6 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
         bf16* const cp0 = (bf16*)g.C + (long)m0 * g.ldc + n;
         const bf16* const rp0 = g.R ? (const bf16*)g.R + (long)m0 * g.ldr + n : nullptr;
         const long ldc = g.ldc, ldr = g.R ? g.ldr : 0;
-        auto run = [&](auto actc) __attribute__((always_inline)) {
-            constexpr int ACT = decltype(actc)::value;
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                const bool mrow = m0 + i * 16 < g.M;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 4; ++p) {
-                    // the accumulators are "redefined" here for the compiler: otherwise every epilogue variant's 256 accumulator reads are hoisted above
-                    // the variant branch as common subexpressions (256 live registers: 57 spilled VGPRs, 460 scratch accesses around the epilogue)
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    if (mrow && n + 32 * p < g.N && !(g.dbg & 1))
-                        epilogue_fast8<ACT>(acc[i][2 * p], acc[i][2 * p + 1], b[p], g.bias != nullptr, rp0 ? rp0 + (i * 16) * ldr + 32 * p : nullptr,
-                                            cp0 + (i * 16) * ldc + 32 * p);
-                }
-            }
-        };
         // Quantised output: act(acc + bias) -> e4m3 + one E8M0 per 32 columns, from the fp32 values (the separate quantiser pass over a bf16
         // copy costs a read of 2 and a write of 1 byte per element: 53 ms of a 541 ms config-5 step for the ViT-L fc1 outputs alone).
         // A 32-column block of a row lives in the 4 lanes fq = 0..3 of one fr: amax through two cross-row shuffles.  Scale image (layout 0):
@@ -281,16 +257,16 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
         // CONSUMER (128 columns): this lane's row blocks i = 4 a + i' fill whole words; lane fq writes the words of block p == fq.
         auto run_q = [&](auto actc) __attribute__((always_inline)) {
             constexpr int ACT = decltype(actc)::value;
-            // the eight scale words of the lane as named scalars, updated through compile-time indices (f8_static_for): as an array indexed by
+            // the eight scale words of the lane as named scalars, updated through compile-time indices (avg::static_for): as an array indexed by
             // the unrolled loop variables they stayed in scratch memory -- a scratch load + vmcnt(0) + scratch store behind every chunk's
             // global store, i.e. one store acknowledgement of latency per chunk
             uint32_t sw00 = 0u, sw01 = 0u, sw02 = 0u, sw03 = 0u, sw10 = 0u, sw11 = 0u, sw12 = 0u, sw13 = 0u;
             uint8_t* const qp0 = g.Cq + (long)m0 * g.ldcq + n;
             const long ldcq = g.ldcq;
-            f8_static_for<0, 8>([&](auto ic) __attribute__((always_inline)) {
+            avg::static_for<0, 8>([&](auto ic) __attribute__((always_inline)) {
                 constexpr int i = decltype(ic)::value;
                 const bool mrow = m0 + i * 16 < g.M;
-                f8_static_for<0, 4>([&](auto pc) __attribute__((always_inline)) {
+                avg::static_for<0, 4>([&](auto pc) __attribute__((always_inline)) {
                     constexpr int p = decltype(pc)::value;
                     asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
                     const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
@@ -337,75 +313,15 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
             if (col_ok && rb0 < RBo) g.SCq[(((long)t * RBo + rb0) * 4 + fq) * 16 + fr] = wv0;
             if (col_ok && rb0 + 1 < RBo) g.SCq[(((long)t * RBo + rb0 + 1) * 4 + fq) * 16 + fr] = wv1;
         };
-        // full tile, bf16 output: the lean forms of gemm_bf16_wp_kernel (no bounds test, no select, no branch per chunk; with a residual, all 32
-        // residual chunks of the lane requested in one burst into registers that are dead here and consumed behind ONE constant wait count:
-        // 31 - c younger loads + c stores behind chunk c's load)
+        // bf16 output: the forms of gemm_shared.h, with one row block of residual chunks ahead of the stores (this kernel carries the next tile's
+        // 128 fragment registers through the epilogue, so the whole-tile burst of the bf16 kernel does not fit)
         const bool full = relaxed;
-        auto run_full = [&](auto actc, auto hasbc) __attribute__((always_inline)) {
-            constexpr int ACT = decltype(actc)::value;
-            constexpr bool HASB = decltype(hasbc)::value;
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                bf16* const cpi = cp0 + (long)(i * 16) * ldc;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 4; ++p) {
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
-                    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (HASB) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] += b[p][c];
-                    }
-                    if constexpr (ACT != AV_ACT_NONE) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] = act_apply_fast(v[c], ACT);
-                    }
-                    store_f<8>(cpi + 32 * p, v);
-                }
-            }
-        };
-        auto run_res_full = [&](auto hasbc) __attribute__((always_inline)) {
-            constexpr bool HASB = decltype(hasbc)::value;
-            // one row block of residual chunks ahead of the stores (this kernel carries the next tile's 128 fragment registers through the
-            // epilogue, so the whole-tile burst of the bf16 kernel does not fit): asm loads + hand-counted waits, see gemm.hip
-            constexpr int RD = 1;
-            typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_;
-            u32x4_ rr[RD + 1][4];
-            auto fetch = [&](int i) __attribute__((always_inline)) {
-                const bf16* rp = rp0 + (long)(i * 16) * ldr;
-                asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:64\n\t"
-                             "global_load_dwordx4 %2, %4, off offset:128\n\tglobal_load_dwordx4 %3, %4, off offset:192"
-                             : "=&v"(rr[i % (RD + 1)][0]), "=&v"(rr[i % (RD + 1)][1]), "=&v"(rr[i % (RD + 1)][2]), "=&v"(rr[i % (RD + 1)][3]) : "v"(rp) : "memory");
-            };
-            fetch(0);
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                if (i + RD < 8) fetch(i + RD);
-                bf16* const cpi = cp0 + (long)(i * 16) * ldc;
-                const int nw = 3 + 4 * (RD < 7 - i ? RD : 7 - i) + 4 * (RD < i ? RD : i);
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 4; ++p) {
-                    u32x4_& x = rr[i % (RD + 1)][p];
-                    if (nw == 7) asm volatile("s_waitcnt vmcnt(7)" : "+v"(x) :: "memory");
-                    else if (nw == 11) asm volatile("s_waitcnt vmcnt(11)" : "+v"(x) :: "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(x) :: "memory");
-                    const bf16x8 r = __builtin_bit_cast(bf16x8, x);
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
-                    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (HASB) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] += b[p][c];
-                    }
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) v[c] += (float)r[c];
-                    store_f<8>(cpi + 32 * p, v);
-                }
-            }
-        };
+        const bool hb = g.bias != nullptr;
+        auto run = [&](auto actc) __attribute__((always_inline)) { avg::acc_store_general<4, decltype(actc)::value>(acc, b, hb, cp0, rp0, ldc, ldr, m0, n, g.M, g.N, g.dbg); };
+        auto run_full = [&](auto actc, auto hasbc) __attribute__((always_inline)) { avg::acc_store_full<4, decltype(actc)::value, decltype(hasbc)::value>(acc, b, cp0, ldc); };
+        auto run_res_full = [&](auto hasbc) __attribute__((always_inline)) { avg::acc_store_full_res<4, 1, decltype(hasbc)::value>(acc, b, cp0, rp0, ldc, ldr); };
         const std::true_type yes{};
         const std::false_type no{};
-        const bool hb = g.bias != nullptr;
         if (g.Cq) {
             if (g.act == AV_ACT_NONE) run_q(std::integral_constant<int, AV_ACT_NONE>{});
             else if (g.act == AV_ACT_GELU) run_q(std::integral_constant<int, AV_ACT_GELU>{});
@@ -428,8 +344,8 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
         {
             const int dx = bo ? STAGE : -STAGE;                       // ad[] already points at the other buffer: undo the last swap
             const int a0 = ad[0] + dx, a1 = ad[1] + dx, b0 = ad[2] + dx, b1 = ad[3] + dx;
-#define F8_RE_A(I) F8_RD(FA[I].lo, a0, (I) * 2048); F8_RD(FA[I].hi, a1, (I) * 2048)
-#define F8_RE_B(J) F8_RD(FB[J].lo, b0, F8_BOFF(J)); F8_RD(FB[J].hi, b1, F8_BOFF(J))
+#define F8_RE_A(I) AV_W_RD(FA[I].lo, a0, (I) * 2048); AV_W_RD(FA[I].hi, a1, (I) * 2048)
+#define F8_RE_B(J) AV_W_RD(FB[J].lo, b0, WP_BOFF(J, 128)); AV_W_RD(FB[J].hi, b1, WP_BOFF(J, 128))
             F8_RE_B(0); F8_RE_B(1); F8_RE_B(2); F8_RE_B(3); F8_RE_B(4); F8_RE_B(5); F8_RE_B(6); F8_RE_B(7);
             F8_RE_A(0); F8_RE_A(1); F8_RE_A(2); F8_RE_A(3); F8_RE_A(4); F8_RE_A(5); F8_RE_A(6); F8_RE_A(7);
 #undef F8_RE_A
@@ -441,8 +357,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        F8_PIN8(0); F8_PIN8(1); F8_PIN8(2); F8_PIN8(3); F8_PIN8(4); F8_PIN8(5); F8_PIN8(6); F8_PIN8(7);
-#undef F8_PIN8
+        AV_W_PIN8(0); AV_W_PIN8(1); AV_W_PIN8(2); AV_W_PIN8(3); AV_W_PIN8(4); AV_W_PIN8(5); AV_W_PIN8(6); AV_W_PIN8(7);
         vid += G;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // in-flight DMA writes / reads must not outlive the workgroup's LDS allocation

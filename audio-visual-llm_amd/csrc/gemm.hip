@@ -101,12 +101,7 @@ __device__ __forceinline__ void epilogue_store8(const EpiParams& e, int m, int n
     else store_f<8>((bf16*)e.C + orow * e.ldc + n0, v);
 }
 
-using avg::epilogue_fast8; using avg::xcd_remap; using avg::tile_coords;
-
-// cache-policy bits of the operand DMA of the 4-wave kernels (experiment: tools/gemm_dma_policy.sh builds one library per policy); default none
-#ifndef AVLLM_DMA_POLICY
-#define AVLLM_DMA_POLICY ""
-#endif
+using avg::epilogue_fast8; using avg::xcd_remap; using avg::tile_coords; using avg::stage_rows8; using avg::wave_tile_64x64;
 
 // ------------------------------------------------------------------------------------------ bf16
 constexpr int BM = 128, BN = 128, BK = 64;
@@ -121,23 +116,6 @@ struct GemmArgs {
     int dbg;             // experiment knobs of the persistent kernel (env AVLLM_GEMM_DBG): bit 0 = no epilogue stores, bit 1 = strict first-K-step wait, bit 2 = row-major tile order instead of 8 x 4 blocks, bit 3 = per-XCD contiguous id ranges instead of one block per XCD and round, bits 4.. = start-stagger phases (1 = off)
     EpiParams e;
 };
-
-__device__ __forceinline__ void stage_tile(const bf16* __restrict__ base, long ld, int row0, int rows_max,
-                                           int k0, char* lds, int wave, int lane) {
-    // one wave-instruction = 8 rows x 128 B.  4 waves x 4 passes = 128 rows.
-    const int rsub = lane >> 3;                       // row inside the 8-row group == (row & 7)
-    const int chunk_src = (lane & 7) ^ rsub;          // inverse swizzle on the source
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int r = p * 32 + wave * 8 + rsub;
-        int gr = row0 + r;
-        gr = gr < rows_max ? gr : rows_max - 1;       // clamp: rows past the edge are never stored
-        const bf16* src = base + (long)gr * ld + k0 + chunk_src * 8;
-        char* dst = lds + (p * 32 + wave * 8) * 128;  // wave-uniform base; hardware adds lane*16
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    }
-}
 
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages x (A tile + B tile) = 64 KiB
@@ -158,13 +136,14 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
     auto stage = [&](int t, int buf) {
         char* a_lds = smem + buf * (2 * TILE_BYTES);
         char* b_lds = a_lds + TILE_BYTES;
-        if (t < nt1) {
-            stage_tile(g.A, g.lda, m0, g.e.M, t * BK, a_lds, wave, lane);
-            stage_tile(g.B, g.ldb, n0, g.e.N, t * BK, b_lds, wave, lane);
-        } else {
-            stage_tile(g.A2, g.lda2, m0, g.e.M, (t - nt1) * BK, a_lds, wave, lane);
-            stage_tile(g.B2, g.ldb2, n0, g.e.N, (t - nt1) * BK, b_lds, wave, lane);
-        }
+        auto rows = [&](const bf16* Ap, long la, const bf16* Bp, long lb, int k0) {      // 4 waves x 4 passes = 128 rows of each operand
+#pragma unroll
+            for (int p = 0; p < 4; ++p) stage_rows8(Ap, la, m0, g.e.M, k0, a_lds, p * 4 + wave, lane);
+#pragma unroll
+            for (int p = 0; p < 4; ++p) stage_rows8(Bp, lb, n0, g.e.N, k0, b_lds, p * 4 + wave, lane);
+        };
+        if (t < nt1) rows(g.A, g.lda, g.B, g.ldb, t * BK);
+        else rows(g.A2, g.lda2, g.B2, g.ldb2, (t - nt1) * BK);
     };
 
     stage(0, 0);
@@ -175,26 +154,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
         if (t + 1 < nt) stage(t + 1, cur ^ 1);
         const char* a_lds = smem + cur * (2 * TILE_BYTES);
         const char* b_lds = a_lds + TILE_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xa[4], wb[4];
-            const int chunk = ks * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = wm * 64 + i * 16 + fr;
-                xa[i] = *(const bf16x8*)(a_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = wn * 64 + j * 16 + fr;
-                wb[j] = *(const bf16x8*)(b_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-        }
+        wave_tile_64x64(acc, a_lds, b_lds, wm, wn, fr, fq);
         __syncthreads();
     }
     // acc[i][j][reg]: output row m = m0 + wm*64 + i*16 + (lane&15); column n = n0 + wn*64 + j*16 + (lane>>4)*4 + reg
@@ -216,17 +176,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs g) {
 constexpr int LBM = 256, LBN = 128;
 constexpr int LSTAGE = (LBM + LBN) * BK * 2;      // 48 KiB
 constexpr int LNSTAGE = 3;
-
-__device__ __forceinline__ void stage_rows8(const bf16* __restrict__ base, long ld, int row0, int rows_max, int k0, char* lds,
-                                            int group, int lane) {
-    // one wave-instruction: 8 rows x 128 B at LDS rows [group*8, group*8+8)
-    const int rsub = lane >> 3;
-    int gr = row0 + group * 8 + rsub;
-    gr = gr < rows_max ? gr : rows_max - 1;
-    const bf16* src = base + (long)gr * ld + k0 + (((lane & 7) ^ rsub) << 3);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(lds + group * 1024), 16, 0, 0);
-}
 
 __global__ __launch_bounds__(512, 2) void gemm_bf16_l_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -267,26 +216,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_l_kernel(GemmArgs g) {
         if (t + 2 < nt) stage(t + 2, buf >= 1 ? buf - 1 : LNSTAGE - 1);      // (t+2) % 3 == (buf+2) % 3
         const char* a_lds = smem + buf * LSTAGE;
         const char* b_lds = a_lds + LBM * BK * 2;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xa[4], wb[4];
-            const int chunk = ks * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = wm * 64 + i * 16 + fr;
-                xa[i] = *(const bf16x8*)(a_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = wn * 64 + j * 16 + fr;
-                wb[j] = *(const bf16x8*)(b_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-        }
+        wave_tile_64x64(acc, a_lds, b_lds, wm, wn, fr, fq);
         buf = buf + 1 == LNSTAGE ? 0 : buf + 1;
     }
 #pragma unroll
@@ -361,26 +291,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_bf16_h_kernel(GemmArgs g) {
         if (t + 1 < nt) stage(t + 1, cur ^ 1);
         const char* a_lds = smem + cur * HSTAGE;
         const char* b_lds = a_lds + HBM_ * BK * 2;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xa[4], wb[4];
-            const int chunk = ks * 4 + fq;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = wm * 64 + i * 16 + fr;
-                xa[i] = *(const bf16x8*)(a_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = wn * 64 + j * 16 + fr;
-                wb[j] = *(const bf16x8*)(b_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-        }
+        wave_tile_64x64(acc, a_lds, b_lds, wm, wn, fr, fq);
         __syncthreads();
     }
     if (g.wide_epi) {
@@ -421,10 +332,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_bf16_h_kernel(GemmArgs g) {
                     __syncthreads();
                 }
             };
-            if (g.e.act == AV_ACT_NONE) run(std::integral_constant<int, AV_ACT_NONE>{});
-            else if (g.e.act == AV_ACT_GELU) run(std::integral_constant<int, AV_ACT_GELU>{});
-            else if (g.e.act == AV_ACT_QUICK_GELU) run(std::integral_constant<int, AV_ACT_QUICK_GELU>{});
-            else run(std::integral_constant<int, AV_ACT_SILU>{});
+            avg::with_act(g.e.act, run);
             return;
         }
 #pragma unroll
@@ -476,39 +384,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_bf16_h_kernel(GemmArgs g) {
 // barriers and three full lgkmcnt waits per 128 MFMAs, every ds_read issued >= 10 MFMAs before its wait, loads one per 2-3
 // MFMAs with SGPR base + 32-bit tile-relative VGPR offsets (no 64-bit address arithmetic, no operand-size limit).
 // tools/ubench/gemm_pingpong.hip g4h: 1.25-1.40 PF/s at 4096x4096x11008 against 1.15-1.17 for the 16-wave kernel in the same run.
-template <int N, int BUF>
-__device__ __forceinline__ void wgemm_step(f32x4 (&acc)[8][8], bf16x8 (&FA)[2][8], bf16x8 (&FB)[2][8], const int (&la)[2][2], const int (&lb)[2][2],
-                                           const unsigned (&vA)[8], const unsigned (&vB)[8], const bf16* pA, const bf16* pB, int m0A, int m0B) {
-    constexpr int h = N >> 6, n = N & 63, I = n >> 3, J = n & 7;
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[I][J]) : "v"(FB[h][J]), "v"(FA[h][I]));
-#define AV_W_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define AV_W_LD(voff, base, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" AVLLM_DMA_POLICY :: "s"(m0v), "v"(voff), "s"(base) : "memory")
-    if constexpr (h == 0) {
-        if constexpr (n < 16 && (n & 1)) AV_W_RD(FB[1][n >> 1], lb[BUF][1], (n >> 1) * 2048);
-        if constexpr (n == 20) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (n == 21) __builtin_amdgcn_s_barrier();                          // every wave has read all of B(cur)
-        if constexpr (n >= 22 && n < 38 && !(n & 1)) AV_W_LD(vB[(n - 22) >> 1], pB, m0B + ((n - 22) >> 1) * 1024);
-        if constexpr (n >= 23 && n < 39 && (n & 1)) AV_W_RD(FA[1][(n - 23) >> 1], la[BUF][1], ((n - 23) >> 1) * 2048);
-        if constexpr (n == 50) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (n == 51) __builtin_amdgcn_s_barrier();                          // ... and all of A(cur)
-        if constexpr (n == 52 || n == 55 || n == 58 || n == 61) AV_W_LD(vA[(n - 52) / 3], pA, m0A + ((n - 52) / 3) * 1024);
-    } else {
-        if constexpr (n == 0) AV_W_LD(vA[4], pA, m0A + 4 * 1024);
-        if constexpr (n == 26) asm volatile("s_waitcnt vmcnt(13)" ::: "memory");      // 13 loads of this step issued so far: all older ones have landed
-        if constexpr (n == 27) __builtin_amdgcn_s_barrier();                          // the other buffer is complete for every wave
-        if constexpr (n >= 28 && n < 36) AV_W_RD(FB[0][n - 28], lb[BUF ^ 1][0], (n - 28) * 2048);
-        if constexpr (n >= 37 && n < 53 && (n & 1)) AV_W_RD(FA[0][(n - 37) >> 1], la[BUF ^ 1][0], ((n - 37) >> 1) * 2048);
-        if constexpr (n == 32 || n == 40 || n == 48) AV_W_LD(vA[5 + (n - 32) / 8], pA, m0A + (5 + (n - 32) / 8) * 1024);
-        if constexpr (n == 62) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-}
-
-template <int BUF, int... Ns>
-__device__ __forceinline__ void wgemm_kstep(std::integer_sequence<int, Ns...>, f32x4 (&acc)[8][8], bf16x8 (&FA)[2][8], bf16x8 (&FB)[2][8], const int (&la)[2][2],
-                                            const int (&lb)[2][2], const unsigned (&vA)[8], const unsigned (&vB)[8], const bf16* pA, const bf16* pB, int m0A, int m0B) {
-    (wgemm_step<Ns, BUF>(acc, FA, FB, la, lb, vA, vB, pA, pB, m0A, m0B), ...);
-}
-
+// The K-step table itself: gemm_shared.h wgemm_step, here with MODE 0 and the weight fragments in row order.
 __global__ __launch_bounds__(256, 1) void gemm_bf16_w_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -582,7 +458,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w_kernel(GemmArgs g) {
         unsigned va[8], vb[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) { va[q] = s2 ? vA2[q] : vA1[q]; vb[q] = s2 ? vB2[q] : vB1[q]; }
-        wgemm_kstep<BUF>(Seq{}, acc, FA, FB, la, lb, va, vb, pa, pb, mw + BUF * HSTAGE, mw + BUF * HSTAGE + HBM_ * 128);
+        avg::wgemm_kstep<0, avg::BoffLinear>(Seq{}, acc, FA, FB, la[BUF][1], la[BUF ^ 1][0], lb[BUF][1], lb[BUF ^ 1][0], va, vb, pa, pb, mw + BUF * HSTAGE,
+                                             mw + BUF * HSTAGE + HBM_ * 128);
     };
     int t = 0;
     for (; t + 1 < nt; t += 2) { kstep(t, std::integral_constant<int, 0>{}); kstep(t + 1, std::integral_constant<int, 1>{}); }
@@ -592,18 +469,14 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w_kernel(GemmArgs g) {
     // keeps compiler-generated readers (register copies, spill stores) behind them -- without that hipcc placed a scratch store of the
     // last accumulator directly after its MFMA and spilled a stale value.
     asm volatile("s_waitcnt vmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-#define AV_W_PIN8(I) asm volatile("" : "+a"(acc[I][0]), "+a"(acc[I][1]), "+a"(acc[I][2]), "+a"(acc[I][3]), "+a"(acc[I][4]), "+a"(acc[I][5]), "+a"(acc[I][6]), "+a"(acc[I][7]))
     AV_W_PIN8(0); AV_W_PIN8(1); AV_W_PIN8(2); AV_W_PIN8(3); AV_W_PIN8(4); AV_W_PIN8(5); AV_W_PIN8(6); AV_W_PIN8(7);
-#undef AV_W_PIN8
     __syncthreads();
-#undef AV_W_RD
-#undef AV_W_LD
     if (g.wide_epi) {
-        // Epilogue through LDS, as in the 16-wave kernel: each 128-row half goes to LDS as fp32 and comes back as whole 16-byte row chunks
+        // Epilogue through LDS, as in gemm_bf16_h_kernel (where the reasons are): each 128-row half goes to LDS as fp32 and comes back as whole 16-byte row chunks
         constexpr int CT_LD = 256;
         float* ct = (float*)smem;                                    // [128][256] fp32 = both stage buffers
         if (g.e.alpha == 1.f && g.e.drop_p <= 0.f && g.e.g_in <= 0 && !g.e.out_f32 && g.e.r_mod <= 0 && m0 + HBM_ <= g.e.M && n0 + HBN_ <= g.e.N) {
-            // lean items (see the 16-wave kernel): thread = 8-column chunk (tid & 31) of rows (tid >> 5) + 8 p
+            // lean items (see gemm_bf16_h_kernel): thread = 8-column chunk (tid & 31) of rows (tid >> 5) + 8 p
             const int ch = tid & 31, prow = tid >> 5;
             float b[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             if (g.e.bias) load_f<8>((const bf16*)g.e.bias + n0 + ch * 8, b);
@@ -634,10 +507,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w_kernel(GemmArgs g) {
                     __syncthreads();
                 }
             };
-            if (g.e.act == AV_ACT_NONE) run(std::integral_constant<int, AV_ACT_NONE>{});
-            else if (g.e.act == AV_ACT_GELU) run(std::integral_constant<int, AV_ACT_GELU>{});
-            else if (g.e.act == AV_ACT_QUICK_GELU) run(std::integral_constant<int, AV_ACT_QUICK_GELU>{});
-            else run(std::integral_constant<int, AV_ACT_SILU>{});
+            avg::with_act(g.e.act, run);
             return;
         }
 #pragma unroll
@@ -681,54 +551,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w_kernel(GemmArgs g) {
 // Persistent form of the 4-wave kernel for calls the lean epilogue covers (bf16 output, alpha 1, no dropout / row remap / broadcast
 // residual).  One workgroup per CU walks tiles vid, vid+G, ...; the K-step pipeline never drains between them: the last two K-steps of a
 // tile issue the loads of the NEXT tile's first two K-steps (where the one-shot kernel issues dummy loads), so a tile's prologue latency
-// and the workgroup relaunch disappear behind the previous tile.  The epilogue therefore stays out of the two stage buffers: each wave
-// transposes its own 128x128 quadrant 16 rows at a time through a private 8-KiB slice of the remaining 32 KiB of LDS (same-wave LDS
-// traffic is in order: no workgroup barrier), and the accumulators are re-initialised for free by the first K-step's MFMAs taking 0 as
-// their C operand.  Buffers alternate by address arithmetic, so any K-step count and tile parity runs the same loop body.
-// B-operand (weight) fragment j of a wave reads LDS rows 32 (j >> 1) + 4 (j & 1) + 8 (fr >> 2) + (fr & 3) of its 128-row half: MFMA tiles 2p and
-// 2p+1 then hold, in lane (fr, fq), output columns 32p + 8fq + {0..3} and + {4..7} of row fr -- one 16-byte bf16 chunk per lane and tile
-// pair, stored straight from the accumulators (no LDS transpose in the epilogue).  Byte offset of fragment j from the lane's base row:
-#define WP_BOFF(j) ((((j) >> 1) * 32 + ((j) & 1) * 4) * 128)
-// MODE 0: any K-step but a tile's first; 1: a tile's first K-step (accumulators start from 0); 2: the same right after the epilogue of a
-// tile that lay fully inside the matrix.  vmcnt counts loads and stores together in issue order, so the counted wait of the K-step would
-// also wait for the 32 epilogue stores issued just before it (their write acknowledgements take several microseconds when the whole
-// grid stores at once); mode 2 allows exactly those 32 to stay in flight: everything OLDER (the K-step's operands) has still landed.
-template <int N, int MODE>
-__device__ __forceinline__ void wpgemm_step(f32x4 (&acc)[8][8], bf16x8 (&FA)[2][8], bf16x8 (&FB)[2][8], const int (&la)[2], const int (&lb)[2],
-                                            const unsigned (&vA)[8], const unsigned (&vB)[8], const bf16* pA, const bf16* pB, int m0A, int m0B) {
-    constexpr int h = N >> 6, n = N & 63, I = n >> 3, J = n & 7;
-    constexpr bool FIRST = MODE != 0;
-    if constexpr (FIRST && h == 0) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc[I][J]) : "v"(FB[h][J]), "v"(FA[h][I]));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[I][J]) : "v"(FB[h][J]), "v"(FA[h][I]));
-#define AV_W_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define AV_W_LD(voff, base, m0v) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" AVLLM_DMA_POLICY :: "s"(m0v), "v"(voff), "s"(base) : "memory")
-    // la/lb[1]: this lane's k-half-1 fragment address in the CURRENT buffer; la/lb[0]: k-half 0 in the OTHER buffer (next K-step)
-    if constexpr (h == 0) {
-        if constexpr (n < 16 && (n & 1)) AV_W_RD(FB[1][n >> 1], lb[1], WP_BOFF(n >> 1));
-        if constexpr (n == 20) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (n == 21) __builtin_amdgcn_s_barrier();
-        if constexpr (n >= 22 && n < 38 && !(n & 1)) AV_W_LD(vB[(n - 22) >> 1], pB, m0B + ((n - 22) >> 1) * 1024);
-        if constexpr (n >= 23 && n < 39 && (n & 1)) AV_W_RD(FA[1][(n - 23) >> 1], la[1], ((n - 23) >> 1) * 2048);
-        if constexpr (n == 50) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (n == 51) __builtin_amdgcn_s_barrier();
-        if constexpr (n == 52 || n == 55 || n == 58 || n == 61) AV_W_LD(vA[(n - 52) / 3], pA, m0A + ((n - 52) / 3) * 1024);
-    } else {
-        if constexpr (n == 0) AV_W_LD(vA[4], pA, m0A + 4 * 1024);
-        if constexpr (n == 26) { if constexpr (MODE == 2) asm volatile("s_waitcnt vmcnt(45)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); }
-        if constexpr (n == 27) __builtin_amdgcn_s_barrier();
-        if constexpr (n >= 28 && n < 36) AV_W_RD(FB[0][n - 28], lb[0], WP_BOFF(n - 28));
-        if constexpr (n >= 37 && n < 53 && (n & 1)) AV_W_RD(FA[0][(n - 37) >> 1], la[0], ((n - 37) >> 1) * 2048);
-        if constexpr (n == 32 || n == 40 || n == 48) AV_W_LD(vA[5 + (n - 32) / 8], pA, m0A + (5 + (n - 32) / 8) * 1024);
-        if constexpr (n == 62) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-}
-
-template <int MODE, int... Ns>
-__device__ __forceinline__ void wpgemm_kstep(std::integer_sequence<int, Ns...>, f32x4 (&acc)[8][8], bf16x8 (&FA)[2][8], bf16x8 (&FB)[2][8], const int (&la)[2],
-                                             const int (&lb)[2], const unsigned (&vA)[8], const unsigned (&vB)[8], const bf16* pA, const bf16* pB, int m0A, int m0B) {
-    (wpgemm_step<Ns, MODE>(acc, FA, FB, la, lb, vA, vB, pA, pB, m0A, m0B), ...);
-}
-
+// and the workgroup relaunch disappear behind the previous tile.  The epilogue therefore stays out of LDS: the weight fragments are
+// column-interleaved (gemm_shared.h WP_BOFF), so each lane stores 16-byte chunks straight from its accumulators (avg::acc_store_general / _full / _full_res), and the
+// accumulators are re-initialised for free by the first K-step's MFMAs taking 0 as their C operand (avg::wgemm_step MODE 1 / 2).  Buffers alternate by address arithmetic, so any K-step count and tile parity runs the same loop body.
 #ifndef WP_RES_DEPTH
 #define WP_RES_DEPTH 7
 #endif
@@ -743,6 +568,33 @@ __device__ unsigned long long g_wp_stamps[256 * 4 * 8];
                             __builtin_amdgcn_sched_barrier(0); st_acc[slot] += t_ - st_prev; st_prev = t_; } while (0)
 #else
 #define WP_STAMP(slot) do { } while (0)
+#endif
+
+#ifdef AVLLM_EXPERIMENT_KNOBS
+// Store cache-policy experiment of the full-tile epilogue form (bits 20..22 of GEMM_DBG): 1 = non-temporal builtin, 2.. = explicit policy bits,
+// 7 = all of the epilogue's arithmetic, ONE store per lane and tile (the folded chunks)
+struct WpStorePolicy {
+    static constexpr bool on = true;
+    int sm; u32x4 fold;
+    __device__ __forceinline__ bool store(bf16* sp, const float (&v)[8], bool last) {
+        if (!sm) return false;
+        bf16x8 t;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) t[c] = (bf16)v[c];
+        const u32x4 tv = __builtin_bit_cast(u32x4, t);
+        if (sm == 1) __builtin_nontemporal_store(t, (bf16x8*)sp);
+        else if (sm == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0" :: "v"(sp), "v"(tv) : "memory");
+        else if (sm == 3) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(sp), "v"(tv) : "memory");
+        else if (sm == 4) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(sp), "v"(tv) : "memory");
+        else if (sm == 5) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(sp), "v"(tv) : "memory");
+        else if (sm == 6) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" :: "v"(sp), "v"(tv) : "memory");
+        else {
+            fold[0] ^= tv[0]; fold[1] ^= tv[1]; fold[2] ^= tv[2]; fold[3] ^= tv[3];
+            if (last) *(u32x4*)sp = fold;
+        }
+        return true;
+    }
+};
 #endif
 
 template <bool HAS2>
@@ -846,7 +698,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_wp_kernel(GemmArgs g) {
     {
         int a0 = rowA + pc0;
         const int b0 = rowB + pcB0;
-#define AV_WP_RDB(J) AV_W_RD(FB[0][J], b0, WP_BOFF(J))
+#define AV_WP_RDB(J) AV_W_RD(FB[0][J], b0, WP_BOFF(J, 128))
         AV_WP_RDB(0); AV_WP_RDB(1); AV_WP_RDB(2); AV_WP_RDB(3); AV_WP_RDB(4); AV_WP_RDB(5); AV_WP_RDB(6); AV_WP_RDB(7);
 #pragma unroll
         for (int i = 0; i < 8; ++i) { AV_W_RD(FA[0][i], a0, 0); a0 += 2048; }
@@ -854,16 +706,17 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_wp_kernel(GemmArgs g) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     using Seq = std::make_integer_sequence<int, 128>;
     auto kstep = [&](auto modec) __attribute__((always_inline)) {
-        constexpr int FIRST = decltype(modec)::value;                // MODE of wpgemm_step
+        constexpr int FIRST = decltype(modec)::value;                // MODE of wgemm_step
         if constexpr (HAS2) {
             unsigned va[8], vb[8];
             const bf16 *pa = tA1 + (long)lt * BK, *pb = tB1 + (long)lt * BK;
 #pragma unroll
             for (int q = 0; q < 8; ++q) { va[q] = vA1[q]; vb[q] = vB1[q]; }
             if (lt >= nt1) seg2_offsets(va, vb, pa, pb);
-            wpgemm_kstep<FIRST>(Seq{}, acc, FA, FB, la, lb, va, vb, pa, pb, mw + bo, mw + bo + HBM_ * 128);
+            avg::wgemm_kstep<FIRST, avg::BoffPaired>(Seq{}, acc, FA, FB, la[1], la[0], lb[1], lb[0], va, vb, pa, pb, mw + bo, mw + bo + HBM_ * 128);
         } else {
-            wpgemm_kstep<FIRST>(Seq{}, acc, FA, FB, la, lb, vA1, vB1, tA1 + (long)lt * BK, tB1 + (long)lt * BK, mw + bo, mw + bo + HBM_ * 128);
+            avg::wgemm_kstep<FIRST, avg::BoffPaired>(Seq{}, acc, FA, FB, la[1], la[0], lb[1], lb[0], vA1, vB1, tA1 + (long)lt * BK, tB1 + (long)lt * BK, mw + bo,
+                                                     mw + bo + HBM_ * 128);
         }
         const int d = bo ? -HSTAGE : HSTAGE;
         la[1] += d; lb[1] += d; la[0] -= d; lb[0] -= d; bo += d;
@@ -891,18 +744,12 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_wp_kernel(GemmArgs g) {
         // result latency of the last MFMAs (invisible to the compiler's hazard recogniser): nops, and every accumulator named as an in/out
         // operand so that compiler-generated readers stay behind them
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#define AV_W_PIN8(I) asm volatile("" : "+a"(acc[I][0]), "+a"(acc[I][1]), "+a"(acc[I][2]), "+a"(acc[I][3]), "+a"(acc[I][4]), "+a"(acc[I][5]), "+a"(acc[I][6]), "+a"(acc[I][7]))
         AV_W_PIN8(0); AV_W_PIN8(1); AV_W_PIN8(2); AV_W_PIN8(3); AV_W_PIN8(4); AV_W_PIN8(5); AV_W_PIN8(6); AV_W_PIN8(7);
-#undef AV_W_PIN8
-        // Epilogue straight from the accumulators: lane (fr, fq) holds, for row block i and column pair p, the 8 consecutive output columns
-        // 32p + 8fq .. +7 of row 16i + fr (acc[i][2p] = the first four, acc[i][2p+1] = the last four): bias / activation / residual on the
-        // fp32 values, one rounding, one 16-byte store per pair; a store instruction covers 16 rows x 64 contiguous bytes.
         int tm, tn;
         tile_coords(tile_id(vid), tiles_m, tiles_n, tm, tn, !(g.dbg & 4), g.gw);
         const int m0 = tm * HBM_ + wr * 128 + fr, n = tn * HBN_ + wc * 128 + fq * 8;
         const bool full = (tm + 1) * HBM_ <= g.e.M && (tn + 1) * HBN_ <= g.e.N && !(g.dbg & 3);      // wave-uniform: every lane stores all 32 chunks
         stores_in_flight = full;                                     // dbg bit 1: experiment, strict wait
-        // (the bias cannot ride in the accumulators' initial value: an MFMA's C and D operands share one register-file bit, and D is an AGPR)
         float b[4][8];
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -910,136 +757,21 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_wp_kernel(GemmArgs g) {
             for (int c = 0; c < 8; ++c) b[p][c] = 0.f;
             if (g.e.bias && n + 32 * p < g.e.N) load_f<8>((const bf16*)g.e.bias + n + 32 * p, b[p]);
         }
-        // this lane's first row; item (i, p) is 16 i rows down and 32 p columns right: uniform (scalar) multiples of the row strides
         bf16* const cp0 = (bf16*)g.e.C + (long)m0 * g.e.ldc + n;
         const bf16* const rp0 = g.e.R ? (const bf16*)g.e.R + (long)m0 * g.e.ldr + n : nullptr;
         const long ldc = g.e.ldc, ldr = g.e.R ? g.e.ldr : 0;
-        // edge tiles (and activation + residual, which no model call makes): per-chunk bounds tests
-        auto run = [&](auto actc) __attribute__((always_inline)) {
-            constexpr int ACT = decltype(actc)::value;
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                const bool mrow = m0 + i * 16 < g.e.M;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 4; ++p) {
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    if (mrow && n + 32 * p < g.e.N && !(g.dbg & 1))
-                        epilogue_fast8<ACT>(acc[i][2 * p], acc[i][2 * p + 1], b[p], g.e.bias != nullptr, rp0 ? rp0 + (i * 16) * ldr + 32 * p : nullptr,
-                                            cp0 + (i * 16) * ldc + 32 * p);
-                }
-            }
-        };
-        // full tile, no residual: 8 accumulator reads, 8 bias adds (only in the instantiation with a bias), the activation, 4 packed converts and
-        // one 16-byte store per chunk -- no bounds test, no select, no branch (the general form above spends ~40 instructions per chunk:
-        // tools/gemm_stamps.py measured the epilogue at a quarter of a K = 768 tile)
-        auto run_full = [&](auto actc, auto hasbc) __attribute__((always_inline)) {
-            constexpr int ACT = decltype(actc)::value;
-            constexpr bool HASB = decltype(hasbc)::value;
 #ifdef AVLLM_EXPERIMENT_KNOBS
-            u32x4 fold = {0u, 0u, 0u, 0u};
+        WpStorePolicy sp{(g.dbg >> 20) & 7, {0u, 0u, 0u, 0u}};
+#else
+        avg::PlainStores sp;
 #endif
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                bf16* const cpi = cp0 + (long)(i * 16) * ldc;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 4; ++p) {
-                    // the accumulators are "redefined" here for the compiler: without it every epilogue variant's 256 accumulator reads are hoisted
-                    // above the variant branch as common subexpressions -- 256 live registers, ~130 spills around the epilogue
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
-                    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (HASB) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] += b[p][c];
-                    }
-                    if constexpr (ACT != AV_ACT_NONE) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] = act_apply_fast(v[c], ACT);
-                    }
-#ifdef AVLLM_EXPERIMENT_KNOBS
-                    {   // store cache-policy experiment (bits 20..22 of GEMM_DBG): 1 = non-temporal builtin, 2.. = explicit policy bits
-                        const int sm = (g.dbg >> 20) & 7;
-                        if (sm) {
-                            bf16x8 t;
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) t[c] = (bf16)v[c];
-                            const u32x4 tv = __builtin_bit_cast(u32x4, t);
-                            bf16* sp = cpi + 32 * p;
-                            if (sm == 1) __builtin_nontemporal_store(t, (bf16x8*)sp);
-                            else if (sm == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0" :: "v"(sp), "v"(tv) : "memory");
-                            else if (sm == 3) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(sp), "v"(tv) : "memory");
-                            else if (sm == 4) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(sp), "v"(tv) : "memory");
-                            else if (sm == 5) asm volatile("global_store_dwordx4 %0, %1, off nt" :: "v"(sp), "v"(tv) : "memory");
-                            else if (sm == 6) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" :: "v"(sp), "v"(tv) : "memory");
-                            else {                                   // 7: all of the epilogue's arithmetic, ONE store per lane and tile (the folded chunks)
-                                fold[0] ^= tv[0]; fold[1] ^= tv[1]; fold[2] ^= tv[2]; fold[3] ^= tv[3];
-                                if (i == 7 && p == 3) *(u32x4*)sp = fold;
-                            }
-                            continue;
-                        }
-                    }
-#endif
-                    store_f<8>(cpi + 32 * p, v);
-                }
-            }
-        };
-        // full tile + residual (out-projection, fc2, o, down, gradient sums): ALL 32 residual chunks of the lane are requested in one burst into
-        // the 128 registers the operand fragments occupy during the K loop (dead here: the next tile's are re-read after the epilogue), then
-        // consumed in issue order.  The tile pays one memory latency instead of one per row block (tools/gemm_stamps.py: 12 us of a 29 us
-        // out-projection tile with the one-row-block-ahead form).  A load may alias a later store (in-place residual): every load is issued
-        // before the first store, and a lane only ever reads the bytes it writes itself.  Behind chunk c's load at its wait: 31 - c younger
-        // loads and the c stores issued so far = 31 operations, whatever c: one constant vmcnt.  asm loads + explicit waits because
-        // compiler-visible loads consumed later leave the wait-count pass with pending state that reaches the K loop as vmcnt(0) per K-step.
-        auto run_res_full = [&](auto hasbc) __attribute__((always_inline)) {
-            constexpr bool HASB = decltype(hasbc)::value;
-            constexpr int RD = WP_RES_DEPTH;                         // residual row blocks requested ahead of the one being stored (7 = the whole tile at once)
-            u32x4 rr[RD + 1][4];
-            auto fetch = [&](int i) __attribute__((always_inline)) {
-                const bf16* rp = rp0 + (long)(i * 16) * ldr;
-                asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %4, off offset:64\n\t"
-                             "global_load_dwordx4 %2, %4, off offset:128\n\tglobal_load_dwordx4 %3, %4, off offset:192"
-                             : "=&v"(rr[i % (RD + 1)][0]), "=&v"(rr[i % (RD + 1)][1]), "=&v"(rr[i % (RD + 1)][2]), "=&v"(rr[i % (RD + 1)][3]) : "v"(rp) : "memory");
-            };
-#pragma clang loop unroll(full)
-            for (int i = 0; i < RD && i < 8; ++i) fetch(i);
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                if (i + RD < 8) fetch(i + RD);
-                bf16* const cpi = cp0 + (long)(i * 16) * ldc;
-                // younger operations behind row block i's loads at their wait: 3 of its own asm statement, 4 per later row block in flight,
-                // 4 stores per row block stored since the loads were issued (all of them = 31 with the whole tile in flight)
-                constexpr int dummy = 0; (void)dummy;
-                const int ahead = (i + RD < 8 ? i + RD : 7) - i, behind = RD < i ? RD : i;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 4; ++p) {
-                    u32x4& x = rr[i % (RD + 1)][p];
-                    const int nw = 3 + 4 * ahead + 4 * behind;
-                    if (nw == 7) asm volatile("s_waitcnt vmcnt(7)" : "+v"(x) :: "memory");
-                    else if (nw == 11) asm volatile("s_waitcnt vmcnt(11)" : "+v"(x) :: "memory");
-                    else if (nw == 15) asm volatile("s_waitcnt vmcnt(15)" : "+v"(x) :: "memory");
-                    else if (nw == 19) asm volatile("s_waitcnt vmcnt(19)" : "+v"(x) :: "memory");
-                    else if (nw == 23) asm volatile("s_waitcnt vmcnt(23)" : "+v"(x) :: "memory");
-                    else if (nw == 27) asm volatile("s_waitcnt vmcnt(27)" : "+v"(x) :: "memory");
-                    else if (nw == 31) asm volatile("s_waitcnt vmcnt(31)" : "+v"(x) :: "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(x) :: "memory");
-                    const bf16x8 r = __builtin_bit_cast(bf16x8, x);
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
-                    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (HASB) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] += b[p][c];
-                    }
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) v[c] += (float)r[c];
-                    store_f<8>(cpi + 32 * p, v);
-                }
-            }
-        };
+        const bool hb = g.e.bias != nullptr;
+        auto run = [&](auto actc) __attribute__((always_inline)) { avg::acc_store_general<4, decltype(actc)::value>(acc, b, hb, cp0, rp0, ldc, ldr, m0, n, g.e.M, g.e.N, g.dbg); };
+        auto run_full = [&](auto actc, auto hasbc) __attribute__((always_inline)) { avg::acc_store_full<4, decltype(actc)::value, decltype(hasbc)::value>(acc, b, cp0, ldc, sp); };
+        auto run_res_full = [&](auto hasbc) __attribute__((always_inline)) { avg::acc_store_full_res<4, WP_RES_DEPTH, decltype(hasbc)::value>(acc, b, cp0, rp0, ldc, ldr); };
         // the combinations the model calls make get the lean forms; anything else (and every edge tile) the general one
         const std::true_type yes{};
         const std::false_type no{};
-        const bool hb = g.e.bias != nullptr;
 #ifdef AVLLM_EXPERIMENT_KNOBS
         if (g.dbg & 0x80000) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // experiment: no operand load in flight while the epilogue stores
 #endif
@@ -1084,8 +816,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_wp_kernel(GemmArgs g) {
     }
 #endif
 #undef AV_WP_RDB
-#undef AV_W_RD
-#undef AV_W_LD
 }
 
 // Persistent form of the 16-wave kernel (gemm_bf16_h_kernel): one workgroup per CU walks tiles id, id+G, id+2G, ... and issues the FIRST K-tile of its
@@ -1135,26 +865,7 @@ __global__ __launch_bounds__(1024, 4) void gemm_bf16_hp_kernel(GemmArgs g) {
             else if (next < ntiles) stage(nm0, nn0, 0, cur ^ 1);
             const char* a_lds = smem + cur * HSTAGE;
             const char* b_lds = a_lds + HBM_ * BK * 2;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 xa[4], wb[4];
-                const int chunk = ks * 4 + fq;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int r = wm * 64 + i * 16 + fr;
-                    xa[i] = *(const bf16x8*)(a_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int r = wn * 64 + j * 16 + fr;
-                    wb[j] = *(const bf16x8*)(b_lds + r * 128 + ((chunk ^ (r & 7)) << 4));
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-            }
+            wave_tile_64x64(acc, a_lds, b_lds, wm, wn, fr, fq);
             __syncthreads();
             cur ^= 1;
         }

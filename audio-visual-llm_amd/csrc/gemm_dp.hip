@@ -29,7 +29,7 @@
 
 namespace {
 
-using avg::epilogue_fast8; using avg::xcd_remap; using avg::tile_coords;
+using avg::xcd_remap; using avg::tile_coords;
 
 constexpr int DTM = 256, DTN = 128, DBK = 32;
 constexpr int DOFFB = DTM * DBK * 2;                     // 16 KiB: the weight image of a stage follows the activation image
@@ -45,8 +45,6 @@ struct DpArgs {
     int act, dbg;
 };
 
-#define DP_BOFF(j) ((((j) >> 1) * 32 + ((j) & 1) * 4) * 64)
-#define DP_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 // One DMA instruction: LDS rows rowbase + (lane >> 2) of an image, 16 bytes per lane.  The source offset -- min(row, last row) * row bytes + swizzled
 // chunk -- is built right here from scalars (4 VALU slots between MFMAs cost nothing): twelve precomputed offsets per macro step were the
 // registers that pushed the first cut of this kernel into scratch.
@@ -69,8 +67,8 @@ __device__ __forceinline__ void dp_slot(f32x4 (&acc)[8][4], bf16x8 (&FA)[2][8], 
     else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[I][J]) : "v"(FB[h][J]), "v"(FA[h][I]));
     if constexpr (n == 2) { if constexpr (MODE == 2) asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
     if constexpr (n == 3) __builtin_amdgcn_s_barrier();
-    if constexpr (n >= 4 && n < 8) DP_RD(FB[h ^ 1][n - 4], rb[h], DP_BOFF(n - 4));
-    if constexpr (n >= 8 && n < 16) DP_RD(FA[h ^ 1][n - 8], ra[h], (n - 8) * 1024);
+    if constexpr (n >= 4 && n < 8) AV_W_RD(FB[h ^ 1][n - 4], rb[h], WP_BOFF(n - 4, 64));
+    if constexpr (n >= 8 && n < 16) AV_W_RD(FA[h ^ 1][n - 8], ra[h], (n - 8) * 1024);
     if constexpr (n >= 16 && n < 20) DP_LD(dl.l4, rowA + (n - 16) * 16, cx[h].ma, cx[h].la2, dl.cA, cx[h].pa, mA[h] + (n - 16) * 1024);
     if constexpr (n == 20) DP_LD(dl.l4, rowB, cx[h].mb, cx[h].lb2, dl.cB0, cx[h].pb, mB[h]);
     if constexpr (n == 21) DP_LD(dl.l4, rowB + 16, cx[h].mb, cx[h].lb2, dl.cB1, cx[h].pb, mB[h] + 1024);
@@ -168,9 +166,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_dp_kernel(DpArgs g) {
     __builtin_amdgcn_s_barrier();
     int s0 = 0, s1 = DSTAGE, s2 = 2 * DSTAGE;                        // stage of the sub-step being multiplied, of the next one, of the one after
 #define DP_REREAD() do { const int a0_ = fa + s0, b0_ = fb + s0; \
-        DP_RD(FB[0][0], b0_, DP_BOFF(0)); DP_RD(FB[0][1], b0_, DP_BOFF(1)); DP_RD(FB[0][2], b0_, DP_BOFF(2)); DP_RD(FB[0][3], b0_, DP_BOFF(3)); \
-        DP_RD(FA[0][0], a0_, 0); DP_RD(FA[0][1], a0_, 1024); DP_RD(FA[0][2], a0_, 2048); DP_RD(FA[0][3], a0_, 3072); \
-        DP_RD(FA[0][4], a0_, 4096); DP_RD(FA[0][5], a0_, 5120); DP_RD(FA[0][6], a0_, 6144); DP_RD(FA[0][7], a0_, 7168); \
+        AV_W_RD(FB[0][0], b0_, WP_BOFF(0, 64)); AV_W_RD(FB[0][1], b0_, WP_BOFF(1, 64)); AV_W_RD(FB[0][2], b0_, WP_BOFF(2, 64)); AV_W_RD(FB[0][3], b0_, WP_BOFF(3, 64)); \
+        AV_W_RD(FA[0][0], a0_, 0); AV_W_RD(FA[0][1], a0_, 1024); AV_W_RD(FA[0][2], a0_, 2048); AV_W_RD(FA[0][3], a0_, 3072); \
+        AV_W_RD(FA[0][4], a0_, 4096); AV_W_RD(FA[0][5], a0_, 5120); AV_W_RD(FA[0][6], a0_, 6144); AV_W_RD(FA[0][7], a0_, 7168); \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); } while (0)
     using Seq = std::make_integer_sequence<int, 64>;
     auto mstep = [&](auto modec) __attribute__((always_inline)) {
@@ -196,9 +194,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_dp_kernel(DpArgs g) {
         // result latency of the last MFMAs (invisible to the compiler's hazard recogniser): nops, and every accumulator named as an in/out
         // operand so that compiler-generated readers stay behind them
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#define DP_PIN4(I) asm volatile("" : "+a"(acc[I][0]), "+a"(acc[I][1]), "+a"(acc[I][2]), "+a"(acc[I][3]))
-        DP_PIN4(0); DP_PIN4(1); DP_PIN4(2); DP_PIN4(3); DP_PIN4(4); DP_PIN4(5); DP_PIN4(6); DP_PIN4(7);
-#undef DP_PIN4
+        AV_W_PIN4(0); AV_W_PIN4(1); AV_W_PIN4(2); AV_W_PIN4(3); AV_W_PIN4(4); AV_W_PIN4(5); AV_W_PIN4(6); AV_W_PIN4(7);
         // lane (fr, fq), row block i, column pair p: the 8 consecutive output columns 32p + 8fq .. +7 of row 16i + fr
         int tm, tn;
         tile_of(vid, tm, tn);
@@ -217,80 +213,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_dp_kernel(DpArgs g) {
         bf16* const cp0 = g.C + (long)m0 * g.ldc + n;
         const bf16* const rp0 = g.R ? g.R + (long)m0 * g.ldr + n : nullptr;
         const long ldc = g.ldc, ldr = g.R ? g.ldr : 0;
-        // edge tiles (and activation + residual, which no model call makes): per-chunk bounds tests
-        auto run = [&](auto actc) __attribute__((always_inline)) {
-            constexpr int ACT = decltype(actc)::value;
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                const bool mrow = m0 + i * 16 < g.M;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 2; ++p) {
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    if (mrow && n + 32 * p < g.N && !(g.dbg & 1))
-                        epilogue_fast8<ACT>(acc[i][2 * p], acc[i][2 * p + 1], b[p], g.bias != nullptr, rp0 ? rp0 + (i * 16) * ldr + 32 * p : nullptr,
-                                            cp0 + (i * 16) * ldc + 32 * p);
-                }
-            }
-        };
-        // full tile, no residual: 8 accumulator reads, the bias adds, the activation, 4 packed converts and one 16-byte store per chunk
-        auto run_full = [&](auto actc, auto hasbc) __attribute__((always_inline)) {
-            constexpr int ACT = decltype(actc)::value;
-            constexpr bool HASB = decltype(hasbc)::value;
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                bf16* const cpi = cp0 + (long)(i * 16) * ldc;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 2; ++p) {
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));      // no hoisting of all accumulator reads above the variant branch
-                    const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
-                    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (HASB) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] += b[p][c];
-                    }
-                    if constexpr (ACT != AV_ACT_NONE) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] = act_apply_fast(v[c], ACT);
-                    }
-                    store_f<8>(cpi + 32 * p, v);
-                }
-            }
-        };
-        // full tile + residual: all 16 residual chunks of the lane requested in one burst into the (dead) fragment registers, consumed in issue
-        // order behind one constant vmcnt(15): 15 - c younger loads + c stores behind chunk c.  asm loads with explicit waits (compiler-visible
-        // loads consumed later reach the K loop as vmcnt(0) per K-step); every load is issued before the first store (in-place residual).
-        auto run_res_full = [&](auto hasbc) __attribute__((always_inline)) {
-            constexpr bool HASB = decltype(hasbc)::value;
-            u32x4 rr[8][2];
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                const bf16* rp = rp0 + (long)(i * 16) * ldr;
-                asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %2, off offset:64" : "=&v"(rr[i][0]), "=&v"(rr[i][1]) : "v"(rp) : "memory");
-            }
-#pragma clang loop unroll(full)
-            for (int i = 0; i < 8; ++i) {
-                bf16* const cpi = cp0 + (long)(i * 16) * ldc;
-#pragma clang loop unroll(full)
-                for (int p = 0; p < 2; ++p) {
-                    u32x4& x = rr[i][p];
-                    asm volatile("s_waitcnt vmcnt(15)" : "+v"(x) :: "memory");
-                    const bf16x8 r = __builtin_bit_cast(bf16x8, x);
-                    asm volatile("" : "+a"(acc[i][2 * p]), "+a"(acc[i][2 * p + 1]));
-                    const f32x4 lo = acc[i][2 * p], hi = acc[i][2 * p + 1];
-                    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    if constexpr (HASB) {
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) v[c] += b[p][c];
-                    }
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) v[c] += (float)r[c];
-                    store_f<8>(cpi + 32 * p, v);
-                }
-            }
-        };
+        // the forms: gemm_shared.h; the combinations the model calls make get the lean ones, anything else (and every edge tile) the general one
+        const bool hb = g.bias != nullptr;
+        auto run = [&](auto actc) __attribute__((always_inline)) { avg::acc_store_general<2, decltype(actc)::value>(acc, b, hb, cp0, rp0, ldc, ldr, m0, n, g.M, g.N, g.dbg); };
+        auto run_full = [&](auto actc, auto hasbc) __attribute__((always_inline)) { avg::acc_store_full<2, decltype(actc)::value, decltype(hasbc)::value>(acc, b, cp0, ldc); };
+        auto run_res_full = [&](auto hasbc) __attribute__((always_inline)) { avg::acc_store_full_res<2, 7, decltype(hasbc)::value>(acc, b, cp0, rp0, ldc, ldr); };
         const std::true_type yes{};
         const std::false_type no{};
-        const bool hb = g.bias != nullptr;
         if (full && !g.R && g.act == AV_ACT_NONE && !hb) run_full(std::integral_constant<int, AV_ACT_NONE>{}, no);
         else if (full && !g.R && g.act == AV_ACT_NONE && hb) run_full(std::integral_constant<int, AV_ACT_NONE>{}, yes);
         else if (full && !g.R && g.act == AV_ACT_GELU && hb) run_full(std::integral_constant<int, AV_ACT_GELU>{}, yes);

@@ -44,8 +44,10 @@ def test_mx_quantizer_bit_exact(dev, layout, R, K, dtype):
 
 
 @pytest.mark.parametrize("M,N,K", [(64, 128, 128), (256, 256, 512), (300, 200, 384), (4096, 4096, 1024), (130, 1000, 256), (4096, 4096, 256), (5000, 2304, 768),
-                                   (4100, 4104, 384), (20000, 768, 3072)])
+                                   (4100, 4104, 384), (20000, 768, 3072), (512, 512, 256), (300, 264, 256), (2048, 2048, 256)])
 def test_gemm_f8_matches_fake_quant_product(dev, M, N, K):
+    """(512, 512, 256) and (300, 264, 256) have fewer than 64 tiles of 256 x 256, which the reference-grade kernel takes; (2048, 2048, 256) is
+    the smallest shape of full tiles only that the fast kernel takes: 64 tiles, two K-steps."""
     from avllm import lib as L
     from avllm import ops
     A = rnd(M, K, dtype=torch.bfloat16, seed=11)
@@ -63,6 +65,12 @@ def test_gemm_f8_matches_fake_quant_product(dev, M, N, K):
     z = ref + bias.float().cpu()
     ref2 = z * torch.sigmoid(1.702 * z) + Rr.float().cpu()
     assert rel_l2(full, ref2) < 4e-3
+    # every bf16-output form of the accumulator epilogue (gemm_shared.h acc_store_*; full tiles and edge tiles by shape), same oracle, same bar:
+    # residual with and without bias, and each activation with bias
+    for b_, r_, act, want in ((None, Rr, L.ACT_NONE, ref + Rr.float().cpu()), (bias, Rr, L.ACT_NONE, z + Rr.float().cpu()), (bias, None, L.ACT_NONE, z),
+                              (bias, None, L.ACT_GELU, torch.nn.functional.gelu(z)), (bias, None, L.ACT_QUICK_GELU, z * torch.sigmoid(1.702 * z))):
+        got = ops.gemm_f8(Aq, As, Wq, Ws, bias=b_, R=r_, act=act).float().cpu()
+        assert rel_l2(got, want) < 4e-3, (act, b_ is not None, r_ is not None, rel_l2(got, want))
     # how far fp8 is from the unquantised product (information: ~2^-4 / sqrt(3) per operand, averaged over K)
     exact = A.float().cpu() @ W.float().cpu().T
     assert rel_l2(ref, exact) < 6e-2
