@@ -54,6 +54,7 @@ class LlamaCfg:
     rope_scaling: tuple = ()    # () = plain RoPE; (factor, low_freq_factor, high_freq_factor, original_max_position_embeddings) = "llama3" scaling
     qkv_bias: bool = False      # q_proj / k_proj / v_proj carry a (frozen) bias: Qwen2 / Qwen2.5, or a Llama config with attention_bias
     o_bias: bool = False        # o_proj carries one too: attention_bias only
+    qk_norm: bool = False       # per-head RMSNorm on q and k before RoPE (weight [head_dim], the model's eps): Qwen3
 
     @property
     def head_dim(self):
@@ -198,6 +199,11 @@ def synth_llama(c, device, dtype, seed):
         for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
             if getattr(c, "o_bias" if nm == "o_proj" else "qkv_bias", False):
                 sd[f"model.layers.{i}.self_attn.{nm}.bias"] = g.n((dkv if nm in ("k_proj", "v_proj") else d,), 0.3)
+    # and the head norms after the biases, for the same reason
+    if getattr(c, "qk_norm", False):
+        for i in range(c.layers):
+            for nm in ("q_norm", "k_norm"):
+                sd[f"model.layers.{i}.self_attn.{nm}.weight"] = g.n((c.head_dim,), 0.1, 1.0)
     return sd
 
 
@@ -229,7 +235,7 @@ def _cfg_from_hf_dir(path, kind):
     kvh = c.get("num_key_value_heads", c["num_attention_heads"])
     qkv_bias, o_bias = _attn_biases(c.get)
     return LlamaCfg(c["hidden_size"], c["num_attention_heads"], c["num_hidden_layers"], c["intermediate_size"], c["vocab_size"],
-                    c.get("rms_norm_eps", 1e-5), rope, 0 if kvh == c["num_attention_heads"] else kvh, rs, qkv_bias, o_bias)
+                    c.get("rms_norm_eps", 1e-5), rope, 0 if kvh == c["num_attention_heads"] else kvh, rs, qkv_bias, o_bias, _qk_norm(c.get))
 
 
 def _attn_biases(get):
@@ -241,15 +247,26 @@ def _attn_biases(get):
     return ab or get("model_type", None) == "qwen2", ab
 
 
+def _qk_norm(get):
+    """qk_norm of a HuggingFace config read through `get(name, default)`: Qwen3 normalises every q and k head before RoPE.  An exact match:
+    qwen3_moe (and whatever else carries the prefix) is another architecture."""
+    return get("model_type", None) == "qwen3"
+
+
 def check_llama_keys(sd, cfg):
     """The attention-bias keys of a Llama-architecture state dict agree with the config, and tensors of other architectures that would
     otherwise be skipped in silence (the model computed would be a different one) are refused by name."""
     for k in sd:
         if k.endswith(("mlp.gate_proj.bias", "mlp.up_proj.bias", "mlp.down_proj.bias")):
             raise NotImplementedError(f"{k}: MLP biases are not implemented")
-        if k.endswith(("self_attn.q_norm.weight", "self_attn.k_norm.weight")):
-            raise NotImplementedError(f"{k}: q/k norms (Qwen3) are not implemented")
+        if k.endswith(("self_attn.q_norm.weight", "self_attn.k_norm.weight")) and not getattr(cfg, "qk_norm", False):
+            raise NotImplementedError(f"{k}: q/k norms (Qwen3) in the checkpoint, but the config does not declare them (model_type qwen3 "
+                                      "decides it): refused rather than skipped")
     for i in range(cfg.layers):
+        for nm in ("q_norm", "k_norm") if getattr(cfg, "qk_norm", False) else ():
+            key = f"model.layers.{i}.self_attn.{nm}.weight"
+            if key not in sd:
+                raise ValueError(f"{key} is missing but the config says qk_norm=True (model_type qwen3)")
         for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
             key = f"model.layers.{i}.self_attn.{nm}.bias"
             want = bool(getattr(cfg, "o_bias" if nm == "o_proj" else "qkv_bias", False))
@@ -321,10 +338,13 @@ def resolve_arch(llm_path, whisper_model, clip_model, config, weights, seed, lor
                 else:
                     kvh = getattr(hc, "num_key_value_heads", None) or hc.num_attention_heads
                     rope = getattr(hc, "rope_theta", None) or (getattr(hc, "rope_parameters", None) or {}).get("rope_theta", 10000.0)
-                    qkv_bias, o_bias = _attn_biases(lambda name, default, hc=hc: getattr(hc, name, default))
+                    get = lambda name, default, hc=hc: getattr(hc, name, default)
+                    if get("head_dim", None) not in (None, hc.hidden_size // hc.num_attention_heads):
+                        raise NotImplementedError("head_dim != hidden_size / num_attention_heads is not implemented")
+                    qkv_bias, o_bias = _attn_biases(get)
                     parts[kind] = LlamaCfg(hc.hidden_size, hc.num_attention_heads, hc.num_hidden_layers, hc.intermediate_size,
                                            hc.vocab_size, hc.rms_norm_eps, rope, 0 if kvh == hc.num_attention_heads else kvh,
-                                           _rope_scaling(getattr(hc, "rope_scaling", None) or {}), qkv_bias, o_bias)
+                                           _rope_scaling(getattr(hc, "rope_scaling", None) or {}), qkv_bias, o_bias, _qk_norm(get))
             elif isinstance(path, str) and os.path.isdir(path) and os.path.exists(os.path.join(path, "config.json")):
                 parts[kind] = _cfg_from_hf_dir(path, kind)
             else:

@@ -283,6 +283,10 @@ class LlamaEngine:
                 ly.bqkv = put(torch.cat([sd[p + f"self_attn.{nm}.bias"] for nm in LORA_TARGETS[:3]], 0)).data_ptr()
             if getattr(cfg, "o_bias", False):
                 ly.bo = put(sd[p + "self_attn.o_proj.bias"]).data_ptr()
+            # frozen per-head q/k RMSNorm weights [hd] (Qwen3), in the model dtype like every norm weight (fp32 mode keeps them fp32)
+            if getattr(cfg, "qk_norm", False):
+                ly.q_norm_w = put(sd[p + "self_attn.q_norm.weight"]).data_ptr()
+                ly.k_norm_w = put(sd[p + "self_attn.k_norm.weight"]).data_ptr()
             if training:
                 ly.wqkv_t, ly.wo_t = put(wqkv.t()).data_ptr(), put(wo.t()).data_ptr()
                 ly.wgu_t, ly.wdown_t = put(wgu.t()).data_ptr(), put(wdown.t()).data_ptr()

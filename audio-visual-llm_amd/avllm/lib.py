@@ -56,7 +56,7 @@ class LlamaLayer(C.Structure):
                [("lora", LoraMod * 4)] + [(n, vp) for n in ("wqkv8", "sqkv8", "wo8", "so8", "wgu8", "sgu8", "wdown8", "sdown8")] + \
                [(n, vp) for n in ("eqkv8", "eo8", "egu8", "edown8")] + \
                [(n, vp) for n in ("wqkv4", "wo4", "wgu4", "wdown4", "eqkv4", "eo4", "egu4", "edown4")] + \
-               [(n, vp) for n in ("bqkv", "bo")]
+               [(n, vp) for n in ("bqkv", "bo")] + [(n, vp) for n in ("q_norm_w", "k_norm_w")]
 
 
 class Llama(C.Structure):
@@ -79,7 +79,7 @@ class DecProjDesc(C.Structure):
                 ("C", vp), ("ldc", i64), ("out_f32", i32), ("R", vp), ("ldr", i64), ("dq", i32), ("dkv", i32), ("hd", i32), ("rope", vp),
                 ("kc", vp), ("vc", vp), ("Tmax", i32), ("pos", i32), ("pos_dev", vp),
                 ("lora_t", vp), ("ld_lora_t", i64), ("lora_b", vp * 3), ("lora_r", i32), ("lora_scale", f32), ("W8", vp), ("E8", vp), ("W4", vp),
-                ("bias", vp)]
+                ("bias", vp), ("raw_qkv", i32)]
 
 
 class StepState(C.Structure):
@@ -190,6 +190,8 @@ _SIGS = {
     "avllm_norm_mxq": ([vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, f32, vp], i32),
     "avllm_lora_rank3": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, i32, vp], i32),
     "avllm_gemm_tn_multi": ([vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, i32, vp], i32),
+    "avllm_qk_norm_rope": ([vp, i64, i64, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp], i32),
+    "avllm_qk_norm_bwd": ([vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, i32, vp], i32),
     "avllm_attention_decode": ([vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, f32, i32, i32, vp], i32),
 }
 

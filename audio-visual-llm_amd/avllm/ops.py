@@ -114,6 +114,31 @@ def rope_tab_(x2d, T, heads, hd, tab, inverse=False):
     return x2d
 
 
+def qk_norm_rope_(x2d, T, heads, kv_heads, hd, q_w, k_w, eps, tab, save=False, kc=None, vc=None, pos=0, pos_dev=None):
+    """Per-head RMSNorm of the q and k heads + rotary embedding, in place on the first (heads + kv_heads) * hd columns of the [rows, ld] q|k|v
+    view x2d (avllm_qk_norm_rope); row r reads table row r % T.  save: -> (pre-norm q|k [rows, (heads + kv_heads) hd], rstd [rows, heads +
+    kv_heads] f32).  kc, vc [rows, Tmax, kv_heads hd]: the cache form (T == 1): rotated k and untouched v go to cache row pos (+ *pos_dev)."""
+    rows, nqk = x2d.shape[0], heads + kv_heads
+    assert tab.dtype == torch.float32 and tab.is_contiguous() and tab.numel() == T * hd and q_w.dtype == x2d.dtype and k_w.dtype == x2d.dtype
+    pre = torch.empty(rows, nqk * hd, device=x2d.device, dtype=x2d.dtype) if save else None
+    rstd = torch.empty(rows, nqk, device=x2d.device, dtype=torch.float32) if save else None
+    if kc is not None:
+        assert kc.shape == vc.shape == (rows, kc.shape[1], kv_heads * hd) and kc.is_contiguous() and vc.is_contiguous() and kc.dtype == x2d.dtype
+    L.check(L.load().avllm_qk_norm_rope(L.ptr(x2d), _ld(x2d), rows, T, heads, kv_heads, hd, L.ptr(q_w), L.ptr(k_w), eps, L.ptr(tab), L.ptr(pre),
+                                        L.ptr(rstd), L.ptr(kc), L.ptr(vc), kc.shape[1] if kc is not None else 0, pos, L.ptr(pos_dev), L.dt_of(x2d),
+                                        L.stream_ptr()))
+    return pre, rstd
+
+
+def qk_norm_bwd_(dy2d, heads, kv_heads, hd, q_w, k_w, pre, rstd):
+    """In place on the q and k slices of dy2d [rows, ld]: the gradient of the normed pre-RoPE heads -> the gradient of the projections'
+    outputs, from qk_norm_rope_'s saves (avllm_qk_norm_bwd)."""
+    assert pre.is_contiguous() and rstd.is_contiguous() and rstd.dtype == torch.float32 and pre.dtype == dy2d.dtype
+    L.check(L.load().avllm_qk_norm_bwd(L.ptr(dy2d), _ld(dy2d), dy2d.shape[0], heads, kv_heads, hd, L.ptr(q_w), L.ptr(k_w), L.ptr(pre), L.ptr(rstd),
+                                       L.dt_of(dy2d), L.stream_ptr()))
+    return dy2d
+
+
 def kv_append(k, v, kc, vc, T, pos0):
     """kc[b, pos0 + t, :] = k[b*T + t, :] and the same for v (avllm_kv_append): k, v [B*T, d] views with one row stride, caches [B, Tmax, d] contiguous."""
     B, Tmax, d = kc.shape
@@ -622,14 +647,15 @@ def norm_mxq(x, w, b=None, eps=1e-5, want_y=False, want_rstd=False):
 
 
 def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=False, rope=None, kc=None, vc=None, pos=0, pos_dev=None, dq=0, dkv=0, hd=0,
-             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None, W4=None, bias=None):
+             lora_t=None, lora_b=None, lora_r=0, lora_scale=0.0, W8=None, E8=None, W4=None, bias=None, raw_qkv=False):
     """One projection of a decode token step (avllm_dec_proj): A [M<=16, K] bf16, W [rows, K] bf16.
     mode 0: out[M, rows] = rmsnorm?(A) . W^T (+ R);  mode 1: W = [gate; up], out[M, rows/2] = silu(gate) * up;
     mode 2: W = [q; k; v]: RoPE on q, k with `rope` [hd/2, 2]; q -> out[M, dq]; k, v -> kc / vc [M, Tmax, dkv] at row pos (+ *pos_dev);
     hd must be a power of two >= 32 (any other head dim raises ValueError).
     fp8 weight form: W8 = e4m3 codes uint8 [rows, K], E8 = exponents uint8 [rows, K/32] (mx_quantize(w, 2)); W may then be None.
     fp4 weight form: W4 = MXFP4 codes uint8 [rows, K/2], E8 = their exponents uint8 [rows, K/32] (mx4_quantize(w)); not together with W8.
-    bias: bf16 [rows] in W's row order, added before adapters, residual and RoPE (modes 0 and 2)."""
+    bias: bf16 [rows] in W's row order, added before adapters, residual and RoPE (modes 0 and 2).
+    raw_qkv (mode 2): no rotation, no cache write; q, k and v all go to out[M, rows] in logical column order (a head norm follows: qk_norm_rope_)."""
     M, K = A.shape
     d = L.DecProjDesc()
     Wr = W4 if W4 is not None else (W8 if W8 is not None else W)
@@ -644,11 +670,13 @@ def dec_proj(A, W, mode=0, norm_w=None, eps=1e-5, R=None, out=None, out_f32=Fals
     N = Wr.shape[0] // 2 if mode == 1 else Wr.shape[0]
     d.N = N
     if out is None:
-        out = torch.empty(M, dq if mode == 2 else N, device=A.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+        out = torch.empty(M, dq if mode == 2 and not raw_qkv else N, device=A.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
     d.C, d.ldc, d.out_f32 = L.ptr(out), _ld(out), int(out.dtype == torch.float32)
     if R is not None:
         d.R, d.ldr = L.ptr(R), _ld(R)
-    if mode == 2:
+    if mode == 2 and raw_qkv:
+        d.dq, d.dkv, d.hd, d.raw_qkv = dq, dkv, hd, 1
+    elif mode == 2:
         d.dq, d.dkv, d.hd, d.rope, d.kc, d.vc, d.Tmax, d.pos = dq, dkv, hd, L.ptr(rope), L.ptr(kc), L.ptr(vc), kc.shape[1], pos
         d.pos_dev = L.ptr(pos_dev)
     if lora_t is not None:          # adapters: lora_t [M, >= 64 per module] f32 rank-side products, lora_b = padded B images [rows, 64] (one, or q / k / v)

@@ -87,6 +87,12 @@ int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st);
 struct AvRopeScale { float factor = 1.f, low_freq_factor = 1.f, high_freq_factor = 4.f; int orig_ctx = 0; };      // orig_ctx == 0: plain RoPE
 int av_rope_table(float* tab, int T, int hd, int pos0, float theta, hipStream_t st, const int* pos_dev = nullptr, AvRopeScale sc = AvRopeScale());
 int av_rope_tab(void* x, long ld, long rows, int T, int heads, int hd, const float* tab, int inverse, int dtype, hipStream_t st);
+// per-head RMSNorm of the q and k heads + rotary embedding in place (qk_norm.hip); pre / rstd: optional saves for av_qk_norm_bwd; kc / vc:
+// cache form (T == 1): rotated k and untouched v go to cache row pos + *pos_dev instead, q stays in x
+int av_qk_norm_rope(void* x, long ld, long M, int T, int H, int Hkv, int hd, const void* wq, const void* wk, float eps, const float* tab, void* pre,
+                    float* rstd, void* kc, void* vc, int Tmax, int pos, const int* pos_dev, int dtype, hipStream_t st);
+int av_qk_norm_bwd(void* dy, long ld, long M, int H, int Hkv, int hd, const void* wq, const void* wk, const void* pre, const float* rstd, int dtype,
+                   hipStream_t st);
 int av_dropout(const void* x, void* y, long rows, int d, uint32_t seed, float p, int dtype, hipStream_t st, const uint32_t* seed_dev = nullptr);
 bool av_lora_dx_masked_supported(int dtype, int N, int r, const long* ldt, const long* ldat, int nj, long ldr, long ldo);
 int av_lora_dx_masked(const void* const* T, const long* ldt, const void* const* AT, const long* ldat, const uint32_t* seeds, int nj, int r,

@@ -10,6 +10,9 @@
 //   dec_proj<NORM, SwiGLU>   RMSNorm folded in, gate|up projection, silu(gate)*up in the epilogue
 //   dec_proj<plain + R>      down projection + residual
 //
+// A model whose q and k heads are normalised before RoPE (Qwen3) runs 6: the q|k|v projection leaves its columns raw (raw_qkv below) and one
+// avllm_qk_norm_rope launch (qk_norm.hip) normalises, rotates and writes the cache row before attn_decode1.
+//
 // dec_proj: M <= 16 activation rows ride as one MFMA operand, a workgroup owns 16 weight rows (a contiguous 16*K*2-byte block of
 // HBM), its 8 waves split K, each wave keeps a ring of DEPTH 1 KiB weight loads in flight (non-temporal: the stream must not evict
 // the activations from L2) and the 8 partial 16x16 tiles meet in LDS.
@@ -52,6 +55,10 @@ struct DecArgs {
     // frozen projection bias (Qwen2 q|k|v, attention_bias o): [N] in logical output column order, added to the fp32 sum after the RMS scale,
     // before the adapter term, the residual and RoPE (peft: base_layer(x) with its bias, + adapter).  PLAIN and QKV only.
     const bf16* bias;
+    // QKV: columns below rot_end are rotated (their rows paired inside a workgroup), columns below q_end go to C, the rest to the cache.  The
+    // fused form has rot_end = dq + dkv, q_end = dq; raw_qkv (a head norm follows: qk_norm.hip) has rot_end = 0, q_end = N: the plain row
+    // mapping, no rotation, no cache write.  Run-time data, so both forms are the same kernels.
+    int rot_end, q_end;
 };
 
 // fragment row fr (0..15) of workgroup b -> weight row, and the logical output column it produces
@@ -62,7 +69,7 @@ __device__ __forceinline__ int dec_wrow(const DecArgs& a, int b, int fr, int& co
     }
     if (a.mode == DEC_QKV) {
         const int c0 = 16 * b;
-        if (c0 < a.dq + a.dkv) {        // rotary region: 8 columns of the first half of a head + their 8 partners
+        if (c0 < a.rot_end) {           // rotary region: 8 columns of the first half of a head + their 8 partners
             const int per_head = a.hd >> 4;
             const int h = b / per_head, s = b - h * per_head;
             col = h * a.hd + 8 * s + (fr & 7) + (fr < 8 ? 0 : a.hd >> 1);
@@ -369,7 +376,7 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     // DEC_QKV
     const int pos = a.pos + (a.pos_dev ? *a.pos_dev : 0);
     float o = s;
-    if (ocol < a.dq + a.dkv) {
+    if (ocol < a.rot_end) {
         const int i = (ocol % a.hd) & ((a.hd >> 1) - 1);
         const float c = a.rope[2 * i], sn = a.rope[2 * i + 1];
         o = nn < 8 ? s * c - other * sn : s * c + other * sn;
@@ -377,7 +384,7 @@ __device__ __forceinline__ void dec_proj_body(const DecArgs& a) {
     // position from device memory: the host could not check it.  A step replayed past the end of the cache writes nothing (the cache
     // rows of the last valid position stay as they are) instead of running over [B, Tmax, dkv]; attn_decode1_kernel clamps its length alike.
     const bool in_cache = pos >= 0 && pos < a.Tmax;
-    if (ocol < a.dq) ((bf16*)a.C)[(long)m * a.ldc + ocol] = (bf16)o;
+    if (ocol < a.q_end) ((bf16*)a.C)[(long)m * a.ldc + ocol] = (bf16)o;
     else if (!in_cache) return;
     else if (ocol < a.dq + a.dkv) a.kc[((long)m * a.Tmax + pos) * a.dkv + ocol - a.dq] = (bf16)o;
     else a.vc[((long)m * a.Tmax + pos) * a.dkv + ocol - a.dq - a.dkv] = (bf16)o;
@@ -553,11 +560,17 @@ int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
         AV_CHECK_ARG(d->C && d->ldc >= d->N && !d->R && !d->out_f32, "dec_proj(SwiGLU): bf16 output [M,F] without residual");
         a.F = d->N;
     } else {
-        AV_CHECK_ARG(d->C && d->kc && d->vc && d->rope && d->dq > 0 && d->dkv > 0 && d->N == d->dq + 2 * d->dkv && d->dq % d->hd == 0 && d->dkv % d->hd == 0 &&
-                     d->ldc >= d->dq && !d->R && !d->out_f32, "dec_proj(q|k|v): N=%d must be dq + 2 dkv (dq=%d dkv=%d) in whole heads of %d", d->N, d->dq, d->dkv, d->hd);
-        AV_CHECK_ARG(d->Tmax > 0 && d->pos >= 0 && (d->pos_dev || d->pos < d->Tmax), "dec_proj(q|k|v): pos=%d outside the cache (Tmax=%d)", d->pos, d->Tmax);
-        a.dq = d->dq; a.dkv = d->dkv; a.hd = d->hd; a.rope = d->rope; a.kc = (bf16*)d->kc; a.vc = (bf16*)d->vc; a.Tmax = d->Tmax; a.pos = d->pos;
-        a.pos_dev = d->pos_dev;
+        const bool raw = d->raw_qkv != 0;
+        AV_CHECK_ARG(d->C && (raw || (d->kc && d->vc && d->rope)) && d->dq > 0 && d->dkv > 0 && d->N == d->dq + 2 * d->dkv && d->dq % d->hd == 0 &&
+                     d->dkv % d->hd == 0 && d->ldc >= (raw ? d->N : d->dq) && !d->R && !d->out_f32,
+                     "dec_proj(q|k|v): N=%d must be dq + 2 dkv (dq=%d dkv=%d) in whole heads of %d; raw_qkv: ldc >= N", d->N, d->dq, d->dkv, d->hd);
+        a.dq = d->dq; a.dkv = d->dkv; a.hd = d->hd;
+        if (raw) { a.rot_end = 0; a.q_end = d->N; }
+        else {
+            AV_CHECK_ARG(d->Tmax > 0 && d->pos >= 0 && (d->pos_dev || d->pos < d->Tmax), "dec_proj(q|k|v): pos=%d outside the cache (Tmax=%d)", d->pos, d->Tmax);
+            a.rot_end = d->dq + d->dkv; a.q_end = d->dq;
+            a.rope = d->rope; a.kc = (bf16*)d->kc; a.vc = (bf16*)d->vc; a.Tmax = d->Tmax; a.pos = d->pos; a.pos_dev = d->pos_dev;
+        }
     }
     if (d->lora_t) {
         const int nmod = d->mode == DEC_QKV ? 3 : 1;

@@ -176,9 +176,13 @@ inline const void* llama_bias(const avllm_llama* m, const avllm_llama_layer& P, 
     return P.bqkv ? (const char*)P.bqkv + (size_t)llama_off(m, j) * av_dtype_size(m->dtype) : nullptr;
 }
 
+// per-head q/k RMSNorm (Qwen3): a model has it on every layer or on none (check_llama)
+inline bool llama_qk_norm(const avllm_llama* m) { return m->layer && m->layer[0].q_norm_w != nullptr; }
+
 struct LlamaLayerAct {
     void *xn1, *qkv, *att, *tqkv, *to, *h1, *gu;
     float *rstd1, *rstd2, *lse;
+    void* qk_pre; float* qk_rstd;      // q/k head norm only: the pre-norm q|k [M, d + dkv] and rstd [M, H + Hkv] for avllm_qk_norm_bwd
 };
 struct LlamaTrainWs {
     void** resid;            // host array [layers+1]
@@ -227,6 +231,13 @@ void carve_llama_train(const avllm_llama* m, int B, int S, Bump& b, LlamaTrainWs
     w.dtqkv = b.take((size_t)M * 3 * AVLLM_LORA_PAD * es);
     w.dto = b.take((size_t)M * AVLLM_LORA_PAD * es);
     if (m->fp8) carve_f8(b, w.f8, M, f > d ? f : d);
+    // after everything else, and only for a model that has the head norms: every other model's layout and size stay what they were
+    for (int l = 0; l < m->layers; ++l) {
+        act[l].qk_pre = nullptr; act[l].qk_rstd = nullptr;
+        if (!llama_qk_norm(m)) continue;
+        act[l].qk_pre = b.take((size_t)M * (d + llama_dkv(m)) * es);
+        act[l].qk_rstd = (float*)b.take((size_t)M * (m->heads + llama_kv_heads(m)) * 4);
+    }
 }
 // The training workspace laid out in ws (null with an unlimited size: the dry run that sizes it), with the host arrays its layout points into
 struct LlamaTrainFrame {
@@ -239,6 +250,12 @@ int check_llama(const avllm_llama* m) {
     AV_CHECK_ARG(m->d % m->heads == 0 && m->d % 64 == 0 && m->ffn % 64 == 0, "llama: d=%d ffn=%d must be multiples of 64", m->d, m->ffn);
     AV_CHECK_ARG(m->layers > 0 && m->layers <= 256, "llama: layers=%d", m->layers);
     AV_CHECK_ARG(m->kv_heads >= 0 && (m->kv_heads == 0 || m->heads % m->kv_heads == 0), "llama: heads=%d kv_heads=%d", m->heads, m->kv_heads);
+    for (int l = 0; l < m->layers; ++l) {
+        const avllm_llama_layer& P = m->layer[l];
+        AV_CHECK_ARG((P.q_norm_w != nullptr) == (P.k_norm_w != nullptr) && (P.q_norm_w != nullptr) == llama_qk_norm(m),
+                     "llama layer %d: q_norm_w and k_norm_w go together, on every layer or on none", l);
+    }
+    AV_CHECK_ARG(!llama_qk_norm(m) || m->d / m->heads == 64 || m->d / m->heads == 128, "llama: q/k head norms need a head dim of 64 or 128 (%d)", m->d / m->heads);
     if (m->fp8)
         for (int l = 0; l < m->layers; ++l) {
             const avllm_llama_layer& P = m->layer[l];
@@ -478,7 +495,10 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
             AV_TRY(lora_linear(m, a.xn1, d, fq ? nullptr : (const char*)P.wqkv + (size_t)v[j].off * d * es, llama_bias(m, P, j), v[j].wid, *v[j].mod,
                                xl, v[j].seed, dr.fused_p(), v[j].t, v[j].ldt, batch_qkv, (char*)a.qkv + (size_t)v[j].off * es, qw, nullptr, 0, M, st));
         }
-        AV_TRY(av_rope_tab(a.qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));      // q and k slices are adjacent: H + Hkv heads
+        // q and k slices are adjacent: H + Hkv heads.  With head norms the one pass normalises, rotates and saves what its backward reads.
+        if (P.q_norm_w) AV_TRY(av_qk_norm_rope(a.qkv, qw, M, S, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, a.qk_pre, a.qk_rstd, nullptr,
+                                               nullptr, 0, 0, nullptr, dt, st));
+        else AV_TRY(av_rope_tab(a.qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));
         const char* qkv = (const char*)a.qkv;
         AV_TRY(av_attention_fwd(qkv, qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, a.att, a.lse, B, S, S, H, hd, qw, qw,
                                 qw, d, 1.0f / sqrtf((float)hd), 1, dt, 0, st, Hkv));
@@ -566,6 +586,8 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
                                 dqkv + (size_t)(d + dkv) * es, w.delta, B, S, H, hd, qw, qw, qw, d, qw, qw, qw,
                                 1.0f / sqrtf((float)hd), 1, dt, 0, st, Hkv, fuse_rope ? w.rope_tab : nullptr));
         if (!fuse_rope) AV_TRY(av_rope_tab(dqkv, qw, M, S, H + Hkv, hd, w.rope_tab, 1, dt, st));
+        // dqkv's q and k slices now hold the gradient of the normed pre-RoPE heads: through the head norm, before any projection gradient reads it
+        if (P.q_norm_w) AV_TRY(av_qk_norm_bwd(dqkv, qw, M, H, Hkv, hd, P.q_norm_w, P.k_norm_w, a.qk_pre, a.qk_rstd, dt, st));
         // ---- q,k,v projections (+LoRA)
         bool any = false, contiguous = true;      // contiguous: all three present, their AT_pad images the slices of one [d,192] matrix
         for (int j = 0; j < 3; ++j) { any |= v[j].mod->A_pad != nullptr; contiguous &= v[j].mod->A_pad && v[j].at_slice; }
@@ -639,7 +661,9 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
                            w.t, AVLLM_LORA_PAD, false, (char*)w.qkv + (size_t)llama_off(m, j) * es, qw, nullptr, 0, M, st));
     char* qkv = (char*)w.qkv;
     if (l == 0) AV_TRY(av_rope_table(w.rope_tab, S, hd, pos0, m->theta, st, nullptr, llama_rope_scale(m)));
-    AV_TRY(av_rope_tab(qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));
+    if (P.q_norm_w) AV_TRY(av_qk_norm_rope(qkv, qw, M, S, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                                           nullptr, dt, st));
+    else AV_TRY(av_rope_tab(qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));
     AV_TRY(av_kv_append(qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, qw, kcl, vcl, B, S, pos0, Tmax, dkv, dt, st));
     const float scale = 1.0f / sqrtf((float)hd);
     if (S == 1) {
@@ -751,7 +775,12 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         p.lora_t = w.lt; p.ld_lora_t = LT; p.lora_r = m->lora_r; p.lora_scale = m->lora_scale;
         for (int j = 0; j < 3; ++j) p.lora_b[j] = P.lora[j].B_pad;
     }
+    // head norms: a head's columns belong to hd / 16 workgroups of the projection, so q|k|v leave it raw and one launch normalises, rotates
+    // and writes the cache row (6 launches per layer, 8 with adapters)
+    p.raw_qkv = P.q_norm_w != nullptr;
     AV_TRY(av_dec_proj(&p, st));
+    if (P.q_norm_w) AV_TRY(av_qk_norm_rope(w.qkv, qw, B, 1, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, kcl, vcl, Tmax, pos,
+                                           pos_dev, AV_BF16, st));
     AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
     p = {};
     if (lora) {      // lora_A(attention output) -> lt[:, 192:192+16]: only the rank's own 16 rows of the padded image are streamed

@@ -501,6 +501,11 @@ typedef struct avllm_llama_layer {
      * every path (training forward in bf16 / fp32 / fp8, prefill, token step in every weight form); peft's order: base_layer(x) with its bias,
      * plus the adapter term, then RoPE.  No gradient is formed for them. */
     const void *bqkv, *bo;
+    /* per-head RMSNorm weights of q and k, [hd] each in the model dtype (Qwen3: transformers/models/qwen3/modeling_qwen3.py
+     * Qwen3Attention.forward, q_norm / k_norm); NULL = none, either both or neither.  eps is the model's.  Order on every path: base_layer(x)
+     * with its bias, plus the adapter term, then the head norm, then RoPE.  Frozen: no gradient is formed for them.  Qwen3-1.7B / 8B / 14B
+     * geometry (hd = d / heads = 128); hd is 64 or 128. */
+    const void *q_norm_w, *k_norm_w;
 } avllm_llama_layer;
 
 typedef struct avllm_llama {
@@ -633,8 +638,32 @@ typedef struct avllm_dec_proj_desc {
      * fp32 sum after the norm fold's scale and before the adapter term, the residual and RoPE.  Modes 0 and 2; refused in mode 1.  NULL: the
      * launch is the bias-free kernel (the epilogue is templated on the bias). */
     const void* bias;
+    /* raw_qkv != 0 (mode 2 only): the projection of a model whose q and k heads are normalised before the rotary embedding (Qwen3).  A head's
+     * columns belong to several workgroups, so the norm cannot sit in this epilogue: no rotation and no cache write here; q, k and v all go
+     * to C[M, N] in logical column order (ldc >= N; the plain col = 16 b + fr row mapping), bias and adapter terms added exactly as above;
+     * rope, kc, vc, Tmax, pos, pos_dev are ignored.  One avllm_qk_norm_rope launch in its cache form follows.  Run-time data of the same
+     * kernels: with raw_qkv == 0 a launch is what it always was. */
+    int32_t raw_qkv;
 } avllm_dec_proj_desc;
 int avllm_dec_proj(const avllm_dec_proj_desc* d, void* stream);
+/* Per-head RMSNorm of q and k fused with the rotary embedding (transformers/models/qwen3/modeling_qwen3.py Qwen3Attention.forward:
+ * q_norm(q_proj(x).view(.., hd)), k_norm(..), then apply_rotary_pos_emb).  x [rows, ld] is a q|k|v buffer whose first (heads + kv_heads) * hd
+ * columns are the adjacent q and k slices; they are rewritten in place, v and any padding columns are never written.  For each (row, head):
+ * y = x * rsqrt(mean(x^2) + eps) * w with w = q_norm_w or k_norm_w [hd] by head index (no "+1" offset), then the rotary pair (i, i + hd/2)
+ * from tab [T][hd/2][2] (avllm_rope_table; row r reads table row r % T).  fp32 arithmetic, one rounding.  hd is 64 or 128; dtype f32 / bf16;
+ * rows of ld elements are multiples of 16 bytes.
+ *   pre, rstd (optional, training): the pre-norm q|k values [rows, (heads + kv_heads) * hd] and rstd [rows, heads + kv_heads] f32.
+ *   kc, vc (optional, both or neither: the token step): T == 1 and row m is sequence m; the rotated k and the untouched v of the row go to
+ *   cache row kc / vc [m][pos + *pos_dev][kv_heads * hd] (pos_dev may be NULL) when 0 <= pos + *pos_dev < Tmax and nowhere otherwise; q is
+ *   rewritten in x, the k and v columns of x stay as they are. */
+int avllm_qk_norm_rope(void* x, int64_t ld, int64_t rows, int32_t T, int32_t heads, int32_t kv_heads, int32_t hd, const void* q_norm_w,
+                       const void* k_norm_w, float eps, const float* tab, void* pre, float* rstd, void* kc, void* vc, int32_t Tmax, int32_t pos,
+                       const int32_t* pos_dev, int32_t dtype, void* stream);
+/* Its backward, in place on the q and k slices of dy [rows, ld]: dy arrives as the gradient with respect to the normed PRE-RoPE heads (what
+ * avllm_attention_bwd_rope leaves, or avllm_attention_bwd followed by avllm_rope_tab(inverse = 1)) and leaves as
+ * dx = rstd * (g - xhat * mean(g * xhat)) with g = w * dy, xhat = pre * rstd, from the forward's saves.  No weight gradient: the norms are frozen. */
+int avllm_qk_norm_bwd(void* dy, int64_t ld, int64_t rows, int32_t heads, int32_t kv_heads, int32_t hd, const void* q_norm_w, const void* k_norm_w,
+                      const void* pre, const float* rstd, int32_t dtype, void* stream);
 /* Single-query attention over the cache rows [0, Tk + *tk_dev) (tk_dev may be NULL) of kc/vc [B][Tmax][(H/kv_group)*hd]: one pass with
  * an online softmax; q [B, H*hd] (row stride ldq), o [B, H*hd] (ldo).  LlamaAttention.forward with q_len == 1 (eager softmax(QK^T/sqrt(hd))V). */
 int avllm_attention_decode(const void* q, int64_t ldq, const void* kc, const void* vc, void* o, int64_t ldo, int32_t B, int32_t H, int32_t hd,
