@@ -82,6 +82,16 @@ class DecProjDesc(C.Structure):
                 ("bias", vp), ("raw_qkv", i32)]
 
 
+class LogitsProcDesc(C.Structure):
+    """avllm_logits_proc_desc (include/avllm.h): avllm_logits_process's arguments plus the four device tables of avllm_logits_process_ex."""
+    _fields_ = [("scores", vp), ("ld", i64), ("rows", i64), ("V", i32), ("dtype", i32),
+                ("history", vp), ("ldh", i64), ("append", vp), ("cur", i32), ("cur_dev", vp),
+                ("repetition_penalty", f32), ("no_repeat_ngram_size", i32), ("min_new_tokens", i32), ("eos", i64), ("log_softmax", i32),
+                ("bias_tokens", vp), ("bias_lengths", vp), ("bias_values", vp), ("n_bias", i32), ("bias_max_len", i32),
+                ("bad_tokens", vp), ("bad_lengths", vp), ("n_bad", i32), ("bad_max_len", i32),
+                ("suppress", vp), ("n_suppress", i32), ("begin_suppress", vp), ("n_begin_suppress", i32)]
+
+
 class StepState(C.Structure):
     """avllm_step_state: per-step scalars in DEVICE memory (this mirror is only used for sizes / field offsets / host reads)."""
     _fields_ = [("step", C.c_uint32), ("dropout_seed", C.c_uint32), ("lr", f32), ("bc1", f32), ("bc2_sqrt", f32), ("skipped", f32),
@@ -140,6 +150,7 @@ _SIGS = {
     "avllm_beam_topk": ([vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp], i32),
     "avllm_beam_topk_logprobs": ([vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp], i32),
     "avllm_logits_process": ([vp, i64, i64, i32, vp, i64, vp, i32, vp, f32, i32, i32, i64, i32, i32, vp], i32),
+    "avllm_logits_process_ex": ([C.POINTER(LogitsProcDesc), vp], i32),
     "avllm_kv_gather_rows": ([vp, vp, i32, i64, vp, vp, i32, i64, i32, i32, vp, i32, i32, i32, vp], i32),
     "avllm_embedding": ([vp, vp, vp, i64, i32, i32, vp], i32),
     "avllm_cast": ([vp, i32, vp, i32, i64, vp], i32),

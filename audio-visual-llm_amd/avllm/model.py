@@ -16,6 +16,8 @@ Differences that are deliberate and documented:
 from __future__ import annotations
 
 import logging
+import math
+import numbers
 import os
 import types
 
@@ -26,7 +28,30 @@ from . import ops
 from .arch import ModelCfg, resolve_arch
 from .connector import ModalityConnector, create_modality_connector
 from .engine import ClipEngine, LlamaEngine, WhisperEngine
-from .tokenizer import load_tokenizer
+from .tokenizer import load_tokenizer, phrase_token_ids
+
+
+def hotword_sequence_bias(tokenizer, hotwords, hotword_bias, sequence_bias=None):
+    """generate(hotwords=, hotword_bias=) as a sequence_bias dict: each hotword is tokenised with and without a leading space (no special
+    tokens), and every prefix t[:1] ... t[:L] of each distinct tokenisation gets hotword_bias, so the whole path of the word is boosted,
+    not only its last token.  Prefixes shared by several hotwords are merged into one entry.  The user's own sequence_bias entries come
+    first; a hotword prefix equal to one of their keys is a ValueError (which bias is meant cannot be told).
+    HF's SequenceBiasLogitsProcessor considers a sequence of L tokens only once L tokens have been generated (L <= n, not L - 1 <= n), so
+    token k > 1 of a hotword is not boosted while fewer than k tokens exist: a hotword that starts the utterance gets its first token
+    boosted and the rest only from the point where the history is as long as the prefix."""
+    if isinstance(hotwords, str) or not isinstance(hotwords, (list, tuple)) or any(not isinstance(w, str) or not w.strip() for w in hotwords):
+        raise ValueError(f"hotwords must be a list of non-empty strings, got {hotwords!r}")
+    if isinstance(hotword_bias, bool) or not isinstance(hotword_bias, numbers.Real) or not math.isfinite(hotword_bias):
+        raise ValueError(f"hotword_bias must be a finite float, got {hotword_bias!r}")
+    out = dict(ops._normalise_logits_bias(sequence_bias, None, None, None, None, None)[0] or {})
+    user = set(out)
+    for w in hotwords:
+        for ids in phrase_token_ids(tokenizer, w):
+            for k in range(1, len(ids) + 1):
+                if ids[:k] in user:
+                    raise ValueError(f"hotword {w!r}: its token prefix {ids[:k]} is also a sequence_bias key")
+                out[ids[:k]] = float(hotword_bias)
+    return out
 
 
 class _LoraLoss(torch.autograd.Function):
@@ -452,7 +477,8 @@ class ClipWhisperModel:
     @torch.no_grad()
     def generate(self, audio=None, video=None, prompt=None, pixel_values=None, max_new_tokens=100, do_sample=False,
                  temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False,
-                 return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0):
+                 return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sequence_bias=None,
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, hotwords=None, hotword_bias=0.0):
         """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search, or with do_sample=True its sampling: temperature -> top_k
         (HF's GenerationConfig default 50; 0 = off) -> top_p -> one draw per row on the device (ops.sample_rows).  seed=None draws the
         seed from torch's default CPU generator, so torch.manual_seed makes a sampled run repeat; row b draws with seed + b.
@@ -462,7 +488,15 @@ class ClipWhisperModel:
         repetition_penalty (> 0, 1.0 = off), no_repeat_ngram_size (0 = off) and min_new_tokens are HF's logits processors of those names, in
         every mode, applied on the device (ops.logits_process) to a row's generated tokens, which is all HF's processors see with
         inputs_embeds: on the logits before the argmax or the sampling chain, and in beam search on the log-probabilities (log-softmax
-        first, as HF's _beam_search does).  With the three defaults nothing is launched."""
+        first, as HF's _beam_search does).  With the three defaults nothing is launched.
+        sequence_bias ({tuple of ids: float} or [[ids, float], ...]), bad_words_ids ([[ids], ...]), suppress_tokens and begin_suppress_tokens
+        (lists of ids) are HF's keywords of those names, in the same launch and in HF's order: sequence bias, repetition penalty, n-gram
+        ban, bad words, min_new_tokens, suppress, begin-suppress (the first generated token, HF's begin_index 0 with inputs_embeds).  Their
+        device tables are built once per call (ops.logits_bias_tables; its capacities are refused by name); with all of them None nothing
+        new is launched or allocated.  The 1024-token limit of the older processors also holds when a sequence has more than one token.
+        hotwords: a list of strings boosted by hotword_bias (contextual biasing): each is tokenised with and without a leading space and
+        every prefix of each tokenisation becomes a sequence_bias entry (hotword_sequence_bias below).  HF considers a sequence of L tokens
+        only once L tokens have been generated, so token k of a hotword is not boosted when the word starts the utterance."""
         if video is None and pixel_values is not None:
             video = pixel_values
         if max_new_tokens is None:
@@ -488,6 +522,19 @@ class ClipWhisperModel:
                 raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_new_tokens support at most {ops.LOGITS_PROCESS_MAX_HISTORY} "
                                  f"new tokens, got max_new_tokens = {max_new_tokens}")
             proc = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens))
+        if hotwords:
+            sequence_bias = hotword_sequence_bias(self.tokenizer, hotwords, hotword_bias, sequence_bias)
+        tables = {}
+        if not (sequence_bias is None and bad_words_ids is None and suppress_tokens is None and begin_suppress_tokens is None):
+            tables = ops.logits_bias_tables(sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens, vocab=self.cfg.llama.vocab,
+                                            eos=self.eos_token_id, device=self.device)
+        # the row history feeds the three older processors and sequences of more than one token
+        need_hist = bool(proc) or any(isinstance(t, ops.SequenceTable) and t.max_len > 1 for t in tables.values())
+        if need_hist and max_new_tokens > ops.LOGITS_PROCESS_MAX_HISTORY:
+            raise ValueError(f"sequence_bias / bad_words_ids with sequences of more than one token support at most "
+                             f"{ops.LOGITS_PROCESS_MAX_HISTORY} new tokens, got max_new_tokens = {max_new_tokens}")
+        if tables and not proc:
+            proc = (1.0, 0, 0)
         original = self.modality
         if audio is not None and video is not None:
             self.modality = "both"
@@ -500,7 +547,8 @@ class ClipWhisperModel:
         finally:
             self.modality = original
         if num_beams > 1:
-            return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores, proc)
+            return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores, proc,
+                                     tables, need_hist)
         eng = self.llm_engine
         B, S, _ = x.shape
         kc, vc = eng.alloc_cache(B, S + max_new_tokens)
@@ -510,11 +558,11 @@ class ClipWhisperModel:
         out = []
         row_seeds = torch.arange(B, dtype=torch.int32, device=x.device) if do_sample else None
         # the processors' history: row b's generated tokens (pad after its EOS, as HF feeds them); the kernel itself appends the last token
-        hist = torch.full((B, max_new_tokens), pad, dtype=torch.int64, device=x.device) if proc else None
+        hist = torch.full((B, max_new_tokens), pad, dtype=torch.int64, device=x.device) if need_hist else None
         nxt = None
         for step in range(max_new_tokens):
             if proc:
-                ops.logits_process(logits, hist, step, *proc, eos=eos, append=nxt)
+                ops.logits_process(logits, hist, step, *proc, eos=eos, append=nxt if need_hist else None, **tables)
             if do_sample:
                 nxt = ops.sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=unfinished if eos is not None else None,
                                       eos=eos, pad=pad, row_seeds=row_seeds)
@@ -529,7 +577,7 @@ class ClipWhisperModel:
             logits = eng.decode_step(nxt, S + step, kc, vc)
         return torch.stack(out, dim=1)
 
-    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores, proc=None):
+    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores, proc=None, tables=None, need_hist=True):
         """GenerationMixin._beam_search (transformers 5.x, generation/utils.py) for inputs_embeds x [B, S, d]: decoder_prompt_len = 0, so a
         hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
         the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
@@ -540,7 +588,8 @@ class ClipWhisperModel:
         B*nb <= 16 rows take the fused bf16 token step (LlamaEngine.decode_is_fused); more rows take the general step.
         proc = (repetition_penalty, no_repeat_ngram_size, min_new_tokens): HF runs its logits processors between the log_softmax and the
         addition of the running beam scores, on running_sequences[:, :, :cur]; ops.logits_process(log_softmax=True) does both on the
-        B*nb rows and beam_topk then takes the rows as log-probabilities."""
+        B*nb rows and beam_topk then takes the rows as log-probabilities.  tables: generate()'s prepared sequence_bias / bad_words_ids /
+        suppress_tokens / begin_suppress_tokens, for the same launch; need_hist: whether any of it reads running_sequences."""
         eng = self.llm_engine
         dev = x.device
         B, S, _ = x.shape
@@ -568,7 +617,7 @@ class ClipWhisperModel:
         for cur in range(N):
             # _get_top_k_continuations
             if proc:
-                ops.logits_process(logits, running_seq.view(R, N), cur, *proc, eos=eos, log_softmax=True)
+                ops.logits_process(logits, running_seq.view(R, N) if need_hist else None, cur, *proc, eos=eos, log_softmax=True, **(tables or {}))
             topk_lp, topk_beam, topk_tok = ops.beam_topk(logits, running_scores.view(-1), nb, k, logprobs=bool(proc))
             topk_seq = torch.gather(running_seq, 1, topk_beam.long()[:, :, None].expand(B, k, N)).clone()
             topk_seq[:, :, cur] = topk_tok

@@ -2,9 +2,12 @@
 all arithmetic happens in libavllm.so on the current torch stream."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import math
 import numbers
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -311,33 +314,175 @@ def check_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_to
     return float(p) != 1.0 or no_repeat_ngram_size > 0 or min_new_tokens > 0
 
 
+LOGITS_BIAS_MAX_SEQUENCES, LOGITS_BIAS_MAX_SEQUENCE_LENGTH = 4096, 16      # AVLLM_LOGITS_MAX_SEQUENCES / _SEQUENCE_LEN of include/avllm.h
+
+# Prepared device tables of logits_process (built by logits_bias_tables).  SequenceTable: tokens int32 [n, 16] (-1 padded), lengths int32 [n],
+# values f32 [n] (None for bad words), entries grouped by last token; TokenTable: ids int32 [n], distinct and ascending.
+SequenceTable = collections.namedtuple("SequenceTable", "tokens lengths values n max_len vocab")
+TokenTable = collections.namedtuple("TokenTable", "ids n vocab")
+
+
+def _token_ids(name, ids, vocab):
+    """A list of token ids: non-negative integers below the vocabulary size (when it is known)."""
+    if hasattr(ids, "tolist"):
+        ids = ids.tolist()
+    if isinstance(ids, (str, bytes, dict)) or not hasattr(ids, "__iter__"):
+        raise ValueError(f"{name} must be a list of token ids, got {ids!r}")
+    ids = list(ids)
+    for t in ids:
+        if isinstance(t, bool) or not isinstance(t, numbers.Integral) or t < 0:
+            raise ValueError(f"{name} must hold non-negative integers, got {t!r}")
+        if vocab is not None and t >= vocab:
+            raise ValueError(f"{name}: token id {t} is outside the vocabulary of {vocab} entries")
+    return [int(t) for t in ids]
+
+
+def _sequences(name, seqs):
+    if len(seqs) > LOGITS_BIAS_MAX_SEQUENCES:
+        raise ValueError(f"{name} has {len(seqs)} sequences: at most LOGITS_BIAS_MAX_SEQUENCES = {LOGITS_BIAS_MAX_SEQUENCES} are supported")
+    for q in seqs:
+        if len(q) == 0:
+            raise ValueError(f"{name} has an empty sequence")
+        if len(q) > LOGITS_BIAS_MAX_SEQUENCE_LENGTH:
+            raise ValueError(f"{name} has a sequence of {len(q)} tokens: at most LOGITS_BIAS_MAX_SEQUENCE_LENGTH = "
+                             f"{LOGITS_BIAS_MAX_SEQUENCE_LENGTH} are supported")
+    return seqs
+
+
+def _normalise_logits_bias(sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens, vocab, eos):
+    """The four arguments in one form each, or None where the processor is off: {tuple of ids: float} in HF's dict order, a list of distinct
+    tuples ([eos] dropped), two ascending lists of distinct ids."""
+    sb = bw = None
+    if sequence_bias is not None:
+        if isinstance(sequence_bias, dict):
+            if any(not isinstance(k, tuple) for k in sequence_bias):
+                raise ValueError(f"sequence_bias has to be a dict with tuples of token ids as keys, got {sequence_bias!r}")
+            items = list(sequence_bias.items())
+        elif isinstance(sequence_bias, (list, tuple)):
+            if any(not isinstance(e, (list, tuple)) or len(e) != 2 or not isinstance(e[0], (list, tuple)) for e in sequence_bias):
+                raise ValueError(f"sequence_bias has to be a list of [token ids, bias] pairs, got {sequence_bias!r}")
+            items = [(tuple(e[0]), e[1]) for e in sequence_bias]
+        else:
+            raise ValueError(f"sequence_bias has to be a non-empty dict or list of [token ids, bias] pairs, got {sequence_bias!r}")
+        if not items:
+            raise ValueError("sequence_bias has to be non-empty")
+        sb = {}
+        for k, b in items:
+            if isinstance(b, bool) or not isinstance(b, (float, np.floating)) or not math.isfinite(b):
+                raise ValueError(f"sequence_bias: the bias of {k!r} must be a finite float, got {b!r}")
+            sb[tuple(_token_ids("sequence_bias", k, vocab))] = float(b)
+        _sequences("sequence_bias", list(sb))
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, (list, tuple)) or len(bad_words_ids) == 0:
+            raise ValueError(f"bad_words_ids has to be a non-empty list, got {bad_words_ids!r}")
+        if any(not isinstance(w, (list, tuple)) for w in bad_words_ids):
+            raise ValueError(f"bad_words_ids has to be a list of lists of token ids, got {bad_words_ids!r}")
+        bw = [tuple(_token_ids("bad_words_ids", w, vocab)) for w in bad_words_ids]
+        bw = list(dict.fromkeys(w for w in bw if eos is None or w != (int(eos),)))         # HF's constructor drops [eos]
+        if not bw:
+            raise ValueError("bad_words_ids holds nothing but [eos], which HF drops: no sequence is left to ban")
+        _sequences("bad_words_ids", bw)
+    st = None if suppress_tokens is None else sorted(set(_token_ids("suppress_tokens", suppress_tokens, vocab)))
+    bs = None if begin_suppress_tokens is None else sorted(set(_token_ids("begin_suppress_tokens", begin_suppress_tokens, vocab)))
+    return sb, bw, st or None, bs or None
+
+
+def check_logits_bias(sequence_bias=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, vocab=None, eos=None):
+    """The argument rules of HF's SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor / SuppressTokensLogitsProcessor /
+    SuppressTokensAtBeginLogitsProcessor and this library's capacities (LOGITS_BIAS_MAX_SEQUENCES sequences of at most
+    LOGITS_BIAS_MAX_SEQUENCE_LENGTH tokens per table; suppress lists of any length): ValueError on token ids that are not non-negative
+    integers (below `vocab` when given), empty sequences, biases that are not finite floats.  sequence_bias: {tuple of ids: float} or
+    [[ids, float], ...]; bad_words_ids: [[ids], ...] ([eos] entries are dropped as HF drops them).  Returns True when any of the four is on."""
+    return any(t is not None for t in _normalise_logits_bias(sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens, vocab, eos))
+
+
+def logits_bias_tables(sequence_bias=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, *, vocab, eos=None,
+                       device="cuda"):
+    """The device tables logits_process takes under the same four names, as a dict to splat into it (empty when all four are off); built once
+    per generate() call.  vocab: the width V of the score rows; eos: the model's EOS id or None."""
+    sb, bw, st, bs = _normalise_logits_bias(sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens, int(vocab), eos)
+
+    def seq_table(seqs, values):
+        tok = np.full((len(seqs), LOGITS_BIAS_MAX_SEQUENCE_LENGTH), -1, dtype=np.int32)
+        for i, q in enumerate(seqs):
+            tok[i, :len(q)] = q
+        ln = np.array([len(q) for q in seqs], dtype=np.int32)
+        dev = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+        return SequenceTable(dev(tok), dev(ln), None if values is None else dev(np.array(values, dtype=np.float32)), len(seqs), int(ln.max()),
+                             int(vocab))
+
+    out = {}
+    if sb is not None:
+        # one fp32 total per last token, accumulated as HF does: the length-1 entry, then the longer sequences in the dict's order
+        keys = sorted(sb, key=lambda q: (q[-1], len(q) != 1))                              # stable: dict order inside a group
+        out["sequence_bias"] = seq_table(keys, [sb[q] for q in keys])
+    if bw is not None:
+        out["bad_words_ids"] = seq_table(bw, None)
+    for name, ids in (("suppress_tokens", st), ("begin_suppress_tokens", bs)):
+        if ids is not None:
+            out[name] = TokenTable(torch.tensor(ids, dtype=torch.int32).to(device), len(ids), int(vocab))
+    return out
+
+
 def logits_process(scores, history, cur, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos=None, log_softmax=False,
-                   append=None):
-    """HF's repetition-penalty, no-repeat-n-gram and min-new-tokens processors, in that order, IN PLACE on scores [rows, V] (f32 or bf16,
-    row stride free) before argmax_rows / sample_rows / beam_topk(logprobs=True) (csrc/logits_process.hip).  history: int64 [rows, ld] on
+                   append=None, *, sequence_bias=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None):
+    """HF's logits processors IN PLACE on scores [rows, V] (f32 or bf16, row stride free) before argmax_rows / sample_rows /
+    beam_topk(logprobs=True) (csrc/logits_process.hip), in GenerationMixin._get_logits_processor's order: sequence bias, repetition penalty,
+    no-repeat n-gram, bad words, min-new-tokens, suppress, begin-suppress.  history: int64 [rows, ld] on
     the device, row r's first `cur` entries are its generated tokens; cur: int, or an int32 device tensor of one element (read by the
     kernel; then ld <= LOGITS_PROCESS_MAX_HISTORY).  eos: the model's EOS id or None (min_new_tokens then does nothing).  log_softmax (f32
     only): the row is first replaced by its log-softmax: HF's beam search runs the processors on log-probabilities.  append: optional int64
-    [rows], stored at history[:, cur-1] before the history is read.  Returns scores."""
+    [rows], stored at history[:, cur-1] before the history is read.  sequence_bias / bad_words_ids / suppress_tokens /
+    begin_suppress_tokens: prepared device tables (logits_bias_tables(...), built for V = scores.shape[1]) or None.  With tables only of
+    single-token entries and the three older processors and append off, history may be None and cur has no limit.  Returns scores."""
     check_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens)
     if scores.dim() != 2 or not scores.is_cuda or scores.stride(1) != 1:
         raise ValueError("logits_process: scores must be a 2-d device tensor with unit column stride")
     rows, V = scores.shape
+    for name, t, kind in (("sequence_bias", sequence_bias, SequenceTable), ("bad_words_ids", bad_words_ids, SequenceTable),
+                          ("suppress_tokens", suppress_tokens, TokenTable), ("begin_suppress_tokens", begin_suppress_tokens, TokenTable)):
+        if t is not None and not isinstance(t, kind):
+            raise ValueError(f"logits_process: {name} must be a prepared {kind.__name__} (ops.logits_bias_tables), got {type(t).__name__}")
+        if t is not None and t.vocab != V:
+            raise ValueError(f"logits_process: the {name} table was built for a vocabulary of {t.vocab}, the scores have {V} columns")
+    ex = not (sequence_bias is None and bad_words_ids is None and suppress_tokens is None and begin_suppress_tokens is None)
     cur_dev = None
     if torch.is_tensor(cur):
         assert cur.dtype == torch.int32 and cur.numel() == 1 and cur.is_cuda
         cur_dev, cur = cur, 0
-    if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or not history.is_cuda or \
-            (history.shape[1] > 1 and history.stride(1) != 1):
-        raise ValueError(f"logits_process: history must be an int64 device tensor [{rows}, ld] with unit column stride")
+    if history is None and ex:
+        hptr, ldh = None, 0                        # the library refuses when something needs the history
+    else:
+        if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or not history.is_cuda or \
+                (history.shape[1] > 1 and history.stride(1) != 1):
+            raise ValueError(f"logits_process: history must be an int64 device tensor [{rows}, ld] with unit column stride")
+        ldh = history.stride(0) if rows > 1 and history.shape[1] > 0 else history.shape[1]
+        if cur_dev is None and int(cur) > history.shape[1]:
+            raise ValueError(f"logits_process: history length {cur} > the {history.shape[1]} columns of history")
+        hptr = L.ptr(history) if history.numel() else None
     if append is not None:
         assert append.dtype == torch.int64 and append.shape == (rows,) and append.is_contiguous() and append.is_cuda
-    ldh = history.stride(0) if rows > 1 and history.shape[1] > 0 else history.shape[1]
-    if cur_dev is None and int(cur) > history.shape[1]:
-        raise ValueError(f"logits_process: history length {cur} > the {history.shape[1]} columns of history")
-    L.check(L.load().avllm_logits_process(L.ptr(scores), _ld(scores), rows, V, L.ptr(history) if history.numel() else None, ldh, L.ptr(append),
-                                          int(cur), L.ptr(cur_dev), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
-                                          -1 if eos is None else int(eos), int(bool(log_softmax)), L.dt_of(scores), L.stream_ptr()))
+    eos = -1 if eos is None else int(eos)
+    if not ex:
+        L.check(L.load().avllm_logits_process(L.ptr(scores), _ld(scores), rows, V, hptr, ldh, L.ptr(append),
+                                              int(cur), L.ptr(cur_dev), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
+                                              eos, int(bool(log_softmax)), L.dt_of(scores), L.stream_ptr()))
+        return scores
+    d = L.LogitsProcDesc(scores=L.ptr(scores), ld=_ld(scores), rows=rows, V=V, dtype=L.dt_of(scores), history=hptr, ldh=ldh, append=L.ptr(append),
+                         cur=int(cur), cur_dev=L.ptr(cur_dev), repetition_penalty=float(repetition_penalty),
+                         no_repeat_ngram_size=int(no_repeat_ngram_size), min_new_tokens=int(min_new_tokens), eos=eos,
+                         log_softmax=int(bool(log_softmax)))
+    if sequence_bias is not None:
+        t = sequence_bias
+        d.bias_tokens, d.bias_lengths, d.bias_values, d.n_bias, d.bias_max_len = L.ptr(t.tokens), L.ptr(t.lengths), L.ptr(t.values), t.n, t.max_len
+    if bad_words_ids is not None:
+        t = bad_words_ids
+        d.bad_tokens, d.bad_lengths, d.n_bad, d.bad_max_len = L.ptr(t.tokens), L.ptr(t.lengths), t.n, t.max_len
+    if suppress_tokens is not None:
+        d.suppress, d.n_suppress = L.ptr(suppress_tokens.ids), suppress_tokens.n
+    if begin_suppress_tokens is not None:
+        d.begin_suppress, d.n_begin_suppress = L.ptr(begin_suppress_tokens.ids), begin_suppress_tokens.n
+    L.check(L.load().avllm_logits_process_ex(C.byref(d), L.stream_ptr()))
     return scores
 
 

@@ -43,6 +43,19 @@ class ByteTokenizer:
         return [self.decode(row, skip_special_tokens) for row in batch]
 
 
+def plain_token_ids(tokenizer, text):
+    """The ids of `text` alone: no BOS / EOS or other special tokens."""
+    if isinstance(tokenizer, ByteTokenizer):
+        return tokenizer.encode(text, add_bos=False)
+    return [int(t) for t in tokenizer.encode(text, add_special_tokens=False)]
+
+
+def phrase_token_ids(tokenizer, phrase):
+    """The distinct tokenisations of a phrase as it occurs at the start of a text and after a space: [ids of "phrase", ids of " phrase"]."""
+    phrase = phrase.strip()
+    return list(dict.fromkeys(tuple(plain_token_ids(tokenizer, p)) for p in (phrase, " " + phrase) if p.strip()))
+
+
 _TOKENIZER_FILES = ("tokenizer.json", "tokenizer.model", "tokenizer_config.json")
 
 

@@ -138,6 +138,7 @@ int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int6
     return av_logits_process(scores, ld, rows, V, history, ldh, append, cur, cur_dev, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
                              log_softmax, dtype, ST);
 }
+int avllm_logits_process_ex(const avllm_logits_proc_desc* d, void* stream) { return av_logits_process_ex(d, ST); }
 int avllm_kv_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
                          int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, int32_t dtype, void* stream) {
     return av_kv_gather_rows(k_src, v_src, src_rows, src_T, k_dst, v_dst, dst_rows, dst_T, layers, dkv, parent, t0, t1, dtype, ST);

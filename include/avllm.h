@@ -295,6 +295,35 @@ int avllm_beam_topk_logprobs(const float* logprobs, int64_t ld, int32_t B, int32
 int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int64_t* history, int64_t ldh, const int64_t* append, int32_t cur,
                          const int32_t* cur_dev, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens, int64_t eos,
                          int32_t log_softmax, int32_t dtype, void* stream);
+/* avllm_logits_process plus HF's SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor, SuppressTokensLogitsProcessor and
+ * SuppressTokensAtBeginLogitsProcessor (generate(sequence_bias=, bad_words_ids=, suppress_tokens=, begin_suppress_tokens=)), still one launch,
+ * in GenerationMixin._get_logits_processor's order: [log-softmax,] sequence bias, repetition penalty, n-gram ban, bad words, min_new_tokens,
+ * suppress, begin-suppress; each reads the scores the previous one left.  The fields up to log_softmax are avllm_logits_process's arguments.
+ * The tables are in device memory and may be shared by every step of a generate() call:
+ *   sequence table (bias_* / bad_*): n entries; entry i is the ids tokens[i * AVLLM_LOGITS_MAX_SEQUENCE_LEN + j], j < lengths[i], 1 <=
+ *     lengths[i] <= *_max_len <= AVLLM_LOGITS_MAX_SEQUENCE_LEN, n <= AVLLM_LOGITS_MAX_SEQUENCES.  An entry of length 1 always applies; a
+ *     longer one when lengths[i] <= n (HF's rule; not lengths[i] - 1 <= n) and the row's last lengths[i] - 1 tokens equal its first ones.
+ *   sequence bias: the entries must be ordered so that those with one last token are adjacent (the length-1 entry first, then HF's dict
+ *     order); the biases of the entries that apply are summed in fp32 in table order from +0 and added to the last token's score once
+ *     (f32 scores: HF's bits; bf16: one rounding).  No atomics; deterministic.
+ *   bad words: an entry that applies sets its last token's score to -inf ([eos] entries are the caller's to drop, as HF's constructor does).
+ *   suppress / begin_suppress: n_* distinct ids (n_* <= V) set to -inf, always / for a row with n == 0 generated tokens (HF's begin_index with
+ *     inputs_embeds is 0).
+ * Ids outside [0, V) are never used as an index.  The history and its 1024-token limit are needed only when repetition_penalty != 1,
+ * no_repeat_ngram_size > 0, min_new_tokens > 0, append, or a table entry longer than one token is present; otherwise history may be NULL
+ * and n = cur + *cur_dev is unbounded.  With every n_* zero this is avllm_logits_process exactly (the same launch, or none). */
+#define AVLLM_LOGITS_MAX_SEQUENCES 4096
+#define AVLLM_LOGITS_MAX_SEQUENCE_LEN 16
+typedef struct avllm_logits_proc_desc {
+    void* scores; int64_t ld; int64_t rows; int32_t V; int32_t dtype;
+    int64_t* history; int64_t ldh; const int64_t* append; int32_t cur; const int32_t* cur_dev;
+    float repetition_penalty; int32_t no_repeat_ngram_size; int32_t min_new_tokens; int64_t eos; int32_t log_softmax;
+    const int32_t* bias_tokens; const int32_t* bias_lengths; const float* bias_values; int32_t n_bias; int32_t bias_max_len;
+    const int32_t* bad_tokens; const int32_t* bad_lengths; int32_t n_bad; int32_t bad_max_len;
+    const int32_t* suppress; int32_t n_suppress;
+    const int32_t* begin_suppress; int32_t n_begin_suppress;
+} avllm_logits_proc_desc;
+int avllm_logits_process_ex(const avllm_logits_proc_desc* d, void* stream);
 /* KV-cache row gather for beam search (the `_reorder_cache` / `Cache.reorder_cache(beam_idx)` step of GenerationMixin._beam_search):
  * dst[l, r, t, :] = src[l, parent[r], t, :] for every layer l < layers, row r < dst_rows and position t0 <= t < t1, on K and V.  The caches
  * are [layers, rows, T, dkv] contiguous (f32 or bf16, any dkv); src may have fewer rows than dst (prefix broadcast after prefill) and another

@@ -11,7 +11,11 @@ Additions of this build (not reference flags): --do_sample / --top_p (default 0.
 temperature -> top-k -> top-p on the device, its seed drawn after torch.manual_seed(--seed); without --do_sample decoding stays
 greedy and --temperature is ignored, as in the reference), --num_beams (default 1: greedy or sampled as above) / --length_penalty
 (default 1.0) (HF beam search, the best hypothesis per utterance), --repetition_penalty (default 1.0) / --no_repeat_ngram_size (default 0) /
---min_new_tokens (default 0) (HF's logits processors of those names, on the device, in every decoding mode), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
+--min_new_tokens (default 0) (HF's logits processors of those names, on the device, in every decoding mode), --suppress_tokens /
+--begin_suppress_tokens (comma-separated token ids, or @FILE with ids separated by commas or white space: never generated / not generated
+as the first token), --bad_words FILE (one phrase per line, never generated: each is tokenised with and without a leading space and
+passed as bad_words_ids), --hotwords FILE (one word or phrase per line) / --hotword_bias F (added to the score of every token on the
+path of a hotword; generate(hotwords=, hotword_bias=)), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -58,6 +62,11 @@ def parse_args(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=1.0, help="> 1 lowers the score of every token already generated (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size is generated twice (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=0, help="EOS is not generated before this many new tokens")
+    p.add_argument("--suppress_tokens", type=str, default=None, help="token ids that are never generated: 1,2,3 or @FILE")
+    p.add_argument("--begin_suppress_tokens", type=str, default=None, help="token ids not generated as the first token: 1,2,3 or @FILE")
+    p.add_argument("--bad_words", type=str, default=None, help="file with one phrase per line that is never generated")
+    p.add_argument("--hotwords", type=str, default=None, help="file with one word or phrase per line to boost (contextual biasing)")
+    p.add_argument("--hotword_bias", type=float, default=0.0, help="added to the score of every token on a hotword's path")
     p.add_argument("--decode_weights", type=str, choices=["bf16", "fp8", "fp4"], default="bf16",
                    help="fp8: the token steps stream the LLM's frozen projections as block-scaled e4m3 (needs bf16; prefill stays bf16); "
                         "fp4: as OCP MXFP4 with lm_head as e4m3 (coarser: about 11.5 %% weight error, effect on WER not measured)")
@@ -68,6 +77,18 @@ def parse_args(argv=None):
     p.add_argument("--frames", type=int, default=125)
     p.add_argument("--synthetic-weights", action="store_true", help="seeded random weights + byte tokenizer (implied by --tiny)")
     return p.parse_args(argv)
+
+
+def token_id_list(arg):
+    """--suppress_tokens / --begin_suppress_tokens: '1,2,3', or '@FILE' holding ids separated by commas or white space."""
+    if arg is None:
+        return None
+    text = open(arg[1:]).read() if arg.startswith("@") else arg
+    return [int(t) for t in text.replace(",", " ").split()]
+
+
+def lines_of(path):
+    return None if path is None else [ln.strip() for ln in open(path) if ln.strip()]
 
 
 def match_references(ids, texts):
@@ -130,6 +151,12 @@ def main(argv=None):
         if isinstance(mc, dict):
             model.max_seq_len = mc.get("max_seq_len", 256); model.fusion_scale = mc.get("fusion_scale", 0.5)
 
+    from avllm.tokenizer import phrase_token_ids
+    bad_words = lines_of(a.bad_words)
+    bias_kw = dict(suppress_tokens=token_id_list(a.suppress_tokens), begin_suppress_tokens=token_id_list(a.begin_suppress_tokens),
+                   bad_words_ids=[list(ids) for w in bad_words or [] for ids in phrase_token_ids(model.tokenizer, w)] or None,
+                   hotwords=lines_of(a.hotwords), hotword_bias=a.hotword_bias)
+
     references, utt_ids = {}, None
     if a.synthetic:
         ds = SyntheticClips(a.synthetic, model.cfg, 5 if a.tiny else a.frames, model.tokenizer, 11)
@@ -172,7 +199,7 @@ def main(argv=None):
             ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
                                  do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k, num_beams=a.num_beams,
                                  length_penalty=a.length_penalty, repetition_penalty=a.repetition_penalty,
-                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens)
+                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, **bias_kw)
             out = model.tokenizer.batch_decode(ids.cpu(), skip_special_tokens=True)
             if a.calculate_loss:
                 lab = model.tokenizer(list(texts), padding="max_length", truncation=True, max_length=256, return_tensors="pt").input_ids
