@@ -146,6 +146,9 @@ _SIGS = {
     "avllm_ce_bwd": ([vp, i64, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp], i32),
     "avllm_argmax_rows": ([vp, i64, i64, i32, vp, i32, vp], i32),
     "avllm_sample_rows": ([vp, i64, i64, i32, f32, i32, f32, C.c_uint32, vp, i32, vp, vp, i64, i64, vp, i32, vp], i32),
+    "avllm_sample_rows_scored": ([vp, i64, i64, i32, f32, i32, f32, C.c_uint32, vp, i32, vp, vp, i64, i64, vp, vp, i32, vp], i32),
+    "avllm_row_scores": ([vp, i64, i64, i32, vp, f32, vp, vp, i32, vp], i32),
+    "avllm_row_scores_logprobs": ([vp, i64, i64, i32, vp, vp, vp, i32, vp], i32),
     "avllm_beam_topk_workspace_bytes": ([i64, i32, i32], sz),
     "avllm_beam_topk": ([vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp], i32),
     "avllm_beam_topk_logprobs": ([vp, i64, i32, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp], i32),

@@ -20,6 +20,7 @@ import math
 import numbers
 import os
 import types
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -52,6 +53,17 @@ def hotword_sequence_bias(tokenizer, hotwords, hotword_bias, sequence_bias=None)
                     raise ValueError(f"hotword {w!r}: its token prefix {ids[:k]} is also a sequence_bias key")
                 out[ids[:k]] = float(hotword_bias)
     return out
+
+
+class GenerateOutput(NamedTuple):
+    """generate(return_token_scores=True).  sequences: int64 [rows, L] new tokens; sequences_scores: float32 [rows], beam search only
+    (else None); token_scores: float32 [rows, L], the log-probability of every returned token (HF's compute_transition_scores), 0.0
+    after a row's EOS or beyond a hypothesis' length; token_entropy: float32 [rows, L], the entropy in nats of the distribution each
+    token was chosen from, masked the same way."""
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor]
+    token_scores: torch.Tensor
+    token_entropy: torch.Tensor
 
 
 class _LoraLoss(torch.autograd.Function):
@@ -478,7 +490,8 @@ class ClipWhisperModel:
     def generate(self, audio=None, video=None, prompt=None, pixel_values=None, max_new_tokens=100, do_sample=False,
                  temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                  return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sequence_bias=None,
-                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, hotwords=None, hotword_bias=0.0):
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, hotwords=None, hotword_bias=0.0,
+                 return_token_scores=False, num_return_sequences=1):
         """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search, or with do_sample=True its sampling: temperature -> top_k
         (HF's GenerationConfig default 50; 0 = off) -> top_p -> one draw per row on the device (ops.sample_rows).  seed=None draws the
         seed from torch's default CPU generator, so torch.manual_seed makes a sampled run repeat; row b draws with seed + b.
@@ -496,7 +509,17 @@ class ClipWhisperModel:
         new is launched or allocated.  The 1024-token limit of the older processors also holds when a sequence has more than one token.
         hotwords: a list of strings boosted by hotword_bias (contextual biasing): each is tokenised with and without a leading space and
         every prefix of each tokenisation becomes a sequence_bias entry (hotword_sequence_bias below).  HF considers a sequence of L tokens
-        only once L tokens have been generated, so token k of a hotword is not boosted when the word starts the utterance."""
+        only once L tokens have been generated, so token k of a hotword is not boosted when the word starts the utterance.
+        return_token_scores=True returns a GenerateOutput (sequences, sequences_scores, token_scores, token_entropy): the log-probability
+        of every returned token, HF's compute_transition_scores, computed at the token step (ops.row_scores; no second prefill), 0.0 after
+        a row's EOS.  Greedy: log-softmax of the processed logits at the argmax (normalize_logits=True).  Sampled: the draw's
+        log-probability under the distribution it was drawn from, after temperature, top_k and top_p (ops.sample_rows); token_entropy is
+        that of the UNTRUNCATED distribution, softmax(processed logits / temperature).  Beam search: each token's log-probability as the
+        beam scorer added it (processed, with processors on), carried through the beam reorderings; sequences_scores as HF.
+        num_return_sequences=n: HF's keyword: rows [B*n, L], item-major; beam search returns the n best hypotheses of each item, best
+        first (n <= num_beams); sampling draws n sequences per clip (encoders and connectors run once per clip; the result equals a call
+        on the clips repeated n times); greedy decoding with n > 1 is a ValueError, as in HF.  With both at their defaults nothing new
+        is launched or allocated and the return value is unchanged."""
         if video is None and pixel_values is not None:
             video = pixel_values
         if max_new_tokens is None:
@@ -512,6 +535,14 @@ class ClipWhisperModel:
                 raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
         elif return_sequence_scores:
             raise ValueError("return_sequence_scores needs num_beams > 1 (HF returns sequences_scores for beam search only)")
+        n_ret = num_return_sequences
+        if isinstance(n_ret, bool) or not isinstance(n_ret, numbers.Integral) or n_ret < 1:
+            raise ValueError(f"num_return_sequences must be a positive integer, got {n_ret!r}")
+        n_ret = int(n_ret)
+        if num_beams > 1 and n_ret > num_beams:
+            raise ValueError(f"num_return_sequences ({n_ret}) has to be smaller or equal to num_beams ({num_beams})")
+        if num_beams == 1 and not do_sample and n_ret > 1:
+            raise ValueError(f"greedy decoding cannot return {n_ret} sequences: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
         if do_sample:
             ops.check_sampling(temperature, top_k, top_p)
             if seed is None:
@@ -548,7 +579,9 @@ class ClipWhisperModel:
             self.modality = original
         if num_beams > 1:
             return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores, proc,
-                                     tables, need_hist)
+                                     tables, need_hist, n_ret=n_ret, token_scores=bool(return_token_scores))
+        if n_ret > 1:
+            x = x.repeat_interleave(n_ret, dim=0)                   # after the encoders and connectors, which ran once per clip
         eng = self.llm_engine
         B, S, _ = x.shape
         kc, vc = eng.alloc_cache(B, S + max_new_tokens)
@@ -560,24 +593,39 @@ class ClipWhisperModel:
         # the processors' history: row b's generated tokens (pad after its EOS, as HF feeds them); the kernel itself appends the last token
         hist = torch.full((B, max_new_tokens), pad, dtype=torch.int64, device=x.device) if need_hist else None
         nxt = None
+        tok_lp, tok_ent = [], []
         for step in range(max_new_tokens):
             if proc:
                 ops.logits_process(logits, hist, step, *proc, eos=eos, append=nxt if need_hist else None, **tables)
+            if return_token_scores:
+                alive = unfinished.clone()                          # rows that still choose a token at this step
             if do_sample:
                 nxt = ops.sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=unfinished if eos is not None else None,
-                                      eos=eos, pad=pad, row_seeds=row_seeds)
+                                      eos=eos, pad=pad, row_seeds=row_seeds, return_logprob=bool(return_token_scores))
+                if return_token_scores:
+                    nxt, lp = nxt                                   # 0 for finished rows already
+                    ent = ops.row_scores(logits, nxt, temperature, entropy=True)[1]
             else:
                 nxt = ops.argmax_rows(logits)
+                if return_token_scores:
+                    lp, ent = ops.row_scores(logits, nxt, entropy=True)
+                    lp = torch.where(alive, lp, torch.zeros_like(lp))
                 if eos is not None:
                     nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
                     unfinished = unfinished & (nxt != eos)
             out.append(nxt)
+            if return_token_scores:
+                tok_lp.append(lp)
+                tok_ent.append(torch.where(alive, ent, torch.zeros_like(ent)))
             if step + 1 == max_new_tokens or (eos is not None and not bool(unfinished.any())):
                 break
             logits = eng.decode_step(nxt, S + step, kc, vc)
+        if return_token_scores:
+            return GenerateOutput(torch.stack(out, dim=1), None, torch.stack(tok_lp, dim=1), torch.stack(tok_ent, dim=1))
         return torch.stack(out, dim=1)
 
-    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores, proc=None, tables=None, need_hist=True):
+    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores, proc=None, tables=None, need_hist=True,
+                     n_ret=1, token_scores=False):
         """GenerationMixin._beam_search (transformers 5.x, generation/utils.py) for inputs_embeds x [B, S, d]: decoder_prompt_len = 0, so a
         hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
         the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
@@ -589,7 +637,12 @@ class ClipWhisperModel:
         proc = (repetition_penalty, no_repeat_ngram_size, min_new_tokens): HF runs its logits processors between the log_softmax and the
         addition of the running beam scores, on running_sequences[:, :, :cur]; ops.logits_process(log_softmax=True) does both on the
         B*nb rows and beam_topk then takes the rows as log-probabilities.  tables: generate()'s prepared sequence_bias / bad_words_ids /
-        suppress_tokens / begin_suppress_tokens, for the same launch; need_hist: whether any of it reads running_sequences."""
+        suppress_tokens / begin_suppress_tokens, for the same launch; need_hist: whether any of it reads running_sequences.
+        n_ret: the n best finished hypotheses of each item are returned, rows [B*n_ret, L] item-major, best first (HF's
+        num_return_sequences).  token_scores: every candidate's own log-probability, read from the row it came from (the processed
+        log-probability with proc; logit - logsumexp of the raw row otherwise, ops.row_scores), and that row's entropy are carried in
+        [B, nb, N] tensors through the gathers that reorder the sequences; returns a GenerateOutput.  Never derived as
+        topk_lp - running_scores[parent]: that difference loses the low bits of a long hypothesis."""
         eng = self.llm_engine
         dev = x.device
         B, S, _ = x.shape
@@ -609,6 +662,9 @@ class ClipWhisperModel:
         beam_scores = torch.full((B, nb), NEG, dtype=torch.float32, device=dev)
         lengths = torch.zeros((B, nb), dtype=torch.int64, device=dev)             # generated length of each finished hypothesis
         is_sent_finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
+        if token_scores:
+            running_tok_lp = torch.zeros((B, nb, N), dtype=torch.float32, device=dev)
+            running_ent, tok_lp, tok_ent = running_tok_lp.clone(), running_tok_lp.clone(), running_tok_lp.clone()
         unsatisfied = torch.ones((B, 1), dtype=torch.bool, device=dev)
         top_mask = torch.arange(k, device=dev) < nb
         offset = (torch.arange(B, device=dev, dtype=torch.int32) * nb)[:, None]
@@ -622,6 +678,17 @@ class ClipWhisperModel:
             topk_seq = torch.gather(running_seq, 1, topk_beam.long()[:, :, None].expand(B, k, N)).clone()
             topk_seq[:, :, cur] = topk_tok
             topk_parent = topk_beam + offset
+            if token_scores:
+                # the candidates' own log-probabilities and their rows' entropies, from the B*nb rows beam_topk selected from
+                norm, row_ent = ops.row_scores(logits, None, entropy=True, logprobs=bool(proc))    # norm: -logsumexp (0 for log-probabilities)
+                cand_lp = logits[topk_parent.long(), topk_tok]
+                if not proc:
+                    cand_lp = cand_lp + norm[topk_parent.long()]
+                bidx = topk_beam.long()[:, :, None].expand(B, k, N)
+                topk_tok_lp = torch.gather(running_tok_lp, 1, bidx).clone()
+                topk_tok_lp[:, :, cur] = cand_lp
+                topk_ent = torch.gather(running_ent, 1, bidx).clone()
+                topk_ent[:, :, cur] = row_ent[topk_parent.long()]
             # stopping criteria: EOS, or max_length reached
             if cur + 1 >= N:
                 hits = torch.ones((B, k), dtype=torch.bool, device=dev)
@@ -635,6 +702,9 @@ class ClipWhisperModel:
             running_seq = torch.gather(topk_seq, 1, nxt[:, :, None].expand(B, nb, N))
             running_scores = torch.gather(topk_running_lp, 1, nxt)
             parent = torch.gather(topk_parent, 1, nxt)
+            if token_scores:
+                running_tok_lp = torch.gather(topk_tok_lp, 1, nxt[:, :, None].expand(B, nb, N))
+                running_ent = torch.gather(topk_ent, 1, nxt[:, :, None].expand(B, nb, N))
             # _update_finished_beams
             just = hits & top_mask[None, :]
             fin_lp = topk_lp / ((cur + 1) ** length_penalty)
@@ -648,6 +718,9 @@ class ClipWhisperModel:
             beam_scores = torch.gather(m_scores, 1, sel)
             lengths = torch.gather(torch.cat((lengths, torch.full((B, k), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, sel)
             is_sent_finished = torch.gather(torch.cat((is_sent_finished, just), dim=1), 1, sel)
+            if token_scores:
+                tok_lp = torch.gather(torch.cat((tok_lp, topk_tok_lp), dim=1), 1, sel[:, :, None].expand(B, nb, N))
+                tok_ent = torch.gather(torch.cat((tok_ent, topk_ent), dim=1), 1, sel[:, :, None].expand(B, nb, N))
             if cur + 1 >= N:                                        # every candidate hit max_length: HF's loop ends here
                 break
             # _check_early_stop_heuristic at cur_len = cur + 1, then _beam_search_has_unfinished_sequences
@@ -667,6 +740,9 @@ class ClipWhisperModel:
             ev.synchronize()
             if bool(done_host[0]):
                 break
-        L = int(lengths[:, 0].max())
-        out = sequences[:, 0, :L].clone()
-        return (out, beam_scores[:, 0].clone()) if return_scores else out
+        L = int(lengths[:, :n_ret].max())
+        out = sequences[:, :n_ret, :L].reshape(B * n_ret, L)
+        scores = beam_scores[:, :n_ret].reshape(B * n_ret)
+        if token_scores:
+            return GenerateOutput(out, scores, tok_lp[:, :n_ret, :L].reshape(B * n_ret, L), tok_ent[:, :n_ret, :L].reshape(B * n_ret, L))
+        return (out, scores) if return_scores else out

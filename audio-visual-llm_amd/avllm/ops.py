@@ -275,11 +275,42 @@ def check_sampling(temperature, top_k, top_p):
         raise ValueError(f"top_k must be a non-negative integer, got {top_k}")
 
 
-def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, eos=None, pad=None, row_seeds=None):
+def row_scores(logits, tokens, temperature=1.0, entropy=False, logprobs=False):
+    """Token scores of float32 logits [rows, V] (row stride free, unit column stride) in one pass (csrc/token_score.hip): the
+    log-probability log_softmax(logits / temperature)[r, tokens[r]] of one token per row, float32 [rows], and with entropy=True also the
+    entropy of softmax(logits / temperature) per row in nats: returns logprob, or (logprob, entropy).  tokens: int64 [rows] on the
+    device; the host cannot check their range without a sync, so the kernel clamps them to [0, V).  tokens=None returns -logsumexp per
+    row instead, so that logits[r, v] / temperature + result[r] is the log-probability of any v.  Entries of -inf (banned tokens) carry
+    probability 0; a chosen token that is -inf scores -inf; a row of nothing but -inf gives NaN.
+    logprobs=True: the rows are log-probabilities already (logits_process(log_softmax=True)): nothing is normalised, temperature is not
+    applied, logprob is logits[r, tokens[r]] bit for bit and the entropy is -sum exp(x) * x."""
+    if not (torch.is_tensor(logits) and logits.dim() == 2 and logits.is_cuda and logits.stride(1) == 1
+            and logits.dtype in (torch.float32, torch.bfloat16)):      # bf16 is refused by the library itself (AV_ERR_UNSUPPORTED)
+        raise ValueError("row_scores: logits must be a 2-d float32 device tensor with unit column stride")
+    rows, V = logits.shape
+    if tokens is not None and not (torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tokens.shape == (rows,) and tokens.is_cuda
+                                   and tokens.is_contiguous()):
+        raise ValueError(f"row_scores: tokens must be int64 [{rows}] on the device")
+    if not logprobs and not (float(temperature) > 0.0 and float(temperature) < float("inf")):
+        raise ValueError(f"temperature must be a strictly positive float, got {temperature}")
+    lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    ent = torch.empty(rows, device=logits.device, dtype=torch.float32) if entropy else None
+    lib = L.load()
+    if logprobs:
+        L.check(lib.avllm_row_scores_logprobs(L.ptr(logits), _ld(logits), rows, V, L.ptr(tokens), L.ptr(lp), L.ptr(ent), L.dt_of(logits),
+                                              L.stream_ptr()))
+    else:
+        L.check(lib.avllm_row_scores(L.ptr(logits), _ld(logits), rows, V, L.ptr(tokens), float(temperature), L.ptr(lp), L.ptr(ent),
+                                     L.dt_of(logits), L.stream_ptr()))
+    return (lp, ent) if entropy else lp
+
+
+def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, eos=None, pad=None, row_seeds=None, return_logprob=False):
     """One sampled token per row of fp32/bf16 logits [rows, V]: temperature -> top-k (0 = off) -> top-p -> draw (csrc/sample.hip).
     seed: uint32 (row r uses seed + row_seeds[r] when row_seeds, an int32 device tensor [rows], is given); step: int, or an int32 device
     tensor of one element (read by the kernel).  unfinished: optional bool [rows], updated in place: finished rows get pad, a row that draws
-    eos is finished.  Returns int64 [rows]."""
+    eos is finished.  Returns int64 [rows]; with return_logprob=True (tokens, logprob): float32 [rows], each draw's log-probability under
+    the distribution it was drawn from (after temperature, top-k and top-p, renormalised), 0 for finished rows and for top_k = 1."""
     check_sampling(temperature, top_k, top_p)
     rows, V = logits.shape
     out = torch.empty(rows, device=logits.device, dtype=torch.int64)
@@ -293,6 +324,12 @@ def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, 
         assert row_seeds.dtype == torch.int32 and row_seeds.shape == (rows,) and row_seeds.is_contiguous()
     eos = -1 if eos is None else int(eos)
     pad = (eos if eos >= 0 else 0) if pad is None else int(pad)
+    if return_logprob:
+        lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
+        L.check(L.load().avllm_sample_rows_scored(L.ptr(logits), _ld(logits), rows, V, float(temperature), int(top_k), float(top_p),
+                                                  int(seed) & 0xFFFFFFFF, L.ptr(row_seeds), int(step), L.ptr(step_dev), L.ptr(unfinished),
+                                                  eos, pad, L.ptr(out), L.ptr(lp), L.dt_of(logits), L.stream_ptr()))
+        return out, lp
     L.check(L.load().avllm_sample_rows(L.ptr(logits), _ld(logits), rows, V, float(temperature), int(top_k), float(top_p),
                                        int(seed) & 0xFFFFFFFF, L.ptr(row_seeds), int(step), L.ptr(step_dev), L.ptr(unfinished), eos, pad,
                                        L.ptr(out), L.dt_of(logits), L.stream_ptr()))

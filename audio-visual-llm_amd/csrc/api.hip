@@ -121,7 +121,21 @@ int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, i
 int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
                       const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
                       int64_t* out, int32_t dtype, void* stream) {
-    return av_sample_rows(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, dtype, ST);
+    return av_sample_rows(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, nullptr, dtype, ST);
+}
+int avllm_sample_rows_scored(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
+                             const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
+                             int64_t* out, float* out_logprob, int32_t dtype, void* stream) {
+    return av_sample_rows(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, out_logprob, dtype,
+                          ST);
+}
+int avllm_row_scores(const void* logits, int64_t ld, int64_t rows, int32_t V, const int64_t* tokens, float temperature, float* out_logprob,
+                     float* out_entropy, int32_t dtype, void* stream) {
+    return av_row_scores(logits, ld, rows, V, tokens, temperature, out_logprob, out_entropy, 0, dtype, ST);
+}
+int avllm_row_scores_logprobs(const void* logprobs, int64_t ld, int64_t rows, int32_t V, const int64_t* tokens, float* out_logprob,
+                              float* out_entropy, int32_t dtype, void* stream) {
+    return av_row_scores(logprobs, ld, rows, V, tokens, 1.0f, out_logprob, out_entropy, 1, dtype, ST);
 }
 size_t avllm_beam_topk_workspace_bytes(int64_t rows, int32_t V, int32_t k) { return av_beam_topk_workspace_bytes(rows, V, k); }
 int avllm_beam_topk(const float* logits, int64_t ld, int32_t B, int32_t num_beams, int32_t V, const float* beam_scores, int32_t k,

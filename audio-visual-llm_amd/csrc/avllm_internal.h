@@ -39,7 +39,9 @@ int av_ce_bwd(const void* logits, long ld, const int64_t* labels, const float* r
 int av_argmax_rows(const void* logits, long ld, long rows, int V, int64_t* out, int dtype, hipStream_t st);
 int av_sample_rows(const void* logits, long ld, long rows, int V, float temperature, int top_k, float top_p, uint32_t seed,
                    const uint32_t* row_seeds, int step, const int* step_dev, uint8_t* unfinished, long long eos, long long pad,
-                   int64_t* out, int dtype, hipStream_t st);
+                   int64_t* out, float* out_logprob, int dtype, hipStream_t st);
+int av_row_scores(const void* logits, long ld, long rows, int V, const int64_t* tokens, float temperature, float* out_logprob, float* out_entropy,
+                  int logprobs, int dtype, hipStream_t st);
 size_t av_beam_topk_workspace_bytes(long rows, int V, int k);
 int av_beam_topk(const float* logits, long ld, int B, int nb, int V, const float* beam_scores, int k, float* out_scores, int32_t* out_beams,
                  int64_t* out_tokens, void* ws, size_t ws_bytes, int logprobs, hipStream_t st);

@@ -12,6 +12,9 @@
 // Masses are fixed-point integers (exp(x - max) * 2^40, summed in uint64), so every histogram, scan and total is exact: the result repeats
 // bit for bit whatever the order the threads add in, and no float atomic is used.  top_k == 1 is the argmax with argmax_kernel's rule
 // (lowest index among equal maxima, temperature irrelevant).
+// out_logprob (optional): the draw's log-probability under the distribution it was drawn from, HF's transition score of a sampled token:
+// (x_id - max) - log(W * 2^-40), W the exact kept mass the draw already holds; 0 where the kernel returns the argmax or pad.  One thread
+// computes it after the draw: a null pointer leaves every pass, the LDS layout and the draws as they are.
 // Rows of at most LDS_MAX_V entries are read from HBM once into LDS as keys; longer rows (Llama-3's 128,256) re-read the row, from L2, each pass.
 #include "common.h"
 #include "avllm_internal.h"
@@ -112,11 +115,11 @@ template <typename T, bool IN_LDS>
 __global__ __launch_bounds__(NT) void sample_kernel(const T* __restrict__ logits, long ld, int V, float temp, int top_k, float top_p,
                                                     uint32_t seed, const uint32_t* __restrict__ row_seeds, int step,
                                                     const int* __restrict__ step_dev, uint8_t* __restrict__ unfinished, long long eos,
-                                                    long long pad, int64_t* __restrict__ out) {
+                                                    long long pad, int64_t* __restrict__ out, float* __restrict__ out_logprob) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int row = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (unfinished && !unfinished[row]) {
-        if (threadIdx.x == 0) out[row] = pad;
+        if (threadIdx.x == 0) { out[row] = pad; if (out_logprob) out_logprob[row] = 0.f; }
         return;
     }
     uint32_t* keys = (uint32_t*)smem;
@@ -142,6 +145,7 @@ __global__ __launch_bounds__(NT) void sample_kernel(const T* __restrict__ logits
     const uint32_t kmax = (uint32_t)(best >> 32);
     const float xmax = from_key(kmax);
     int64_t id = (int64_t)(0xffffffffu - (uint32_t)best);
+    float lp = 0.f;                                    // log-probability of the draw; the argmax paths return their token with probability one
     const Row<T, IN_LDS> r{g, keys, temp};
 
     if (top_k != 1 && xmax > -INFINITY && xmax < INFINITY) {
@@ -234,17 +238,20 @@ __global__ __launch_bounds__(NT) void sample_kernel(const T* __restrict__ logits
                 if (hit) { id = t * TILE + j * 64 + __ffsll((unsigned long long)hit) - 1; break; }
                 rel -= __shfl(c, 63);
             }
+            // the draw's log-probability under the kept, renormalised distribution: W is the kept mass in units of 2^-40 * exp(xmax)
+            if (out_logprob && threadIdx.x == 0) lp = (from_key(r.key((int)id)) - xmax) - logf((float)W * 0x1p-40f);
         }
     }
     if (threadIdx.x == 0) {
         out[row] = id;
+        if (out_logprob) out_logprob[row] = lp;
         if (unfinished && eos >= 0 && id == eos) unfinished[row] = 0;
     }
 }
 
 template <typename T, bool IN_LDS>
 int launch(const void* logits, long ld, long rows, int V, float temp, int top_k, float top_p, uint32_t seed, const uint32_t* row_seeds,
-           int step, const int* step_dev, uint8_t* unfinished, long long eos, long long pad, int64_t* out, hipStream_t st) {
+           int step, const int* step_dev, uint8_t* unfinished, long long eos, long long pad, int64_t* out, float* out_logprob, hipStream_t st) {
     const size_t lds = IN_LDS ? ((size_t)V * 4 + 15) / 16 * 16 + LDS_FIXED : LDS_FIXED;
     if (IN_LDS) {
         static bool attr[64] = {};
@@ -257,7 +264,7 @@ int launch(const void* logits, long ld, long rows, int V, float temp, int top_k,
         }
     }
     hipLaunchKernelGGL((sample_kernel<T, IN_LDS>), dim3(rows), dim3(NT), lds, st, (const T*)logits, ld, V, temp, top_k, top_p, seed, row_seeds,
-                       step, step_dev, unfinished, eos, pad, out);
+                       step, step_dev, unfinished, eos, pad, out, out_logprob);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
@@ -266,7 +273,7 @@ int launch(const void* logits, long ld, long rows, int V, float temp, int top_k,
 
 int av_sample_rows(const void* logits, long ld, long rows, int V, float temperature, int top_k, float top_p, uint32_t seed,
                    const uint32_t* row_seeds, int step, const int* step_dev, uint8_t* unfinished, long long eos, long long pad,
-                   int64_t* out, int dtype, hipStream_t st) {
+                   int64_t* out, float* out_logprob, int dtype, hipStream_t st) {
     AV_CHECK_ARG(logits && out && rows > 0 && V > 0 && ld >= V, "sample_rows: bad args");
     AV_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "sample_rows: temperature must be > 0 (got %g)", (double)temperature);
     AV_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "sample_rows: top_p must be in (0, 1] (got %g)", (double)top_p);
@@ -275,8 +282,8 @@ int av_sample_rows(const void* logits, long ld, long rows, int V, float temperat
     if (V > MAX_V) return av_set_error(AV_ERR_UNSUPPORTED, "sample_rows: V = %d > %d", V, MAX_V);
     const bool in_lds = V <= LDS_MAX_V;
     if (dtype == AV_F32)
-        return in_lds ? launch<float, true>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, st)
-                      : launch<float, false>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, st);
-    return in_lds ? launch<bf16, true>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, st)
-                  : launch<bf16, false>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, st);
+        return in_lds ? launch<float, true>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, out_logprob, st)
+                      : launch<float, false>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, out_logprob, st);
+    return in_lds ? launch<bf16, true>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, out_logprob, st)
+                  : launch<bf16, false>(logits, ld, rows, V, temperature, top_k, top_p, seed, row_seeds, step, step_dev, unfinished, eos, pad, out, out_logprob, st);
 }

@@ -260,6 +260,28 @@ int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, i
 int avllm_sample_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
                       const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
                       int64_t* out, int32_t dtype, void* stream);
+/* avllm_sample_rows that also returns the score of each draw (generate(do_sample=True, return_token_scores=True); HF's
+ * compute_transition_scores of a sampled token): out_logprob [rows] (f32) = the log-probability of the drawn token under the distribution
+ * it was drawn from, i.e. after temperature, top-k and top-p, renormalised over the kept set: (x_id / temperature - max) - log(kept mass).
+ * 0 where the kernel returns the argmax with probability one (top_k == 1, an infinite maximum) and for finished rows, which get pad.
+ * Tokens are those of avllm_sample_rows for the same arguments; out_logprob == NULL is avllm_sample_rows exactly. */
+int avllm_sample_rows_scored(const void* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p, uint32_t seed,
+                             const uint32_t* row_seeds, int32_t step, const int32_t* step_dev, uint8_t* unfinished, int64_t eos, int64_t pad,
+                             int64_t* out, float* out_logprob, int32_t dtype, void* stream);
+/* Token scores (generate(return_token_scores=True); HF's output_scores / compute_transition_scores(normalize_logits=True), transformers
+ * generation/utils.py): for each row of f32 logits [rows, V] (row stride ld >= V), with y = logits[r] / temperature and
+ * lse = log(sum_v exp(y[v])): out_logprob[r] = y[tokens[r]] - lse and out_entropy[r] = lse - sum_v softmax(y)[v] * y[v], the entropy of
+ * the row in nats (>= 0).  One pass over the row, one workgroup per row, deterministic (no atomics).  tokens: int64 [rows], clamped to
+ * [0, V); NULL: out_logprob[r] = -lse.  out_logprob or out_entropy may be NULL (not both).  Entries of -inf (tokens banned by
+ * avllm_logits_process) carry probability 0 in both sums; a chosen token that is -inf scores -inf; a row of nothing but -inf is NOT
+ * refused and gives NaN in both outputs.  temperature > 0; V <= 524288; dtype must be AVLLM_F32 (bf16: AV_ERR_UNSUPPORTED). */
+int avllm_row_scores(const void* logits, int64_t ld, int64_t rows, int32_t V, const int64_t* tokens, float temperature, float* out_logprob,
+                     float* out_entropy, int32_t dtype, void* stream);
+/* avllm_row_scores for rows that are log-probabilities already (beam search after avllm_logits_process with log_softmax = 1, the rows
+ * avllm_beam_topk_logprobs selects from): nothing is normalised.  out_logprob[r] = logprobs[r][tokens[r]] bit for bit (0 with tokens ==
+ * NULL) and out_entropy[r] = -sum_v exp(x[v]) * x[v] over the entries above -inf (0 for a row of nothing but -inf). */
+int avllm_row_scores_logprobs(const void* logprobs, int64_t ld, int64_t rows, int32_t V, const int64_t* tokens, float* out_logprob,
+                              float* out_entropy, int32_t dtype, void* stream);
 /* Beam-search candidate selection (GenerationMixin._beam_search with num_beams > 1, clip_whisper_model.py:1326-1340; transformers
  * generation/utils.py `log_softmax` + `_get_top_k_continuations`).  logits: f32 rows r = b*num_beams + j of length V, row stride ld;
  * beam_scores: f32 [B*num_beams] running sums of log-probabilities (-1e9 and -inf allowed).  For each batch item b, the k best of

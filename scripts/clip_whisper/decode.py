@@ -15,7 +15,10 @@ greedy and --temperature is ignored, as in the reference), --num_beams (default 
 --begin_suppress_tokens (comma-separated token ids, or @FILE with ids separated by commas or white space: never generated / not generated
 as the first token), --bad_words FILE (one phrase per line, never generated: each is tokenised with and without a leading space and
 passed as bad_words_ids), --hotwords FILE (one word or phrase per line) / --hotword_bias F (added to the score of every token on the
-path of a hotword; generate(hotwords=, hotword_bias=)), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
+path of a hotword; generate(hotwords=, hotword_bias=)), --nbest N (beam search returns the N best hypotheses of each utterance; needs
+--num_beams >= N; WER stays on the 1-best), --confidence (adds tokens, token_logprobs, avg_logprob and word_confidences of the 1-best to each
+utterance of the --output_file JSON, and with --nbest > 1 an nbest list of {hypothesis, score}), --min_avg_logprob F (utterances whose mean
+token log-probability is below F are listed in the log; they still count in the WER), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -67,6 +70,9 @@ def parse_args(argv=None):
     p.add_argument("--bad_words", type=str, default=None, help="file with one phrase per line that is never generated")
     p.add_argument("--hotwords", type=str, default=None, help="file with one word or phrase per line to boost (contextual biasing)")
     p.add_argument("--hotword_bias", type=float, default=0.0, help="added to the score of every token on a hotword's path")
+    p.add_argument("--nbest", type=int, default=1, help="beam search: the N best hypotheses per utterance (needs --num_beams >= N)")
+    p.add_argument("--confidence", action="store_true", help="token log-probabilities and word confidences in the --output_file JSON")
+    p.add_argument("--min_avg_logprob", type=float, default=None, help="list utterances whose mean token log-probability is below this")
     p.add_argument("--decode_weights", type=str, choices=["bf16", "fp8", "fp4"], default="bf16",
                    help="fp8: the token steps stream the LLM's frozen projections as block-scaled e4m3 (needs bf16; prefill stays bf16); "
                         "fp4: as OCP MXFP4 with lm_head as e4m3 (coarser: about 11.5 %% weight error, effect on WER not measured)")
@@ -76,7 +82,14 @@ def parse_args(argv=None):
     p.add_argument("--tiny", action="store_true")
     p.add_argument("--frames", type=int, default=125)
     p.add_argument("--synthetic-weights", action="store_true", help="seeded random weights + byte tokenizer (implied by --tiny)")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.nbest < 1:
+        p.error(f"--nbest must be at least 1, got {a.nbest}")
+    if a.nbest > 1 and a.do_sample:
+        p.error("--nbest > 1 is beam search: it cannot be combined with --do_sample")
+    if a.nbest > 1 and a.num_beams < a.nbest:
+        p.error(f"--nbest {a.nbest} needs --num_beams >= {a.nbest}, got --num_beams {a.num_beams}")
+    return a
 
 
 def token_id_list(arg):
@@ -103,6 +116,27 @@ def match_references(ids, texts):
         if "/" in uid:
             refs[uid.split("/")[-1]] = t
     return refs
+
+
+def utterance_scores(tokenizer, out, nbest, eos):
+    """--confidence: per utterance, from generate(return_token_scores=True, num_return_sequences=nbest): the 1-best's tokens (up to and
+    including its EOS), their log-probabilities, the mean of those, its word confidences, and with nbest > 1 the n-best list."""
+    from avllm.confidence import word_confidences
+    seqs, lps = out.sequences.cpu(), out.token_scores.cpu()
+    scores = None if out.sequences_scores is None else out.sequences_scores.cpu().tolist()
+    conf = word_confidences(tokenizer, seqs[::nbest], lps[::nbest])
+    res = []
+    for u in range(seqs.shape[0] // nbest):
+        row = seqs[u * nbest].tolist()
+        n = row.index(eos) + 1 if eos is not None and eos in row else len(row)
+        tl = [float(v) for v in lps[u * nbest, :n]]
+        d = {"tokens": row[:n], "token_logprobs": tl, "avg_logprob": sum(tl) / max(len(tl), 1),
+             "word_confidences": [[w, c] for w, c in conf[u]]}
+        if nbest > 1:
+            hyps = tokenizer.batch_decode(seqs[u * nbest:(u + 1) * nbest], skip_special_tokens=True)
+            d["nbest"] = [{"hypothesis": h.strip(), "score": scores[u * nbest + i]} for i, h in enumerate(hyps)]
+        res.append(d)
+    return res
 
 
 def main(argv=None):
@@ -189,6 +223,9 @@ def main(argv=None):
                 audio, video = device_collate(b["raw"], *feats)
                 yield audio, video, b["texts"]
 
+    scored = a.confidence or a.nbest > 1 or a.min_avg_logprob is not None
+    score_kw = dict(return_token_scores=True, num_return_sequences=a.nbest) if scored else {}
+    low_confidence = []
     results, all_refs, all_hyps, losses = [], [], [], []
     seen = 0
     print(f"Starting decoding with modality: {a.modality}\nEach hypothesis will be shown as it's generated.\n")
@@ -199,7 +236,11 @@ def main(argv=None):
             ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
                                  do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k, num_beams=a.num_beams,
                                  length_penalty=a.length_penalty, repetition_penalty=a.repetition_penalty,
-                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, **bias_kw)
+                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, **bias_kw, **score_kw)
+            extras = None
+            if scored:
+                extras = utterance_scores(model.tokenizer, ids, a.nbest, model.eos_token_id)
+                ids = ids.sequences[::a.nbest]
             out = model.tokenizer.batch_decode(ids.cpu(), skip_special_tokens=True)
             if a.calculate_loss:
                 lab = model.tokenizer(list(texts), padding="max_length", truncation=True, max_length=256, return_tensors="pt").input_ids
@@ -213,6 +254,10 @@ def main(argv=None):
                 if ref is not None:
                     all_refs.append(ref); all_hyps.append(hyp)
                     results.append({"utt_id": uid, "hypothesis": hyp, "reference": ref, "wer": calculate_wer([ref], [hyp])})
+                    if a.confidence:
+                        results[-1].update(extras[j])
+                if extras is not None and a.min_avg_logprob is not None and extras[j]["avg_logprob"] < a.min_avg_logprob:
+                    low_confidence.append((uid, extras[j]["avg_logprob"]))
             seen += len(out)
         except Exception as e:                                   # noqa: BLE001  decode.py:647-650: log and go on with the next batch
             logging.error(f"Error processing batch {bi}: {e}")
@@ -234,6 +279,10 @@ def main(argv=None):
     if losses:
         summary["mean_loss"] = sum(losses) / len(losses)
     json.dump(summary, open(os.path.join(a.output_dir, os.path.basename(a.output_file)), "w"), indent=1)
+    if a.min_avg_logprob is not None:
+        logging.info(f"{len(low_confidence)} utterances with avg_logprob < {a.min_avg_logprob} (kept in the WER):")
+        for uid, v in low_confidence:
+            logging.info(f"  low confidence: {uid} avg_logprob {v:.4f}")
     logging.info(f"Overall WER: {wer:.4f}")
     print("\n" + "=" * 80 + f"\nDECODING SUMMARY\nModality: {a.modality}\nOverall WER: {wer:.4f}\nTotal samples: {len(all_refs)}\n" + "=" * 80)
     return 0
