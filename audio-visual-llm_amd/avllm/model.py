@@ -16,11 +16,8 @@ Differences that are deliberate and documented:
 from __future__ import annotations
 
 import logging
-import math
-import numbers
 import os
 import types
-from typing import NamedTuple, Optional
 
 import torch
 
@@ -29,41 +26,8 @@ from . import ops
 from .arch import ModelCfg, resolve_arch
 from .connector import ModalityConnector, create_modality_connector
 from .engine import ClipEngine, LlamaEngine, WhisperEngine
-from .tokenizer import load_tokenizer, phrase_token_ids
-
-
-def hotword_sequence_bias(tokenizer, hotwords, hotword_bias, sequence_bias=None):
-    """generate(hotwords=, hotword_bias=) as a sequence_bias dict: each hotword is tokenised with and without a leading space (no special
-    tokens), and every prefix t[:1] ... t[:L] of each distinct tokenisation gets hotword_bias, so the whole path of the word is boosted,
-    not only its last token.  Prefixes shared by several hotwords are merged into one entry.  The user's own sequence_bias entries come
-    first; a hotword prefix equal to one of their keys is a ValueError (which bias is meant cannot be told).
-    HF's SequenceBiasLogitsProcessor considers a sequence of L tokens only once L tokens have been generated (L <= n, not L - 1 <= n), so
-    token k > 1 of a hotword is not boosted while fewer than k tokens exist: a hotword that starts the utterance gets its first token
-    boosted and the rest only from the point where the history is as long as the prefix."""
-    if isinstance(hotwords, str) or not isinstance(hotwords, (list, tuple)) or any(not isinstance(w, str) or not w.strip() for w in hotwords):
-        raise ValueError(f"hotwords must be a list of non-empty strings, got {hotwords!r}")
-    if isinstance(hotword_bias, bool) or not isinstance(hotword_bias, numbers.Real) or not math.isfinite(hotword_bias):
-        raise ValueError(f"hotword_bias must be a finite float, got {hotword_bias!r}")
-    out = dict(ops._normalise_logits_bias(sequence_bias, None, None, None, None, None)[0] or {})
-    user = set(out)
-    for w in hotwords:
-        for ids in phrase_token_ids(tokenizer, w):
-            for k in range(1, len(ids) + 1):
-                if ids[:k] in user:
-                    raise ValueError(f"hotword {w!r}: its token prefix {ids[:k]} is also a sequence_bias key")
-                out[ids[:k]] = float(hotword_bias)
-    return out
-
-
-class GenerateOutput(NamedTuple):
-    """generate(return_token_scores=True).  sequences: int64 [rows, L] new tokens; sequences_scores: float32 [rows], beam search only
-    (else None); token_scores: float32 [rows, L], the log-probability of every returned token (HF's compute_transition_scores), 0.0
-    after a row's EOS or beyond a hypothesis' length; token_entropy: float32 [rows, L], the entropy in nats of the distribution each
-    token was chosen from, masked the same way."""
-    sequences: torch.Tensor
-    sequences_scores: Optional[torch.Tensor]
-    token_scores: torch.Tensor
-    token_entropy: torch.Tensor
+from .generation import GenerateOutput, beam_search, hotword_sequence_bias, parse_arguments, token_loop  # noqa: F401  (the first and third are re-exported)
+from .tokenizer import load_tokenizer
 
 
 class _LoraLoss(torch.autograd.Function):
@@ -492,80 +456,45 @@ class ClipWhisperModel:
                  return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sequence_bias=None,
                  bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, hotwords=None, hotword_bias=0.0,
                  return_token_scores=False, num_return_sequences=1):
-        """clip_whisper_model.py:1240-1348 -> GenerationMixin greedy search, or with do_sample=True its sampling: temperature -> top_k
-        (HF's GenerationConfig default 50; 0 = off) -> top_p -> one draw per row on the device (ops.sample_rows).  seed=None draws the
-        seed from torch's default CPU generator, so torch.manual_seed makes a sampled run repeat; row b draws with seed + b.
-        With do_sample=False, temperature / top_k / top_p are ignored.  Returns NEW tokens only [B, <=max_new_tokens].
-        num_beams > 1: HF's beam search (see _beam_search; length_penalty, early_stopping in {True, False, "never"} as in HF); returns the
-        best hypothesis per item, padded with pad_token_id, and with return_sequence_scores=True also HF's sequences_scores [B].
-        repetition_penalty (> 0, 1.0 = off), no_repeat_ngram_size (0 = off) and min_new_tokens are HF's logits processors of those names, in
-        every mode, applied on the device (ops.logits_process) to a row's generated tokens, which is all HF's processors see with
-        inputs_embeds: on the logits before the argmax or the sampling chain, and in beam search on the log-probabilities (log-softmax
-        first, as HF's _beam_search does).  With the three defaults nothing is launched.
-        sequence_bias ({tuple of ids: float} or [[ids, float], ...]), bad_words_ids ([[ids], ...]), suppress_tokens and begin_suppress_tokens
-        (lists of ids) are HF's keywords of those names, in the same launch and in HF's order: sequence bias, repetition penalty, n-gram
-        ban, bad words, min_new_tokens, suppress, begin-suppress (the first generated token, HF's begin_index 0 with inputs_embeds).  Their
-        device tables are built once per call (ops.logits_bias_tables; its capacities are refused by name); with all of them None nothing
-        new is launched or allocated.  The 1024-token limit of the older processors also holds when a sequence has more than one token.
-        hotwords: a list of strings boosted by hotword_bias (contextual biasing): each is tokenised with and without a leading space and
-        every prefix of each tokenisation becomes a sequence_bias entry (hotword_sequence_bias below).  HF considers a sequence of L tokens
-        only once L tokens have been generated, so token k of a hotword is not boosted when the word starts the utterance.
-        return_token_scores=True returns a GenerateOutput (sequences, sequences_scores, token_scores, token_entropy): the log-probability
-        of every returned token, HF's compute_transition_scores, computed at the token step (ops.row_scores; no second prefill), 0.0 after
-        a row's EOS.  Greedy: log-softmax of the processed logits at the argmax (normalize_logits=True).  Sampled: the draw's
-        log-probability under the distribution it was drawn from, after temperature, top_k and top_p (ops.sample_rows); token_entropy is
-        that of the UNTRUNCATED distribution, softmax(processed logits / temperature).  Beam search: each token's log-probability as the
-        beam scorer added it (processed, with processors on), carried through the beam reorderings; sequences_scores as HF.
-        num_return_sequences=n: HF's keyword: rows [B*n, L], item-major; beam search returns the n best hypotheses of each item, best
-        first (n <= num_beams); sampling draws n sequences per clip (encoders and connectors run once per clip; the result equals a call
-        on the clips repeated n times); greedy decoding with n > 1 is a ValueError, as in HF.  With both at their defaults nothing new
-        is launched or allocated and the return value is unchanged."""
+        """clip_whisper_model.py:1240-1348 -> GenerationMixin's greedy search, sampling or beam search on the fused inputs (avllm/generation.py).
+        Returns NEW tokens only, int64 [B, <= max_new_tokens], pad_token_id after a row's EOS.  With every keyword at its default nothing but
+        the greedy loop is launched or allocated.  video is also taken as pixel_values; max_new_tokens=None means max_length, else 100.
+        do_sample, temperature, top_k, top_p, seed: HF's sampling: temperature -> top_k (HF's GenerationConfig default 50; 0 = off) -> top_p ->
+          one draw per row on the device (ops.sample_rows).  seed=None draws the seed from torch's default CPU generator, so
+          torch.manual_seed makes a sampled run repeat; row b draws with seed + b.  With do_sample=False the other four are ignored.
+        num_beams > 1, length_penalty, early_stopping (True, False or "never", as in HF), return_sequence_scores: HF's beam search
+          (generation.beam_search); returns the best hypothesis per item, padded with pad_token_id, and with return_sequence_scores=True
+          also HF's sequences_scores [B].  Beam sampling (do_sample=True with it) is NotImplementedError.
+        repetition_penalty (> 0, 1.0 = off), no_repeat_ngram_size (0 = off), min_new_tokens: HF's logits processors of those names, in every
+          mode, applied on the device (ops.logits_process) to a row's generated tokens, which is all HF's processors see with inputs_embeds:
+          on the logits before the argmax or the sampling chain, and in beam search on the log-probabilities (log-softmax first, as HF's
+          _beam_search does).  With the three defaults nothing is launched.
+        sequence_bias ({tuple of ids: float} or [[ids, float], ...]), bad_words_ids ([[ids], ...]), suppress_tokens, begin_suppress_tokens
+          (lists of ids): HF's keywords of those names, in the same launch and in HF's order: sequence bias, repetition penalty, n-gram ban,
+          bad words, min_new_tokens, suppress, begin-suppress (the first generated token, HF's begin_index 0 with inputs_embeds).  Their
+          device tables are built once per call (ops.logits_bias_tables; its capacities are refused by name); with all of them None nothing
+          new is launched or allocated.  The 1024-token limit of the older processors also holds when a sequence has more than one token.
+        hotwords, hotword_bias: a list of strings boosted by hotword_bias (contextual biasing): each is tokenised with and without a leading
+          space and every prefix of each tokenisation becomes a sequence_bias entry (generation.hotword_sequence_bias).  HF considers a sequence
+          of L tokens only once L tokens have been generated, so token k of a hotword is not boosted when the word starts the utterance.
+        return_token_scores=True: returns a GenerateOutput (sequences, sequences_scores, token_scores, token_entropy): the log-probability
+          of every returned token, HF's compute_transition_scores, computed at the token step (ops.row_scores; no second prefill), 0.0
+          after a row's EOS.  Greedy: log-softmax of the processed logits at the argmax (normalize_logits=True).  Sampled: the draw's
+          log-probability under the distribution it was drawn from, after temperature, top_k and top_p (ops.sample_rows); token_entropy is
+          that of the UNTRUNCATED distribution, softmax(processed logits / temperature).  Beam search: each token's log-probability as the
+          beam scorer added it (processed, with processors on), carried through the beam reorderings; sequences_scores as HF.
+        num_return_sequences=n: HF's keyword: rows [B*n, L], item-major; beam search returns the n best hypotheses of each item, best first
+          (n <= num_beams); sampling draws n sequences per clip (encoders and connectors run once per clip; the result equals a call on the
+          clips repeated n times); greedy decoding with n > 1 is a ValueError, as in HF."""
         if video is None and pixel_values is not None:
             video = pixel_values
-        if max_new_tokens is None:
-            max_new_tokens = max_length if max_length is not None else 100
-        if int(num_beams) != num_beams or num_beams < 1:
-            raise ValueError(f"num_beams must be a positive integer, got {num_beams}")
-        if num_beams > 1:
-            if do_sample:
-                raise NotImplementedError("beam sampling (do_sample=True with num_beams > 1) is not supported")
-            if num_beams > ops.BEAM_MAX_BEAMS:
-                raise ValueError(f"num_beams must be at most {ops.BEAM_MAX_BEAMS}, got {num_beams}")
-            if early_stopping not in (True, False, "never"):
-                raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
-        elif return_sequence_scores:
-            raise ValueError("return_sequence_scores needs num_beams > 1 (HF returns sequences_scores for beam search only)")
-        n_ret = num_return_sequences
-        if isinstance(n_ret, bool) or not isinstance(n_ret, numbers.Integral) or n_ret < 1:
-            raise ValueError(f"num_return_sequences must be a positive integer, got {n_ret!r}")
-        n_ret = int(n_ret)
-        if num_beams > 1 and n_ret > num_beams:
-            raise ValueError(f"num_return_sequences ({n_ret}) has to be smaller or equal to num_beams ({num_beams})")
-        if num_beams == 1 and not do_sample and n_ret > 1:
-            raise ValueError(f"greedy decoding cannot return {n_ret} sequences: num_return_sequences > 1 needs do_sample=True or num_beams > 1")
-        if do_sample:
-            ops.check_sampling(temperature, top_k, top_p)
-            if seed is None:
-                seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        proc = None
-        if ops.check_logits_processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens):
-            if max_new_tokens > ops.LOGITS_PROCESS_MAX_HISTORY:
-                raise ValueError(f"repetition_penalty / no_repeat_ngram_size / min_new_tokens support at most {ops.LOGITS_PROCESS_MAX_HISTORY} "
-                                 f"new tokens, got max_new_tokens = {max_new_tokens}")
-            proc = (float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens))
-        if hotwords:
-            sequence_bias = hotword_sequence_bias(self.tokenizer, hotwords, hotword_bias, sequence_bias)
-        tables = {}
-        if not (sequence_bias is None and bad_words_ids is None and suppress_tokens is None and begin_suppress_tokens is None):
-            tables = ops.logits_bias_tables(sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens, vocab=self.cfg.llama.vocab,
-                                            eos=self.eos_token_id, device=self.device)
-        # the row history feeds the three older processors and sequences of more than one token
-        need_hist = bool(proc) or any(isinstance(t, ops.SequenceTable) and t.max_len > 1 for t in tables.values())
-        if need_hist and max_new_tokens > ops.LOGITS_PROCESS_MAX_HISTORY:
-            raise ValueError(f"sequence_bias / bad_words_ids with sequences of more than one token support at most "
-                             f"{ops.LOGITS_PROCESS_MAX_HISTORY} new tokens, got max_new_tokens = {max_new_tokens}")
-        if tables and not proc:
-            proc = (1.0, 0, 0)
+        eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
+        max_new_tokens, n_ret, sample, processors = parse_arguments(
+            self.tokenizer, self.cfg.llama.vocab, eos, self.device, max_new_tokens=max_new_tokens, max_length=max_length, do_sample=do_sample,
+            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, num_beams=num_beams, early_stopping=early_stopping,
+            return_sequence_scores=return_sequence_scores, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+            min_new_tokens=min_new_tokens, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
+            begin_suppress_tokens=begin_suppress_tokens, hotwords=hotwords, hotword_bias=hotword_bias, num_return_sequences=num_return_sequences)
         original = self.modality
         if audio is not None and video is not None:
             self.modality = "both"
@@ -578,171 +507,8 @@ class ClipWhisperModel:
         finally:
             self.modality = original
         if num_beams > 1:
-            return self._beam_search(x, max_new_tokens, int(num_beams), float(length_penalty), early_stopping, return_sequence_scores, proc,
-                                     tables, need_hist, n_ret=n_ret, token_scores=bool(return_token_scores))
+            return beam_search(self.llm_engine, x, eos, pad, max_new_tokens, int(num_beams), float(length_penalty), early_stopping,
+                               processors, n_ret=n_ret, return_scores=return_sequence_scores, token_scores=bool(return_token_scores))
         if n_ret > 1:
             x = x.repeat_interleave(n_ret, dim=0)                   # after the encoders and connectors, which ran once per clip
-        eng = self.llm_engine
-        B, S, _ = x.shape
-        kc, vc = eng.alloc_cache(B, S + max_new_tokens)
-        logits, _ = eng.prefill(x, kc, vc)
-        eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
-        unfinished = torch.ones(B, dtype=torch.bool, device=x.device)
-        out = []
-        row_seeds = torch.arange(B, dtype=torch.int32, device=x.device) if do_sample else None
-        # the processors' history: row b's generated tokens (pad after its EOS, as HF feeds them); the kernel itself appends the last token
-        hist = torch.full((B, max_new_tokens), pad, dtype=torch.int64, device=x.device) if need_hist else None
-        nxt = None
-        tok_lp, tok_ent = [], []
-        for step in range(max_new_tokens):
-            if proc:
-                ops.logits_process(logits, hist, step, *proc, eos=eos, append=nxt if need_hist else None, **tables)
-            if return_token_scores:
-                alive = unfinished.clone()                          # rows that still choose a token at this step
-            if do_sample:
-                nxt = ops.sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=unfinished if eos is not None else None,
-                                      eos=eos, pad=pad, row_seeds=row_seeds, return_logprob=bool(return_token_scores))
-                if return_token_scores:
-                    nxt, lp = nxt                                   # 0 for finished rows already
-                    ent = ops.row_scores(logits, nxt, temperature, entropy=True)[1]
-            else:
-                nxt = ops.argmax_rows(logits)
-                if return_token_scores:
-                    lp, ent = ops.row_scores(logits, nxt, entropy=True)
-                    lp = torch.where(alive, lp, torch.zeros_like(lp))
-                if eos is not None:
-                    nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
-                    unfinished = unfinished & (nxt != eos)
-            out.append(nxt)
-            if return_token_scores:
-                tok_lp.append(lp)
-                tok_ent.append(torch.where(alive, ent, torch.zeros_like(ent)))
-            if step + 1 == max_new_tokens or (eos is not None and not bool(unfinished.any())):
-                break
-            logits = eng.decode_step(nxt, S + step, kc, vc)
-        if return_token_scores:
-            return GenerateOutput(torch.stack(out, dim=1), None, torch.stack(tok_lp, dim=1), torch.stack(tok_ent, dim=1))
-        return torch.stack(out, dim=1)
-
-    def _beam_search(self, x, max_new_tokens, nb, length_penalty, early_stopping, return_scores, proc=None, tables=None, need_hist=True,
-                     n_ret=1, token_scores=False):
-        """GenerationMixin._beam_search (transformers 5.x, generation/utils.py) for inputs_embeds x [B, S, d]: decoder_prompt_len = 0, so a
-        hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
-        the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
-        (_get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic,
-        _beam_search_has_unfinished_sequences) restated on small device tensors, and ops.kv_gather_rows reordering only the generated
-        positions [S, S + step): every beam of an item shares the prefix [0, S), which is copied once from the B-row prefill cache.
-        Equal scores keep candidate order (stable sorts where HF calls torch.topk).  One host sync per step, for the stopping test.
-        B*nb <= 16 rows take the fused bf16 token step (LlamaEngine.decode_is_fused); more rows take the general step.
-        proc = (repetition_penalty, no_repeat_ngram_size, min_new_tokens): HF runs its logits processors between the log_softmax and the
-        addition of the running beam scores, on running_sequences[:, :, :cur]; ops.logits_process(log_softmax=True) does both on the
-        B*nb rows and beam_topk then takes the rows as log-probabilities.  tables: generate()'s prepared sequence_bias / bad_words_ids /
-        suppress_tokens / begin_suppress_tokens, for the same launch; need_hist: whether any of it reads running_sequences.
-        n_ret: the n best finished hypotheses of each item are returned, rows [B*n_ret, L] item-major, best first (HF's
-        num_return_sequences).  token_scores: every candidate's own log-probability, read from the row it came from (the processed
-        log-probability with proc; logit - logsumexp of the raw row otherwise, ops.row_scores), and that row's entropy are carried in
-        [B, nb, N] tensors through the gathers that reorder the sequences; returns a GenerateOutput.  Never derived as
-        topk_lp - running_scores[parent]: that difference loses the low bits of a long hypothesis."""
-        eng = self.llm_engine
-        dev = x.device
-        B, S, _ = x.shape
-        R, k, N = B * nb, 2 * nb, max_new_tokens
-        eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
-        kc0, vc0 = eng.alloc_cache(B, S)
-        logits, _ = eng.prefill(x, kc0, vc0)
-        kc, vc = eng.alloc_cache(R, S + N)
-        ops.kv_gather_rows(kc0, vc0, kc, vc, torch.arange(R, device=dev, dtype=torch.int32) // nb, 0, S)    # prefix broadcast
-        del kc0, vc0
-        logits = logits.repeat_interleave(nb, dim=0)                # step 0: every beam of an item sees the prefill logits
-        NEG = -1.0e9
-        running_seq = torch.full((B, nb, N), pad, dtype=torch.int64, device=dev)
-        sequences = running_seq.clone()
-        running_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
-        running_scores[:, 1:] = NEG
-        beam_scores = torch.full((B, nb), NEG, dtype=torch.float32, device=dev)
-        lengths = torch.zeros((B, nb), dtype=torch.int64, device=dev)             # generated length of each finished hypothesis
-        is_sent_finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
-        if token_scores:
-            running_tok_lp = torch.zeros((B, nb, N), dtype=torch.float32, device=dev)
-            running_ent, tok_lp, tok_ent = running_tok_lp.clone(), running_tok_lp.clone(), running_tok_lp.clone()
-        unsatisfied = torch.ones((B, 1), dtype=torch.bool, device=dev)
-        top_mask = torch.arange(k, device=dev) < nb
-        offset = (torch.arange(B, device=dev, dtype=torch.int32) * nb)[:, None]
-        done_host = torch.zeros(1, dtype=torch.bool).pin_memory()
-        ev = torch.cuda.Event()
-        for cur in range(N):
-            # _get_top_k_continuations
-            if proc:
-                ops.logits_process(logits, running_seq.view(R, N) if need_hist else None, cur, *proc, eos=eos, log_softmax=True, **(tables or {}))
-            topk_lp, topk_beam, topk_tok = ops.beam_topk(logits, running_scores.view(-1), nb, k, logprobs=bool(proc))
-            topk_seq = torch.gather(running_seq, 1, topk_beam.long()[:, :, None].expand(B, k, N)).clone()
-            topk_seq[:, :, cur] = topk_tok
-            topk_parent = topk_beam + offset
-            if token_scores:
-                # the candidates' own log-probabilities and their rows' entropies, from the B*nb rows beam_topk selected from
-                norm, row_ent = ops.row_scores(logits, None, entropy=True, logprobs=bool(proc))    # norm: -logsumexp (0 for log-probabilities)
-                cand_lp = logits[topk_parent.long(), topk_tok]
-                if not proc:
-                    cand_lp = cand_lp + norm[topk_parent.long()]
-                bidx = topk_beam.long()[:, :, None].expand(B, k, N)
-                topk_tok_lp = torch.gather(running_tok_lp, 1, bidx).clone()
-                topk_tok_lp[:, :, cur] = cand_lp
-                topk_ent = torch.gather(running_ent, 1, bidx).clone()
-                topk_ent[:, :, cur] = row_ent[topk_parent.long()]
-            # stopping criteria: EOS, or max_length reached
-            if cur + 1 >= N:
-                hits = torch.ones((B, k), dtype=torch.bool, device=dev)
-            elif eos is not None:
-                hits = topk_tok == eos
-            else:
-                hits = torch.zeros((B, k), dtype=torch.bool, device=dev)
-            # _get_running_beams_for_next_iteration
-            topk_running_lp = topk_lp + hits.to(torch.float32) * NEG
-            nxt = torch.sort(topk_running_lp, dim=1, descending=True, stable=True)[1][:, :nb]
-            running_seq = torch.gather(topk_seq, 1, nxt[:, :, None].expand(B, nb, N))
-            running_scores = torch.gather(topk_running_lp, 1, nxt)
-            parent = torch.gather(topk_parent, 1, nxt)
-            if token_scores:
-                running_tok_lp = torch.gather(topk_tok_lp, 1, nxt[:, :, None].expand(B, nb, N))
-                running_ent = torch.gather(topk_ent, 1, nxt[:, :, None].expand(B, nb, N))
-            # _update_finished_beams
-            just = hits & top_mask[None, :]
-            fin_lp = topk_lp / ((cur + 1) ** length_penalty)
-            full = torch.all(is_sent_finished, dim=-1, keepdim=True) & (early_stopping is True)
-            fin_lp += full.to(torch.float32) * NEG
-            fin_lp += (~unsatisfied).to(torch.float32) * NEG
-            fin_lp += (~just) * NEG
-            m_scores = torch.cat((beam_scores, fin_lp), dim=1)
-            sel = torch.sort(m_scores, dim=1, descending=True, stable=True)[1][:, :nb]
-            sequences = torch.gather(torch.cat((sequences, topk_seq), dim=1), 1, sel[:, :, None].expand(B, nb, N))
-            beam_scores = torch.gather(m_scores, 1, sel)
-            lengths = torch.gather(torch.cat((lengths, torch.full((B, k), cur + 1, dtype=torch.int64, device=dev)), dim=1), 1, sel)
-            is_sent_finished = torch.gather(torch.cat((is_sent_finished, just), dim=1), 1, sel)
-            if token_scores:
-                tok_lp = torch.gather(torch.cat((tok_lp, topk_tok_lp), dim=1), 1, sel[:, :, None].expand(B, nb, N))
-                tok_ent = torch.gather(torch.cat((tok_ent, topk_ent), dim=1), 1, sel[:, :, None].expand(B, nb, N))
-            if cur + 1 >= N:                                        # every candidate hit max_length: HF's loop ends here
-                break
-            # _check_early_stop_heuristic at cur_len = cur + 1, then _beam_search_has_unfinished_sequences
-            if early_stopping == "never" and length_penalty > 0.0:
-                best_len = N
-            else:
-                best_len = cur + 1
-            best_running = running_scores[:, :1] / (best_len ** length_penalty)
-            worst_finished = torch.where(is_sent_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], NEG)
-            unsatisfied = unsatisfied & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
-            done = ~(torch.any(unsatisfied) & ~(torch.all(is_sent_finished) & (early_stopping is True)) & ~torch.all(hits))
-            done_host.copy_(done.view(1), non_blocking=True)
-            ev.record()
-            # the next token step is queued before the host waits on the stopping test (only the small copy above is awaited)
-            ops.kv_gather_rows(kc, vc, kc, vc, parent.view(-1).to(torch.int32), S, S + cur)
-            logits = eng.decode_step(running_seq[:, :, cur].reshape(-1), S + cur, kc, vc)
-            ev.synchronize()
-            if bool(done_host[0]):
-                break
-        L = int(lengths[:, :n_ret].max())
-        out = sequences[:, :n_ret, :L].reshape(B * n_ret, L)
-        scores = beam_scores[:, :n_ret].reshape(B * n_ret)
-        if token_scores:
-            return GenerateOutput(out, scores, tok_lp[:, :n_ret, :L].reshape(B * n_ret, L), tok_ent[:, :n_ret, :L].reshape(B * n_ret, L))
-        return (out, scores) if return_scores else out
+        return token_loop(self.llm_engine, x, eos, pad, max_new_tokens, processors, sample=sample, token_scores=bool(return_token_scores))

@@ -324,16 +324,11 @@ def sample_rows(logits, temperature, top_k, top_p, seed, step, unfinished=None, 
         assert row_seeds.dtype == torch.int32 and row_seeds.shape == (rows,) and row_seeds.is_contiguous()
     eos = -1 if eos is None else int(eos)
     pad = (eos if eos >= 0 else 0) if pad is None else int(pad)
-    if return_logprob:
-        lp = torch.empty(rows, device=logits.device, dtype=torch.float32)
-        L.check(L.load().avllm_sample_rows_scored(L.ptr(logits), _ld(logits), rows, V, float(temperature), int(top_k), float(top_p),
-                                                  int(seed) & 0xFFFFFFFF, L.ptr(row_seeds), int(step), L.ptr(step_dev), L.ptr(unfinished),
-                                                  eos, pad, L.ptr(out), L.ptr(lp), L.dt_of(logits), L.stream_ptr()))
-        return out, lp
-    L.check(L.load().avllm_sample_rows(L.ptr(logits), _ld(logits), rows, V, float(temperature), int(top_k), float(top_p),
-                                       int(seed) & 0xFFFFFFFF, L.ptr(row_seeds), int(step), L.ptr(step_dev), L.ptr(unfinished), eos, pad,
-                                       L.ptr(out), L.dt_of(logits), L.stream_ptr()))
-    return out
+    lp = torch.empty(rows, device=logits.device, dtype=torch.float32) if return_logprob else None
+    L.check(L.load().avllm_sample_rows_scored(L.ptr(logits), _ld(logits), rows, V, float(temperature), int(top_k), float(top_p),
+                                              int(seed) & 0xFFFFFFFF, L.ptr(row_seeds), int(step), L.ptr(step_dev), L.ptr(unfinished),
+                                              eos, pad, L.ptr(out), L.ptr(lp), L.dt_of(logits), L.stream_ptr()))
+    return (out, lp) if return_logprob else out
 
 
 LOGITS_PROCESS_MAX_HISTORY = 1024
@@ -357,6 +352,13 @@ LOGITS_BIAS_MAX_SEQUENCES, LOGITS_BIAS_MAX_SEQUENCE_LENGTH = 4096, 16      # AVL
 # values f32 [n] (None for bad words), entries grouped by last token; TokenTable: ids int32 [n], distinct and ascending.
 SequenceTable = collections.namedtuple("SequenceTable", "tokens lengths values n max_len vocab")
 TokenTable = collections.namedtuple("TokenTable", "ids n vocab")
+# generate()'s keyword -> (table type, {field of avllm_logits_proc_desc: attribute of the table})
+_TABLE_FIELDS = {
+    "sequence_bias": (SequenceTable, dict(bias_tokens="tokens", bias_lengths="lengths", bias_values="values", n_bias="n", bias_max_len="max_len")),
+    "bad_words_ids": (SequenceTable, dict(bad_tokens="tokens", bad_lengths="lengths", n_bad="n", bad_max_len="max_len")),
+    "suppress_tokens": (TokenTable, dict(suppress="ids", n_suppress="n")),
+    "begin_suppress_tokens": (TokenTable, dict(begin_suppress="ids", n_begin_suppress="n")),
+}
 
 
 def _token_ids(name, ids, vocab):
@@ -476,20 +478,12 @@ def logits_process(scores, history, cur, repetition_penalty=1.0, no_repeat_ngram
     if scores.dim() != 2 or not scores.is_cuda or scores.stride(1) != 1:
         raise ValueError("logits_process: scores must be a 2-d device tensor with unit column stride")
     rows, V = scores.shape
-    for name, t, kind in (("sequence_bias", sequence_bias, SequenceTable), ("bad_words_ids", bad_words_ids, SequenceTable),
-                          ("suppress_tokens", suppress_tokens, TokenTable), ("begin_suppress_tokens", begin_suppress_tokens, TokenTable)):
-        if t is not None and not isinstance(t, kind):
-            raise ValueError(f"logits_process: {name} must be a prepared {kind.__name__} (ops.logits_bias_tables), got {type(t).__name__}")
-        if t is not None and t.vocab != V:
-            raise ValueError(f"logits_process: the {name} table was built for a vocabulary of {t.vocab}, the scores have {V} columns")
-    ex = not (sequence_bias is None and bad_words_ids is None and suppress_tokens is None and begin_suppress_tokens is None)
     cur_dev = None
     if torch.is_tensor(cur):
         assert cur.dtype == torch.int32 and cur.numel() == 1 and cur.is_cuda
         cur_dev, cur = cur, 0
-    if history is None and ex:
-        hptr, ldh = None, 0                        # the library refuses when something needs the history
-    else:
+    hptr, ldh = None, 0                            # no history: the library refuses when something needs it
+    if history is not None:
         if history.dtype != torch.int64 or history.dim() != 2 or history.shape[0] != rows or not history.is_cuda or \
                 (history.shape[1] > 1 and history.stride(1) != 1):
             raise ValueError(f"logits_process: history must be an int64 device tensor [{rows}, ld] with unit column stride")
@@ -499,26 +493,20 @@ def logits_process(scores, history, cur, repetition_penalty=1.0, no_repeat_ngram
         hptr = L.ptr(history) if history.numel() else None
     if append is not None:
         assert append.dtype == torch.int64 and append.shape == (rows,) and append.is_contiguous() and append.is_cuda
-    eos = -1 if eos is None else int(eos)
-    if not ex:
-        L.check(L.load().avllm_logits_process(L.ptr(scores), _ld(scores), rows, V, hptr, ldh, L.ptr(append),
-                                              int(cur), L.ptr(cur_dev), float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens),
-                                              eos, int(bool(log_softmax)), L.dt_of(scores), L.stream_ptr()))
-        return scores
     d = L.LogitsProcDesc(scores=L.ptr(scores), ld=_ld(scores), rows=rows, V=V, dtype=L.dt_of(scores), history=hptr, ldh=ldh, append=L.ptr(append),
                          cur=int(cur), cur_dev=L.ptr(cur_dev), repetition_penalty=float(repetition_penalty),
-                         no_repeat_ngram_size=int(no_repeat_ngram_size), min_new_tokens=int(min_new_tokens), eos=eos,
+                         no_repeat_ngram_size=int(no_repeat_ngram_size), min_new_tokens=int(min_new_tokens), eos=-1 if eos is None else int(eos),
                          log_softmax=int(bool(log_softmax)))
-    if sequence_bias is not None:
-        t = sequence_bias
-        d.bias_tokens, d.bias_lengths, d.bias_values, d.n_bias, d.bias_max_len = L.ptr(t.tokens), L.ptr(t.lengths), L.ptr(t.values), t.n, t.max_len
-    if bad_words_ids is not None:
-        t = bad_words_ids
-        d.bad_tokens, d.bad_lengths, d.n_bad, d.bad_max_len = L.ptr(t.tokens), L.ptr(t.lengths), t.n, t.max_len
-    if suppress_tokens is not None:
-        d.suppress, d.n_suppress = L.ptr(suppress_tokens.ids), suppress_tokens.n
-    if begin_suppress_tokens is not None:
-        d.begin_suppress, d.n_begin_suppress = L.ptr(begin_suppress_tokens.ids), begin_suppress_tokens.n
+    for (name, (kind, fields)), t in zip(_TABLE_FIELDS.items(), (sequence_bias, bad_words_ids, suppress_tokens, begin_suppress_tokens)):
+        if t is None:
+            continue
+        if not isinstance(t, kind):
+            raise ValueError(f"logits_process: {name} must be a prepared {kind.__name__} (ops.logits_bias_tables), got {type(t).__name__}")
+        if t.vocab != V:
+            raise ValueError(f"logits_process: the {name} table was built for a vocabulary of {t.vocab}, the scores have {V} columns")
+        for field, attr in fields.items():
+            v = getattr(t, attr)
+            setattr(d, field, L.ptr(v) if torch.is_tensor(v) else v)
     L.check(L.load().avllm_logits_process_ex(C.byref(d), L.stream_ptr()))
     return scores
 

@@ -149,10 +149,14 @@ int avllm_beam_topk_logprobs(const float* logprobs, int64_t ld, int32_t B, int32
 int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int64_t* history, int64_t ldh, const int64_t* append, int32_t cur,
                          const int32_t* cur_dev, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens, int64_t eos,
                          int32_t log_softmax, int32_t dtype, void* stream) {
-    return av_logits_process(scores, ld, rows, V, history, ldh, append, cur, cur_dev, repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos,
-                             log_softmax, dtype, ST);
+    avllm_logits_proc_desc d = {};                 // no tables: the descriptor entry below with every n_* zero
+    d.scores = scores; d.ld = ld; d.rows = rows; d.V = V; d.dtype = dtype;
+    d.history = history; d.ldh = ldh; d.append = append; d.cur = cur; d.cur_dev = cur_dev;
+    d.repetition_penalty = repetition_penalty; d.no_repeat_ngram_size = no_repeat_ngram_size; d.min_new_tokens = min_new_tokens;
+    d.eos = eos; d.log_softmax = log_softmax;
+    return av_logits_process(&d, ST);
 }
-int avllm_logits_process_ex(const avllm_logits_proc_desc* d, void* stream) { return av_logits_process_ex(d, ST); }
+int avllm_logits_process_ex(const avllm_logits_proc_desc* d, void* stream) { return av_logits_process(d, ST); }
 int avllm_kv_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
                          int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, int32_t dtype, void* stream) {
     return av_kv_gather_rows(k_src, v_src, src_rows, src_T, k_dst, v_dst, dst_rows, dst_T, layers, dkv, parent, t0, t1, dtype, ST);

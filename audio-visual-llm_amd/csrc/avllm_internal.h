@@ -45,9 +45,7 @@ int av_row_scores(const void* logits, long ld, long rows, int V, const int64_t* 
 size_t av_beam_topk_workspace_bytes(long rows, int V, int k);
 int av_beam_topk(const float* logits, long ld, int B, int nb, int V, const float* beam_scores, int k, float* out_scores, int32_t* out_beams,
                  int64_t* out_tokens, void* ws, size_t ws_bytes, int logprobs, hipStream_t st);
-int av_logits_process(void* scores, long ld, long rows, int V, int64_t* history, long ldh, const int64_t* append, int cur, const int* cur_dev,
-                      float penalty, int ngram, int min_new, long long eos, int log_softmax, int dtype, hipStream_t st);
-int av_logits_process_ex(const avllm_logits_proc_desc* d, hipStream_t st);
+int av_logits_process(const avllm_logits_proc_desc* d, hipStream_t st);
 int av_kv_gather_rows(const void* k_src, const void* v_src, int src_rows, long src_T, void* k_dst, void* v_dst, int dst_rows, long dst_T,
                       int layers, int dkv, const int32_t* parent, int t0, int t1, int dtype, hipStream_t st);
 int av_embedding(const void* table, const int64_t* ids, void* out, long n, int d, int dtype, hipStream_t st);

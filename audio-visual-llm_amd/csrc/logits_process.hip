@@ -18,7 +18,7 @@
 // `append` (optional, int64 [rows]): the token the selection kernel produced for position n-1, which this launch stores into the history
 // before using it: the token loop keeps its history on the device without a copy launch of its own.
 //
-// avllm_logits_process_ex (process_kernel<T, true>, the same launch with four device tables) adds SequenceBiasLogitsProcessor,
+// With device tables in the descriptor (process_kernel<T, true>, the same launch) it adds SequenceBiasLogitsProcessor,
 // NoBadWordsLogitsProcessor, SuppressTokensLogitsProcessor and SuppressTokensAtBeginLogitsProcessor at their places in HF's order:
 //   0. log-softmax   0b. sequence bias   1. penalty   2. n-gram ban   2b. bad words   3. min_new_tokens   4. suppress   5. begin-suppress
 //   0b. sequence bias: entries (tokens[L], fp32 bias), L <= MAX_SEQ_LEN, SORTED by the caller so that the entries with one last token are
@@ -161,33 +161,10 @@ void launch(void* scores, long ld, long rows, int V, int64_t* history, long ldh,
 
 }  // namespace
 
-int av_logits_process(void* scores, long ld, long rows, int V, int64_t* history, long ldh, const int64_t* append, int cur, const int* cur_dev,
-                      float penalty, int ngram, int min_new, long long eos, int log_softmax, int dtype, hipStream_t st) {
-    AV_CHECK_ARG(scores && rows > 0 && V > 0 && ld >= V, "logits_process: bad args");
-    AV_CHECK_ARG(dtype == AV_F32 || dtype == AV_BF16, "logits_process: dtype");
-    AV_CHECK_ARG(!log_softmax || dtype == AV_F32, "logits_process: the log-softmax mode takes f32 rows");
-    AV_CHECK_ARG(penalty > 0.f && penalty < INFINITY, "logits_process: repetition_penalty must be > 0 (got %g)", (double)penalty);
-    AV_CHECK_ARG(ngram >= 0, "logits_process: no_repeat_ngram_size must be >= 0 (got %d)", ngram);
-    AV_CHECK_ARG(min_new >= 0, "logits_process: min_new_tokens must be >= 0 (got %d)", min_new);
-    AV_CHECK_ARG(cur >= 0 && ldh >= 0, "logits_process: history length %d, row stride %ld", cur, ldh);
-    AV_CHECK_ARG(cur <= MAX_HIST, "logits_process: a history of %d tokens (at most %d are supported)", cur, MAX_HIST);
-    AV_CHECK_ARG(cur <= ldh, "logits_process: history length %d > row stride %ld", cur, ldh);
-    // the length in device memory cannot be checked here: the kernel clamps it to the row stride, which must then be within the limit
-    AV_CHECK_ARG(!cur_dev || ldh <= MAX_HIST, "logits_process: a history of up to %ld tokens (at most %d are supported)", ldh, MAX_HIST);
-    AV_CHECK_ARG(history || (cur == 0 && !cur_dev), "logits_process: null history");
-    AV_CHECK_ARG(rows < (1L << 31), "logits_process: rows");
-    if (penalty == 1.0f && ngram == 0 && min_new == 0 && !log_softmax && !append) return AV_OK;
-    launch<false>(scores, ld, rows, V, history, ldh, append, cur, cur_dev, penalty, ngram, min_new, eos, log_softmax, dtype, Tables{}, st);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
-int av_logits_process_ex(const avllm_logits_proc_desc* d, hipStream_t st) {
-    AV_CHECK_ARG(d, "logits_process_ex: null descriptor");
-    const bool tables = d->n_bias || d->n_bad || d->n_suppress || d->n_begin_suppress;
-    if (!tables)                                   // nothing new: the launch (or no launch) of avllm_logits_process
-        return av_logits_process(d->scores, d->ld, d->rows, d->V, d->history, d->ldh, d->append, d->cur, d->cur_dev, d->repetition_penalty,
-                                 d->no_repeat_ngram_size, d->min_new_tokens, d->eos, d->log_softmax, d->dtype, st);
+// The one host entry: avllm_logits_process fills a descriptor with no tables and comes here too.  process_kernel<T, true> when any table is
+// non-empty, process_kernel<T, false> otherwise; no launch when there is nothing to do.
+int av_logits_process(const avllm_logits_proc_desc* d, hipStream_t st) {
+    AV_CHECK_ARG(d, "logits_process: null descriptor");
     const float penalty = d->repetition_penalty;
     const int ngram = d->no_repeat_ngram_size, min_new = d->min_new_tokens, cur = d->cur, V = d->V;
     AV_CHECK_ARG(d->scores && d->rows > 0 && V > 0 && d->ld >= V, "logits_process: bad args");
@@ -198,10 +175,8 @@ int av_logits_process_ex(const avllm_logits_proc_desc* d, hipStream_t st) {
     AV_CHECK_ARG(min_new >= 0, "logits_process: min_new_tokens must be >= 0 (got %d)", min_new);
     AV_CHECK_ARG(cur >= 0 && d->ldh >= 0, "logits_process: history length %d, row stride %ld", cur, (long)d->ldh);
     AV_CHECK_ARG(d->rows < (1L << 31), "logits_process: rows");
-    AV_CHECK_ARG(d->n_bias >= 0 && d->n_bias <= MAX_SEQS, "logits_process: sequence_bias has %d sequences (at most %d are supported)", d->n_bias,
-                 MAX_SEQS);
-    AV_CHECK_ARG(d->n_bad >= 0 && d->n_bad <= MAX_SEQS, "logits_process: bad_words_ids has %d sequences (at most %d are supported)", d->n_bad,
-                 MAX_SEQS);
+    AV_CHECK_ARG(d->n_bias >= 0 && d->n_bias <= MAX_SEQS, "logits_process: sequence_bias has %d sequences (at most %d are supported)", d->n_bias, MAX_SEQS);
+    AV_CHECK_ARG(d->n_bad >= 0 && d->n_bad <= MAX_SEQS, "logits_process: bad_words_ids has %d sequences (at most %d are supported)", d->n_bad, MAX_SEQS);
     AV_CHECK_ARG(!d->n_bias || (d->bias_tokens && d->bias_lengths && d->bias_values), "logits_process: null sequence_bias table");
     AV_CHECK_ARG(!d->n_bad || (d->bad_tokens && d->bad_lengths), "logits_process: null bad_words_ids table");
     AV_CHECK_ARG(!d->n_bias || (d->bias_max_len >= 1 && d->bias_max_len <= MAX_SEQ_LEN),
@@ -215,24 +190,22 @@ int av_logits_process_ex(const avllm_logits_proc_desc* d, hipStream_t st) {
     // the history is read by the three older processors, by append, and by table entries longer than one token
     const bool need_hist = penalty != 1.0f || ngram > 0 || min_new > 0 || d->append || (d->n_bias && d->bias_max_len > 1) ||
                            (d->n_bad && d->bad_max_len > 1);
-    int64_t* history = nullptr;
-    long ldh = 0;
     if (need_hist) {
         AV_CHECK_ARG(cur <= MAX_HIST, "logits_process: a history of %d tokens (at most %d are supported)", cur, MAX_HIST);
         AV_CHECK_ARG(cur <= d->ldh, "logits_process: history length %d > row stride %ld", cur, (long)d->ldh);
+        // the length in device memory cannot be checked here: the kernel clamps it to the row stride, which must then be within the limit
         AV_CHECK_ARG(!d->cur_dev || d->ldh <= MAX_HIST, "logits_process: a history of up to %ld tokens (at most %d are supported)", (long)d->ldh,
                      MAX_HIST);
         AV_CHECK_ARG(d->history || (cur == 0 && !d->cur_dev), "logits_process: null history");
-        history = d->history;
-        ldh = d->history ? d->ldh : 0;
     }
-    Tables tb;
-    tb.bias = SeqTable{d->bias_tokens, d->bias_lengths, d->bias_values, d->n_bias};
-    tb.bad = SeqTable{d->bad_tokens, d->bad_lengths, nullptr, d->n_bad};
-    tb.suppress = d->suppress; tb.n_suppress = d->n_suppress;
-    tb.begin = d->begin_suppress; tb.n_begin = d->n_begin_suppress;
-    launch<true>(d->scores, d->ld, d->rows, V, history, ldh, need_hist ? d->append : nullptr, cur, d->cur_dev, penalty, ngram, min_new, d->eos,
-                 d->log_softmax, d->dtype, tb, st);
+    int64_t* const history = need_hist ? d->history : nullptr;
+    const long ldh = history ? d->ldh : 0;
+    const bool tables = d->n_bias || d->n_bad || d->n_suppress || d->n_begin_suppress;
+    if (!tables && !need_hist && !d->log_softmax) return AV_OK;      // every processor off: nothing to do
+    const Tables tb{SeqTable{d->bias_tokens, d->bias_lengths, d->bias_values, d->n_bias}, SeqTable{d->bad_tokens, d->bad_lengths, nullptr, d->n_bad},
+                    d->suppress, d->n_suppress, d->begin_suppress, d->n_begin_suppress};
+    (tables ? launch<true> : launch<false>)(d->scores, d->ld, d->rows, V, history, ldh, d->append, cur, d->cur_dev, penalty, ngram, min_new, d->eos,
+                                            d->log_softmax, d->dtype, tb, st);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -313,7 +313,8 @@ int avllm_beam_topk_logprobs(const float* logprobs, int64_t ld, int32_t B, int32
  * append (optional, int64 [rows]): stored at history[r][n-1] before the history is read (the token chosen since the previous call), which
  * spares the token loop a copy launch.  n <= 1024: a larger cur is AV_ERR_ARG, and with cur_dev ldh <= 1024 is required (the kernel
  * clamps n to ldh).  One launch, one workgroup per row, O(n) work plus three passes over V with log_softmax; deterministic.  With every
- * processor off, log_softmax = 0 and no append, nothing is launched. */
+ * processor off, log_softmax = 0 and no append, nothing is launched.  This is avllm_logits_process_ex with a descriptor of no tables:
+ * the history and its limits are checked when a processor or append reads it (see below). */
 int avllm_logits_process(void* scores, int64_t ld, int64_t rows, int32_t V, int64_t* history, int64_t ldh, const int64_t* append, int32_t cur,
                          const int32_t* cur_dev, float repetition_penalty, int32_t no_repeat_ngram_size, int32_t min_new_tokens, int64_t eos,
                          int32_t log_softmax, int32_t dtype, void* stream);

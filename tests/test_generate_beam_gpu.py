@@ -1,9 +1,10 @@
 """ClipWhisperModel.generate(num_beams > 1) on the tiny golden model (tests/golden/g2_tiny_e2e.npz): beam search through the B*nb-row
-token step, ops.beam_topk, HF's bookkeeping and ops.kv_gather_rows, against `hf_beam_search` below, a CPU restatement of transformers'
+token step, ops.beam_topk, HF's bookkeeping and ops.kv_gather_rows, against generate_ref.hf_beam_search, a CPU restatement of transformers'
 GenerationMixin._beam_search (5.x, generation/utils.py) driving the oracle's llama_hidden with a KV cache that it reorders in full, as HF's
 _reorder_cache does.  Where transformers is importable, the restatement and generate() are both pinned to LlamaForCausalLM.generate on the
 same embeddings and weights.  Also: num_beams=1 is the golden greedy path, bf16 teacher-forced scores, fused / general token steps, row
 independence and decode.py --num_beams."""
+import functools
 import glob
 import json
 import os
@@ -15,102 +16,19 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import generate_ref  # noqa: E402
 from avllm import ops  # noqa: E402
 from bars import BF16_LOGIT_MAX_ABS  # noqa: E402
+from generate_ref import hf_beam_search, oracle_step_fn, with_eos  # noqa: E402,F401
 from oracle import avsr_oracle as O  # noqa: E402
 from oracle import weights as Wt  # noqa: E402
 from test_model_gpu import T, make_model, tiny  # noqa: E402,F401
 
 N_NEW = 10
+gen = functools.partial(generate_ref.gen, max_new_tokens=N_NEW)
 # eos: tokens the tiny model's greedy decode emits at steps 2 and 1 (golden generate_ids rows [77 239 53 ...] and [151 77 239 ...]), so
 # hypotheses finish early and length normalisation and padding are exercised
 EOS_IDS = (53, 239)
-
-
-def hf_beam_search(step, B, nb, V, max_new, eos, pad, length_penalty=1.0, early_stopping=False):
-    """GenerationMixin._beam_search for inputs_embeds (decoder_prompt_len = 0, max_length = max_new), one EOS id or none.
-    step(tokens, beam_idx): tokens None -> the prefill logits [B*nb, V] (beams of an item repeated); otherwise reorder the cache rows by
-    beam_idx [B*nb] and run one token per row.  Returns (sequences [B, L], sequences_scores [B])."""
-    k = 2 * nb
-    running_sequences = torch.full((B, nb, max_new), pad, dtype=torch.int64)
-    sequences = running_sequences.clone()
-    running_beam_scores = torch.zeros((B, nb))
-    running_beam_scores[:, 1:] = -1e9
-    beam_scores = torch.full((B, nb), -1e9)
-    is_sent_finished = torch.zeros((B, nb), dtype=torch.bool)
-    unsatisfied = torch.ones((B, 1), dtype=torch.bool)
-    running_beam_indices = torch.full((B, nb, max_new), -1, dtype=torch.int32)
-    beam_indices = running_beam_indices.clone()
-    top_num_beam_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(k - nb, dtype=torch.bool)))
-    gather = lambda t, idx: torch.take_along_dim(t, idx.view(*idx.shape, *([1] * (t.dim() - 2))), dim=1)  # noqa: E731
-    logits = step(None, None)
-    cur_len = 0
-    while True:
-        log_probs = torch.log_softmax(logits.float(), dim=-1).view(B, nb, V) + running_beam_scores[:, :, None]
-        log_probs = log_probs.reshape(B, nb * V)
-        # _get_top_k_continuations
-        topk_log_probs, topk_indices = torch.topk(log_probs, k=k)
-        topk_beam = topk_indices // V
-        topk_running_beam_indices = gather(running_beam_indices, topk_beam).clone()
-        topk_running_sequences = gather(running_sequences, topk_beam).clone()
-        topk_ids = topk_indices % V
-        topk_running_sequences[:, :, cur_len] = topk_ids
-        topk_running_beam_indices[:, :, cur_len] = (topk_beam + torch.arange(B)[:, None] * nb).to(torch.int32)
-        # stopping criteria: MaxLengthCriteria, EosTokenCriteria
-        hits = torch.full((B, k), cur_len + 1 >= max_new)
-        if eos is not None:
-            hits = hits | (topk_ids == eos)
-        # _get_running_beams_for_next_iteration
-        topk_running_log_probs = topk_log_probs + hits.to(torch.float32) * -1.0e9
-        nxt = torch.topk(topk_running_log_probs, k=nb)[1]
-        running_sequences = gather(topk_running_sequences, nxt)
-        running_beam_scores = gather(topk_running_log_probs, nxt)
-        running_beam_indices = gather(topk_running_beam_indices, nxt)
-        # _update_finished_beams
-        just = hits & top_num_beam_mask[None, :]
-        fin = topk_log_probs / ((cur_len + 1) ** length_penalty)
-        fin += (torch.all(is_sent_finished, dim=-1, keepdim=True) & (early_stopping is True)).to(torch.float32) * -1.0e9
-        fin += (~unsatisfied).to(torch.float32) * -1.0e9
-        fin += (~just) * -1.0e9
-        merged = torch.cat((beam_scores, fin), dim=1)
-        sel = torch.topk(merged, k=nb)[1]
-        sequences = gather(torch.cat((sequences, topk_running_sequences), dim=1), sel)
-        beam_scores = gather(merged, sel)
-        beam_indices = gather(torch.cat((beam_indices, topk_running_beam_indices), dim=1), sel)
-        is_sent_finished = gather(torch.cat((is_sent_finished, just), dim=1), sel)
-        beam_idx = running_beam_indices[:, :, cur_len].reshape(-1).long()
-        cur_len += 1
-        # _check_early_stop_heuristic, _beam_search_has_unfinished_sequences
-        best_len = max_new if (early_stopping == "never" and length_penalty > 0.0) else cur_len
-        best_running = running_beam_scores[:, :1] / (best_len ** length_penalty)
-        worst_finished = torch.where(is_sent_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], -1.0e9)
-        unsatisfied = unsatisfied & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
-        going = bool(torch.any(unsatisfied) & ~(torch.all(is_sent_finished) & (early_stopping is True)) & ~torch.all(hits))
-        if not going:
-            break
-        logits = step(running_sequences[:, :, cur_len - 1].reshape(-1), beam_idx)
-    L = int(((beam_indices[:, 0] + 1) != 0).sum(dim=1).max())
-    return sequences[:, 0, :L], beam_scores[:, 0]
-
-
-def oracle_step_fn(W, cfg, x, nb, lora=True):
-    """The oracle's llama_hidden with a per-layer KV cache (HF's DynamicCache), reordered in full by beam_idx at every step."""
-    sd, c = W["llama"], cfg.llama
-    lw = W.get("lora") if lora else None
-    past = [None] * c.layers
-    state = {"pos": x.shape[1]}
-
-    def step(tokens, beam_idx):
-        with torch.no_grad():
-            if tokens is None:
-                h = O.llama_hidden(sd, lw, c, cfg.lora, x.repeat_interleave(nb, dim=0), past=past, pos0=0)
-            else:
-                for i in range(c.layers):
-                    past[i] = (past[i][0].index_select(0, beam_idx), past[i][1].index_select(0, beam_idx))
-                h = O.llama_hidden(sd, lw, c, cfg.lora, sd["model.embed_tokens.weight"][tokens][:, None], past=past, pos0=state["pos"])
-                state["pos"] += 1
-            return h[:, -1] @ sd["lm_head.weight"].T
-    return step
 
 
 @pytest.fixture(scope="module")
@@ -130,22 +48,6 @@ def embeds(dev, tiny):  # noqa: F811
     return x
 
 
-def gen(m, audio, video, dev, **kw):
-    out = m.generate(audio=audio.to(dev), video=video.to(dev), max_new_tokens=kw.pop("max_new_tokens", N_NEW), **kw)
-    return tuple(t.cpu() for t in out) if isinstance(out, tuple) else out.cpu()
-
-
-def with_eos(m, eos):
-    class _Ctx:
-        def __enter__(self_):
-            self_.old = m.eos_token_id
-            m.eos_token_id = eos
-
-        def __exit__(self_, *a):
-            m.eos_token_id = self_.old
-    return _Ctx()
-
-
 def test_one_beam_is_greedy(dev, tiny, m32):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     ids = gen(m32, audio, video, dev, max_new_tokens=12, num_beams=1)
@@ -159,7 +61,7 @@ def test_one_beam_is_greedy(dev, tiny, m32):  # noqa: F811
 def test_fp32_matches_restatement(dev, tiny, m32, embeds, nb, length_penalty, early_stopping, eos):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, V, pad = embeds.shape[0], oc.llama.vocab, m32.tokenizer.pad_token_id
-    want, want_s = hf_beam_search(oracle_step_fn(W, oc, embeds, nb), B, nb, V, N_NEW, eos, pad, length_penalty, early_stopping)
+    want, want_s, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, nb), B, nb, V, N_NEW, eos, pad, None, length_penalty, early_stopping)
     with with_eos(m32, eos):
         got, got_s = gen(m32, audio, video, dev, num_beams=nb, length_penalty=length_penalty, early_stopping=early_stopping,
                          return_sequence_scores=True)
@@ -172,7 +74,7 @@ def test_fp32_matches_restatement(dev, tiny, m32, embeds, nb, length_penalty, ea
 def test_no_eos_runs_to_max_length(dev, tiny, m32, embeds):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, V, pad = embeds.shape[0], oc.llama.vocab, m32.tokenizer.pad_token_id
-    want, want_s = hf_beam_search(oracle_step_fn(W, oc, embeds, 3), B, 3, V, 7, None, pad)
+    want, want_s, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, 3), B, 3, V, 7, None, pad)
     with with_eos(m32, None):
         got, got_s = gen(m32, audio, video, dev, num_beams=3, max_new_tokens=7, return_sequence_scores=True)
     assert got.shape == (B, 7) and torch.equal(got, want)
@@ -197,7 +99,7 @@ def test_pinned_to_transformers(dev, tiny, m32, embeds):  # noqa: F811
             hf = llm.generate(inputs_embeds=embeds, attention_mask=torch.ones(embeds.shape[:2], dtype=torch.long), num_beams=nb,
                               max_new_tokens=N_NEW, do_sample=False, length_penalty=lp, early_stopping=es, eos_token_id=eos,
                               pad_token_id=pad, return_dict_in_generate=True, output_scores=True, num_return_sequences=1)
-        want, want_s = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=False), B, nb, V, N_NEW, eos, pad, lp, es)
+        want, want_s, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=False), B, nb, V, N_NEW, eos, pad, None, lp, es)
         assert torch.equal(hf.sequences, want), (nb, lp, es, hf.sequences, want)
         assert (hf.sequences_scores - want_s).abs().max() < 1e-5
         with with_eos(m32, eos), m32.llm_engine.adapters_disabled():

@@ -11,6 +11,7 @@ Each case also shows that its knob acted (see `acted`).
 
 bf16 (fused and general token step; bf16, fp8 and fp4 weight streams): properties only."""
 import contextlib
+import functools
 import glob
 import json
 import os
@@ -22,15 +23,17 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import generate_ref  # noqa: E402
 from avllm.model import hotword_sequence_bias  # noqa: E402
 from bars import F32_LOGITS_ABS  # noqa: E402
+from generate_ref import hf_beam_search, oracle_step_fn, token_loop, trim, with_eos  # noqa: E402
 from logits_bias_ref import chain  # noqa: E402
-from test_generate_beam_gpu import embeds, oracle_step_fn, with_eos  # noqa: E402,F401
-from test_generate_processors_gpu import batch, draw, edge, trim  # noqa: E402
+from test_generate_beam_gpu import embeds  # noqa: E402,F401
+from test_generate_processors_gpu import batch  # noqa: E402
 from test_model_gpu import make_model, tiny  # noqa: E402,F401
-from test_sample_gpu import kept  # noqa: E402
 
 N_NEW = 12
+gen = functools.partial(generate_ref.gen, max_new_tokens=N_NEW)
 MARGIN = 2 * F32_LOGITS_ABS
 SAMPLE_T = 0.1
 OFF = dict(sequence_bias=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None)
@@ -75,106 +78,6 @@ def process_fn(eos, kw):
     return lambda s, hist: chain(s, hist, eos=eos, **kw)
 
 
-def token_loop(step, B, n_new, eos, pad, kw, sample=None):
-    """generate()'s greedy / sampled loop on the oracle's logits with the processor chain.  sample = (temperature, top_k, top_p, seed) or
-    None.  Returns (tokens [B, L], the smallest decision margin of an unfinished row)."""
-    process = process_fn(eos, kw)
-    logits = step(None, None)
-    hist = torch.zeros(B, 0, dtype=torch.int64)
-    unfinished = torch.ones(B, dtype=torch.bool)
-    margin = float("inf")
-    for cur in range(n_new):
-        s = process(logits.float(), hist)
-        nxt = torch.full((B,), pad, dtype=torch.int64)
-        for b in range(B):
-            if not unfinished[b]:
-                continue
-            if sample is None:
-                top = torch.topk(s[b], 2).values
-                nxt[b], mg = int(torch.argmax(s[b])), float(top[0] - top[1])
-            else:
-                t, k, tp, seed = sample
-                _, probs = kept(s[b].numpy(), t, k, tp)
-                tok, mg = draw(probs, seed, b, cur)
-                nxt[b] = tok
-            margin = min(margin, mg)
-        if eos is not None:
-            unfinished = unfinished & (nxt != eos)
-        hist = torch.cat([hist, nxt[:, None]], 1)
-        if cur + 1 == n_new or not bool(unfinished.any()):
-            break
-        logits = step(nxt, torch.arange(B))
-    return hist, margin
-
-
-def hf_beam_search(step, B, nb, V, max_new, eos, pad, kw, length_penalty=1.0, early_stopping=False):
-    """test_generate_processors_gpu.hf_beam_search with the seven-processor chain at GenerationMixin._beam_search's processor call:
-    log_softmax, the processors on the log-probabilities with running_sequences[:, :, :cur_len] as input_ids, then the running beam scores.
-    Returns (sequences, scores, the smallest gap at a selection edge of any step)."""
-    process = process_fn(eos, kw)
-    k = 2 * nb
-    running_sequences = torch.full((B, nb, max_new), pad, dtype=torch.int64)
-    sequences = running_sequences.clone()
-    running_beam_scores = torch.zeros((B, nb))
-    running_beam_scores[:, 1:] = -1e9
-    beam_scores = torch.full((B, nb), -1e9)
-    is_sent_finished = torch.zeros((B, nb), dtype=torch.bool)
-    unsatisfied = torch.ones((B, 1), dtype=torch.bool)
-    running_beam_indices = torch.full((B, nb, max_new), -1, dtype=torch.int32)
-    beam_indices = running_beam_indices.clone()
-    top_num_beam_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(k - nb, dtype=torch.bool)))
-    gather = lambda t, idx: torch.take_along_dim(t, idx.view(*idx.shape, *([1] * (t.dim() - 2))), dim=1)  # noqa: E731
-    logits = step(None, None)
-    cur_len = 0
-    gap = float("inf")
-    while True:
-        log_probs = torch.log_softmax(logits.float(), dim=-1)
-        log_probs = process(log_probs, running_sequences[:, :, :cur_len].reshape(B * nb, cur_len))
-        log_probs = log_probs.view(B, nb, V) + running_beam_scores[:, :, None]
-        log_probs = log_probs.reshape(B, nb * V)
-        gap = min(gap, edge(torch.topk(log_probs, k=k + 1)[0], k))                                  # which candidates make the k best
-        topk_log_probs, topk_indices = torch.topk(log_probs, k=k)
-        topk_beam = topk_indices // V
-        topk_running_beam_indices = gather(running_beam_indices, topk_beam).clone()
-        topk_running_sequences = gather(running_sequences, topk_beam).clone()
-        topk_ids = topk_indices % V
-        topk_running_sequences[:, :, cur_len] = topk_ids
-        topk_running_beam_indices[:, :, cur_len] = (topk_beam + torch.arange(B)[:, None] * nb).to(torch.int32)
-        hits = torch.full((B, k), cur_len + 1 >= max_new)
-        if eos is not None:
-            hits = hits | (topk_ids == eos)
-        topk_running_log_probs = topk_log_probs + hits.to(torch.float32) * -1.0e9
-        nxt = torch.topk(topk_running_log_probs, k=nb)[1]
-        gap = min(gap, edge(torch.sort(topk_running_log_probs, dim=1, descending=True)[0], nb))     # which of them stay running beams
-        running_sequences = gather(topk_running_sequences, nxt)
-        running_beam_scores = gather(topk_running_log_probs, nxt)
-        running_beam_indices = gather(topk_running_beam_indices, nxt)
-        just = hits & top_num_beam_mask[None, :]
-        fin = topk_log_probs / ((cur_len + 1) ** length_penalty)
-        fin += (torch.all(is_sent_finished, dim=-1, keepdim=True) & (early_stopping is True)).to(torch.float32) * -1.0e9
-        fin += (~unsatisfied).to(torch.float32) * -1.0e9
-        fin += (~just) * -1.0e9
-        merged = torch.cat((beam_scores, fin), dim=1)
-        sel = torch.topk(merged, k=nb)[1]
-        gap = min(gap, edge(torch.sort(merged, dim=1, descending=True)[0], nb))                     # which hypotheses stay finished ones
-        sequences = gather(torch.cat((sequences, topk_running_sequences), dim=1), sel)
-        beam_scores = gather(merged, sel)
-        beam_indices = gather(torch.cat((beam_indices, topk_running_beam_indices), dim=1), sel)
-        is_sent_finished = gather(torch.cat((is_sent_finished, just), dim=1), sel)
-        beam_idx = running_beam_indices[:, :, cur_len].reshape(-1).long()
-        cur_len += 1
-        best_len = max_new if (early_stopping == "never" and length_penalty > 0.0) else cur_len
-        best_running = running_beam_scores[:, :1] / (best_len ** length_penalty)
-        worst_finished = torch.where(is_sent_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], -1.0e9)
-        unsatisfied = unsatisfied & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
-        going = bool(torch.any(unsatisfied) & ~(torch.all(is_sent_finished) & (early_stopping is True)) & ~torch.all(hits))
-        if not going:
-            break
-        logits = step(running_sequences[:, :, cur_len - 1].reshape(-1), beam_idx)
-    L = int(((beam_indices[:, 0] + 1) != 0).sum(dim=1).max())
-    return sequences[:, 0, :L], beam_scores[:, 0], gap
-
-
 def occurs(rows, seq):
     seq = list(seq)
     return any(r[i:i + len(seq)] == seq for r in rows for i in range(len(r) - len(seq) + 1))
@@ -210,11 +113,6 @@ def m32(dev, tiny):  # noqa: F811
     return make_model(oc, W, "fp32", max_seq_len=256).eval()
 
 
-def gen(m, audio, video, dev, **kw):
-    out = m.generate(audio=audio.to(dev), video=video.to(dev), max_new_tokens=kw.pop("max_new_tokens", N_NEW), **kw)
-    return tuple(t.cpu() for t in out) if isinstance(out, tuple) else out.cpu()
-
-
 def adapters(m, lora):
     return contextlib.nullcontext() if lora else m.llm_engine.adapters_disabled()
 
@@ -223,10 +121,10 @@ def adapters(m, lora):
 def test_greedy_fp32_matches_restatement(dev, tiny, m32, embeds, eos, kw, checks):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, pad = embeds.shape[0], m32.tokenizer.pad_token_id
-    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, full(kw, m32.tokenizer))
+    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, process_fn(eos, full(kw, m32.tokenizer)))
     print(f"greedy eos={eos} {kw}: smallest top-2 margin {margin:.3e}")
     assert margin > MARGIN, margin
-    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, OFF)
+    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, process_fn(eos, OFF))
     acted(plain.tolist(), want.tolist(), eos, pad, checks)
     with with_eos(m32, eos):
         got = gen(m32, audio, video, dev, **kw)
@@ -238,10 +136,10 @@ def test_sampled_fp32_matches_restatement(dev, tiny, m32, embeds, seed, eos, kw,
     g, oc, W, audio, video, labels, prompt = tiny
     B, pad = embeds.shape[0], m32.tokenizer.pad_token_id
     sample = (SAMPLE_T, 0, 1.0, seed)
-    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, full(kw), sample=sample)
+    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, process_fn(eos, full(kw)), sample=sample)
     print(f"sampled seed={seed} eos={eos} {kw}: smallest CDF margin {margin:.3e}")
     assert margin > MARGIN / SAMPLE_T, margin
-    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, OFF, sample=sample)
+    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, process_fn(eos, OFF), sample=sample)
     acted(plain.tolist(), want.tolist(), eos, pad, checks)
     with with_eos(m32, eos):
         got = gen(m32, audio, video, dev, do_sample=True, temperature=SAMPLE_T, top_k=0, top_p=1.0, seed=seed, **kw)
@@ -252,10 +150,10 @@ def test_sampled_fp32_matches_restatement(dev, tiny, m32, embeds, seed, eos, kw,
 def test_beam_fp32_matches_restatement(dev, tiny, m32, embeds, nb, eos, kw, checks, lora):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, V, pad = embeds.shape[0], oc.llama.vocab, m32.tokenizer.pad_token_id
-    want, want_s, gap = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=lora), B, nb, V, N_NEW, eos, pad, full(kw))
+    want, want_s, gap = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=lora), B, nb, V, N_NEW, eos, pad, process_fn(eos, full(kw)))
     print(f"beams nb={nb} eos={eos} {kw}: smallest candidate gap {gap:.3e}")
     assert gap > MARGIN, gap
-    plain, _, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=lora), B, nb, V, N_NEW, eos, pad, OFF)
+    plain, _, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=lora), B, nb, V, N_NEW, eos, pad, process_fn(eos, OFF))
     acted(plain.tolist(), want.tolist(), eos, pad, checks)
     with with_eos(m32, eos), adapters(m32, lora):
         got, got_s = gen(m32, audio, video, dev, num_beams=nb, return_sequence_scores=True, **kw)
@@ -289,9 +187,9 @@ def test_pinned_to_transformers(dev, tiny, m32, embeds):  # noqa: F811
             hf = llm.generate(inputs_embeds=embeds, attention_mask=mask, num_beams=nb, max_new_tokens=N_NEW, do_sample=False, eos_token_id=eos,
                               pad_token_id=pad, return_dict_in_generate=True, output_scores=True, num_return_sequences=1, **hf_keywords(kw))
         if nb == 1:
-            want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=False), B, N_NEW, eos, pad, full(kw))
+            want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=False), B, N_NEW, eos, pad, process_fn(eos, full(kw)))
         else:
-            want, want_s, margin = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=False), B, nb, V, N_NEW, eos, pad, full(kw))
+            want, want_s, margin = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=False), B, nb, V, N_NEW, eos, pad, process_fn(eos, full(kw)))
             assert (hf.sequences_scores - want_s).abs().max() < 1e-5
         assert margin > MARGIN, (nb, eos, kw, margin)
         assert torch.equal(hf.sequences, want), (nb, eos, kw, hf.sequences, want)

@@ -2,8 +2,8 @@
 (tests/golden/g2_tiny_e2e.npz), greedy, sampled and beam search.
 
 fp32: tokens identical to a restatement loop on the CPU: the oracle's logits -> test_logits_process_cpu.restate (HF's three processors) ->
-the selection (argmax; the sampling chain of test_sample_gpu.kept plus `draw` below, the kernel's inverse-CDF draw; `hf_beam_search`
-below, test_generate_beam_gpu.hf_beam_search with the processors between the log_softmax and the beam scores, as
+the selection (argmax; the sampling chain of test_sample_gpu.kept plus generate_ref.draw, the kernel's inverse-CDF draw;
+generate_ref.hf_beam_search with the processors between the log_softmax and the beam scores, as
 GenerationMixin._beam_search has them), and where transformers imports to LlamaForCausalLM.generate with the same keywords.
 The cases were chosen on the CPU so that the restatement's decisions are clear of the fp32 logit bar (tests/bars.py F32_LOGITS_ABS = 1e-3
 on each logit, so 2e-3 on a difference) at every step; each test asserts that margin again, no case is dropped at run time:
@@ -19,6 +19,7 @@ one does not.
 
 bf16 (fused and general token step, bf16 and fp8 weight streams): properties only."""
 import contextlib
+import functools
 import glob
 import json
 import os
@@ -31,15 +32,18 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import generate_ref  # noqa: E402
 from avllm import ops  # noqa: E402
 from bars import F32_LOGITS_ABS  # noqa: E402
-from test_generate_beam_gpu import embeds, oracle_step_fn, with_eos  # noqa: E402,F401
+from generate_ref import hf_beam_search, oracle_step_fn, token_loop, trim, with_eos  # noqa: E402
+from test_generate_beam_gpu import embeds  # noqa: E402,F401
 from test_generate_sample_gpu import BOUNDARY_TOL  # noqa: E402
 from test_logits_process_cpu import restate  # noqa: E402
 from test_model_gpu import make_model, tiny  # noqa: E402,F401
 from test_sample_gpu import kept  # noqa: E402
 
 N_NEW = 12
+gen = functools.partial(generate_ref.gen, max_new_tokens=N_NEW)
 MARGIN = 2 * F32_LOGITS_ABS
 # (eos, repetition_penalty, no_repeat_ngram_size, min_new_tokens, n-gram size the unprocessed output repeats and the processed must not (0:
 # none), the unprocessed output ends before min_new_tokens, adapters on: with them the penalised cases have a 8e-4 margin at one step)
@@ -69,156 +73,21 @@ BEAM_CASES = [
 ]
 
 
+def processors(p, n, m, eos):
+    """HF's three processors as generate_ref's process(scores, hist)."""
+    return lambda s, hist: restate(s, hist, p, n, m, eos)
+
+
 def has_repeat(row, n):
     """True when an n-gram occurs twice in the token list."""
     grams = [tuple(row[i:i + n]) for i in range(len(row) - n + 1)]
     return len(set(grams)) < len(grams)
 
 
-def trim(row, eos, pad):
-    """A returned row without its padding: up to and including the first eos."""
-    row = [int(t) for t in row]
-    if eos is not None and eos in row:
-        return row[:row.index(eos) + 1]
-    return row
-
-
-def h32(x):
-    x &= 0xFFFFFFFF
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & 0xFFFFFFFF
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & 0xFFFFFFFF
-    x ^= x >> 16
-    return x
-
-
-def draw(probs, seed, row, step):
-    """The sampling kernel's draw (csrc/sample.hip): u = 24-bit hash of (seed + row, step), inverse CDF over the kept tokens in
-    vocabulary-index order.  Returns (token, distance of u to the nearer end of the token's CDF interval)."""
-    u = (h32(h32((seed + row + 0x9E3779B9) & 0xFFFFFFFF) ^ step) >> 8) * 2.0 ** -24
-    cum = np.cumsum(probs)
-    tok = int(np.argmax(cum > u * cum[-1]))
-    lo = cum[tok] - probs[tok]
-    return tok, min(u * cum[-1] - lo, cum[tok] - u * cum[-1])
-
-
-def token_loop(step, B, n_new, eos, pad, p, n, m, sample=None):
-    """generate()'s greedy / sampled loop on the oracle's logits with HF's processors.  sample = (temperature, top_k, top_p, seed) or None.
-    Returns (tokens [B, L], the smallest decision margin of an unfinished row)."""
-    logits = step(None, None)
-    hist = torch.zeros(B, 0, dtype=torch.int64)
-    unfinished = torch.ones(B, dtype=torch.bool)
-    margin = float("inf")
-    for cur in range(n_new):
-        s = restate(logits.float(), hist, p, n, m, eos)
-        nxt = torch.full((B,), pad, dtype=torch.int64)
-        for b in range(B):
-            if not unfinished[b]:
-                continue
-            if sample is None:
-                top = torch.topk(s[b], 2).values
-                nxt[b], mg = int(torch.argmax(s[b])), float(top[0] - top[1])
-            else:
-                t, k, tp, seed = sample
-                _, probs = kept(s[b].numpy(), t, k, tp)
-                tok, mg = draw(probs, seed, b, cur)
-                nxt[b] = tok
-            margin = min(margin, mg)
-        if eos is not None:
-            unfinished = unfinished & (nxt != eos)
-        hist = torch.cat([hist, nxt[:, None]], 1)
-        if cur + 1 == n_new or not bool(unfinished.any()):
-            break
-        logits = step(nxt, torch.arange(B))
-    return hist, margin
-
-
-def edge(sorted_scores, j):
-    """The gap between the j-th and the j+1-th of each row's descending scores, where the j-th is a real score (not a -1e9 placeholder)."""
-    a, b = sorted_scores[:, j - 1], sorted_scores[:, j]
-    live = a > -1e8
-    return float((a - b)[live].min()) if bool(live.any()) else float("inf")
-
-
-def hf_beam_search(step, B, nb, V, max_new, eos, pad, length_penalty, early_stopping, p, n, m):
-    """test_generate_beam_gpu.hf_beam_search with GenerationMixin._beam_search's processor call: log_softmax, then the processors on the
-    log-probabilities with running_sequences[:, :, :cur_len] as their input_ids, then the running beam scores.  Also returns the smallest
-    gap at a selection edge of any step: between the k-th and k+1-th candidate, between the last running beam kept and the first dropped,
-    and between the last finished hypothesis kept and the first dropped.  (The order inside a selected set only permutes the beams.)"""
-    k = 2 * nb
-    running_sequences = torch.full((B, nb, max_new), pad, dtype=torch.int64)
-    sequences = running_sequences.clone()
-    running_beam_scores = torch.zeros((B, nb))
-    running_beam_scores[:, 1:] = -1e9
-    beam_scores = torch.full((B, nb), -1e9)
-    is_sent_finished = torch.zeros((B, nb), dtype=torch.bool)
-    unsatisfied = torch.ones((B, 1), dtype=torch.bool)
-    running_beam_indices = torch.full((B, nb, max_new), -1, dtype=torch.int32)
-    beam_indices = running_beam_indices.clone()
-    top_num_beam_mask = torch.cat((torch.ones(nb, dtype=torch.bool), torch.zeros(k - nb, dtype=torch.bool)))
-    gather = lambda t, idx: torch.take_along_dim(t, idx.view(*idx.shape, *([1] * (t.dim() - 2))), dim=1)  # noqa: E731
-    logits = step(None, None)
-    cur_len = 0
-    gap = float("inf")
-    while True:
-        log_probs = torch.log_softmax(logits.float(), dim=-1)
-        log_probs = restate(log_probs, running_sequences[:, :, :cur_len].reshape(B * nb, cur_len), p, n, m, eos)
-        log_probs = log_probs.view(B, nb, V) + running_beam_scores[:, :, None]
-        log_probs = log_probs.reshape(B, nb * V)
-        best = torch.topk(log_probs, k=k + 1)[0]
-        gap = min(gap, edge(best, k))                            # which candidates make the k best
-        topk_log_probs, topk_indices = torch.topk(log_probs, k=k)
-        topk_beam = topk_indices // V
-        topk_running_beam_indices = gather(running_beam_indices, topk_beam).clone()
-        topk_running_sequences = gather(running_sequences, topk_beam).clone()
-        topk_ids = topk_indices % V
-        topk_running_sequences[:, :, cur_len] = topk_ids
-        topk_running_beam_indices[:, :, cur_len] = (topk_beam + torch.arange(B)[:, None] * nb).to(torch.int32)
-        hits = torch.full((B, k), cur_len + 1 >= max_new)
-        if eos is not None:
-            hits = hits | (topk_ids == eos)
-        topk_running_log_probs = topk_log_probs + hits.to(torch.float32) * -1.0e9
-        nxt = torch.topk(topk_running_log_probs, k=nb)[1]
-        gap = min(gap, edge(torch.sort(topk_running_log_probs, dim=1, descending=True)[0], nb))     # which of them stay running beams
-        running_sequences = gather(topk_running_sequences, nxt)
-        running_beam_scores = gather(topk_running_log_probs, nxt)
-        running_beam_indices = gather(topk_running_beam_indices, nxt)
-        just = hits & top_num_beam_mask[None, :]
-        fin = topk_log_probs / ((cur_len + 1) ** length_penalty)
-        fin += (torch.all(is_sent_finished, dim=-1, keepdim=True) & (early_stopping is True)).to(torch.float32) * -1.0e9
-        fin += (~unsatisfied).to(torch.float32) * -1.0e9
-        fin += (~just) * -1.0e9
-        merged = torch.cat((beam_scores, fin), dim=1)
-        sel = torch.topk(merged, k=nb)[1]
-        gap = min(gap, edge(torch.sort(merged, dim=1, descending=True)[0], nb))                     # which hypotheses stay finished ones
-        sequences = gather(torch.cat((sequences, topk_running_sequences), dim=1), sel)
-        beam_scores = gather(merged, sel)
-        beam_indices = gather(torch.cat((beam_indices, topk_running_beam_indices), dim=1), sel)
-        is_sent_finished = gather(torch.cat((is_sent_finished, just), dim=1), sel)
-        beam_idx = running_beam_indices[:, :, cur_len].reshape(-1).long()
-        cur_len += 1
-        best_len = max_new if (early_stopping == "never" and length_penalty > 0.0) else cur_len
-        best_running = running_beam_scores[:, :1] / (best_len ** length_penalty)
-        worst_finished = torch.where(is_sent_finished, torch.min(beam_scores, dim=1, keepdim=True)[0], -1.0e9)
-        unsatisfied = unsatisfied & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
-        going = bool(torch.any(unsatisfied) & ~(torch.all(is_sent_finished) & (early_stopping is True)) & ~torch.all(hits))
-        if not going:
-            break
-        logits = step(running_sequences[:, :, cur_len - 1].reshape(-1), beam_idx)
-    L = int(((beam_indices[:, 0] + 1) != 0).sum(dim=1).max())
-    return sequences[:, 0, :L], beam_scores[:, 0], gap
-
-
 @pytest.fixture(scope="module")
 def m32(dev, tiny):  # noqa: F811
     g, oc, W, *_ = tiny
     return make_model(oc, W, "fp32", max_seq_len=256).eval()
-
-
-def gen(m, audio, video, dev, **kw):
-    out = m.generate(audio=audio.to(dev), video=video.to(dev), max_new_tokens=kw.pop("max_new_tokens", N_NEW), **kw)
-    return tuple(t.cpu() for t in out) if isinstance(out, tuple) else out.cpu()
 
 
 def knob_did_something(plain, got, eos, pad, n_rep, m, early):
@@ -236,10 +105,10 @@ def knob_did_something(plain, got, eos, pad, n_rep, m, early):
 def test_greedy_fp32_matches_restatement(dev, tiny, m32, embeds, eos, p, n, m, n_rep, early, lora):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, pad = embeds.shape[0], m32.tokenizer.pad_token_id
-    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=lora), B, N_NEW, eos, pad, p, n, m)
+    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=lora), B, N_NEW, eos, pad, processors(p, n, m, eos))
     print(f"greedy eos={eos} p={p} n={n} m={m}: smallest top-2 margin {margin:.3e}")
     assert margin > MARGIN, margin
-    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=lora), B, N_NEW, eos, pad, 1.0, 0, 0)
+    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=lora), B, N_NEW, eos, pad, processors(1.0, 0, 0, eos))
     knob_did_something(plain.tolist(), want.tolist(), eos, pad, n_rep, m, early)
     with with_eos(m32, eos), (contextlib.nullcontext() if lora else m32.llm_engine.adapters_disabled()):
         got = gen(m32, audio, video, dev, repetition_penalty=p, no_repeat_ngram_size=n, min_new_tokens=m)
@@ -251,10 +120,10 @@ def test_greedy_fp32_matches_restatement(dev, tiny, m32, embeds, eos, p, n, m, n
 def test_sampled_fp32_matches_restatement(dev, tiny, m32, embeds, seed, eos, p, n, m, n_rep, early):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, pad = embeds.shape[0], m32.tokenizer.pad_token_id
-    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, p, n, m, sample=(SAMPLE_T, 0, 1.0, seed))
+    want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, processors(p, n, m, eos), sample=(SAMPLE_T, 0, 1.0, seed))
     print(f"sampled seed={seed} eos={eos} p={p} n={n} m={m}: smallest CDF margin {margin:.3e}")
     assert margin > MARGIN / SAMPLE_T, margin
-    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, 1.0, 0, 0, sample=(SAMPLE_T, 0, 1.0, seed))
+    plain, _ = token_loop(oracle_step_fn(W, oc, embeds, 1), B, N_NEW, eos, pad, processors(1.0, 0, 0, eos), sample=(SAMPLE_T, 0, 1.0, seed))
     knob_did_something(plain.tolist(), want.tolist(), eos, pad, n_rep, m, early)
     with with_eos(m32, eos):
         got = gen(m32, audio, video, dev, do_sample=True, temperature=SAMPLE_T, top_k=0, top_p=1.0, seed=seed, repetition_penalty=p,
@@ -266,10 +135,10 @@ def test_sampled_fp32_matches_restatement(dev, tiny, m32, embeds, seed, eos, p, 
 def test_beam_fp32_matches_restatement(dev, tiny, m32, embeds, nb, eos, p, n, m, lp, es, n_rep, early):  # noqa: F811
     g, oc, W, audio, video, labels, prompt = tiny
     B, V, pad = embeds.shape[0], oc.llama.vocab, m32.tokenizer.pad_token_id
-    want, want_s, gap = hf_beam_search(oracle_step_fn(W, oc, embeds, nb), B, nb, V, N_NEW, eos, pad, lp, es, p, n, m)
+    want, want_s, gap = hf_beam_search(oracle_step_fn(W, oc, embeds, nb), B, nb, V, N_NEW, eos, pad, processors(p, n, m, eos), lp, es)
     print(f"beams nb={nb} eos={eos} p={p} n={n} m={m}: smallest candidate gap {gap:.3e}")
     assert gap > MARGIN, gap
-    plain, _, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, nb), B, nb, V, N_NEW, eos, pad, lp, es, 1.0, 0, 0)
+    plain, _, _ = hf_beam_search(oracle_step_fn(W, oc, embeds, nb), B, nb, V, N_NEW, eos, pad, processors(1.0, 0, 0, eos), lp, es)
     knob_did_something(plain.tolist(), want.tolist(), eos, pad, n_rep, m, early)
     with with_eos(m32, eos):
         got, got_s = gen(m32, audio, video, dev, num_beams=nb, length_penalty=lp, early_stopping=es, return_sequence_scores=True,
@@ -298,9 +167,9 @@ def test_pinned_to_transformers(dev, tiny, m32, embeds):  # noqa: F811
             hf = llm.generate(inputs_embeds=embeds, attention_mask=mask, num_beams=nb, max_new_tokens=N_NEW, do_sample=False, eos_token_id=eos,
                               pad_token_id=pad, return_dict_in_generate=True, output_scores=True, num_return_sequences=1, **kw)
         if nb == 1:
-            want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=False), B, N_NEW, eos, pad, p, n, m)
+            want, margin = token_loop(oracle_step_fn(W, oc, embeds, 1, lora=False), B, N_NEW, eos, pad, processors(p, n, m, eos))
         else:
-            want, want_s, margin = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=False), B, nb, V, N_NEW, eos, pad, 1.0, False, p, n, m)
+            want, want_s, margin = hf_beam_search(oracle_step_fn(W, oc, embeds, nb, lora=False), B, nb, V, N_NEW, eos, pad, processors(p, n, m, eos))
             assert (hf.sequences_scores - want_s).abs().max() < 1e-5
         assert margin > MARGIN, (nb, eos, p, n, m, margin)
         assert torch.equal(hf.sequences, want), (nb, eos, p, n, m, hf.sequences, want)
