@@ -11,7 +11,8 @@
 //   draw  : inverse CDF over the kept tokens in vocabulary-index order, u = 24-bit hash of (seed [+ row_seeds[r]], step).
 // Masses are fixed-point integers (exp(x - max) * 2^40, summed in uint64), so every histogram, scan and total is exact: the result repeats
 // bit for bit whatever the order the threads add in, and no float atomic is used.  top_k == 1 is the argmax with argmax_kernel's rule
-// (lowest index among equal maxima, temperature irrelevant).
+// (lowest index among equal maxima, temperature irrelevant).  NaN follows that rule in every mode: to_key reads a NaN of either sign as -inf,
+// so it is never the maximum, carries no mass and is never drawn; a row of nothing but NaN and -inf returns token 0, as argmax_kernel does.
 // out_logprob (optional): the draw's log-probability under the distribution it was drawn from, HF's transition score of a sampled token:
 // (x_id - max) - log(W * 2^-40), W the exact kept mass the draw already holds; 0 where the kernel returns the argmax or pad.  One thread
 // computes it after the draw: a null pointer leaves every pass, the LDS layout and the draws as they are.
@@ -30,7 +31,7 @@ constexpr int LDS_FIXED = HB * 8 + 2 * NWV * 8 + 16;
 constexpr int LDS_MAX_V = (160 * 1024 - LDS_FIXED) / 4 / 16 * 16;
 
 __device__ __forceinline__ uint32_t to_key(float x) {
-    const uint32_t u = __float_as_uint(x + 0.0f);   // -0 -> +0: equal values, equal keys (argmax_kernel compares floats)
+    const uint32_t u = __float_as_uint(x == x ? x + 0.0f : -INFINITY);   // -0 -> +0: equal values, equal keys (argmax_kernel compares floats); NaN -> -inf
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float from_key(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }

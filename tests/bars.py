@@ -493,3 +493,53 @@ def dec_proj_bar(ref, exact=False):
         e = torch.where(rotary, c.abs() * e + sn.abs() * e[:, p] + U32 * ((ref.z * c).abs() + (zp * sn).abs() + ref.out.abs()), e)
     e = e + FP32_DENORM
     return e if ref.out_f32 else e + BF16_OUT_REL * ref.out.abs()
+
+
+# ---- token selection against float64 (tests/test_select_pin_gpu.py; restatements, host emulations and families in tests/refs64_select.py).  No
+# number here comes from a kernel's output.  The kernels (sample.hip, beam.hip, token_score.hip, the log-softmax stage of logits_process.hip) form
+# y = x / t (one IEEE division), d = y - m against the row maximum, e = expf(d), a sum of the e, its logarithm and one or two more sums.  The exact
+# family of beam_topk(logprobs=True) carries the bar 0: its log-probabilities and beam scores are multiples of 2^-3 in [-16, 0], every sum is a
+# multiple of 2^-3 below 32 and exact in fp32, so the whole order, ties included, is determined.
+def _t64(a):
+    import torch
+    return torch.as_tensor(a).double()
+
+
+def select_logprob_bar(ref64, cpu32, V, sizes=()):
+    """A log-probability (row_scores, the score of a sample_rows draw, a row of the log-softmax stage) or a beam_topk score, one number per tensor:
+    fp32_bar of the host's fp32 evaluation of the same formula from the same inputs (the different order of the V-term sum, the logarithm)
+    + ce_lse_expf_term(V), what the exponentials add to the log of their sum (the bound holds for any libm within expf_rel, not only __expf)
+    + one rounding (2^-24 relative) for each of the division, the subtraction from the maximum and the final sums, at the size of their results:
+    `sizes` holds the float64 magnitudes |y|, |y - m|, |y - m - log s| and, for beam_topk, |beam score + log p| (tensors or numbers; the
+    largest entry of each counts).  Entries of -inf are compared exactly by the tests and must not be passed in."""
+    import torch
+    extra = sum(float(_t64(s).abs().max()) for s in sizes)
+    return fp32_bar(_t64(ref64), torch.as_tensor(cpu32)) + ce_lse_expf_term(V) + U32 * extra
+
+
+def select_entropy_bar(y64, ent64, ent_cpu32):
+    """row_scores' entropy H = log s - t / s with d_i = y_i - m <= 0, e_i = expf(d_i), s = sum e_i, t = sum e_i d_i, one number per row set.  With
+    r_i = expf_rel(d_i) the relative error of e_i:  |ds| <= sum e_i r_i,  |dt| <= sum e_i |d_i| r_i, and
+        |dH| <= |ds| / s + |dt| / s + |t| |ds| / s^2 = sum_i p_i r_i (1 + |d_i| + |t| / s),   p = e / s,
+    elementwise over the row and summed (the rescale factors expf(old max - new max) of the online form multiply partial sums that the same bound
+    covers, as in ce_lse_expf_term), + fp32_bar of the host's fp32 evaluation for the sums' order, the logarithm and the division.  y64 [rows, V]:
+    the scaled rows in float64, -inf where banned."""
+    import torch
+    y = _t64(y64)
+    m = y.max(-1, keepdim=True).values
+    d = torch.where(torch.isinf(y), torch.zeros_like(y), y - m)
+    e = torch.where(torch.isinf(y), torch.zeros_like(y), torch.exp(d))
+    s = e.sum(-1, keepdim=True)
+    t = (e * d).sum(-1, keepdim=True)
+    term = ((e / s) * expf_rel(d) * (1.0 + d.abs() + t.abs() / s)).sum(-1)
+    return float(term.max()) + fp32_bar(_t64(ent64), torch.as_tensor(ent_cpu32))
+
+
+def draw_cdf_tol(probs, d, n_kept, W):
+    """|a sample_rows CDF prefix - the float64 one|, both relative to their totals.  The kernel's prefix is sum_{i < j} w_i / sum_i w_i with
+    w_i = floor(expf(d_i) 2^40): a relative error expf_rel(d_i) on each term moves a ratio of two such sums by at most 2 sum_i p_i expf_rel(d_i)
+    (numerator and denominator, each at most sum_i p_i r_i); the truncation loses under 2^-40 per kept token of a total W = sum exp(d_i) (>= 1:
+    the maximum is kept); the target floor(W u) and u's own 24-bit grid are worth 2^-23 together.  probs, d: the float64 probabilities and
+    y_i - max of the kept tokens.  The same number is the delta of refs64_select.kept_band: top-p compares such a prefix with top_p."""
+    p, dd = _t64(probs), _t64(d)
+    return float(2.0 * (p * expf_rel(dd)).sum()) + n_kept * 2.0 ** -40 / W + 2.0 ** -23

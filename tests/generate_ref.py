@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from oracle import avsr_oracle as O
-from test_sample_gpu import kept
+from sample_ref import kept
 
 
 def trim(row, eos, pad):

@@ -5,26 +5,33 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import bars  # noqa: E402
 from avllm import lib as L  # noqa: E402
 from avllm import ops  # noqa: E402
 
 
 def reference(logits, scores, nb, k):
-    """The k + 1 best (score, beam, token) of HF's accumulated log-probabilities, in float64 from fp32 log_softmax (the k + 1-th gives the
-    gap at the boundary)."""
+    """The k + 1 best (score, beam, token) of HF's accumulated log-probabilities in float64 on the float32 inputs (the k + 1-th gives the gap
+    at the boundary), and the float32 evaluation of the same entries (the yardstick of bars.select_logprob_bar)."""
     rows, V = logits.shape
-    acc = (torch.log_softmax(logits.float(), dim=-1) + scores[:, None]).view(rows // nb, nb * V)
+    lp64 = torch.log_softmax(logits.double(), dim=-1)
+    acc = (lp64 + scores.double()[:, None]).view(rows // nb, nb * V)
     s, i = torch.topk(acc, k=min(k + 1, nb * V), dim=1)
-    return s, (i // V).to(torch.int32), i % V
+    acc32 = (torch.log_softmax(logits.float(), dim=-1) + scores[:, None]).view(rows // nb, nb * V).gather(1, i)
+    lp = lp64.view(rows // nb, nb * V).gather(1, i)
+    d = (logits.double() - logits.double().max(-1, keepdim=True).values).view(rows // nb, nb * V).gather(1, i)
+    return s, (i // V).to(torch.int32), i % V, acc32, (d, lp)
 
 
 def check(logits, scores, nb, k, tol=None):
     got_s, got_b, got_t = ops.beam_topk(logits, scores, nb, k)
-    ref_s, ref_b, ref_t = reference(logits, scores, nb, k)
-    if tol is None:                                          # fp32 rounding of log_softmax and of the add, a few ulps of the operands
-        tol = 8 * torch.finfo(torch.float32).eps * (ref_s.abs().max().item() + 1.0) + 1e-6
+    ref_s, ref_b, ref_t, cpu32, (d, lp) = reference(logits, scores, nb, k)
+    if tol is None:
+        # the derived bar of tests/bars.py where it is not larger than this file's earlier hand-set one (8 eps (max + 1) + 1e-6), else that one
+        hand = 8 * torch.finfo(torch.float32).eps * (ref_s.abs().max().item() + 1.0) + 1e-6
+        tol = min(hand, bars.select_logprob_bar(ref_s.cpu(), cpu32.cpu(), logits.shape[1], sizes=(d.cpu(), lp.cpu(), ref_s.cpu())))
     assert got_s.shape == (logits.shape[0] // nb, k)
-    assert (got_s - ref_s[:, :k]).abs().max().item() <= tol
+    assert (got_s.double() - ref_s[:, :k]).abs().max().item() <= tol
     # a candidate's identity is pinned wherever its score is more than the rounding away from its neighbours'
     pad = torch.full_like(ref_s[:, :1], float("inf"))
     prev = torch.cat([pad, ref_s[:, :-1]], 1)[:, :k]
@@ -178,3 +185,25 @@ def test_gather_many_rows_and_bad_arguments(dev):
         ops.kv_gather_rows(k, v, k, v, parent[:-1], 0, 1)
     with pytest.raises(ValueError):
         ops.kv_gather_rows(k, v, k, v, parent.long(), 0, 1)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_gather_at_the_row_limit(dev, dtype):
+    """2048 destination rows: with the row count at the staging capacity every workgroup stages exactly one vector per row (all 2048 slots of its
+    LDS buffer); 2049 rows must be refused and leave the caches as they were."""
+    layers, T, dkv = 1, 2, 8
+    for R_, ok in ((2048, True), (2049, False)):
+        k, v = caches(layers, R_, T, dkv, dtype, R_)
+        parent = torch.randint(0, R_, (R_,), device="cuda", dtype=torch.int32, generator=torch.Generator(device="cuda").manual_seed(R_))
+        k0, v0 = k.clone(), v.clone()
+        if ok:
+            ops.kv_gather_rows(k, v, k, v, parent, 0, T)                            # in place, rows read and overwritten
+            assert torch.equal(k, k0[:, parent.long()]) and torch.equal(v, v0[:, parent.long()])
+            kd, vd = torch.zeros_like(k0), torch.zeros_like(v0)
+            ops.kv_gather_rows(k0, v0, kd, vd, parent, 1, T)                        # out of place, one position
+            assert torch.equal(kd[:, :, 1:], k0[:, parent.long(), 1:]) and torch.equal(vd[:, :, 1:], v0[:, parent.long(), 1:])
+            assert not kd[:, :, :1].any() and not vd[:, :, :1].any()
+        else:
+            with pytest.raises(ValueError, match="2048"):
+                ops.kv_gather_rows(k, v, k, v, parent, 0, T)
+            assert torch.equal(k, k0) and torch.equal(v, v0)

@@ -9,44 +9,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from avllm import ops  # noqa: E402
+from refs64_select import draw_delta  # noqa: E402  (bars.draw_cdf_tol of a row: the derived slack of top-p membership)
+from sample_ref import kept, kept_from_scaled, rows  # noqa: E402,F401  (the restatement lives there; importers of this file keep finding it here)
 
 ALPHA = 1e-3            # significance level of the chi-square tests (fixed seeds: the outcome is deterministic)
-P_SLACK = 1e-5          # top-p membership is checked against the kept set at top_p + P_SLACK (fp32 exp + fixed-point mass vs float64)
-
-
-def kept_from_scaled(x, top_k, top_p):
-    """Boolean mask of the kept tokens and their probabilities, x = scaled logits (float64)."""
-    V = x.shape[0]
-    if top_k == 1:
-        keep = np.zeros(V, bool)
-        keep[int(np.argmax(x))] = True
-        return keep, keep.astype(np.float64)
-    keep = x > -np.inf
-    if 0 < top_k < V:
-        kth = np.sort(x)[::-1][top_k - 1]
-        keep &= x >= kth
-    m = x[keep].max()
-    if top_p < 1.0:
-        xs = x[keep]
-        w = np.exp(xs - m)
-        order = np.argsort(-xs, kind="stable")
-        S = np.cumsum(w[order])
-        j = int(np.argmax(S >= top_p * S[-1]))
-        keep &= x >= xs[order][j]
-    w = np.where(keep, np.exp(np.where(keep, x, m) - m), 0.0)
-    return keep, w / w.sum()
-
-
-def kept(row, temperature, top_k, top_p):
-    """row: one row of logits as the kernel sees it (fp32 values; bf16 rows upcast exactly); the division happens in fp32 as on the device."""
-    r = np.asarray(row, np.float32)
-    t = np.float32(1.0 if top_k == 1 else temperature)
-    return kept_from_scaled((r / t).astype(np.float64), top_k, top_p)
-
-
-def rows(B, V, seed, scale=3.0, dtype=torch.float32):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(B, V, generator=g) * scale).to(dtype)
+P_SLACK = 1e-5          # top-p membership is checked against the kept set at top_p + the derived bars.draw_cdf_tol, capped at this (fp32 exp + fixed-point mass vs float64)
 
 
 def draws(x, t, k, p, seeds, steps, row_seeds=None):
@@ -87,7 +54,7 @@ def test_sampled_ids_lie_in_kept_set(dev, V, dtype):
     for t, k, p in CFGS:
         ids = draws(x, t, k, p, seeds=range(6), steps=range(8))
         for b in range(B):
-            keep, _ = kept(xf[b], t, k, min(1.0, p + P_SLACK) if p < 1 else p)
+            keep, _ = kept(xf[b], t, k, min(1.0, p + min(P_SLACK, draw_delta(xf[b], t, k))) if p < 1 else p)
             bad = [i for i in ids[:, b] if not keep[i]]
             assert not bad, (V, dtype, t, k, p, b, bad[:5])
 

@@ -8,12 +8,22 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import bars  # noqa: E402
+import refs64_select as R  # noqa: E402
 from avllm import ops  # noqa: E402
 from test_sample_gpu import kept, rows  # noqa: E402
 
 TOL = 1e-4
 CFGS = [(1.0, 0, 1.0), (0.7, 50, 0.9), (1.3, 0, 0.8), (1.0, 5, 1.0), (1.0, 1, 0.9)]
 STEPS = 5
+
+
+def draw_bar(row, t, k, p):
+    """bars.select_logprob_bar of a row's kept distribution, capped at this file's earlier hand-set TOL."""
+    keep, _ = R.kept(row, t, k, p)
+    z = torch.as_tensor(R.scaled(row, t, k)[keep])
+    ref = torch.log_softmax(z, 0)
+    return min(TOL, bars.select_logprob_bar(ref, torch.log_softmax(z.float(), 0), int(keep.sum()), sizes=(z, z - z.max(), ref)))
 
 
 def hf_chain(x, t, k, p):
@@ -41,6 +51,7 @@ def test_logprob_of_the_draw_matches_hf_chain(dev, V):
         # continuous inputs: HF's kept set is the restatement's, so no draw should fall outside it
         for b in range(B):
             assert np.array_equal(kept(x[b].numpy(), t, k, p)[0], torch.isfinite(h[b]).numpy()), (V, t, k, p, b)
+        bar = [draw_bar(x[b].numpy(), t, k, p) for b in range(B)]
         excluded = total = 0
         for step in range(STEPS):
             ids, lp = ops.sample_rows(xd, t, k, p, 11, step, return_logprob=True)
@@ -54,7 +65,7 @@ def test_logprob_of_the_draw_matches_hf_chain(dev, V):
                     continue
                 d = abs(float(lp[b]) - w)
                 worst = max(worst, d)
-                assert d <= TOL, (V, t, k, p, step, b, float(lp[b]), w)
+                assert d <= bar[b], (V, t, k, p, step, b, float(lp[b]), w, bar[b])
                 assert float(lp[b]) <= 0.0
                 if k == 1:
                     assert float(lp[b]) == 0.0

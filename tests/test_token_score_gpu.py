@@ -2,8 +2,8 @@
 float32 values (the division by the float32 temperature included), at every vector edge (V below, at and above one vector per lane; row
 strides that break the 16-byte alignment), with banned (-inf) entries, and the log-probability-input mode beam search uses.
 
-Bar: 1e-4 absolute on both outputs.  Inputs are exact; x - max is exact to an ulp of values below 128 (7.6e-6), the exponential and
-the float32 sum of V positive terms carry a few 1e-6 relative, so log of the sum lies near 1e-5 and 1e-4 leaves an order of magnitude."""
+Bar: per row the derived bars of tests/bars.py (select_logprob_bar, select_entropy_bar), capped at the earlier hand-set 1e-4 absolute, which
+stays the bar of the log-probability-input mode and of tokens=None."""
 import math
 
 import pytest
@@ -12,7 +12,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from avllm import lib as L  # noqa: E402
+import bars  # noqa: E402
 from avllm import ops  # noqa: E402
+from refs64_select import row_scores64 as reference  # noqa: E402  (float64 on the float32 values: (logprob, entropy) per row)
 
 TOL = 1e-4
 VS = [1, 63, 64, 65, 1000, 4097, 32000, 128256, 151936]
@@ -52,13 +54,17 @@ def pattern_rows(V, seed):
     return torch.stack(rows), torch.tensor(toks, dtype=torch.int64)
 
 
-def reference(x, tok, temperature):
-    """float64 on the float32 values: (logprob, entropy) per row."""
-    y = x.double() / float(torch.tensor(temperature, dtype=torch.float32))
-    lse = torch.logsumexp(y, dim=1)
-    lp = y.gather(1, tok[:, None])[:, 0] - lse
-    ent = torch.special.entr(torch.exp(y - lse[:, None])).sum(1)
-    return lp, ent
+def row_bars(x, tok, temperature, want_lp, want_ent):
+    """Per row, the derived bars of tests/bars.py (select_logprob_bar, select_entropy_bar), each capped at this file's earlier hand-set TOL."""
+    cpu_lp, cpu_ent = reference(x, tok, temperature, dtype=torch.float32)
+    y = (x / torch.tensor(temperature, dtype=torch.float32)).double()
+    b_lp, b_ent = torch.full_like(want_lp, TOL), torch.full_like(want_ent, TOL)
+    for r in range(x.shape[0]):
+        fin = y[r][torch.isfinite(y[r])]
+        if torch.isfinite(want_lp[r]):
+            b_lp[r] = min(TOL, bars.select_logprob_bar(want_lp[r:r + 1], cpu_lp[r:r + 1], x.shape[1], sizes=(fin, fin - fin.max(), want_lp[r])))
+        b_ent[r] = min(TOL, bars.select_entropy_bar(y[r:r + 1], want_ent[r:r + 1], cpu_ent[r:r + 1]))
+    return b_lp, b_ent
 
 
 def strided(x, ld, dev):
@@ -68,11 +74,13 @@ def strided(x, ld, dev):
     return buf[:, : x.shape[1]]
 
 
-def close(got, want):
-    """max |got - want| over the finite entries; the infinite ones must agree exactly."""
+def close(got, want, bar=None):
+    """max |got - want| over the finite entries, each within its bar (where one is given); the infinite ones must agree exactly."""
     inf = torch.isinf(want)
     assert torch.equal(torch.isinf(got), inf) and torch.equal(got[inf], want[inf].float()), (got, want)
-    return float((got.double()[~inf] - want[~inf]).abs().max()) if (~inf).any() else 0.0
+    err = (got.double()[~inf] - want[~inf]).abs()
+    assert bar is None or bool((err <= bar[~inf]).all()), (err, bar[~inf])
+    return float(err.max()) if (~inf).any() else 0.0
 
 
 @pytest.mark.parametrize("temperature", [1.0, 0.7, 2.5])
@@ -81,6 +89,7 @@ def test_against_float64(dev, V, temperature):
     x, tok = pattern_rows(V, seed=V)
     want_lp, want_ent = reference(x, tok, temperature)
     P = x.shape[0]
+    bar_lp, bar_ent = row_bars(x, tok, temperature, want_lp, want_ent)
     if V > 1:
         assert want_lp[5] == NEG and torch.isfinite(want_ent[5])
     assert abs(float(want_lp[4])) == 0.0 and abs(float(want_ent[4])) < 1e-12
@@ -92,8 +101,8 @@ def test_against_float64(dev, V, temperature):
                 lp, ent = ops.row_scores(strided(x[idx], ld, dev), tok[idx].to(dev), temperature, entropy=True)
                 only = ops.row_scores(strided(x[idx], ld, dev), tok[idx].to(dev), temperature)
                 assert torch.equal(only.view(torch.int32), lp.view(torch.int32))            # entropy=False: the same logprob
-                worst_lp = max(worst_lp, close(lp.cpu(), want_lp[idx]))
-                worst_ent = max(worst_ent, close(ent.cpu(), want_ent[idx]))
+                worst_lp = max(worst_lp, close(lp.cpu(), want_lp[idx], bar_lp[idx]))
+                worst_ent = max(worst_ent, close(ent.cpu(), want_ent[idx], bar_ent[idx]))
                 assert (ent >= 0).all()
     print(f"row_scores V={V} t={temperature}: max |dlogprob| {worst_lp:.2e}, max |dentropy| {worst_ent:.2e}")
     WORST["logprob"], WORST["entropy"] = max(WORST["logprob"], worst_lp), max(WORST["entropy"], worst_ent)
