@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("AVLLM_LIB_PATH") or os.path.join(_HERE, "libavllm.so"
 F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_SILU = 0, 1, 2, 3
 GEMM_KERNELS = ("SMALLM", "SKINNY64", "128", "RING", "H16", "HP16", "W4", "WP4", "DP", "F32")      # AVLLM_GEMM_<name> of avllm.h, by id
+ATTN_FORMS = ("ref", "short13x7", "short17x9", "mfma64x4", "mfma128x4")                              # AVLLM_ATTN_<name> of avllm.h, by id
 LORA_PAD = 64
 
 i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
@@ -142,6 +143,9 @@ _SIGS = {
     "avllm_attention_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, f32, i32, i32, i32, i32, vp], i32),
     "avllm_attention_bwd": ([vp] * 10 + [i32] * 4 + [i64] * 7 + [f32, i32, i32, i32, i32, vp], i32),
     "avllm_attention_bwd_rope": ([vp] * 10 + [i32] * 4 + [i64] * 7 + [f32, i32, i32, i32, i32, vp, vp], i32),
+    "avllm_attention_plan": ([i32] * 9 + [C.POINTER(i32), C.POINTER(i32)], i32),
+    "avllm_attention_fwd_mxq_ok": ([i32] * 6, i32),
+    "avllm_attention_bwd_fuses_rope": ([i32] * 3, i32),
     "avllm_ce_fwd": ([vp, i64, vp, i32, i32, i32, vp, vp, vp, i32, vp], i32),
     "avllm_ce_bwd": ([vp, i64, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp], i32),
     "avllm_argmax_rows": ([vp, i64, i64, i32, vp, i32, vp], i32),

@@ -162,14 +162,24 @@ def swiglu_bwd(dh, gu):
     return dgu
 
 
-def attention_fwd(qkv, B, T, H, hd, causal, scale=None, impl=0, want_lse=True, kv_heads=None, Tk=None, k=None, v=None, out=None):
+def attention_plan(B, Tq, Tk, H, hd, causal, dtype, impl=0, kv_heads=None):
+    """-> (forward, backward) names (L.ATTN_FORMS) of the kernels avllm_attention_fwd / _bwd give the call; backward None where Tq != Tk."""
+    f, b = L.i32(-1), L.i32(-1)
+    L.check(L.load().avllm_attention_plan(B, Tq, Tk, H, hd, int(causal), dtype, impl, kv_heads or 0, C.byref(f), C.byref(b)))
+    return L.ATTN_FORMS[f.value], (L.ATTN_FORMS[b.value] if b.value >= 0 else None)
+
+
+def attention_fwd(qkv, B, T, H, hd, causal, scale=None, impl=0, want_lse=True, kv_heads=None, Tk=None, k=None, v=None, out=None, plan=False):
     """qkv [B*T, (H + 2*kv_heads)*hd] fused rows [q | k | v] -> (o [B*T, H*hd], lse [B,H,T]).
     k=, v= (both or neither): separate operands, each a [rows, heads*hd] view with its own row stride; qkv is then q alone [B*T, H*hd] and k, v
-    hold B*Tk rows (Tk defaults to T; causal query t sees keys <= t + Tk - T).  out=: a [B*T, H*hd] view to write o into (row stride free)."""
+    hold B*Tk rows (Tk defaults to T; causal query t sees keys <= t + Tk - T).  out=: a [B*T, H*hd] view to write o into (row stride free).
+    plan=True: nothing runs; returns the name (L.ATTN_FORMS) of the kernel this call gets."""
     d = H * hd
     dkv = (kv_heads or H) * hd
     Tk = T if Tk is None else Tk
     assert (k is None) == (v is None) and (k is not None or Tk == T)
+    if plan:
+        return attention_plan(B, T, Tk, H, hd, causal, L.dt_of(qkv), impl, kv_heads)[0]
     o = torch.empty(B * T, d, device=qkv.device, dtype=qkv.dtype) if out is None else out
     assert o.shape == (B * T, d) and o.dtype == qkv.dtype
     lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32) if want_lse else None
@@ -200,9 +210,12 @@ def attention_fwd_mxq(qkv, B, T, H, hd, scale=None):
     return q, s
 
 
-def attention_bwd(qkv, o, dout, lse, B, T, H, hd, causal, scale=None, impl=0, kv_heads=None, rope_tab=None, out=None):
+def attention_bwd(qkv, o, dout, lse, B, T, H, hd, causal, scale=None, impl=0, kv_heads=None, rope_tab=None, out=None, plan=False):
     """-> dqkv [dq | dk | dv] in qkv's layout (out=: a view of qkv's shape to write into, row stride free).  rope_tab (ops.rope_table's f32
-    [T, hd/2, 2]): the inverse rotary is fused into dq | dk (avllm_attention_bwd_rope: bf16, impl 0, head_dim 64 / 128 only)."""
+    [T, hd/2, 2]): the inverse rotary is fused into dq | dk (avllm_attention_bwd_rope: bf16, impl 0, head_dim 64 / 128 only).
+    plan=True: nothing runs; returns the name (L.ATTN_FORMS) of the kernels this call gets."""
+    if plan:
+        return attention_plan(B, T, T, H, hd, causal, L.dt_of(qkv), impl, kv_heads)[1]
     d = H * hd
     dkv = (kv_heads or H) * hd
     dqkv = torch.empty_like(qkv) if out is None else out

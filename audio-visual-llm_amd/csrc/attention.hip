@@ -12,46 +12,35 @@
 // ds_read_b128 row reads and the 4-row transposed reads bank-conflict free (MI355X_MICROARCH §LDS).
 #include "common.h"
 #include "avllm_internal.h"
+#include "attention_tile.h"
 #include <type_traits>
 #include <cstdlib>
 
-int av_attention_fwd_ref(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Tq, int Tk, int H,
-                         int hd, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int dtype, hipStream_t st, int G);
-int av_attention_delta(const void* o, const void* dout, float* delta, int B, int T, int H, int hd, long ldo, long lddo, int dtype, hipStream_t st);
-int av_attention_bwd_ref(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
-                         void* dq, void* dk, void* dv, int B, int T, int H, int hd, long ldq, long ldk, long ldv, long lddo,
-                         long lddq, long lddk, long lddv, float scale, int causal, int dtype, hipStream_t st, int G);
-int av_attention_bwd_mfma(const void* q, const void* k, const void* v, const void* dout, const float* lse, float* delta,
-                          void* dq, void* dk, void* dv, int B, int T, int H, int hd, long ldq, long ldk, long ldv, long lddo,
-                          long lddq, long lddk, long lddv, float scale, int causal, hipStream_t st, int G, const void* o, long ldo, const float* rope_tab);
-
 namespace {
 
-typedef __attribute__((address_space(3))) short4v* lds_s4_ptr;
+using namespace avt;
 
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 __device__ __forceinline__ float max3f(float a, float x, float y) { return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, x), y); }
 
-template <int HD, int NW, bool CAUSAL>
+// How attn_fwd_mfma stages its 64-key K/V tiles (global -> registers -> LDS):
+//   Single: one tile buffer.  The loads of tile t are issued, then a barrier waits until tile t-1 has been consumed, the registers are
+//           stored and a second barrier publishes them: two barriers per tile, and the load latency is covered only by the wait for the
+//           slower waves of the workgroup (nothing of tile t+1 is in flight during tile t's MFMA/softmax work).
+//   Double: two tile buffers.  Tile t+1 is stored into the other buffer right after the barrier that opens iteration t and the loads of
+//           tile t+2 are issued behind it, so they run under tile t's MFMA/softmax work and ONE barrier per tile remains.
+enum class Stage { Single, Double };
+
+template <int HD, int NW, Stage ST, bool CAUSAL>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restrict__ q, const bf16* __restrict__ k,
                                                          const bf16* __restrict__ v, bf16* __restrict__ o, float* __restrict__ lse,
                                                          int Tq, int Tk, int H, long ldq, long ldk, long ldv, long ldo,
                                                          float scale_log2e, int G) {
     constexpr int KS = HD * 2 + 16;      // K tile row stride (bytes)
     constexpr int VS = HD * 2 + 64;      // V tile row stride (bytes)
-    constexpr int CPR = HD / 8;          // 16-byte chunks per row
     constexpr int NT = NW * 64;
-    // short non-causal sequences (CLIP: 197 tokens, 7 waves): the WHOLE K/V of the (item, head) is staged once (224 rows,
-    // 75 KiB -> two workgroups per CU) and the key loop runs without any further barrier; otherwise 64-key tiles.
-    constexpr bool ONESHOT = (HD == 64 && NW == 7 && !CAUSAL);
-    constexpr int LROWS = ONESHOT ? 224 : 64;
-    // DB (long sequences at head_dim 64: Whisper, T = 1500, 24 tiles): the K/V tile buffers are doubled, tile t+1 is parked in the other buffer
-    // right after the barrier that opens iteration t and ONE barrier per tile remains (two with a single buffer: "previous tile consumed" and
-    // "this tile stored").  Two buffers at head_dim 128 would pass the 64 KiB of static LDS.
-    constexpr bool DB = (HD == 64 && NW == 4);
-    constexpr int NBUF = DB ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) char k_lds_[NBUF * LROWS * KS];
-    __shared__ __attribute__((aligned(16))) char v_lds_[NBUF * LROWS * VS];
+    constexpr int NBUF = ST == Stage::Double ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) char k_lds_[NBUF * 64 * KS];
+    __shared__ __attribute__((aligned(16))) char v_lds_[NBUF * 64 * VS];
     char* k_lds = k_lds_;
     char* v_lds = v_lds_;
 
@@ -82,13 +71,10 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
     const bool wave_active = q0 < Tq;
     const int wave_kmax = CAUSAL ? min(Tk - 1, min(Tq - 1, q0 + 31) + off) : Tk - 1;
 
-    // K/V tiles are staged global -> registers -> LDS; the loads of tile t+1 are issued right after tile t has been
-    // written to LDS, so their latency runs under tile t's MFMA/softmax work (async-STAGE split, cdna guide T14).
-    constexpr int NCH = (64 * CPR + NT - 1) / NT;
-    // only where the extra 8*NCH VGPRs do not cost a resident workgroup: long non-causal sequences (Whisper, T=1500)
-    constexpr bool PREFETCH = (HD == 64 && NW == 4);
+    // K and V rows of one tile as a pair: one predicate per 16-byte chunk for both tensors (why not RowRegs: attention_tile.h)
+    constexpr int CPR = HD / 8, NCH = (64 * CPR + NT - 1) / NT;
     u32x4 kreg[NCH], vreg[NCH];
-    auto prefetch = [&](int kb0) {
+    auto prefetch = [&](int kb0) {                  // tile at key kb0, global -> the staged registers
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int c = tid + i * NT;
@@ -101,63 +87,29 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
             }
         }
     };
-    if (ONESHOT) {
-        // every global load of the K/V image is issued before the first LDS store waits on one: a single exposed latency
-        constexpr int NONE = (LROWS * CPR + NT - 1) / NT;
-        u32x4 kall[NONE], vall[NONE];
-#pragma unroll
-        for (int i = 0; i < NONE; ++i) {
-            const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-            kall[i] = (u32x4){0u, 0u, 0u, 0u}; vall[i] = (u32x4){0u, 0u, 0u, 0u};
-            if (c < LROWS * CPR && row < Tk) {
-                kall[i] = *(const u32x4*)(k + ((long)b * Tk + row) * ldk + (long)hk * HD + ch * 8);
-                vall[i] = *(const u32x4*)(v + ((long)b * Tk + row) * ldv + (long)hk * HD + ch * 8);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NONE; ++i) {
-            const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-            if (c < LROWS * CPR) {
-                *(u32x4*)(k_lds + row * KS + ch * 16) = kall[i];
-                *(u32x4*)(v_lds + row * VS + ch * 16) = vall[i];
-            }
-        }
-        __syncthreads();
-    }
     auto park = [&](int buf) {                      // the staged registers -> tile buffer buf
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int c = tid + i * NT;
             if (c < 64 * CPR) {
                 const int row = c / CPR, ch = c % CPR;
-                *(u32x4*)(k_lds_ + buf * LROWS * KS + row * KS + ch * 16) = kreg[i];
-                *(u32x4*)(v_lds_ + buf * LROWS * VS + row * VS + ch * 16) = vreg[i];
+                *(u32x4*)(k_lds_ + buf * 64 * KS + row * KS + ch * 16) = kreg[i];
+                *(u32x4*)(v_lds_ + buf * 64 * VS + row * VS + ch * 16) = vreg[i];
             }
         }
     };
-    if (PREFETCH) prefetch(0);
-    if (DB) { park(0); if (64 < k_end) prefetch(64); }
+    if (ST == Stage::Double) { prefetch(0); park(0); if (64 < k_end) prefetch(64); }
     for (int kb = 0; kb < k_end; kb += 64) {
-        const int lrow0 = ONESHOT ? kb : 0;        // first LDS row of this 64-key step
-        if (DB) {
+        if (ST == Stage::Double) {
             const int buf = (kb >> 6) & 1;
             __syncthreads();                       // tile kb/64 is stored (previous iteration) and the other buffer has been read by everybody
             if (kb + 64 < k_end) { park(buf ^ 1); if (kb + 128 < k_end) prefetch(kb + 128); }
-            k_lds = k_lds_ + buf * LROWS * KS; v_lds = v_lds_ + buf * LROWS * VS;
-        } else if (!ONESHOT) {
-            if (!PREFETCH) prefetch(kb);
+            k_lds = k_lds_ + buf * 64 * KS; v_lds = v_lds_ + buf * 64 * VS;
+        } else {
+            prefetch(kb);
             __syncthreads();                       // previous tile fully consumed
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int c = tid + i * NT;
-                if (c < 64 * CPR) {
-                    const int row = c / CPR, ch = c % CPR;
-                    *(u32x4*)(k_lds + row * KS + ch * 16) = kreg[i];
-                    *(u32x4*)(v_lds + row * VS + ch * 16) = vreg[i];
-                }
-            }
+            park(0);
             __syncthreads();
-            if (PREFETCH && kb + 64 < k_end) prefetch(kb + 64);
         }
         if (!wave_active || kb > wave_kmax) continue;      // wave-uniform
 
@@ -167,13 +119,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
         for (int i = 0; i < 16; ++i) { s0[i] = 0.f; s1[i] = 0.f; }
 #pragma unroll
         for (int ks = 0; ks < HD / 16; ++ks) {
-            const bf16x8 kf0 = *(const bf16x8*)(k_lds + (lrow0 + r) * KS + (2 * ks + half) * 16);
+            const bf16x8 kf0 = *(const bf16x8*)(k_lds + r * KS + (2 * ks + half) * 16);
             s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf0, qf[ks], s0, 0, 0, 0);
         }
         if (two) {
 #pragma unroll
             for (int ks = 0; ks < HD / 16; ++ks) {
-                const bf16x8 kf1 = *(const bf16x8*)(k_lds + (lrow0 + 32 + r) * KS + (2 * ks + half) * 16);
+                const bf16x8 kf1 = *(const bf16x8*)(k_lds + (32 + r) * KS + (2 * ks + half) * 16);
                 s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf1, qf[ks], s1, 0, 0, 0);
             }
         }
@@ -214,7 +166,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
             for (int i = 0; i < 16; ++i) oacc[d][i] *= alpha;
 
         // O^T += V^T . P^T   (k = keys; 2 k-steps of 16 per 32-key sub-block)
-        const int g = lane >> 4, i16 = lane & 15;
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) {
             if (sb == 1 && !two) break;
@@ -223,58 +174,19 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
                 bf16x8 pb;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pb[j] = (bf16)(sb == 0 ? s0[8 * s + j] : s1[8 * s + j]);
-                const int krow = lrow0 + 32 * sb + 16 * s + 4 * half + (i16 >> 2);
 #pragma unroll
                 for (int d = 0; d < HD / 32; ++d) {
-                    const int col = 32 * d + 16 * (g & 1) + 4 * (i16 & 3);
-                    const char* a0 = v_lds + krow * VS + col * 2;
-                    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0));
-                    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0 + 8 * VS));
-                    typedef __attribute__((ext_vector_type(8))) short short8v;
-                    const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    const bf16x8 vt = __builtin_bit_cast(bf16x8, both);
+                    const bf16x8 vt = tr_frag(v_lds, VS, 32 * sb + 16 * s, 32 * d, lane);
                     oacc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vt, pb, oacc[d], 0, 0, 0);
                 }
             }
         }
     }
-    if (ONESHOT) {
-        // Output through LDS: the MFMA layout gives every lane 8-byte pieces of 32 different rows (64 scattered stores per
-        // instruction); parked in the (now free) K image as bf16 rows, the wave's 32 x HD tile leaves as whole 16-byte row chunks.
-        __syncthreads();                                       // every wave is done reading K/V
-        const float l_tot = l_run + __shfl_xor(l_run, 32);
-        const float inv = 1.0f / l_tot;
-        char* ot = k_lds + w * 32 * KS;
-#pragma unroll
-        for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                float vals[4] = {oacc[d][4 * g4] * inv, oacc[d][4 * g4 + 1] * inv, oacc[d][4 * g4 + 2] * inv, oacc[d][4 * g4 + 3] * inv};
-                store_f<4>((bf16*)(ot + r * KS) + 32 * d + 8 * g4 + 4 * half, vals);
-            }
-        if (lse && half == 0 && qpos < Tq) lse[((long)b * H + hh) * Tq + qpos] = (m_run + log2f(l_tot)) * 0.69314718055994531f;
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < 32 * CPR / 64; ++i) {
-            const int c = lane + i * 64, row = c / CPR, ch = c % CPR;
-            if (q0 + row < Tq)
-                *(u32x4*)(o + ((long)b * Tq + q0 + row) * ldo + (long)hh * HD + ch * 8) = *(const u32x4*)(ot + row * KS + ch * 16);
-        }
-        return;
-    }
     if (!wave_active) return;
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
     if (qpos < Tq) {
-        bf16* op = o + ((long)b * Tq + qpos) * ldo + (long)hh * HD;
-#pragma unroll
-        for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                float vals[4] = {oacc[d][4 * g4] * inv, oacc[d][4 * g4 + 1] * inv, oacc[d][4 * g4 + 2] * inv, oacc[d][4 * g4 + 3] * inv};
-                store_f<4>(op + 32 * d + 8 * g4 + 4 * half, vals);
-            }
+        store_acc_rows<HD>(o + ((long)b * Tq + qpos) * ldo + (long)hh * HD, oacc, half, inv);
         if (lse && half == 0) lse[((long)b * H + hh) * Tq + qpos] = (m_run + log2f(l_tot)) * 0.69314718055994531f;
     }
 }
@@ -421,7 +333,6 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict
                 for (int t = 0; t < 4; ++t) {
                     const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(vr + t * 32));
                     const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(vr + t * 32 + 16 * VS));
-                    typedef __attribute__((ext_vector_type(8))) short short8v;
                     const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                     oacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, both), pb, oacc[t], 0, 0, 0);
                 }
@@ -489,47 +400,87 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict
     }
 }
 
+// One form of the short kernel: its dynamic-LDS attribute (once per device) and its launch.
+template <int NKB, int NW, bool QOUT, bool FULLK, bool WLSE, class... Args>
+int launch_short_form(int B, int H, hipStream_t st, Args... args) {
+    constexpr int LDS = NKB * 16 * 160 + ((NKB + 1) / 2) * 32 * 160 + NW * 16 * 80;
+    static bool attr[AV_MAX_DEVICES] = {};
+    int dev = 0;
+    AV_HIP(hipGetDevice(&dev));
+    if (!attr[dev & (AV_MAX_DEVICES - 1)]) {
+        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, QOUT, FULLK, WLSE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        attr[dev & (AV_MAX_DEVICES - 1)] = true;
+    }
+    hipLaunchKernelGGL((attn_fwd_short<NKB, NW, QOUT, FULLK, WLSE>), dim3(H, B), dim3(NW * 64), LDS, st, args...);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// The six forms that exist: quantised output, output + LSE, output alone (go's first two arguments), each with and without FULLK (its third).
 template <int NKB, int NW>
 int launch_fwd_short(const void* q, const void* k, const void* v, void* o, float* lse, int B, int T, int H, long ldq, long ldk, long ldv,
                      long ldo, float scale, hipStream_t st, int G, void* oq = nullptr, long ldoq = 0, void* osc = nullptr) {
-    constexpr int LDS = NKB * 16 * 160 + ((NKB + 1) / 2) * 32 * 160 + NW * 16 * 80;
     AV_CHECK_ARG(!(oq && lse), "attention_fwd_short: the quantised-output form writes no LSE");
-    static bool attr[64] = {};
-    int dev = 0;
-    AV_HIP(hipGetDevice(&dev));
-    if (!attr[dev & 63]) {
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        AV_HIP(hipFuncSetAttribute((const void*)attn_fwd_short<NKB, NW, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr[dev & 63] = true;
-    }
-    const int RBo = (int)(((long)B * T + 255) / 256 * 4);            // mx_groups(rows) of fp8.hip: 64-row groups, padded to whole 256-row tiles
+    const int RBo = oq ? (int)(((long)B * T + 255) / 256 * 4) : 0;   // mx_groups(rows) of fp8.hip: 64-row groups, padded to whole 256-row tiles
     const bool fullk = ((T + 15) >> 4) == NKB;
-#define AV_SHORT(QV, FV, LV, OQ, LDOQ, OSC, RB) hipLaunchKernelGGL((attn_fwd_short<NKB, NW, QV, FV, LV>), dim3(H, B), dim3(NW * 64), LDS, st, (const bf16*)q, (const bf16*)k, \
-        (const bf16*)v, (bf16*)o, lse, T, H, ldq, ldk, ldv, ldo, scale * 1.4426950408889634f, G, OQ, LDOQ, OSC, RB)
-    if (oq) { if (fullk) AV_SHORT(true, true, false, (uint8_t*)oq, ldoq, (uint8_t*)osc, RBo); else AV_SHORT(true, false, false, (uint8_t*)oq, ldoq, (uint8_t*)osc, RBo); }
-    else if (lse) { if (fullk) AV_SHORT(false, true, true, nullptr, 0, nullptr, 0); else AV_SHORT(false, false, true, nullptr, 0, nullptr, 0); }
-    else { if (fullk) AV_SHORT(false, true, false, nullptr, 0, nullptr, 0); else AV_SHORT(false, false, false, nullptr, 0, nullptr, 0); }
-#undef AV_SHORT
-    AV_LAUNCH_CHECK();
-    return AV_OK;
+    auto go = [&](auto qout, auto wlse, auto full) {
+        return launch_short_form<NKB, NW, decltype(qout)::value, decltype(full)::value, decltype(wlse)::value>(
+            B, H, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, T, H, ldq, ldk, ldv, ldo, scale * 1.4426950408889634f, G, (uint8_t*)oq, ldoq,
+            (uint8_t*)osc, RBo);
+    };
+    const std::true_type yes;
+    const std::false_type no;
+    if (oq) return fullk ? go(yes, no, yes) : go(yes, no, no);
+    if (lse) return fullk ? go(no, yes, yes) : go(no, yes, no);
+    return fullk ? go(no, no, yes) : go(no, no, no);
 }
 
-template <int HD, int NW>
+template <int HD>
 int launch_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Tq, int Tk, int H, long ldq,
                long ldk, long ldv, long ldo, float scale, int causal, hipStream_t st, int G) {
+    constexpr int NW = 4;
+    // two tile buffers where they fit: at head_dim 128 they would pass the 64 KiB of static LDS
+    constexpr Stage ST = HD == 64 ? Stage::Double : Stage::Single;
     const dim3 grid(av_cdiv(Tq, 32 * NW), H, B), block(NW * 64);
     const float sl = scale * 1.4426950408889634f;
-    if (causal) hipLaunchKernelGGL((attn_fwd_mfma<HD, NW, true>), grid, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, Tq, Tk, H, ldq, ldk, ldv, ldo, sl, G);
-    else hipLaunchKernelGGL((attn_fwd_mfma<HD, NW, false>), grid, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, Tq, Tk, H, ldq, ldk, ldv, ldo, sl, G);
+    auto go = [&](auto c) {
+        hipLaunchKernelGGL((attn_fwd_mfma<HD, NW, ST, decltype(c)::value>), grid, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, Tq, Tk, H,
+                           ldq, ldk, ldv, ldo, sl, G);
+    };
+    if (causal) go(std::true_type{}); else go(std::false_type{});
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
 
+// the MFMA kernels exist for bf16 at head_dim 64 and 128; impl = 1 asks for the scalar kernels of attention_ref.hip
+bool mfma_takes(int hd, int dtype, int impl) { return impl == 0 && dtype == AV_BF16 && (hd == 64 || hd == 128); }
+bool is_short(int form) { return form == AVLLM_ATTN_SHORT13X7 || form == AVLLM_ATTN_SHORT17X9; }
+
 }  // namespace
+
+// Which kernel a call gets: pure host code, pinned by tests/test_attention_plan_cpu.py.  H and kv_heads do not enter: every kernel takes grouped queries.
+int av_attention_fwd_form(int B, int Tq, int Tk, int hd, int causal, int dtype, int impl) {
+    if (!mfma_takes(hd, dtype, impl)) return AVLLM_ATTN_REF;
+    if (hd == 128) return AVLLM_ATTN_MFMA128X4;
+    // short non-causal self-attention (CLIP: 197 tokens, ViT-L/14: 257): whole-sequence scores in registers, exact two-pass softmax.
+    // One workgroup per (item, head) on grid.y = B; the knob ATTN_SHORT = 0 gives these calls to the general kernel.
+    if (!causal && Tq == Tk && B <= 65535 && av_knob(AV_KNOB_ATTN_SHORT) != 0) {
+        if (Tq <= 208) return AVLLM_ATTN_SHORT13X7;
+        if (Tq <= 272) return AVLLM_ATTN_SHORT17X9;
+    }
+    return AVLLM_ATTN_MFMA64X4;
+}
+int av_attention_bwd_form(int hd, int dtype, int impl) {
+    return !mfma_takes(hd, dtype, impl) ? AVLLM_ATTN_REF : hd == 64 ? AVLLM_ATTN_MFMA64X4 : AVLLM_ATTN_MFMA128X4;
+}
+extern "C" int avllm_attention_plan(int32_t B, int32_t Tq, int32_t Tk, int32_t H, int32_t hd, int32_t causal, int32_t dtype, int32_t impl, int32_t kv_heads,
+                                    int32_t* fwd_form, int32_t* bwd_form) {
+    AV_CHECK_ARG(fwd_form && bwd_form && B > 0 && Tq > 0 && Tk > 0 && H > 0, "attention_plan: bad args");
+    AV_CHECK_ARG(H % (kv_heads <= 0 ? H : kv_heads) == 0, "attention_plan: %d query heads are not a multiple of %d key/value heads", H, kv_heads);
+    *fwd_form = av_attention_fwd_form(B, Tq, Tk, hd, causal, dtype, impl);
+    *bwd_form = Tq == Tk ? av_attention_bwd_form(hd, dtype, impl) : -1;
+    return AV_OK;
+}
 
 int av_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Tq, int Tk, int H,
                      int hd, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int dtype, int impl,
@@ -540,41 +491,38 @@ int av_attention_fwd(const void* q, const void* k, const void* v, void* o, float
     const int G = H / kv_heads;
     AV_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0, "attention_fwd: row strides must be multiples of 8");
     AV_CHECK_ARG(!causal || Tk >= Tq, "attention_fwd: causal needs Tk >= Tq");
-    if (impl == 1 || dtype == AV_F32 || (hd != 64 && hd != 128))
-        return av_attention_fwd_ref(q, k, v, o, lse, B, Tq, Tk, H, hd, ldq, ldk, ldv, ldo, scale, causal, dtype, st, G);
-    if (hd == 64) {
-        // short non-causal self-attention (CLIP: 197 tokens, ViT-L/14: 257): whole-sequence scores in registers, exact two-pass softmax
-        const bool short_off = av_knob(AV_KNOB_ATTN_SHORT) == 0;
-        if (!causal && Tq == Tk && !short_off && B <= 65535) {
-            if (Tq <= 208) return launch_fwd_short<13, 7>(q, k, v, o, lse, B, Tq, H, ldq, ldk, ldv, ldo, scale, st, G);
-            if (Tq <= 272) return launch_fwd_short<17, 9>(q, k, v, o, lse, B, Tq, H, ldq, ldk, ldv, ldo, scale, st, G);
-        }
-        // short sequences (CLIP: 197 tokens): one workgroup covers the whole sequence with 7 waves
-        if (Tq <= 224 && Tq > 128 && Tk <= 224 && !causal) return launch_fwd<64, 7>(q, k, v, o, lse, B, Tq, Tk, H, ldq, ldk, ldv, ldo, scale, causal, st, G);
-        return launch_fwd<64, 4>(q, k, v, o, lse, B, Tq, Tk, H, ldq, ldk, ldv, ldo, scale, causal, st, G);
+    switch (av_attention_fwd_form(B, Tq, Tk, hd, causal, dtype, impl)) {
+    case AVLLM_ATTN_SHORT13X7: return launch_fwd_short<13, 7>(q, k, v, o, lse, B, Tq, H, ldq, ldk, ldv, ldo, scale, st, G);
+    case AVLLM_ATTN_SHORT17X9: return launch_fwd_short<17, 9>(q, k, v, o, lse, B, Tq, H, ldq, ldk, ldv, ldo, scale, st, G);
+    case AVLLM_ATTN_MFMA64X4: return launch_fwd<64>(q, k, v, o, lse, B, Tq, Tk, H, ldq, ldk, ldv, ldo, scale, causal, st, G);
+    case AVLLM_ATTN_MFMA128X4: return launch_fwd<128>(q, k, v, o, lse, B, Tq, Tk, H, ldq, ldk, ldv, ldo, scale, causal, st, G);
+    default: return av_attention_fwd_ref(q, k, v, o, lse, B, Tq, Tk, H, hd, ldq, ldk, ldv, ldo, scale, causal, dtype, st, G);
     }
-    return launch_fwd<128, 4>(q, k, v, o, lse, B, Tq, Tk, H, ldq, ldk, ldv, ldo, scale, causal, st, G);
 }
 
 // Non-causal self-attention of short sequences with the output block-scaled to e4m3 in the epilogue (attn_fwd_short<.., QOUT>): codes
 // oq [B*T, ldoq] + the layout-0 scale image an avllm_gemm_f8 A operand takes.  Only the shapes the one-pass kernel covers.
 bool av_attention_fwd_mxq_ok(int B, int T, int H, int hd, int dtype, int kv_heads) {
-    return dtype == AV_BF16 && hd == 64 && T <= 272 && B <= 65535 && (kv_heads <= 0 || kv_heads == H) && (H * hd) % 128 == 0 && av_knob(AV_KNOB_ATTN_SHORT) != 0 &&
-           !av_knob(AV_KNOB_F8_UNFUSED_QUANT);
+    return is_short(av_attention_fwd_form(B, T, T, hd, 0, dtype, 0)) && (kv_heads <= 0 || kv_heads == H) && (H * hd) % 128 == 0 && !av_knob(AV_KNOB_F8_UNFUSED_QUANT);
 }
 int av_attention_fwd_mxq(const void* q, const void* k, const void* v, void* oq, long ldoq, void* osc, int B, int T, int H, int hd, long ldq, long ldk,
                          long ldv, float scale, hipStream_t st) {
     AV_CHECK_ARG(q && k && v && oq && osc && av_attention_fwd_mxq_ok(B, T, H, hd, AV_BF16, H) && ldoq % 16 == 0 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0,
                  "attention_fwd_mxq: bad args (bf16, head_dim 64, T <= 272, 16-byte aligned code rows)");
-    if (T <= 208) return launch_fwd_short<13, 7>(q, k, v, nullptr, nullptr, B, T, H, ldq, ldk, ldv, 0, scale, st, 1, oq, ldoq, osc);
+    if (av_attention_fwd_form(B, T, T, hd, 0, AV_BF16, 0) == AVLLM_ATTN_SHORT13X7)
+        return launch_fwd_short<13, 7>(q, k, v, nullptr, nullptr, B, T, H, ldq, ldk, ldv, 0, scale, st, 1, oq, ldoq, osc);
     return launch_fwd_short<17, 9>(q, k, v, nullptr, nullptr, B, T, H, ldq, ldk, ldv, 0, scale, st, 1, oq, ldoq, osc);
 }
 extern "C" int avllm_attention_fwd_mxq(const void* q, const void* k, const void* v, void* oq, int64_t ldoq, void* scales, int32_t B, int32_t T, int32_t H,
                                        int32_t hd, int64_t ldq, int64_t ldk, int64_t ldv, float scale, void* stream) {
     return av_attention_fwd_mxq(q, k, v, oq, ldoq, scales, B, T, H, hd, ldq, ldk, ldv, scale, (hipStream_t)stream);
 }
+extern "C" int avllm_attention_fwd_mxq_ok(int32_t B, int32_t T, int32_t H, int32_t hd, int32_t dtype, int32_t kv_heads) {
+    return av_attention_fwd_mxq_ok(B, T, H, hd, dtype, kv_heads);
+}
 
-bool av_attention_bwd_fuses_rope(int dtype, int hd, int impl) { return impl == 0 && dtype == AV_BF16 && (hd == 128 || hd == 64); }
+bool av_attention_bwd_fuses_rope(int dtype, int hd, int impl) { return av_attention_bwd_form(hd, dtype, impl) != AVLLM_ATTN_REF; }
+extern "C" int avllm_attention_bwd_fuses_rope(int32_t dtype, int32_t hd, int32_t impl) { return av_attention_bwd_fuses_rope(dtype, hd, impl); }
 
 int av_attention_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                      void* dq, void* dk, void* dv, float* delta_ws, int B, int T, int H, int hd, long ldq, long ldk,
@@ -586,7 +534,7 @@ int av_attention_bwd(const void* q, const void* k, const void* v, const void* o,
     AV_CHECK_ARG(H % kv_heads == 0, "attention_bwd: %d query heads are not a multiple of %d key/value heads", H, kv_heads);
     const int G = H / kv_heads;
     // dO shares O's row stride.  The MFMA dQ kernel computes delta itself (and leaves it in delta_ws for the dK/dV kernel)
-    if (impl == 0 && dtype == AV_BF16 && (hd == 128 || hd == 64))
+    if (av_attention_bwd_form(hd, dtype, impl) != AVLLM_ATTN_REF)
         return av_attention_bwd_mfma(q, k, v, dout, lse, delta_ws, dq, dk, dv, B, T, H, hd, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, causal, st, G, o, ldo, rope_tab);
     AV_TRY(av_attention_delta(o, dout, delta_ws, B, T, H, hd, ldo, ldo, dtype, st));
     return av_attention_bwd_ref(q, k, v, dout, lse, delta_ws, dq, dk, dv, B, T, H, hd, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, causal, dtype, st, G);

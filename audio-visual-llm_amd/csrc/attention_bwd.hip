@@ -13,52 +13,16 @@
 // transposed operand is needed, as a second image with row stride HD*2+64 B (conflict-free 4-row tr reads).
 #include "common.h"
 #include "avllm_internal.h"
+#include "attention_tile.h"
+#include <type_traits>
 
 namespace {
 
-typedef __attribute__((address_space(3))) short4v* lds_s4_ptr;
-typedef __attribute__((ext_vector_type(8))) short short8v;
+using namespace avt;
 
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-// A operand = X^T fragment for the 32x32x16 MFMA: rows = 32 columns of the LDS tile starting at col0, k = 16 tile rows
-// starting at row0 (permuted order matching an accumulator-as-B operand: element j <-> row 8(j>>2)+4half+(j&3))
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int stride, int row0, int col0, int lane) {
-    const int g = lane >> 4, i16 = lane & 15, half = lane >> 5;
-    const char* a0 = img + (row0 + 4 * half + (i16 >> 2)) * stride + (col0 + 16 * (g & 1) + 4 * (i16 & 3)) * 2;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0 + 8 * stride));
-    const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, both);
-}
-
-// Tiles go global -> registers -> LDS: the loads of the NEXT tile are issued right after the current tile has been written to
-// LDS, so their latency runs under the current tile's MFMA work.  Both kernels are held to 256 registers (two waves per SIMD, i.e.
+// Tiles go global -> registers -> LDS (attention_tile.h RowRegs): the loads of the NEXT tile are issued right after the current tile has been
+// written to LDS, so their latency runs under the current tile's MFMA work.  Both kernels are held to 256 registers (two waves per SIMD, i.e.
 // two workgroups per CU): left alone hipcc takes ~400 and a lone wave per SIMD exposes every barrier and LDS round trip.
-template <int HD, int NT, int ROWS> struct RowRegs { u32x4 v[(ROWS * (HD / 8) + NT - 1) / NT]; };
-
-template <int HD, int NT, int ROWS>
-__device__ __forceinline__ void load_rows(RowRegs<HD, NT, ROWS>& r, const bf16* __restrict__ src, long ld, int row0, int rows_max, int tid) {
-    constexpr int CPR = HD / 8, N = (ROWS * CPR + NT - 1) / NT;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-        r.v[i] = (u32x4){0u, 0u, 0u, 0u};
-        if (c < ROWS * CPR && row0 + row < rows_max) r.v[i] = *(const u32x4*)(src + (long)(row0 + row) * ld + ch * 8);
-    }
-}
-template <int HD, int NT, int ROWS>
-__device__ __forceinline__ void store_rows(const RowRegs<HD, NT, ROWS>& r, char* img_a, int stride_a, char* img_b, int stride_b, int tid) {
-    constexpr int CPR = HD / 8, N = (ROWS * CPR + NT - 1) / NT;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int c = tid + i * NT, row = c / CPR, ch = c % CPR;
-        if (c < ROWS * CPR) {
-            if (img_a) *(u32x4*)(img_a + row * stride_a + ch * 16) = r.v[i];
-            if (img_b) *(u32x4*)(img_b + row * stride_b + ch * 16) = r.v[i];
-        }
-    }
-}
 
 // Inverse rotary embedding on a gradient row held in the MFMA output layout (lane = row, registers [d][4*g4+i] = element
 // 32d + 8g4 + 4half + i): element e < HD/2 pairs with e + HD/2, which the same lane holds in block d + HD/64.  table row t =
@@ -186,14 +150,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dq_mfma(const bf16* __res
     }
     if (!wave_active || qpos >= T) return;
     if (rope_tab) unrope<HD>(acc, rope_tab, qpos, half);          // gradient w.r.t. the pre-RoPE q (transpose of the rotation)
-    bf16* op = dq + ((long)b * T + qpos) * lddq + (long)hh * HD;
-#pragma unroll
-    for (int d = 0; d < HD / 32; ++d)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            float vals[4] = {acc[d][4 * g4], acc[d][4 * g4 + 1], acc[d][4 * g4 + 2], acc[d][4 * g4 + 3]};
-            store_f<4>(op + 32 * d + 8 * g4 + 4 * half, vals);
-        }
+    store_acc_rows<HD>(dq + ((long)b * T + qpos) * lddq + (long)hh * HD, acc, half, 1.0f);
 }
 
 // ------------------------------------------------------------------------------------------------ dK, dV
@@ -317,6 +274,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bwd_dkv_mfma(const bf16* __re
     if (rope_tab) unrope<HD>(dka, rope_tab, kpos, half);
     bf16* okp = dk + ((long)b * T + kpos) * lddk + (long)hh * HD;
     bf16* ovp = dv + ((long)b * T + kpos) * lddv + (long)hh * HD;
+    // Not store_acc_rows: with dva handed to a helper this kernel is compiled differently all the way up (other fma contractions in unrope at
+    // head_dim 64, two more registers at 128, where it sits at its 256), whatever the helper's form (profiles/r14_attention_refactor_isa.txt)
 #pragma unroll
     for (int d = 0; d < HD / 32; ++d)
 #pragma unroll
@@ -334,13 +293,14 @@ int launch_bwd(const void* q, const void* k, const void* v, const void* dout, co
                float scale, int causal, hipStream_t st, int G, const void* o, long ldo, const float* rope_tab) {
     constexpr int NW = 4;
     const dim3 grid(av_cdiv(T, 32 * NW), H, B), gridkv(av_cdiv(T, 32 * NW), H / G, B), block(NW * 64);
-    if (causal) {
-        hipLaunchKernelGGL((attn_bwd_dq_mfma<HD, NW, true>), grid, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, (float*)delta, (bf16*)dq, T, H, ldq, ldk, ldv, lddo, lddq, scale, G, (const bf16*)o, ldo, rope_tab);
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma<HD, NW, true>), gridkv, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, T, H, ldq, ldk, ldv, lddo, lddk, lddv, scale, G, rope_tab);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_mfma<HD, NW, false>), grid, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, (float*)delta, (bf16*)dq, T, H, ldq, ldk, ldv, lddo, lddq, scale, G, (const bf16*)o, ldo, rope_tab);
-        hipLaunchKernelGGL((attn_bwd_dkv_mfma<HD, NW, false>), gridkv, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, T, H, ldq, ldk, ldv, lddo, lddk, lddv, scale, G, rope_tab);
-    }
+    auto go = [&](auto c) {
+        constexpr bool CAUSAL = decltype(c)::value;
+        hipLaunchKernelGGL((attn_bwd_dq_mfma<HD, NW, CAUSAL>), grid, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, (float*)delta,
+                           (bf16*)dq, T, H, ldq, ldk, ldv, lddo, lddq, scale, G, (const bf16*)o, ldo, rope_tab);
+        hipLaunchKernelGGL((attn_bwd_dkv_mfma<HD, NW, CAUSAL>), gridkv, block, 0, st, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta,
+                           (bf16*)dk, (bf16*)dv, T, H, ldq, ldk, ldv, lddo, lddk, lddv, scale, G, rope_tab);
+    };
+    if (causal) go(std::true_type{}); else go(std::false_type{});
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -20,6 +20,19 @@ int av_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rs
 int av_rope(void* x, long ld, long rows, int T, int heads, int hd, int pos0, float theta, int inverse, int dtype, hipStream_t st);
 int av_swiglu_fwd(const void* gu, void* h, long M, int F, int dtype, hipStream_t st);
 int av_swiglu_bwd(const void* dh, const void* gu, void* dgu, long M, int F, int dtype, hipStream_t st);
+// Which kernel an attention call gets (AVLLM_ATTN_<form> of avllm.h): every dispatch below switches on these two
+int av_attention_fwd_form(int B, int Tq, int Tk, int hd, int causal, int dtype, int impl);
+int av_attention_bwd_form(int hd, int dtype, int impl);
+// attention_ref.hip (scalar kernels, delta) and attention_bwd.hip (MFMA backward), reached through av_attention_fwd / av_attention_bwd
+int av_attention_fwd_ref(const void* q, const void* k, const void* v, void* o, float* lse, int B, int Tq, int Tk, int H,
+                         int hd, long ldq, long ldk, long ldv, long ldo, float scale, int causal, int dtype, hipStream_t st, int G);
+int av_attention_delta(const void* o, const void* dout, float* delta, int B, int T, int H, int hd, long ldo, long lddo, int dtype, hipStream_t st);
+int av_attention_bwd_ref(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
+                         void* dq, void* dk, void* dv, int B, int T, int H, int hd, long ldq, long ldk, long ldv, long lddo,
+                         long lddq, long lddk, long lddv, float scale, int causal, int dtype, hipStream_t st, int G);
+int av_attention_bwd_mfma(const void* q, const void* k, const void* v, const void* dout, const float* lse, float* delta,
+                          void* dq, void* dk, void* dv, int B, int T, int H, int hd, long ldq, long ldk, long ldv, long lddo,
+                          long lddq, long lddk, long lddv, float scale, int causal, hipStream_t st, int G, const void* o, long ldo, const float* rope_tab);
 bool av_attention_fwd_mxq_ok(int B, int T, int H, int hd, int dtype, int kv_heads);
 int av_attention_fwd_mxq(const void* q, const void* k, const void* v, void* oq, long ldoq, void* osc, int B, int T, int H, int hd, long ldq, long ldk,
                          long ldv, float scale, hipStream_t st);

@@ -237,6 +237,17 @@ int avllm_attention_bwd_rope(const void* q, const void* k, const void* v, const 
                              int32_t H, int32_t hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddq,
                              int64_t lddk, int64_t lddv, float scale, int32_t causal, int32_t dtype, int32_t impl,
                              int32_t kv_heads, const float* rope_tab, void* stream);
+/* Which kernel avllm_attention_fwd / avllm_attention_bwd run for a call: *fwd_form and *bwd_form = one of the ids below (*bwd_form = -1 where
+ * Tq != Tk: the backward takes one T).  Pure host code, no device needed; the arguments and the knob "ATTN_SHORT" (0 = short non-causal
+ * sequences go to the general kernel) decide.  REF = the scalar kernels (fp32 storage, impl 1, head dims other than 64 and 128); SHORT13X7 /
+ * SHORT17X9 = the one-pass kernel of non-causal self-attention at head_dim 64, T <= 208 / <= 272 (B <= 65535); MFMA64X4 / MFMA128X4 = the flash
+ * kernels.  The backward has no short form.  avllm_attention_fwd_mxq_ok: 1 where avllm_attention_fwd_mxq takes the call (a short form, no
+ * grouped queries, H * hd a multiple of 128); avllm_attention_bwd_fuses_rope: 1 where avllm_attention_bwd_rope takes a table (an MFMA form). */
+enum { AVLLM_ATTN_REF, AVLLM_ATTN_SHORT13X7, AVLLM_ATTN_SHORT17X9, AVLLM_ATTN_MFMA64X4, AVLLM_ATTN_MFMA128X4, AVLLM_ATTN_FORMS };
+int avllm_attention_plan(int32_t B, int32_t Tq, int32_t Tk, int32_t H, int32_t hd, int32_t causal, int32_t dtype, int32_t impl, int32_t kv_heads,
+                         int32_t* fwd_form, int32_t* bwd_form);
+int avllm_attention_fwd_mxq_ok(int32_t B, int32_t T, int32_t H, int32_t hd, int32_t dtype, int32_t kv_heads);
+int avllm_attention_bwd_fuses_rope(int32_t dtype, int32_t hd, int32_t impl);
 /* shifted causal-LM cross entropy (HF:loss/loss_utils.py:49-71): row (b,t) is scored against labels[b,t+1],
  * ignore_index -100 and the last position.  loss_sum/count are ACCUMULATED (zero them first). row_lse [B*T]. */
 int avllm_ce_fwd(const void* logits, int64_t ld, const int64_t* labels, int32_t B, int32_t T, int32_t V,

@@ -293,8 +293,8 @@ GEOMETRIES += [_g("short13x7", T, 64, False, "short") for T in (1, 15, 16, 17, 1
 GEOMETRIES += [_g("short17x9", T, 64, False, "short") for T in (209, 257, 272)]
 GEOMETRIES += [_g("mfma64x4", T, 64, False, "mfma") for T in (273, 330)]
 GEOMETRIES += [_g("mfma64x4", T, 64, True, "mfma") for T in (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200)]
-GEOMETRIES += [_g("mfma64x7", T, 64, False, "mfma", knob=True) for T in (129, 197, 224)]
-GEOMETRIES += [_g("tqtk-mfma64x7", 150, 64, False, "mfma", Tk=200)]       # the one-shot form is also what non-causal 128 < Tq <= 224, Tk != Tq selects
+GEOMETRIES += [_g("mfma64x4", T, 64, False, "mfma", knob=True) for T in (129, 197, 224)]       # short lengths on the general kernel (the knob)
+GEOMETRIES += [_g("tqtk-mfma64x4", 150, 64, False, "mfma", Tk=200)]                              # and without it where Tk != Tq
 GEOMETRIES += [_g("mfma128x4", T, 128, c, "mfma") for c in (True, False) for T in (1, 33, 64, 65, 129, 257)]
 GEOMETRIES += [_g("gqa-mfma128x4", 70, 128, True, "mfma", B=2, H=H, Hkv=Hkv) for H, Hkv in ((4, 2), (4, 1), (8, 1))]
 GEOMETRIES += [_g("gqa-short13x7", 50, 64, False, "short", B=3, H=4, Hkv=2), _g("gqa-mfma64x4", 130, 64, True, "mfma", B=2, H=8, Hkv=2)]
@@ -303,6 +303,11 @@ GEOMETRIES += [_g("tqtk-mfma%dx4" % hd, 50, hd, False, "mfma", Tk=197) for hd in
 GEOMETRIES += [_g("ref", 40, hd, c, "ref", dt=dt) for dt in ("f32", "bf16") for hd in (32, 96, 512) for c in (True, False)]
 GEOMETRIES += [_g("ref-impl1", 70, hd, True, "ref", dt=dt, impl=1) for dt in ("f32", "bf16") for hd in (64, 128)]
 GEOMETRIES += [_g("ref-f32", T, hd, c, "ref", dt="f32") for T, hd, c in ((197, 64, False), (65, 128, True))]
+
+
+def kernel_of(g):
+    """The name (avllm.lib.ATTN_FORMS) of the kernel g.form stands for: the form without its gqa- / tqtk- / rope-bwd- / -impl1 / -f32 decorations."""
+    return next(k for k in ("short13x7", "short17x9", "mfma64x4", "mfma128x4", "ref") if k in g.form.split("-"))
 
 
 def geo_id(g):

@@ -1,5 +1,6 @@
 """The attention kernels (csrc/attention.hip, attention_bwd.hip, attention_ref.hip) against the float64 restatements of tests/refs64_attention.py,
-at every form av_attention_fwd / av_attention_bwd can select (named in each test id) and at the tile edges of each.  Bars: tests/bars.py
+at every form av_attention_fwd / av_attention_bwd can select (named in each test id; every call first asserts that ops.attention_fwd / _bwd
+(plan=True) names it) and at the tile edges of each.  Bars: tests/bars.py
 ("attention against float64"); none is taken from a kernel's output, and tests/test_attention_refs_cpu.py shows on the host that the documented
 arithmetic stays under each while one unmasked / dropped / shifted key, a wrong kv head, a missing delta or query row does not.
 
@@ -64,8 +65,11 @@ def run_fwd(g, c, k_cpu=None, v_cpu=None):
     _, kv = nan_wide(c.k if k_cpu is None else k_cpu, dt)
     _, vv = nan_wide(c.v if v_cpu is None else v_cpu, dt)
     obuf, ov = guarded(g.B * g.Tq, d, dt)
+    kw = dict(impl=g.impl, kv_heads=g.Hkv, Tk=g.Tk, k=kv, v=vv, out=ov)
     with knob_of(g):
-        o, lse = ops.attention_fwd(qv, g.B, g.Tq, g.H, g.hd, g.causal, impl=g.impl, kv_heads=g.Hkv, Tk=g.Tk, k=kv, v=vv, out=ov)
+        planned = ops.attention_fwd(qv, g.B, g.Tq, g.H, g.hd, g.causal, plan=True, **kw)
+        assert planned == A.kernel_of(g), f"{A.geo_id(g)}: planned on {planned}"
+        o, lse = ops.attention_fwd(qv, g.B, g.Tq, g.H, g.hd, g.causal, **kw)
     torch.cuda.synchronize()
     guard_intact(obuf, g.B * g.Tq, d, "attention_fwd")
     return o, lse
@@ -107,9 +111,14 @@ def run_bwd(g, c, rope_tab=None, impl=None):
     _, qkv = nan_wide(torch.cat([c.bq, c.bk, c.bv], 1), dt)
     dout = c.bdout.to(dt).cuda()
     gbuf, gv = guarded(g.B * g.Tq, d + 2 * dkv, dt)
+    # the backward has no short form: those lengths run on its 64-key-tile kernels
+    want = "ref" if impl else "mfma64x4" if A.kernel_of(g).startswith("short") else A.kernel_of(g)
     with knob_of(g):
         o, lse = ops.attention_fwd(qkv, g.B, g.Tq, g.H, g.hd, g.causal, impl=impl, kv_heads=g.Hkv)
-        ops.attention_bwd(qkv, o, dout, lse, g.B, g.Tq, g.H, g.hd, g.causal, impl=impl, kv_heads=g.Hkv, rope_tab=rope_tab, out=gv)
+        kw = dict(impl=impl, kv_heads=g.Hkv, rope_tab=rope_tab, out=gv)
+        planned = ops.attention_bwd(qkv, o, dout, lse, g.B, g.Tq, g.H, g.hd, g.causal, plan=True, **kw)
+        assert planned == want, f"{A.geo_id(g)}: backward planned on {planned}, not {want}"
+        ops.attention_bwd(qkv, o, dout, lse, g.B, g.Tq, g.H, g.hd, g.causal, **kw)
     torch.cuda.synchronize()
     guard_intact(gbuf, g.B * g.Tq, d + 2 * dkv, "attention_bwd")
     return gv[:, :d], gv[:, d:d + dkv], gv[:, d + dkv:]
@@ -173,9 +182,10 @@ def test_backward_fused_inverse_rope(dev, g, pos0):
     # the table exists in the bf16 MFMA kernels only
     with pytest.raises(ValueError):
         run_bwd(g, c, rope_tab=tab, impl=1)
-    cf = A.case(g._replace(dt="f32", emul="ref"), "randn")
+    gf = g._replace(form="ref-f32", dt="f32", emul="ref")
+    cf = A.case(gf, "randn")
     with pytest.raises(ValueError):
-        run_bwd(g._replace(dt="f32", emul="ref"), cf, rope_tab=tab)
+        run_bwd(gf, cf, rope_tab=tab)
 
 
 @pytest.mark.parametrize("fam", ["count", "offset"])

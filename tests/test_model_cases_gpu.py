@@ -155,8 +155,8 @@ def test_grouped_query_llm_golden_and_oracle(dev, golden_dir):
 
 def test_config5_family_geometry_vs_oracle(dev):
     """BASELINE config 5's encoder family at test size: a 128-mel Whisper (large-v3; the reference's 80-bin guard :1074 is lifted), a
-    patch-14 CLIP whose 224-pixel frames give 257 tokens per frame (the ViT-L/14 sequence length: general attention path, not the
-    197-token one-shot kernel), and a grouped-query LLM (Mistral layout).  Whole train step against the oracle, fp32 bars."""
+    patch-14 CLIP whose 224-pixel frames give 257 tokens per frame (the ViT-L/14 sequence length: the 17-block form of the
+    short attention kernel, not the 13-block one of 197 tokens), and a grouped-query LLM (Mistral layout).  Whole train step against the oracle, fp32 bars."""
     oc = Wt.tiny()
     oc.whisper = Wt.WhisperCfg(d_model=128, heads=2, layers=2, ffn=256, n_mels=128)
     oc.clip = Wt.ClipCfg(hidden=128, heads=2, layers=2, mlp=256, image=224, patch=14)

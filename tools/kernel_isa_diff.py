@@ -5,7 +5,9 @@
 
 OLD / NEW: a checkout root (the file is taken from audio-visual-llm_amd/csrc and cross-compiled exactly as tests/test_codegen_cpu.py does)
 or an assembly file (then exactly one source name is given, for the heading only).  Per kernel symbol: `same opcode sequence`, or the
-opcodes whose counts differ; then the metadata of both sides.  A plain opcode and metadata comparison: it knows no particular instruction."""
+opcodes whose counts differ; then the metadata of both sides.  A plain opcode and metadata comparison: it knows no particular instruction.
+--rename REGEX=REPL (repeatable): applied to the mangled kernel names of both sides before they are paired, for a change that adds or drops
+a template parameter, e.g. --rename 'fooILi(\\d+)ELNS_4ModeE\\dE.*=foo<\\1>' --rename 'fooILi(\\d+)E.*=foo<\\1>'."""
 import argparse
 import collections
 import os
@@ -50,15 +52,30 @@ def kernels(asm):
     return code, meta
 
 
+def renamed(code, meta, renames):
+    """code and meta keyed by the kernel name after the substitutions REGEX=REPL."""
+    key = {}
+    for n in code:
+        key[n] = n
+        for r in renames:
+            pat, repl = r.split("=", 1)
+            key[n] = re.sub(pat, repl, key[n])
+    assert len(set(key.values())) == len(key), "--rename maps two kernels of one side to the same name"
+    return {key[n]: code[n] for n in code}, {key[n]: meta[n] for n in code}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("sources", nargs="+")
+    ap.add_argument("--rename", action="append", help="REGEX=REPL on the kernel names of both sides before pairing")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as t0, tempfile.TemporaryDirectory() as t1:
         for name in a.sources:
             (c0, m0), (c1, m1) = kernels(asm_of(a.old, name, t0)), kernels(asm_of(a.new, name, t1))
+            if a.rename:
+                (c0, m0), (c1, m1) = renamed(c0, m0, a.rename), renamed(c1, m1, a.rename)
             print(f"== {name}")
             for k in sorted(set(c0) | set(c1)):
                 if k not in c0 or k not in c1:
