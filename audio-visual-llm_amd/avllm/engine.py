@@ -191,7 +191,7 @@ class LlamaEngine:
     """
 
     def __init__(self, sd, cfg, lora_cfg=None, lora_sd=None, dtype=torch.bfloat16, device="cuda", training=True, fp8=False, decode_fp8=False,
-                 decode_fp4=False):
+                 decode_fp4=False, kv_fp8=False):
         self.cfg, self.lcfg, self.dtype, self.device, self.training = cfg, lora_cfg, dtype, device, training
         self.fp8 = bool(fp8)
         # weight-only fp8 token step (include/avllm.h avllm_llama.decode_fp8): the fused decode path streams e4m3 codes + layout-2 exponents
@@ -202,6 +202,11 @@ class LlamaEngine:
         self.decode_fp4 = bool(decode_fp4)
         if self.decode_fp4 and (dtype != torch.bfloat16 or self.decode_fp8):
             raise ValueError("decode_fp4 needs the bf16 engine and excludes decode_fp8")
+        # fp8 KV cache of generate() (avllm_llama.kv_fp8): alloc_cache() hands out block-scaled e4m3 images for the row counts the fused token
+        # step takes (decode_caches_fp8); prefill() and decode_step() tell the library the form of the cache they are given
+        self.kv_fp8 = bool(kv_fp8)
+        if self.kv_fp8 and dtype != torch.bfloat16:
+            raise ValueError("kv_fp8 needs the bf16 engine")
         self.keep = []
         d, f = cfg.hidden, cfg.ffn
         self.use_lora = lora_cfg is not None
@@ -249,6 +254,7 @@ class LlamaEngine:
 
         m.decode_fp8 = int(self.decode_fp8)
         m.decode_fp4 = int(self.decode_fp4)
+        m.kv_fp8 = int(self.kv_fp8)
         if self.fp8 or self.decode_fp8 or self.decode_fp4:
             m.lm_head8, m.slm_head8, m.elm_head8 = images(head, self.decode_fp8 or self.decode_fp4)
         self.layers = (L.LlamaLayer * cfg.layers)()
@@ -465,9 +471,51 @@ class LlamaEngine:
         n = self.frozen_weight_bytes() // 2
         return n + n // 32
 
-    def alloc_cache(self, B, Tmax):
+    def decode_caches_fp8(self, B):
+        """True when a token step of B sequences runs on the fp8 cache image (kv_fp8 and the fused path: B <= 16, head dim 64 or 128)."""
+        return bool(L.load().avllm_llama_decode_caches_fp8(C.byref(self.desc), B))
+
+    def kv_cache_bytes(self, B, Tmax, fp8=None):
+        """Bytes of K plus V for B sequences of Tmax positions, in the form alloc_cache(B, Tmax, fp8=fp8) hands out."""
+        with self._cache_form(self.decode_caches_fp8(B) if fp8 is None else fp8):
+            return 2 * L.load().avllm_llama_kv_cache_bytes(C.byref(self.desc), B, Tmax)
+
+    def alloc_cache(self, B, Tmax, rows=None, fp8=None):
+        """(K, V) caches of B sequences and Tmax positions.  The form is decided here: fp8 images (ops.kv8_alloc: uint8 [layers, B, Tmax,
+        dkv + dkv/32]) when the engine has kv_fp8 and the token steps that will read the cache -- of `rows` sequences (default B; beam search
+        prefills B and steps B * num_beams) -- take the fused path, else [layers, B, Tmax, dkv] in the engine dtype.  fp8=False: the latter
+        whatever the engine's option (an eval forward keeps its bf16 cache)."""
+        if fp8 is None:
+            fp8 = self.decode_caches_fp8(B if rows is None else rows)
+        if fp8:
+            if not self.kv_fp8:
+                raise ValueError("alloc_cache(fp8=True) on an engine built without kv_fp8")
+            return tuple(ops.kv8_alloc(self.cfg.layers, B, Tmax, dkv=self.dkv, device=self.device) for _ in range(2))
         shape = (self.cfg.layers, B, Tmax, self.dkv)
         return torch.empty(shape, dtype=self.dtype, device=self.device), torch.empty(shape, dtype=self.dtype, device=self.device)
+
+    def _cache_form(self, fp8):
+        """Context manager: the descriptor's kv_fp8 says the form of the cache of the call inside, then is the engine's option again."""
+        eng = self
+
+        class _Ctx:
+            def __enter__(self_):
+                eng.desc.kv_fp8 = int(bool(fp8))
+
+            def __exit__(self_, *a):
+                eng.desc.kv_fp8 = int(eng.kv_fp8)
+        return _Ctx()
+
+    def _check_caches(self, kc, vc):
+        """The form of a cache pair: True for fp8 images (uint8, checked here: the library sees only pointers), False for the engine dtype."""
+        if kc.dtype != torch.uint8 and vc.dtype != torch.uint8:
+            return False
+        if not self.kv_fp8:
+            raise ValueError("an fp8 KV cache needs an engine built with kv_fp8")
+        if kc.shape != vc.shape or kc.dtype != vc.dtype or kc.dim() != 4 or kc.shape[3] != self.dkv + self.dkv // 32 or not (
+                kc.is_contiguous() and vc.is_contiguous()):
+            raise ValueError(f"fp8 KV caches must be a pair from alloc_cache(), got {tuple(kc.shape)} {kc.dtype} and {tuple(vc.shape)} {vc.dtype}")
+        return True
 
     def prefill(self, x, kc, vc, all_logits=False):
         lib = L.load()
@@ -477,8 +525,9 @@ class LlamaEngine:
         ws = self.ws_infer.get(lib.avllm_llama_infer_workspace_bytes(C.byref(self.desc), B, S))
         last = torch.empty(B, self.cfg.vocab, device=self.device, dtype=torch.float32)
         full = torch.empty(B, S, self.cfg.vocab, device=self.device, dtype=self.dtype) if all_logits else None
-        L.check(lib.avllm_llama_prefill(C.byref(self.desc), L.ptr(x), B, S, L.ptr(kc), L.ptr(vc), Tmax, L.ptr(last), L.ptr(full),
-                                        L.ptr(ws), ws.numel(), L.stream_ptr()))
+        with self._cache_form(self._check_caches(kc, vc)):
+            L.check(lib.avllm_llama_prefill(C.byref(self.desc), L.ptr(x), B, S, L.ptr(kc), L.ptr(vc), Tmax, L.ptr(last), L.ptr(full),
+                                            L.ptr(ws), ws.numel(), L.stream_ptr()))
         return last, full
 
     def decode_step(self, ids, pos, kc, vc, pos_dev=None, logits=None):
@@ -489,6 +538,7 @@ class LlamaEngine:
         ws = self.ws_infer.get(lib.avllm_llama_infer_workspace_bytes(C.byref(self.desc), B, 1))
         if logits is None:
             logits = torch.empty(B, self.cfg.vocab, device=self.device, dtype=torch.float32)
-        L.check(lib.avllm_llama_decode_step_at(C.byref(self.desc), L.ptr(ids.contiguous()), B, pos, L.ptr(pos_dev), L.ptr(kc), L.ptr(vc), kc.shape[2],
-                                               L.ptr(logits), L.ptr(ws), ws.numel(), L.stream_ptr()))
+        with self._cache_form(self._check_caches(kc, vc)):
+            L.check(lib.avllm_llama_decode_step_at(C.byref(self.desc), L.ptr(ids.contiguous()), B, pos, L.ptr(pos_dev), L.ptr(kc), L.ptr(vc),
+                                                   kc.shape[2], L.ptr(logits), L.ptr(ws), ws.numel(), L.stream_ptr()))
         return logits

@@ -173,7 +173,8 @@ def beam_search(engine, x, eos, pad, max_new_tokens, nb, length_penalty, early_s
     hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
     the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
     (_get_running_beams_for_next_iteration, _update_finished_beams, _check_early_stop_heuristic,
-    _beam_search_has_unfinished_sequences) restated on small device tensors, and ops.kv_gather_rows reordering only the generated
+    _beam_search_has_unfinished_sequences) restated on small device tensors, and ops.kv_gather_rows (ops.kv8_gather_rows when the engine
+    hands out fp8 cache images: LlamaEngine.alloc_cache) reordering only the generated
     positions [S, S + step): every beam of an item shares the prefix [0, S), which is copied once from the B-row prefill cache.
     Equal scores keep candidate order (stable sorts where HF calls torch.topk).  One host sync per step, for the stopping test.
     B*nb <= 16 rows take the fused bf16 token step (LlamaEngine.decode_is_fused); more rows take the general step.
@@ -187,10 +188,11 @@ def beam_search(engine, x, eos, pad, max_new_tokens, nb, length_penalty, early_s
     dev = x.device
     B, S, _ = x.shape
     R, k, N = B * nb, 2 * nb, max_new_tokens
-    kc0, vc0 = engine.alloc_cache(B, S)
+    kc0, vc0 = engine.alloc_cache(B, S, rows=R)                 # in the form of the R-row cache it is broadcast into
     logits, _ = engine.prefill(x, kc0, vc0)
     kc, vc = engine.alloc_cache(R, S + N)
-    ops.kv_gather_rows(kc0, vc0, kc, vc, torch.arange(R, device=dev, dtype=torch.int32) // nb, 0, S)    # prefix broadcast
+    gather_rows = ops.kv8_gather_rows if kc.dtype == torch.uint8 else ops.kv_gather_rows      # fp8 images: codes and exponents together
+    gather_rows(kc0, vc0, kc, vc, torch.arange(R, device=dev, dtype=torch.int32) // nb, 0, S)    # prefix broadcast
     del kc0, vc0
     logits = logits.repeat_interleave(nb, dim=0)                # step 0: every beam of an item sees the prefill logits
     NEG = -1.0e9
@@ -257,7 +259,7 @@ def beam_search(engine, x, eos, pad, max_new_tokens, nb, length_penalty, early_s
         done_host.copy_(done.view(1), non_blocking=True)
         ev.record()
         # the next token step is queued before the host waits on the stopping test (only the small copy above is awaited)
-        ops.kv_gather_rows(kc, vc, kc, vc, parent.view(-1).to(torch.int32), S, S + cur)
+        gather_rows(kc, vc, kc, vc, parent.view(-1).to(torch.int32), S, S + cur)
         logits = engine.decode_step(run["seq"][:, :, cur].reshape(-1), S + cur, kc, vc)
         ev.synchronize()
         if bool(done_host[0]):

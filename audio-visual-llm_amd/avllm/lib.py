@@ -66,7 +66,7 @@ class Llama(C.Structure):
                [(n, vp) for n in ("dropout_seed_dev", "embed", "norm_w", "lm_head", "lm_head_t")] + [("layer", C.POINTER(LlamaLayer))] + \
                [("fp8", i32), ("lm_head8", vp), ("slm_head8", vp)] + \
                [(n, f32) for n in ("rope_factor", "rope_low_freq_factor", "rope_high_freq_factor")] + [("rope_orig_ctx", i32)] + \
-               [("decode_fp8", i32), ("elm_head8", vp), ("decode_fp4", i32)]
+               [("decode_fp8", i32), ("elm_head8", vp), ("decode_fp4", i32), ("kv_fp8", i32)]
 
 
 class GemmF8Desc(C.Structure):
@@ -202,6 +202,12 @@ _SIGS = {
     "avllm_llama_decode_is_fused": ([C.POINTER(Llama), i32], i32),
     "avllm_llama_decode_streams_fp8": ([C.POINTER(Llama), i32], i32),
     "avllm_llama_decode_streams_fp4": ([C.POINTER(Llama), i32], i32),
+    "avllm_llama_decode_caches_fp8": ([C.POINTER(Llama), i32], i32),
+    "avllm_llama_kv_cache_bytes": ([C.POINTER(Llama), i32, i32], sz),
+    "avllm_kv8_append": ([vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "avllm_kv8_rope_append": ([vp, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp], i32),
+    "avllm_attention_decode_kv8": ([vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, f32, i32, vp], i32),
+    "avllm_kv8_gather_rows": ([vp, vp, i32, i64, vp, vp, i32, i64, i32, i32, vp, i32, i32, vp], i32),
     "avllm_pos_advance": ([vp, i32, vp], i32),
     "avllm_dec_proj": ([C.POINTER(DecProjDesc), vp], i32),
     "avllm_gemm_f8_takes_quantised_output": ([C.POINTER(GemmF8Desc)], i32),

@@ -62,7 +62,7 @@ class ClipWhisperModel:
                  max_seq_len=256, fusion_scale=0.5, connector_type="simple", _provided_tokenizer=None, _provided_llm=None,
                  _provided_whisper=None, _provided_clip=None, *, precision=None, config: ModelCfg | None = None,
                  weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16",
-                 train_connectors: bool = False):
+                 train_connectors: bool = False, kv_cache: str = "bf16"):
         if use_4bit:
             raise NotImplementedError("use_4bit (bitsandbytes nf4) is out of scope of the MI355X hot path (SURVEY.md §8)")
         if not freeze_encoders:
@@ -100,6 +100,15 @@ class ClipWhisperModel:
         if decode_weights != "bf16" and precision == "fp32":
             raise ValueError(f"decode_weights='{decode_weights}' needs precision bf16 or fp8 (the {decode_weights} token step is a bf16-activation path)")
         self.decode_weights = decode_weights
+        # kv_cache="fp8": generate() (greedy, sampled, beam) keeps K and V as e4m3 codes with one E8M0 exponent per 32 elements of a cache row
+        # (33/64 of the bf16 bytes) and its token steps attend over that form directly: K stored after RoPE, V as projected, a token's own row
+        # as stored.  Goes with the fused token step (at most 16 rows, B * num_beams in beam search); more rows get the bf16 cache.  The
+        # prefill's logits, so the first token, are those of "bf16"; forward() keeps its bf16 cache.  A runtime choice: not saved with the model.
+        if kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache must be bf16|fp8, got {kv_cache!r}")
+        if kv_cache == "fp8" and precision == "fp32":
+            raise ValueError("kv_cache='fp8' needs precision bf16 or fp8, not precision='fp32' (the fp8 cache goes with the bf16 fused token step)")
+        self.kv_cache = kv_cache
         self.train_connectors = bool(train_connectors)
         if self.train_connectors:
             if connector_type != "simple":
@@ -129,7 +138,8 @@ class ClipWhisperModel:
         self.whisper_engine = WhisperEngine(W["whisper"], cfg.whisper, self.dtype, device, fp8=self.fp8) if modality in ("audio", "both") else None
         self.clip_engine = ClipEngine(W["clip"], cfg.clip, self.dtype, device, fp8=self.fp8) if modality in ("video", "both") else None
         self.llm_engine = LlamaEngine(W["llama"], cfg.llama, cfg.lora if use_lora else None, W.get("lora"), self.dtype, device,
-                                      training=True, fp8=self.fp8, decode_fp8=decode_weights == "fp8", decode_fp4=decode_weights == "fp4")
+                                      training=True, fp8=self.fp8, decode_fp8=decode_weights == "fp8", decode_fp4=decode_weights == "fp4",
+                                      kv_fp8=kv_cache == "fp8")
         self._setup_projections(W)
         self.lora_param = None
         if use_lora:
@@ -435,7 +445,7 @@ class ClipWhisperModel:
             return {"loss": loss, "logits": logits}
         x = self._llm_inputs(audio, video, prompt)
         B, S, _ = x.shape
-        kc, vc = self.llm_engine.alloc_cache(B, S)
+        kc, vc = self.llm_engine.alloc_cache(B, S, fp8=False)
         _, logits = self.llm_engine.prefill(x, kc, vc, all_logits=True)
         if labels is None:
             return {"logits": logits}

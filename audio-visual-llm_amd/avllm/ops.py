@@ -885,6 +885,101 @@ def attention_decode(q, kc, vc, H, Tk, tk_dev=None, scale=None):
     return o
 
 
+# ---------------------------------------------------------------- fp8 KV cache (csrc/kv_fp8.hip)
+# A cache image is ONE uint8 tensor of shape [..., dkv + dkv/32] whose BYTES are two planes: the codes of all rows, [..., dkv], then the
+# exponents of all rows, [..., dkv/32].  The shape only carries the sizes (rows, Tmax, dkv); read an image through kv8_unpack.
+def kv8_alloc(*lead, dkv, device="cuda"):
+    """An uninitialised image of cache rows [*lead, dkv]."""
+    if dkv % 32:
+        raise ValueError(f"kv8: dkv = {dkv} must be a multiple of 32")
+    return torch.empty(*lead, dkv + dkv // 32, dtype=torch.uint8, device=device)
+
+
+def kv8_dkv(cache):
+    if cache.dtype != torch.uint8 or not cache.is_contiguous() or cache.shape[-1] % 33:
+        raise ValueError("kv8: a cache image is a contiguous uint8 tensor [..., dkv + dkv/32]")
+    return cache.shape[-1] // 33 * 32
+
+
+def kv8_unpack(cache):
+    """-> (codes uint8 [..., dkv], exponents uint8 [..., dkv/32]): views of the image's two planes."""
+    dkv = kv8_dkv(cache)
+    n = cache.numel() // 33 * 32
+    flat = cache.view(-1)
+    return flat[:n].view(*cache.shape[:-1], dkv), flat[n:].view(*cache.shape[:-1], dkv // 32)
+
+
+def kv8_pack(codes, exponents):
+    """The image of codes uint8 [..., dkv] and exponents uint8 [..., dkv/32] (a new tensor)."""
+    dkv = codes.shape[-1]
+    if codes.dtype != torch.uint8 or exponents.dtype != torch.uint8 or exponents.shape != codes.shape[:-1] + (dkv // 32,) or dkv % 32:
+        raise ValueError("kv8_pack: codes uint8 [..., dkv] and exponents uint8 [..., dkv/32]")
+    cache = kv8_alloc(*codes.shape[:-1], dkv=dkv, device=codes.device)
+    q, e = kv8_unpack(cache)
+    q.copy_(codes)
+    e.copy_(exponents)
+    return cache
+
+
+def _kv8_planes(cache):
+    q, e = kv8_unpack(cache)
+    return L.ptr(q), L.ptr(e)
+
+
+def kv8_append(k, v, kc, vc, T, pos0):
+    """kv_append onto the fp8 images kc, vc of cache rows [B, Tmax, dkv]: rows k, v [B*T, dkv] (bf16 views with one row stride) are stored by
+    the MX rule at positions [pos0, pos0 + T) (avllm_kv8_append)."""
+    B, Tmax, dkv = kc.shape[0], kc.shape[1], kv8_dkv(kc)
+    assert kc.dim() == 3 and vc.shape == kc.shape and k.shape == (B * T, dkv) and v.shape == k.shape and _ld(k) == _ld(v) and k.dtype == torch.bfloat16
+    L.check(L.load().avllm_kv8_append(L.ptr(k), L.ptr(v), _ld(k), *_kv8_planes(kc), *_kv8_planes(vc), B, T, pos0, Tmax, dkv, L.stream_ptr()))
+
+
+def kv8_rope_append_(qkv, heads, kv_heads, hd, rope, kc, vc, pos=0, pos_dev=None, rotate=True):
+    """The token step's append (avllm_kv8_rope_append) on the raw q|k|v rows qkv [B, ld] (bf16): q rotated in place, k rotated and quantised,
+    v quantised, the row written at pos (+ *pos_dev) of the images kc, vc of [B, Tmax, kv_heads hd].  rotate=False: q and k are rotated already."""
+    B, Tmax = kc.shape[0], kc.shape[1]
+    assert kc.dim() == 3 and vc.shape == kc.shape and kv8_dkv(kc) == kv_heads * hd and qkv.shape[0] == B and qkv.dtype == torch.bfloat16
+    assert rope is None or (rope.dtype == torch.float32 and rope.is_contiguous() and rope.numel() == hd)
+    L.check(L.load().avllm_kv8_rope_append(L.ptr(qkv), _ld(qkv), B, heads, kv_heads, hd, L.ptr(rope), int(rotate), *_kv8_planes(kc), *_kv8_planes(vc),
+                                           Tmax, pos, L.ptr(pos_dev), L.stream_ptr()))
+    return qkv
+
+
+def attention_decode_kv8(q, kc, vc, H, Tk, tk_dev=None, scale=None):
+    """attention_decode over the fp8 images kc, vc of [B, Tmax, Hkv*hd]; q [B, H*hd] bf16 -> [B, H*hd] (avllm_attention_decode_kv8)."""
+    B, d = q.shape
+    hd = d // H
+    Hkv = kv8_dkv(kc) // hd
+    assert kc.dim() == 3 and vc.shape == kc.shape and kc.shape[0] == B and q.dtype == torch.bfloat16
+    o = torch.empty_like(q)
+    L.check(L.load().avllm_attention_decode_kv8(L.ptr(q), _ld(q), *_kv8_planes(kc), *_kv8_planes(vc), L.ptr(o), _ld(o), B, H, hd, Tk, L.ptr(tk_dev),
+                                                kc.shape[1], float(scale if scale is not None else hd ** -0.5), H // Hkv, L.stream_ptr()))
+    return o
+
+
+def kv8_gather_rows(k_src, v_src, k_dst, v_dst, parent, t0, t1):
+    """kv_gather_rows on fp8 images of [layers, rows, T, dkv]: codes and exponents of positions [t0, t1) move together
+    (avllm_kv8_gather_rows)."""
+    for t in (k_src, v_src, k_dst, v_dst):
+        if not (t.is_cuda and t.dim() == 4):
+            raise ValueError("kv8_gather_rows: caches must be 4-d device images [layers, rows, T, dkv + dkv/32]")
+        kv8_dkv(t)
+    if k_src.shape != v_src.shape or k_dst.shape != v_dst.shape:
+        raise ValueError("kv8_gather_rows: K and V caches must have equal shapes")
+    (Ls, Rs, Ts, _), (Ld, Rd, Td, _) = k_src.shape, k_dst.shape
+    D = kv8_dkv(k_src)
+    if Ls != Ld or D != kv8_dkv(k_dst):
+        raise ValueError(f"kv8_gather_rows: src {tuple(k_src.shape)} and dst {tuple(k_dst.shape)} differ in layers or width")
+    if (k_src.data_ptr() == k_dst.data_ptr()) != (v_src.data_ptr() == v_dst.data_ptr()):
+        raise ValueError("kv8_gather_rows: K and V must both be in place or both out of place")
+    if not (parent.is_cuda and parent.dtype == torch.int32 and parent.is_contiguous() and parent.shape == (Rd,)):
+        raise ValueError(f"kv8_gather_rows: parent must be a contiguous int32 device tensor [{Rd}]")
+    if not 0 <= t0 <= t1 <= min(Ts, Td):
+        raise ValueError(f"kv8_gather_rows: positions [{t0}, {t1}) outside the caches (T = {Ts}, {Td})")
+    L.check(L.load().avllm_kv8_gather_rows(L.ptr(k_src), L.ptr(v_src), Rs, Ts, L.ptr(k_dst), L.ptr(v_dst), Rd, Td, Ls, D, L.ptr(parent), t0, t1,
+                                           L.stream_ptr()))
+
+
 def step_advance(state, base_lr, total_steps, warmup_steps=0, beta1=0.9, beta2=0.95, rank=0):
     """One-thread kernel: state.step += 1 and this step's lr / bias corrections / dropout seed (include/avllm.h avllm_step_state)."""
     sc = L.Schedule(base_lr, beta1, beta2, int(warmup_steps), int(total_steps), int(rank))

@@ -642,7 +642,17 @@ void carve_llama_infer(const avllm_llama* m, int B, int S, Bump& b, LlamaInferWs
     w.lt = (float*)b.take((size_t)16 * 4 * AVLLM_LORA_PAD * 4);      // fused token step with adapters: rank-side products [B <= 16, 4 modules x 64] f32
 }
 
-// one decoder block on M = B*S rows at positions [pos0, pos0+S); K/V appended to the cache
+// The code and exponent planes of layer l in an fp8 cache image (kv_fp8.hip): the codes of all layers [layers, B, Tmax, dkv] first, then the
+// exponents [layers, B, Tmax, dkv/32]
+struct Kv8Layer { char *kq, *ke, *vq, *ve; };
+inline Kv8Layer kv8_layer(const avllm_llama* m, void* kc, void* vc, int l, int B, int Tmax) {
+    const size_t dkv = (size_t)llama_dkv(m), rows = (size_t)B * Tmax, codes = (size_t)m->layers * rows * dkv;
+    const size_t oq = (size_t)l * rows * dkv, oe = codes + (size_t)l * rows * (dkv >> 5);
+    return {(char*)kc + oq, (char*)kc + oe, (char*)vc + oq, (char*)vc + oe};
+}
+
+// one decoder block on M = B*S rows at positions [pos0, pos0+S); K/V appended to the cache (kv_fp8: as codes + exponents; the pass's own
+// attention reads its bf16 q|k|v either way)
 int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S, int pos0, void* kc, void* vc, int Tmax, hipStream_t st) {
     const avllm_llama_layer& P = m->layer[l];
     const int dt = m->dtype, d = m->d, f = m->ffn, H = m->heads, hd = d / H, M = B * S;
@@ -664,9 +674,14 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
     if (P.q_norm_w) AV_TRY(av_qk_norm_rope(qkv, qw, M, S, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, nullptr, nullptr, 0, 0,
                                            nullptr, dt, st));
     else AV_TRY(av_rope_tab(qkv, qw, M, S, H + Hkv, hd, w.rope_tab, 0, dt, st));
+    if (m->kv_fp8) {
+        const Kv8Layer c = kv8_layer(m, kc, vc, l, B, Tmax);
+        AV_TRY(av_kv8_append(qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, qw, c.kq, c.ke, c.vq, c.ve, B, S, pos0, Tmax, dkv, st));
+    } else
     AV_TRY(av_kv_append(qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, qw, kcl, vcl, B, S, pos0, Tmax, dkv, dt, st));
     const float scale = 1.0f / sqrtf((float)hd);
     if (S == 1) {
+        AV_CHECK_ARG(!m->kv_fp8, "llama: the fp8 KV cache goes with the fused token step (avllm_llama_decode_caches_fp8), not the general path");
         AV_TRY(av_attention_decode(qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos0 + 1, Tmax, scale, dt, st, H / Hkv));
     } else {
         AV_CHECK_ARG(pos0 == 0, "llama prefill must start at position 0");
@@ -696,6 +711,7 @@ extern "C" int avllm_llama_prefill(const avllm_llama* m, const void* x, int32_t 
     hipStream_t st = (hipStream_t)stream;
     AV_TRY(check_llama(m));
     AV_CHECK_ARG(x && kcache && vcache && ws && B > 0 && S > 0 && S <= Tmax, "llama_prefill: bad args (S=%d Tmax=%d)", S, Tmax);
+    AV_CHECK_ARG(!m->kv_fp8 || (m->dtype == AV_BF16 && (m->d / m->heads) % 64 == 0), "llama_prefill: kv_fp8 needs bf16 and a head dim of 64 or 128");
     Bump b(ws, ws_bytes);
     LlamaInferWs w;
     carve_llama_infer(m, B, S, b, w, true);
@@ -777,11 +793,21 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
     }
     // head norms: a head's columns belong to hd / 16 workgroups of the projection, so q|k|v leave it raw and one launch normalises, rotates
     // and writes the cache row (6 launches per layer, 8 with adapters)
-    p.raw_qkv = P.q_norm_w != nullptr;
+    // fp8 cache: an MX block is 32 columns of a row, two workgroups of the projection, so q|k|v leave it raw here too and one launch rotates,
+    // quantises and writes the row (one launch more per layer; with head norms their launch rotates in place and the append follows: two more)
+    p.raw_qkv = P.q_norm_w != nullptr || m->kv_fp8;
     AV_TRY(av_dec_proj(&p, st));
-    if (P.q_norm_w) AV_TRY(av_qk_norm_rope(w.qkv, qw, B, 1, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, kcl, vcl, Tmax, pos,
-                                           pos_dev, AV_BF16, st));
-    AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
+    if (m->kv_fp8) {
+        const Kv8Layer c = kv8_layer(m, kc, vc, l, B, Tmax);
+        if (P.q_norm_w) AV_TRY(av_qk_norm_rope(w.qkv, qw, B, 1, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                                               nullptr, AV_BF16, st));
+        AV_TRY(av_kv8_rope_append(w.qkv, qw, B, H, Hkv, hd, w.rope_tab, P.q_norm_w == nullptr, c.kq, c.ke, c.vq, c.ve, Tmax, pos, pos_dev, st));
+        AV_TRY(av_attention_decode_kv8(w.qkv, qw, c.kq, c.ke, c.vq, c.ve, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), H / Hkv, st));
+    } else {
+        if (P.q_norm_w) AV_TRY(av_qk_norm_rope(w.qkv, qw, B, 1, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, kcl, vcl, Tmax, pos,
+                                               pos_dev, AV_BF16, st));
+        AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
+    }
     p = {};
     if (lora) {      // lora_A(attention output) -> lt[:, 192:192+16]: only the rank's own 16 rows of the padded image are streamed
         p.A = w.att; p.lda = d; p.W = P.lora[3].A_pad; p.ldw = d; p.M = B; p.K = d; p.N = 16; p.mode = 0; p.C = w.lt + 3 * AVLLM_LORA_PAD; p.ldc = LT; p.out_f32 = 1;
@@ -813,6 +839,8 @@ extern "C" int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* i
     if (!b.ok) return av_set_error(AV_ERR_WORKSPACE, "llama_decode_step: workspace %zu < %zu bytes", ws_bytes, bump_size(b));
     const int dt = m->dtype, d = m->d;
     AV_TRY(av_embedding(m->embed, ids, w.x, B, d, dt, st));
+    AV_CHECK_ARG(!m->kv_fp8 || llama_decode_fused_ok(m, B),
+                 "llama_decode_step: kv_fp8 needs the fused token step (bf16, B <= 16 (B=%d), head dim 64 or 128): see avllm_llama_decode_caches_fp8", B);
     if (llama_decode_fused_ok(m, B)) {
         AV_TRY(av_rope_table(w.rope_tab, 1, d / m->heads, pos, m->theta, st, pos_dev, llama_rope_scale(m)));
         for (int l = 0; l < m->layers; ++l) AV_TRY(llama_decode_layer_fused(m, l, w, B, pos, pos_dev, kcache, vcache, Tmax, st));
@@ -841,6 +869,16 @@ extern "C" int avllm_llama_decode_streams_fp8(const avllm_llama* m, int32_t B) {
 }
 extern "C" int avllm_llama_decode_streams_fp4(const avllm_llama* m, int32_t B) {
     return m && check_llama(m) == AV_OK && m->decode_fp4 && llama_decode_fused_ok(m, B) ? 1 : 0;
+}
+
+// the fp8 cache goes with the fused step, as the weight forms do
+extern "C" int avllm_llama_decode_caches_fp8(const avllm_llama* m, int32_t B) {
+    return m && check_llama(m) == AV_OK && m->kv_fp8 && llama_decode_fused_ok(m, B) ? 1 : 0;
+}
+extern "C" size_t avllm_llama_kv_cache_bytes(const avllm_llama* m, int32_t B, int32_t Tmax) {
+    if (!m || check_llama(m) != AV_OK || B <= 0 || Tmax <= 0) return 0;
+    const size_t n = (size_t)m->layers * B * Tmax * llama_dkv(m);
+    return m->kv_fp8 ? n + n / 32 : n * av_dtype_size(m->dtype);
 }
 
 extern "C" int avllm_llama_decode_step(const avllm_llama* m, const int64_t* ids, int32_t B, int32_t pos, void* kcache,

@@ -602,6 +602,13 @@ typedef struct avllm_llama {
      * MXFP4 codes (wqkv4 .. wdown4, eqkv4 .. edown4); lm_head -- 2 % of the bytes, and the matrix whose rounding moves the argmax most --
      * streams as e4m3 (lm_head8, elm_head8).  Same shape conditions as decode_fp8; not together with it. */
     int32_t decode_fp4;
+    /* 1: the KV cache handed to avllm_llama_prefill / avllm_llama_decode_step(_at) is the block-scaled e4m3 image (csrc/kv_fp8.hip): for K and
+     * for V the codes uint8 [layers, B, Tmax, dkv] followed by the E8M0 exponents uint8 [layers, B, Tmax, dkv/32], one per 32 consecutive
+     * elements of a row, by avllm_mx_quantize's rule (avllm_llama_kv_cache_bytes each, 33/64 of the bf16 bytes; base 16-byte aligned).  K is
+     * stored after RoPE (and the head norm), V as projected; a token attends to its own row as stored.  The prefill's own attention is
+     * unchanged (only its append quantises); the token step must be the fused one (avllm_llama_decode_caches_fp8), else AV_ERR_ARG.  Needs
+     * bf16 and a head dim of 64 or 128.  0: the cache is [layers][B][Tmax][dkv] in the model dtype, as ever. */
+    int32_t kv_fp8;
 } avllm_llama;
 
 size_t avllm_llama_train_workspace_bytes(const avllm_llama* m, int32_t B, int32_t S);
@@ -657,6 +664,35 @@ int avllm_llama_decode_is_fused(const avllm_llama* m, int32_t B);
 int avllm_llama_decode_streams_fp8(const avllm_llama* m, int32_t B);
 /* The same for the fp4 weight images (decode_fp4).  A decode_fp4 model answers 0 to the fp8 query. */
 int avllm_llama_decode_streams_fp4(const avllm_llama* m, int32_t B);
+/* 1 when a token step of B sequences reads and writes the fp8 cache image (kv_fp8 set and the fused path taken), 0 otherwise: the caller
+ * decides the cache's form with it when it allocates (more rows, or the fused path switched off: kv_fp8 = 0 and the bf16 cache). */
+int avllm_llama_decode_caches_fp8(const avllm_llama* m, int32_t B);
+/* Bytes of ONE of the two caches (K or V) of B sequences and Tmax positions in the model's form: layers * B * Tmax * dkv elements of the model
+ * dtype, or with kv_fp8 that many code bytes plus one exponent byte per 32. */
+size_t avllm_llama_kv_cache_bytes(const avllm_llama* m, int32_t B, int32_t Tmax);
+
+/* The kernels of the fp8 KV cache (csrc/kv_fp8.hip).  An image of cache rows [..., dkv] is two planes, codes uint8 [..., dkv] (e4m3fn) and
+ * exponents uint8 [..., dkv/32] (E8M0, biased by 127), bit-identical to avllm_mx_quantize(layout 2) of the bf16 rows; k_codes / k_exps / v_codes /
+ * v_exps below are the planes of ONE layer, [B, Tmax, dkv] and [B, Tmax, dkv/32].  bf16 only; code planes 16-byte aligned.
+ * avllm_kv8_append: avllm_kv_append's fp8 twin (the prefill's append): rows k, v [B * T, dkv] of stride ld -> positions [pos0, pos0 + T).
+ * pos0 + T <= Tmax, dkv % 32 == 0, ld % 8 == 0, else AV_ERR_ARG. */
+int avllm_kv8_append(const void* k, const void* v, int64_t ld, void* k_codes, void* k_exps, void* v_codes, void* v_exps, int32_t B, int32_t T,
+                     int32_t pos0, int32_t Tmax, int32_t dkv, void* stream);
+/* The token step's append, after a raw_qkv projection: qkv [B, ld] = q [heads hd] | k [kv_heads hd] | v.  rotate = 1: q is rotated in place
+ * (fp32 arithmetic on rope [hd/2][2] = cos, sin; one rounding to bf16), k is rotated in fp32 and quantised from there, v is quantised; rotate = 0
+ * (a head-norm launch has rotated q and k in place already): k and v are quantised as they are, q is not touched.  The row goes to position
+ * pos + *pos_dev (pos_dev may be NULL); a device-side position outside [0, Tmax) writes nothing.  hd 64 or 128. */
+int avllm_kv8_rope_append(void* qkv, int64_t ld, int32_t B, int32_t heads, int32_t kv_heads, int32_t hd, const float* rope, int32_t rotate,
+                          void* k_codes, void* k_exps, void* v_codes, void* v_exps, int32_t Tmax, int32_t pos, const int32_t* pos_dev, void* stream);
+/* avllm_attention_decode (bf16) over the image: Tk + *tk_dev rows (clamped to Tmax), dequantised exactly in registers (code x 2^e); scores,
+ * online softmax and the weighted sum in fp32.  Nothing but the cache is read for K and V. */
+int avllm_attention_decode_kv8(const void* q, int64_t ldq, const void* k_codes, const void* k_exps, const void* v_codes, const void* v_exps, void* o,
+                               int64_t ldo, int32_t B, int32_t H, int32_t hd, int32_t Tk, const int32_t* tk_dev, int32_t Tmax, float scale,
+                               int32_t kv_group, void* stream);
+/* avllm_kv_gather_rows on whole fp8 images (all layers: k_src .. v_dst are the bases of [layers, rows, T, dkv] images): codes and exponents of
+ * positions [t0, t1) move together, two launches of the same kernel on rows of dkv and of dkv/32 bytes.  dkv % 64 == 0. */
+int avllm_kv8_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
+                          int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, void* stream);
 int avllm_pos_advance(int32_t* pos_dev, int32_t by, void* stream);
 
 /* One projection of a decode token step (bf16, 1 <= M <= 16 rows, K % 128 == 0): C = epilogue(rmsnorm?(A) . W^T).  Every weight row

@@ -76,6 +76,9 @@ def parse_args(argv=None):
     p.add_argument("--decode_weights", type=str, choices=["bf16", "fp8", "fp4"], default="bf16",
                    help="fp8: the token steps stream the LLM's frozen projections as block-scaled e4m3 (needs bf16; prefill stays bf16); "
                         "fp4: as OCP MXFP4 with lm_head as e4m3 (coarser: about 11.5 %% weight error, effect on WER not measured)")
+    p.add_argument("--kv_cache", type=str, choices=["bf16", "fp8"], default="bf16",
+                   help="fp8: the KV cache is block-scaled e4m3 (33/64 of the bf16 bytes; needs bf16, token steps of at most 16 rows, else "
+                        "the bf16 cache is used; effect on WER not measured)")
     p.add_argument("--load_lora", action="store_true")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
@@ -171,7 +174,7 @@ def main(argv=None):
         kw["config"] = ModelCfg(WhisperCfg(128, 2, 2, 256), ClipCfg(128, 2, 2, 256, 48, 16), LlamaCfg(256, 2, 2, 512, 512), LoraCfg(16, 32.0))
     model = ClipWhisperModel(llm_path=cfg["llm_path"], whisper_model=cfg["whisper_model"], clip_model=cfg["clip_model"], device=dev,
                              use_fp16=bool(cfg.get("use_fp16")), use_lora=a.load_lora, modality=a.modality, max_seq_len=256,
-                             synthetic_weights=a.synthetic_weights or a.tiny, decode_weights=a.decode_weights, **kw).eval()
+                             synthetic_weights=a.synthetic_weights or a.tiny, decode_weights=a.decode_weights, kv_cache=a.kv_cache, **kw).eval()
     if a.model_path:
         ck = torch.load(a.model_path, map_location="cpu", weights_only=True)
         sd = ck.get("model_state_dict", ck)
