@@ -13,6 +13,7 @@
 #include "common.h"
 #include "avllm_internal.h"
 #include "attention_tile.h"
+#include "mx.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mfma(const bf16* __restri
 //                                  V^T fragments come from the row-major V image through ds_read_b64_tr_b16 in that same order.
 // 197 tokens (ViT-B/16) are 13 blocks of 16 in both directions (208 padded rows instead of the 224 of a 32-row tiling); 7 waves x 2
 // query blocks.  Output leaves through a 16x32 bf16 scratch per wave as 16-byte row chunks.  HF:models/clip/modeling_clip.py:297-335.
-// QOUT: the output leaves block-scaled to e4m3 (OCP MX: one E8M0 per 32 consecutive features, fp8.hip mx_quant_kernel's rule applied to the
+// QOUT: the output leaves block-scaled to e4m3 (OCP MX: one E8M0 per 32 consecutive features, the rule of mx.h applied to the
 // bf16-rounded values, i.e. bit-identical to quantising the bf16 output in a separate pass) as codes oq [rows, ldoq] + the layout-0 scale
 // image osc of an avllm_gemm_f8 A operand: the fp8 out-projection reads it directly and the [M, d] bf16 attention output never exists
 // (1.6 GB written + read back per ViT-L/14 layer at 750 frames x 4 clips).  A 32-feature block of a row = the 4 lanes of one row in the
@@ -364,23 +365,16 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_short(const bf16* __restrict
                 for (int c = 0; c < 8; ++c) { f[c] = (float)vb[c]; amax = fmaxf(amax, fabsf(f[c])); }
                 amax = fmaxf(amax, __shfl_xor(amax, 1));
                 amax = fmaxf(amax, __shfl_xor(amax, 2));
-                int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;              // floor(log2 amax) - 8 (fp8.hip mx_quant_kernel, oracle/mxfp8.py)
-                e = e < -127 ? -127 : (e > 127 ? 127 : e);
-                const float invs = __uint_as_float((uint32_t)(127 - e) << 23);
-#pragma unroll
-                for (int c = 0; c < 8; ++c) f[c] = fminf(fmaxf(f[c] * invs, -448.f), 448.f);
-                int r0 = 0, r1 = 0;
-                r0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], r0, false);
-                r0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], r0, true);
-                r1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], r1, false);
-                r1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], r1, true);
+                const int e = mx_block_exp<MX_EMAX_E4M3>(amax);
+                uint32_t pk[2];
+                mx_pack_e4m3<8>(f, mx_inv_scale(e), pk);
                 if (q0 + row < T) {
                     const long m = (long)b * T + q0 + row;
                     typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-                    *(u32x2*)(oq + m * ldoq + (long)hh * HD + hf * 32 + ch * 8) = (u32x2){(uint32_t)r0, (uint32_t)r1};
+                    *(u32x2*)(oq + m * ldoq + (long)hh * HD + hf * 32 + ch * 8) = (u32x2){pk[0], pk[1]};
                     if (ch == 0) {
                         const int cb = hh * (HD / 32) + hf;
-                        osc[((((long)(cb >> 2) * RBo + (m >> 6)) * 4 + (cb & 3)) * 16 + (m & 15)) * 4 + ((m >> 4) & 3)] = (uint8_t)(e + 127);
+                        osc[((((long)(cb >> 2) * RBo + (m >> 6)) * 4 + (cb & 3)) * 16 + (m & 15)) * 4 + ((m >> 4) & 3)] = (uint8_t)mx_exp_byte(e);
                     }
                 }
             } else {

@@ -88,7 +88,7 @@ int av_attention_decode(const void* q, long ldq, const void* kc, const void* vc,
                         int Tk, int Tmax, float scale, int dtype, hipStream_t st, int G = 1);
 int av_attention_decode1(const void* q, long ldq, const void* kc, const void* vc, void* o, long ldo, int B, int H, int hd, int Tk, const int* tk_dev,
                          int Tmax, float scale, int dtype, hipStream_t st, int G);
-// fp8 KV cache (kv_fp8.hip): kq / ke / vq / ve are the code and exponent planes of one layer's K and V images [B, Tmax, dkv] / [B, Tmax, dkv/32]
+// fp8 KV cache (kv_fp8.hip; its attention: attention_decode.hip): kq / ke / vq / ve are the code and exponent planes of one layer's K and V images [B, Tmax, dkv] / [B, Tmax, dkv/32]
 int av_kv8_append(const void* k, const void* v, long ld, void* kq, void* ke, void* vq, void* ve, int B, int T, int pos0, int Tmax, int dkv, hipStream_t st);
 int av_kv8_rope_append(void* qkv, long ld, int B, int H, int Hkv, int hd, const float* rope, int rotate, void* kq, void* ke, void* vq, void* ve, int Tmax,
                        int pos, const int* pos_dev, hipStream_t st);

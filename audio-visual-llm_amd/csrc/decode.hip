@@ -1,7 +1,8 @@
 // Greedy-decode token step (clip_whisper_model.py:1337-1340 -> GenerationMixin greedy search, one new token per sequence on a KV cache):
 // every frozen weight is streamed from HBM exactly once per step whatever the batch, so the step is a chain of
 // HBM-bound weight streams and its floor is weight bytes / HBM rate.  Round 1 ran 10 launches per decoder layer (norm, q|k|v, RoPE,
-// cache append, attention, o, norm, gate|up, SwiGLU, down), five of them on the ~5 us launch floor; here a layer is 5 launches:
+// cache append, attention, o, norm, gate|up, SwiGLU, down), five of them on the ~5 us launch floor; here a layer is 5 launches, and this
+// file is dec_proj, four of the five (the attention is attention_decode.hip):
 //
 //   dec_proj<NORM, qkv>      RMSNorm folded into the A operand, q|k|v projection, RoPE on q/k in the accumulators, k/v written
 //                            straight into the cache row of this position
@@ -26,6 +27,7 @@
 // DecForm below and nowhere else.  So the result is the bf16 form's on the dequantised weights up to fp32 summation order inside a group.
 #include "common.h"
 #include "avllm_internal.h"
+#include "mx.h"
 #include <type_traits>
 
 namespace {
@@ -253,7 +255,7 @@ __device__ __forceinline__ void dec_k_loop(const DecArgs& a, int fr, int fq, int
             }
         }
         float sc = 0.f;                                  // 2^(e - 127) of the lane's block
-        if constexpr (Fm::EXP) sc = __uint_as_float(((g.ex >> Fm::ebit(j, fq)) & 0xffu) << 23);
+        if constexpr (Fm::EXP) sc = mx_e8m0((g.ex >> Fm::ebit(j, fq)) & 0xffu);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Fm::template operand<j>(g.wb, sc), x, acc, 0, 0, 0);      // D[n][m]
     };
     auto consume = [&](Grp& g, auto behind) { static_for<0, 4>([&](auto jc) { step(g, jc, behind); }); };
@@ -405,96 +407,6 @@ __global__ __launch_bounds__(DW * 64, 2) void dec_bias_f8_kernel(DecArgs a) { de
 template <bool NORM, int AL, bool LORA>
 __global__ __launch_bounds__(DW * 64, 2) void dec_bias_f4_kernel(DecArgs a) { dec_proj_body<WForm::fp4, NORM, AL, LORA, true>(a); }
 
-// ------------------------------------------------------------------------------------------------------------------------------
-// Single-token attention over the cache, ONE pass: a group of G = hd/8 lanes owns cache rows t = g, g + R, ... and carries a running
-// (max, sum, weighted V) triple; K and V rows of a trip are all requested before the first is used.  Groups are merged through
-// shuffles (same wave) and LDS (NW waves).  No score buffer: Tk is unbounded and may come from device memory.
-template <typename T, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_decode1_kernel(const T* __restrict__ q, long ldq, const T* __restrict__ kc, const T* __restrict__ vc,
-                                                               T* __restrict__ o, long ldo, int H, int hd, int Tk, const int* __restrict__ tk_dev,
-                                                               int Tmax, float scale, int GQ) {
-    __shared__ float pacc[NW][128];
-    __shared__ float pm[NW], pl[NW];
-    const int h = blockIdx.x, b = blockIdx.y, d = (H / GQ) * hd;
-    if (tk_dev) Tk += *tk_dev;
-    Tk = Tk > Tmax ? Tmax : Tk;                      // a device-side length the host could not check never reads past the cache
-    const int G = hd >> 3, R = NW * 64 / G;
-    const int tid = threadIdx.x, dc = tid % G, rsub = tid / G;
-    float qv[8];
-    load_f<8>(q + (long)b * ldq + (long)h * hd + dc * 8, qv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) qv[j] *= scale;
-    const T* kbase = kc + ((long)b * Tmax) * d + (long)(h / GQ) * hd + dc * 8;
-    const T* vbase = vc + ((long)b * Tmax) * d + (long)(h / GQ) * hd + dc * 8;
-    constexpr int UN = 4;
-    float mx = -INFINITY, l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int t0 = 0; t0 < Tk; t0 += UN * R) {
-        float kv[UN][8], vv[UN][8];
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int t = t0 + u * R + rsub;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { kv[u][j] = 0.f; vv[u][j] = 0.f; }
-            if (t < Tk) { load_f<8>(kbase + (long)t * d, kv[u]); load_f<8>(vbase + (long)t * d, vv[u]); }
-        }
-        float s[UN], tm = mx;
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int t = t0 + u * R + rsub;
-            float x = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x += qv[j] * kv[u][j];
-            for (int off = G >> 1; off > 0; off >>= 1) x += __shfl_xor(x, off);
-            s[u] = t < Tk ? x : -INFINITY;
-            tm = fmaxf(tm, s[u]);
-        }
-        if (tm > -INFINITY) {
-            const float f = __expf(mx - tm);             // mx = -inf on the first trip: exp(-inf) = 0, acc and l are 0 anyway
-            l *= f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] *= f;
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const float p = __expf(s[u] - tm);       // -inf rows: 0
-                l += p;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc[j] += p * vv[u][j];
-            }
-            mx = tm;
-        }
-    }
-    // merge the row groups of a wave (lanes with equal dc)
-    for (int off = G; off < 64; off <<= 1) {
-        const float m2 = __shfl_xor(mx, off), l2 = __shfl_xor(l, off);
-        const float mn = fmaxf(mx, m2);
-        const float f1 = mx > -INFINITY ? __expf(mx - mn) : 0.f, f2 = m2 > -INFINITY ? __expf(m2 - mn) : 0.f;
-        l = l * f1 + l2 * f2;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = acc[j] * f1 + __shfl_xor(acc[j], off) * f2;
-        mx = mn;
-    }
-    const int w = tid >> 6, lane = tid & 63;
-    if (lane < G) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) pacc[w][lane * 8 + j] = acc[j];
-        if (lane == 0) { pm[w] = mx; pl[w] = l; }
-    }
-    __syncthreads();
-    if (tid < hd) {
-        float mn = -INFINITY;
-#pragma unroll
-        for (int x = 0; x < NW; ++x) mn = fmaxf(mn, pm[x]);
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int x = 0; x < NW; ++x) {
-            const float f = pm[x] > -INFINITY ? __expf(pm[x] - mn) : 0.f;
-            num += pacc[x][tid] * f;
-            den += pl[x] * f;
-        }
-        o[(long)b * ldo + (long)h * hd + tid] = from_f<T>(num / den);
-    }
-}
-
 }  // namespace
 
 bool av_dec_proj_supported(int dtype, int M, int K, int N, int mode, int hd) {
@@ -507,21 +419,10 @@ bool av_dec_proj_supported(int dtype, int M, int K, int N, int mode, int hd) {
 
 static int dec_launch(DecArgs& a, hipStream_t st) {
     // [form][norm][al: 1, 2, 4][adapters]
-    static const decltype(&dec_proj_kernel<false, 1, false>) kernel[3][2][3][2] = {
-        {{{dec_proj_kernel<false, 1, false>, dec_proj_kernel<false, 1, true>}, {dec_proj_kernel<false, 2, false>, dec_proj_kernel<false, 2, true>},
-          {dec_proj_kernel<false, 4, false>, dec_proj_kernel<false, 4, true>}},
-         {{dec_proj_kernel<true, 1, false>, dec_proj_kernel<true, 1, true>}, {dec_proj_kernel<true, 2, false>, dec_proj_kernel<true, 2, true>},
-          {dec_proj_kernel<true, 4, false>, dec_proj_kernel<true, 4, true>}}},
-        {{{dec_proj_f8_kernel<false, 1, false>, dec_proj_f8_kernel<false, 1, true>}, {dec_proj_f8_kernel<false, 2, false>, dec_proj_f8_kernel<false, 2, true>},
-          {dec_proj_f8_kernel<false, 4, false>, dec_proj_f8_kernel<false, 4, true>}},
-         {{dec_proj_f8_kernel<true, 1, false>, dec_proj_f8_kernel<true, 1, true>}, {dec_proj_f8_kernel<true, 2, false>, dec_proj_f8_kernel<true, 2, true>},
-          {dec_proj_f8_kernel<true, 4, false>, dec_proj_f8_kernel<true, 4, true>}}},
-        {{{dec_proj_f4_kernel<false, 1, false>, dec_proj_f4_kernel<false, 1, true>}, {dec_proj_f4_kernel<false, 2, false>, dec_proj_f4_kernel<false, 2, true>},
-          {dec_proj_f4_kernel<false, 4, false>, dec_proj_f4_kernel<false, 4, true>}},
-         {{dec_proj_f4_kernel<true, 1, false>, dec_proj_f4_kernel<true, 1, true>}, {dec_proj_f4_kernel<true, 2, false>, dec_proj_f4_kernel<true, 2, true>},
-          {dec_proj_f4_kernel<true, 4, false>, dec_proj_f4_kernel<true, 4, true>}}}};
 #define DEC_FORM_TABLE(K) {{{K<false, 1, false>, K<false, 1, true>}, {K<false, 2, false>, K<false, 2, true>}, {K<false, 4, false>, K<false, 4, true>}}, \
                            {{K<true, 1, false>, K<true, 1, true>}, {K<true, 2, false>, K<true, 2, true>}, {K<true, 4, false>, K<true, 4, true>}}}
+    static const decltype(&dec_proj_kernel<false, 1, false>) kernel[3][2][3][2] = {DEC_FORM_TABLE(dec_proj_kernel), DEC_FORM_TABLE(dec_proj_f8_kernel),
+                                                                                   DEC_FORM_TABLE(dec_proj_f4_kernel)};
     static const decltype(&dec_proj_kernel<false, 1, false>) kernel_bias[3][2][3][2] = {DEC_FORM_TABLE(dec_bias_kernel), DEC_FORM_TABLE(dec_bias_f8_kernel),
                                                                                         DEC_FORM_TABLE(dec_bias_f4_kernel)};
 #undef DEC_FORM_TABLE
@@ -591,23 +492,6 @@ int av_dec_proj(const avllm_dec_proj_desc* d, hipStream_t st) {
 
 extern "C" int avllm_dec_proj(const avllm_dec_proj_desc* d, void* stream) { return av_dec_proj(d, (hipStream_t)stream); }
 
-int av_attention_decode1(const void* q, long ldq, const void* kc, const void* vc, void* o, long ldo, int B, int H, int hd, int Tk, const int* tk_dev,
-                         int Tmax, float scale, int dtype, hipStream_t st, int G) {
-    AV_CHECK_ARG(q && kc && vc && o && (tk_dev || (Tk > 0 && Tk <= Tmax)) && G > 0 && H % G == 0, "attention_decode: bad args");
-    AV_CHECK_ARG((hd == 64 || hd == 128) && ldq % 8 == 0, "attention_decode: head_dim %d unsupported", hd);
-    const dim3 grid(H, B);
-    // few (sequence, head) pairs: 16 waves each so that a CU still has ~64 KiB of cache rows in flight
-    if ((long)B * H <= 1024) {
-        if (dtype == AV_F32) hipLaunchKernelGGL((attn_decode1_kernel<float, 16>), grid, dim3(1024), 0, st, (const float*)q, ldq, (const float*)kc, (const float*)vc, (float*)o, ldo, H, hd, Tk, tk_dev, Tmax, scale, G);
-        else hipLaunchKernelGGL((attn_decode1_kernel<bf16, 16>), grid, dim3(1024), 0, st, (const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, (bf16*)o, ldo, H, hd, Tk, tk_dev, Tmax, scale, G);
-    } else {
-        if (dtype == AV_F32) hipLaunchKernelGGL((attn_decode1_kernel<float, 4>), grid, dim3(256), 0, st, (const float*)q, ldq, (const float*)kc, (const float*)vc, (float*)o, ldo, H, hd, Tk, tk_dev, Tmax, scale, G);
-        else hipLaunchKernelGGL((attn_decode1_kernel<bf16, 4>), grid, dim3(256), 0, st, (const bf16*)q, ldq, (const bf16*)kc, (const bf16*)vc, (bf16*)o, ldo, H, hd, Tk, tk_dev, Tmax, scale, G);
-    }
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
 __global__ void pos_advance_kernel(int* p, int by) { if (threadIdx.x == 0 && blockIdx.x == 0) *p += by; }
 
 extern "C" int avllm_pos_advance(int32_t* pos_dev, int32_t by, void* stream) {
@@ -615,10 +499,4 @@ extern "C" int avllm_pos_advance(int32_t* pos_dev, int32_t by, void* stream) {
     hipLaunchKernelGGL(pos_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, pos_dev, by);
     AV_LAUNCH_CHECK();
     return AV_OK;
-}
-
-extern "C" int avllm_attention_decode(const void* q, int64_t ldq, const void* kc, const void* vc, void* o, int64_t ldo, int32_t B, int32_t H, int32_t hd,
-                                      int32_t Tk, const int32_t* tk_dev, int32_t Tmax, float scale, int32_t kv_group, int32_t dtype, void* stream) {
-    AV_CHECK_ARG(B > 0 && H > 0 && (dtype == AV_F32 || dtype == AV_BF16), "attention_decode: B=%d H=%d dtype=%d", B, H, dtype);
-    return av_attention_decode1(q, ldq, kc, vc, o, ldo, B, H, hd, Tk, tk_dev, Tmax, scale, dtype, (hipStream_t)stream, kv_group);
 }

@@ -9,6 +9,7 @@
 // Rule (OCP MX v1.0 §6.3 with emax = 2 of e2m1): e = floor(log2(amax)) - 2 clamped to [-127, 127]; elements = RNE(x * 2^-e) saturated to +-6.
 #include "common.h"
 #include "avllm_internal.h"
+#include "mx.h"
 
 namespace {
 
@@ -28,20 +29,12 @@ __global__ __launch_bounds__(256) void mx4_quant_kernel(const T* __restrict__ x,
         const int kb = (int)(idx % nkb);
         const long row = idx / nkb;
         float v[32];
-        const T* xp = x + row * ldx + kb * 32;
-#pragma unroll
-        for (int c = 0; c < 32; c += 8) {
-            float t8[8];
-            load_f<8>(xp + c, t8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[c + j] = t8[j];
-        }
+        mx_load32(x + row * ldx + kb * 32, v);
         float amax = 0.f;
 #pragma unroll
         for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j]));
-        int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 2;                // amax == 0 or subnormal -> smallest scale
-        e = e < -127 ? -127 : (e > 127 ? 127 : e);
-        const float invs = __uint_as_float((uint32_t)(127 - e) << 23);               // 2^-e: e <= 126 for any amax, so the exponent field stays >= 1
+        const int e = mx_block_exp<MX_EMAX_E2M1>(amax);
+        const float invs = mx_inv_scale(e);
         uint32_t pk[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -54,7 +47,7 @@ __global__ __launch_bounds__(256) void mx4_quant_kernel(const T* __restrict__ x,
             pk[j] = wd;
         }
         *(u32x4*)(q + row * ldq + kb * 16) = (u32x4){pk[0], pk[1], pk[2], pk[3]};
-        exps[row * nkb + kb] = (uint8_t)(e + 127);
+        exps[row * nkb + kb] = (uint8_t)mx_exp_byte(e);
     }
 }
 

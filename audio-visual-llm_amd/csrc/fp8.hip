@@ -26,6 +26,7 @@
 #include "common.h"
 #include "avllm_internal.h"
 #include "gemm_shared.h"
+#include "mx.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -56,37 +57,14 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const T* __restrict__ x, 
             const int row = mx_row(layout, rb, i, fr);
             if (row >= R) continue;
             float v[32];
-            const T* xp = x + (long)row * ldx + kb * 32;
-#pragma unroll
-            for (int c = 0; c < 32; c += 8) {
-                float t8[8];
-                load_f<8>(xp + c, t8);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[c + j] = t8[j];
-            }
-            float amax = 0.f;
-#pragma unroll
-            for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j]));
-            // floor(log2(amax)) from the exponent field (amax == 0 or subnormal -> smallest scale)
-            int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
-            e = e < -127 ? -127 : (e > 127 ? 127 : e);
-            const float invs = __uint_as_float((uint32_t)(127 - e) << 23);         // 2^-e: e <= 120 for any finite amax, so the exponent field stays >= 7
+            mx_load32(x + (long)row * ldx + kb * 32, v);
             uint32_t pk[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float a[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) a[c] = fminf(fmaxf(v[4 * j + c] * invs, -448.f), 448.f);
-                int r = 0;
-                r = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], r, false);
-                r = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], r, true);
-                pk[j] = (uint32_t)r;
-            }
+            const int e = mx_block32_quant(v, pk);
             uint8_t* qp = q + (long)row * ldq + kb * 32;
             *(u32x4*)qp = (u32x4){pk[0], pk[1], pk[2], pk[3]};
             *(u32x4*)(qp + 16) = (u32x4){pk[4], pk[5], pk[6], pk[7]};
-            word |= (uint32_t)(e + 127) << (8 * i);
-            if (layout == 2) ((uint8_t*)simg)[(long)row * nkb + kb] = (uint8_t)(e + 127);
+            word |= mx_exp_byte(e) << (8 * i);
+            if (layout == 2) ((uint8_t*)simg)[(long)row * nkb + kb] = (uint8_t)mx_exp_byte(e);
         }
         if (layout != 2) simg[(((long)(kb >> 2) * RB + rb) * 4 + (kb & 3)) * 16 + fr] = word;
     }
@@ -296,20 +274,12 @@ __global__ __launch_bounds__(256) void norm_mxq_kernel(const bf16* __restrict__ 
                 for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(o[e]));
                 amax = fmaxf(amax, __shfl_xor(amax, 1));
                 amax = fmaxf(amax, __shfl_xor(amax, 2));
-                int ex = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
-                ex = ex < -127 ? -127 : (ex > 127 ? 127 : ex);
-                const float invs = __uint_as_float((uint32_t)(127 - ex) << 23);
-                float a8[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) a8[e] = fminf(fmaxf(o[e] * invs, -448.f), 448.f);
-                int r0 = 0, r1 = 0;
-                r0 = __builtin_amdgcn_cvt_pk_fp8_f32(a8[0], a8[1], r0, false);
-                r0 = __builtin_amdgcn_cvt_pk_fp8_f32(a8[2], a8[3], r0, true);
-                r1 = __builtin_amdgcn_cvt_pk_fp8_f32(a8[4], a8[5], r1, false);
-                r1 = __builtin_amdgcn_cvt_pk_fp8_f32(a8[6], a8[7], r1, true);
+                const int ex = mx_block_exp<MX_EMAX_E4M3>(amax);
+                uint32_t pk[2];
+                mx_pack_e4m3<8>(o, mx_inv_scale(ex), pk);
                 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-                *(u32x2*)(q + row * ldq + c * 8) = (u32x2){(uint32_t)r0, (uint32_t)r1};
-                if ((lane & 3) == 0) sb[c >> 2][rloc] = (uint8_t)(ex + 127);
+                *(u32x2*)(q + row * ldq + c * 8) = (u32x2){pk[0], pk[1]};
+                if ((lane & 3) == 0) sb[c >> 2][rloc] = (uint8_t)mx_exp_byte(ex);
             }
         }
     }

@@ -284,7 +284,8 @@ __global__ __launch_bounds__(256, 1) void gemm_f8_wp_kernel(F8Args g) {
                     for (int c = 0; c < 8; ++c) amax = fmaxf(amax, fabsf(v[c]));
                     amax = fmaxf(amax, __shfl_xor(amax, 16));
                     amax = fmaxf(amax, __shfl_xor(amax, 32));
-                    int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;           // floor(log2 amax) - 8 (oracle/mxfp8.py, fp8.hip mx_quant_kernel)
+                    // the rule of mx.h, spelled out: through its helpers this epilogue compiles to other code (96 more VALU adds or a different spill pattern)
+                    int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
                     e = e < -127 ? -127 : (e > 127 ? 127 : e);
                     const float invs = __uint_as_float((uint32_t)(127 - e) << 23);
                     float a8[8];

@@ -1,56 +1,19 @@
 // KV cache in block-scaled e4m3 (OCP MX: one E8M0 exponent, biased by 127, per 32 consecutive elements of a cache row) for the fused token step.
-// A cache row of dkv bf16 values becomes dkv codes + dkv/32 exponent bytes, 33/64 of its bytes, by the rule of mx_quant_kernel (fp8.hip):
-// e = floor(log2 amax) - 8, codes = RNE(x * 2^-e) saturated to +-448, amax == 0 -> exponent -127 (byte 0).  Blocks never straddle a head (hd is
-// 64 or 128).  A cache image is two planes: the codes of every row first ([..., dkv] bytes, rows 64-byte multiples so a lane's 16 codes are one
-// aligned 16-byte load), then the exponents ([..., dkv/32] bytes); the kernels take the two plane pointers of a layer.
+// A cache row of dkv bf16 values becomes dkv codes + dkv/32 exponent bytes, 33/64 of its bytes, by the rule of mx.h (amax == 0 -> byte 0).
+// Blocks never straddle a head (hd is 64 or 128).  A cache image is two planes: the codes of every row first ([..., dkv] bytes, rows 64-byte
+// multiples so a lane's 16 codes are one aligned 16-byte load), then the exponents ([..., dkv/32] bytes); the kernels take the two plane
+// pointers of a layer.  This file writes and moves the image; the token step reads it in attention_decode.hip (the e4m3 row form).
 //
 //   kv8_append_kernel        prefill: rows [B, S] of the rotated k and of v in the q|k|v buffer -> codes + exponents at [pos0, pos0 + S)
 //   kv8_rope_append_kernel   token step, after the raw q|k|v projection: rotates q in place (fp32, one rounding to bf16), rotates k (fp32, no
 //                            bf16 rounding in between), quantises k and v and writes the row at pos (+ *pos_dev); rotate = 0 after a head-norm
 //                            launch that has rotated already (Qwen3)
-//   attn_decode1_kv8_kernel  attn_decode1_kernel (decode.hip) on the image: the same one pass, the same merges, fp32 throughout; a lane owns 16
-//                            codes of a row (one 16-byte load + the block's exponent byte), so a row is hd/16 lanes, a pass of the workgroup
-//                            covers twice the rows of the bf16 kernel and a trip of UN = 4 passes keeps the same bytes per lane in flight
-//                            (4 x 32 code bytes; 128 KiB per 1024-thread workgroup).  Dequantisation is exact: code x 2^e, the power of two applied
-//                            once to the lane's partial score and once to the softmax weight.
 // The beam-search gather moves both planes with the byte-row form of kv_gather_rows (beam.hip): rows of dkv and of dkv/32 bytes.
 #include "common.h"
 #include "avllm_internal.h"
+#include "mx.h"
 
 namespace {
-
-// one MX block: 32 values -> 32 codes at qp (16-byte aligned) and the exponent byte at ep.  mx_quant_kernel's arithmetic, operation for operation.
-__device__ __forceinline__ void mx_block_store(const float (&v)[32], uint8_t* __restrict__ qp, uint8_t* __restrict__ ep) {
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j]));
-    int e = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;
-    e = e < -127 ? -127 : (e > 127 ? 127 : e);
-    const float invs = __uint_as_float((uint32_t)(127 - e) << 23);
-    uint32_t pk[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float a[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) a[c] = fminf(fmaxf(v[4 * j + c] * invs, -448.f), 448.f);
-        int r = 0;
-        r = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], r, false);
-        r = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], r, true);
-        pk[j] = (uint32_t)r;
-    }
-    *(u32x4*)qp = (u32x4){pk[0], pk[1], pk[2], pk[3]};
-    *(u32x4*)(qp + 16) = (u32x4){pk[4], pk[5], pk[6], pk[7]};
-    *ep = (uint8_t)(e + 127);
-}
-__device__ __forceinline__ void load32(const bf16* __restrict__ p, float (&v)[32]) {
-#pragma unroll
-    for (int c = 0; c < 32; c += 8) {
-        float t8[8];
-        load_f<8>(p + c, t8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[c + j] = t8[j];
-    }
-}
 
 struct Kv8Planes { uint8_t *kq, *ke, *vq, *ve; };       // codes [B, Tmax, dkv], exponents [B, Tmax, dkv/32] of K and of V
 
@@ -66,9 +29,9 @@ __global__ __launch_bounds__(256) void kv8_append_kernel(const bf16* __restrict_
         const long row = i / nb;
         const int b = (int)(row / Tn), t = (int)(row % Tn);
         float x[32];
-        load32((isv ? v : k) + row * ld + blk * 32, x);
+        mx_load32((isv ? v : k) + row * ld + blk * 32, x);
         const long crow = (long)b * Tmax + pos0 + t;
-        mx_block_store(x, (isv ? c.vq : c.kq) + crow * dkv + blk * 32, (isv ? c.ve : c.ke) + crow * nb + blk);
+        mx_block32_store(x, (isv ? c.vq : c.kq) + crow * dkv + blk * 32, (isv ? c.ve : c.ke) + crow * nb + blk);
     }
 }
 
@@ -110,8 +73,8 @@ __global__ __launch_bounds__(256) void kv8_rope_append_kernel(Kv8RopeArgs a) {
     if (it < nq + nk) {
         const int i = it - nq, hk = i / (hd >> 6), j = i - hk * (hd >> 6), c0 = hk * hd + 32 * j;
         float x[32], y[32];
-        load32(row + d + c0, x);
-        load32(row + d + c0 + hh, y);
+        mx_load32(row + d + c0, x);
+        mx_load32(row + d + c0 + hh, y);
         if (a.rotate) {
 #pragma unroll
             for (int e = 0; e < 32; ++e) {
@@ -120,123 +83,14 @@ __global__ __launch_bounds__(256) void kv8_rope_append_kernel(Kv8RopeArgs a) {
                 x[e] = ox; y[e] = oy;
             }
         }
-        mx_block_store(x, a.c.kq + crow * dkv + c0, a.c.ke + crow * nb + (c0 >> 5));
-        mx_block_store(y, a.c.kq + crow * dkv + c0 + hh, a.c.ke + crow * nb + ((c0 + hh) >> 5));
+        mx_block32_store(x, a.c.kq + crow * dkv + c0, a.c.ke + crow * nb + (c0 >> 5));
+        mx_block32_store(y, a.c.kq + crow * dkv + c0 + hh, a.c.ke + crow * nb + ((c0 + hh) >> 5));
         return;
     }
     const int blk = it - nq - nk;
     float x[32];
-    load32(row + d + dkv + blk * 32, x);
-    mx_block_store(x, a.c.vq + crow * dkv + blk * 32, a.c.ve + crow * nb + blk);
-}
-
-// 16 e4m3 codes -> fp32 (exact), unscaled
-__device__ __forceinline__ void codes16(const u32x4 c, float (&o)[16]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], true);
-        o[4 * i] = lo[0]; o[4 * i + 1] = lo[1]; o[4 * i + 2] = hi[0]; o[4 * i + 3] = hi[1];
-    }
-}
-__device__ __forceinline__ float e8m0(unsigned e) { return __uint_as_float(e << 23); }      // 2^(e - 127); byte 0 (an all-zero block) -> 0
-
-// attn_decode1_kernel on the image.  A group of G = hd/16 lanes owns cache rows t = g, g + R, ...; see the head of the file.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) void attn_decode1_kv8_kernel(const bf16* __restrict__ q, long ldq, const uint8_t* __restrict__ kq,
-                                                                   const uint8_t* __restrict__ ke, const uint8_t* __restrict__ vq,
-                                                                   const uint8_t* __restrict__ ve, bf16* __restrict__ o, long ldo, int H, int hd, int Tk,
-                                                                   const int* __restrict__ tk_dev, int Tmax, float scale, int GQ) {
-    __shared__ float pacc[NW][128];
-    __shared__ float pm[NW], pl[NW];
-    const int h = blockIdx.x, b = blockIdx.y, d = (H / GQ) * hd, de = d >> 5;
-    if (tk_dev) Tk += *tk_dev;
-    Tk = Tk > Tmax ? Tmax : Tk;                      // a device-side length the host could not check never reads past the cache
-    const int G = hd >> 4, R = NW * 64 / G;
-    const int tid = threadIdx.x, dc = tid % G, rsub = tid / G;
-    float qv[16];
-    load_f<16>(q + (long)b * ldq + (long)h * hd + dc * 16, qv);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) qv[j] *= scale;
-    const long cbase = ((long)b * Tmax) * d + (long)(h / GQ) * hd + dc * 16, ebase = ((long)b * Tmax) * de + (h / GQ) * (hd >> 5) + (dc >> 1);
-    constexpr int UN = 4;
-    float mx = -INFINITY, l = 0.f, acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    for (int t0 = 0; t0 < Tk; t0 += UN * R) {
-        u32x4 kc[UN], vc[UN];
-        unsigned kx[UN], vx[UN];
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int t = t0 + u * R + rsub;
-            kc[u] = (u32x4){0u, 0u, 0u, 0u}; vc[u] = (u32x4){0u, 0u, 0u, 0u}; kx[u] = 0u; vx[u] = 0u;
-            if (t < Tk) {
-                kc[u] = *(const u32x4*)(kq + cbase + (long)t * d);
-                vc[u] = *(const u32x4*)(vq + cbase + (long)t * d);
-                kx[u] = ke[ebase + (long)t * de];
-                vx[u] = ve[ebase + (long)t * de];
-            }
-        }
-        float s[UN], tm = mx;
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int t = t0 + u * R + rsub;
-            float kf[16], x = 0.f;
-            codes16(kc[u], kf);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) x += qv[j] * kf[j];
-            x *= e8m0(kx[u]);
-            for (int off = G >> 1; off > 0; off >>= 1) x += __shfl_xor(x, off);
-            s[u] = t < Tk ? x : -INFINITY;
-            tm = fmaxf(tm, s[u]);
-        }
-        if (tm > -INFINITY) {
-            const float f = __expf(mx - tm);             // mx = -inf on the first trip: exp(-inf) = 0, acc and l are 0 anyway
-            l *= f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] *= f;
-#pragma unroll
-            for (int u = 0; u < UN; ++u) {
-                const float p = __expf(s[u] - tm);       // -inf rows: 0
-                l += p;
-                const float pv = p * e8m0(vx[u]);
-                float vf[16];
-                codes16(vc[u], vf);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) acc[j] += pv * vf[j];
-            }
-            mx = tm;
-        }
-    }
-    // merge the row groups of a wave (lanes with equal dc)
-    for (int off = G; off < 64; off <<= 1) {
-        const float m2 = __shfl_xor(mx, off), l2 = __shfl_xor(l, off);
-        const float mn = fmaxf(mx, m2);
-        const float f1 = mx > -INFINITY ? __expf(mx - mn) : 0.f, f2 = m2 > -INFINITY ? __expf(m2 - mn) : 0.f;
-        l = l * f1 + l2 * f2;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = acc[j] * f1 + __shfl_xor(acc[j], off) * f2;
-        mx = mn;
-    }
-    const int w = tid >> 6, lane = tid & 63;
-    if (lane < G) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) pacc[w][lane * 16 + j] = acc[j];
-        if (lane == 0) { pm[w] = mx; pl[w] = l; }
-    }
-    __syncthreads();
-    if (tid < hd) {
-        float mn = -INFINITY;
-#pragma unroll
-        for (int x = 0; x < NW; ++x) mn = fmaxf(mn, pm[x]);
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int x = 0; x < NW; ++x) {
-            const float f = pm[x] > -INFINITY ? __expf(pm[x] - mn) : 0.f;
-            num += pacc[x][tid] * f;
-            den += pl[x] * f;
-        }
-        o[(long)b * ldo + (long)h * hd + tid] = (bf16)(num / den);
-    }
+    mx_load32(row + d + dkv + blk * 32, x);
+    mx_block32_store(x, a.c.vq + crow * dkv + blk * 32, a.c.ve + crow * nb + blk);
 }
 
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -272,23 +126,6 @@ int av_kv8_rope_append(void* qkv, long ld, int B, int H, int Hkv, int hd, const 
     return AV_OK;
 }
 
-int av_attention_decode_kv8(const void* q, long ldq, const void* kq, const void* ke, const void* vq, const void* ve, void* o, long ldo, int B, int H, int hd,
-                            int Tk, const int* tk_dev, int Tmax, float scale, int G, hipStream_t st) {
-    AV_CHECK_ARG(q && kq && ke && vq && ve && o && B > 0 && H > 0 && Tmax > 0 && (tk_dev || (Tk > 0 && Tk <= Tmax)) && G > 0 && H % G == 0,
-                 "attention_decode_kv8: bad args");
-    AV_CHECK_ARG((hd == 64 || hd == 128) && ldq % 8 == 0 && al16(q) && al16(kq) && al16(vq), "attention_decode_kv8: head_dim %d unsupported (64 or 128), q rows and code planes 16-byte aligned", hd);
-    const dim3 grid(H, B);
-    // few (sequence, head) pairs: 16 waves each, as attn_decode1_kernel
-    if ((long)B * H <= 1024)
-        hipLaunchKernelGGL((attn_decode1_kv8_kernel<16>), grid, dim3(1024), 0, st, (const bf16*)q, ldq, (const uint8_t*)kq, (const uint8_t*)ke, (const uint8_t*)vq,
-                           (const uint8_t*)ve, (bf16*)o, ldo, H, hd, Tk, tk_dev, Tmax, scale, G);
-    else
-        hipLaunchKernelGGL((attn_decode1_kv8_kernel<4>), grid, dim3(256), 0, st, (const bf16*)q, ldq, (const uint8_t*)kq, (const uint8_t*)ke, (const uint8_t*)vq,
-                           (const uint8_t*)ve, (bf16*)o, ldo, H, hd, Tk, tk_dev, Tmax, scale, G);
-    AV_LAUNCH_CHECK();
-    return AV_OK;
-}
-
 // both planes through kv_gather_rows as rows of bytes (its bf16 form with half as many elements): code rows of dkv bytes, exponent rows of dkv/32
 int av_kv8_gather_rows(const void* k_src, const void* v_src, int src_rows, long src_T, void* k_dst, void* v_dst, int dst_rows, long dst_T, int layers,
                        int dkv, const int32_t* parent, int t0, int t1, hipStream_t st) {
@@ -307,11 +144,6 @@ extern "C" int avllm_kv8_append(const void* k, const void* v, int64_t ld, void* 
 extern "C" int avllm_kv8_rope_append(void* qkv, int64_t ld, int32_t B, int32_t heads, int32_t kv_heads, int32_t hd, const float* rope, int32_t rotate,
                                      void* k_codes, void* k_exps, void* v_codes, void* v_exps, int32_t Tmax, int32_t pos, const int32_t* pos_dev, void* stream) {
     return av_kv8_rope_append(qkv, ld, B, heads, kv_heads, hd, rope, rotate, k_codes, k_exps, v_codes, v_exps, Tmax, pos, pos_dev, (hipStream_t)stream);
-}
-extern "C" int avllm_attention_decode_kv8(const void* q, int64_t ldq, const void* k_codes, const void* k_exps, const void* v_codes, const void* v_exps, void* o,
-                                          int64_t ldo, int32_t B, int32_t H, int32_t hd, int32_t Tk, const int32_t* tk_dev, int32_t Tmax, float scale,
-                                          int32_t kv_group, void* stream) {
-    return av_attention_decode_kv8(q, ldq, k_codes, k_exps, v_codes, v_exps, o, ldo, B, H, hd, Tk, tk_dev, Tmax, scale, kv_group, (hipStream_t)stream);
 }
 extern "C" int avllm_kv8_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,
                                      int64_t dst_T, int32_t layers, int32_t dkv, const int32_t* parent, int32_t t0, int32_t t1, void* stream) {

@@ -188,9 +188,13 @@ def test_backward_fused_inverse_rope(dev, g, pos0):
         run_bwd(gf, cf, rope_tab=tab)
 
 
+# B * H > 1024 takes the 4-wave kernel, whose trip is 4 passes of 256 / (hd / 8) rows: 128 rows at hd 64, 64 at hd 128 -- one below, at, one above
+DECODE_CASES = [g + (t,) for g in ((2, 4, 4, 128), (3, 8, 2, 64)) for t in (1, 64, 65, 257)] + \
+               [(17, 64, 8, 64, t) for t in (1, 127, 128, 129)] + [(9, 128, 16, 128, t) for t in (1, 63, 64, 65)]
+
+
 @pytest.mark.parametrize("fam", ["count", "offset"])
-@pytest.mark.parametrize("Tk", [1, 64, 65, 257])
-@pytest.mark.parametrize("B,H,Hkv,hd", [(2, 4, 4, 128), (3, 8, 2, 64)])
+@pytest.mark.parametrize("B,H,Hkv,hd,Tk", DECODE_CASES)
 def test_decode(dev, B, H, Hkv, hd, Tk, fam):
     """Single-query attention over a KV cache: no LSE comes back, so the count family checks the mean of the visible V alone (a row past Tk read, a
     row before it skipped or a wrong kv head is a wrong mean) and the offset family the general sum.  Cache rows past Tk are NaN."""

@@ -1,4 +1,4 @@
-"""The kernels of the fp8 KV cache (csrc/kv_fp8.hip) one by one: the prefill append and the token step's rotate-and-append against the MX rule
+"""The kernels of the fp8 KV cache (csrc/kv_fp8.hip, and its reader in csrc/attention_decode.hip) one by one: the prefill append and the token step's rotate-and-append against the MX rule
 of oracle/mxfp8.py bit for bit (and, where a rotation by real angles precedes the rule, against float64 within the rule's own half ulp), the
 single-token attention over the image against refs64_attention on the dequantised values with test_attention_pin_gpu.py::test_decode's bars, and
 the beam gather byte for byte.  Images are read and built only through ops.kv8_unpack / ops.kv8_pack."""
@@ -189,9 +189,11 @@ def decode_case(B, H, Hkv, hd, Tk, fam):
     return q, imgs[0], imgs[1], o64, bar
 
 
-# a trip of the kernel is 4 passes of 1024 / (hd / 16) rows: 512 rows at hd 128, 1024 at hd 64 -- one below, at, one above
+# a trip of the kernel is 4 passes of 1024 / (hd / 16) rows: 512 rows at hd 128, 1024 at hd 64 -- one below, at, one above; with B * H > 1024 it is
+# the 4-wave kernel and 4 passes of 256 / (hd / 16) rows: 128 rows at hd 128, 256 at hd 64
 @pytest.mark.parametrize("fam", ["count", "offset"])
-@pytest.mark.parametrize("B,H,Hkv,hd,Tk", [(2, 4, 4, 128, t) for t in (1, 64, 65, 257, 511, 512, 513)] + [(3, 8, 2, 64, t) for t in (1, 64, 65, 257, 1023, 1024, 1025)])
+@pytest.mark.parametrize("B,H,Hkv,hd,Tk", [(2, 4, 4, 128, t) for t in (1, 64, 65, 257, 511, 512, 513)] + [(3, 8, 2, 64, t) for t in (1, 64, 65, 257, 1023, 1024, 1025)] +
+                         [(17, 64, 8, 64, t) for t in (1, 255, 256, 257)] + [(9, 128, 16, 128, t) for t in (1, 127, 128, 129)])
 def test_attention_over_the_image(dev, B, H, Hkv, hd, Tk, fam):
     q, kc, vc, o64, bar = decode_case(B, H, Hkv, hd, Tk, fam)
     qd, kd, vd = q.to(dev), kc.to(dev), vc.to(dev)
