@@ -226,23 +226,33 @@ class LlamaEngine:
         if rs:                                                   # Llama-3.1 / 3.2 "llama3" RoPE frequency scaling (include/avllm.h)
             m.rope_factor, m.rope_low_freq_factor, m.rope_high_freq_factor, m.rope_orig_ctx = float(rs[0]), float(rs[1]), float(rs[2]), int(rs[3])
 
-        def put(val):
+        # the LLM's device tensors by their HuggingFace names (the fused q|k|v and gate|up matrices of layer i under (i, "qkv"), (i, "gu")):
+        # what merge_lora() writes into and merged_llm_state_dict() exports
+        self.llm_w = {}
+
+        def put(val, name=None):
             dv = _dev(val, dtype, device)
             self.keep.append(dv)
+            if name is not None:
+                self.llm_w[name] = dv
             return dv
 
-        self.embed = put(sd["model.embed_tokens.weight"])
+        def put_sd(name):
+            return put(sd[name], name)
+
+        self.embed = put_sd("model.embed_tokens.weight")
         m.embed = self.embed.data_ptr()
-        m.norm_w = put(sd["model.norm.weight"]).data_ptr()
-        head = put(sd["lm_head.weight"])
+        m.norm_w = put_sd("model.norm.weight").data_ptr()
+        head = put_sd("lm_head.weight")
         m.lm_head = head.data_ptr()
         if training:
             m.lm_head_t = put(head.t()).data_ptr()
         m.fp8 = int(self.fp8)
 
-        def images(w, decode8=self.decode_fp8):
+        def images(w, decode8=self.decode_fp8, key=None):
             """(codes, layout-1 image, layout-2 exponents) pointers of a frozen matrix for the fp8 modes that are on (None otherwise); the
-            token step's exponents share the codes of the training forward's image when both modes are on (re-quantising writes the same bytes)."""
+            token step's exponents share the codes of the training forward's image when both modes are on (re-quantising writes the same bytes).
+            `key`: the matrix's name in self.llm_w when merge_lora() has to rewrite its images in place."""
             q = s = e = None
             if self.fp8:
                 q, s = ops.mx_quantize(w, 1)
@@ -250,6 +260,8 @@ class LlamaEngine:
             if decode8:
                 q, e = ops.mx_quantize(w, 2, q=q)
                 self.keep += [q, e]
+            if key is not None:
+                self.img8[key] = (q, s, e)
             return tuple(None if t is None else t.data_ptr() for t in (q, s, e))
 
         m.decode_fp8 = int(self.decode_fp8)
@@ -259,6 +271,10 @@ class LlamaEngine:
             m.lm_head8, m.slm_head8, m.elm_head8 = images(head, self.decode_fp8 or self.decode_fp4)
         self.layers = (L.LlamaLayer * cfg.layers)()
         check_llama_keys(sd, cfg)
+        # what else merge_lora() touches: the fp8 (codes, layout-1 image, layout-2 exponents) and fp4 (codes, exponents) images of the
+        # attention matrices by (layer, "qkv" | "o"), which it rewrites, and their transposed training copies, which it frees
+        self.merged = False
+        self.img8, self.img4, self.attn_wt = {}, {}, {}
         # ---- LoRA masters / grads / padded operand images
         self.per_layer = sum(r * (d + do) for do in self.douts)
         n = cfg.layers * self.per_layer
@@ -277,32 +293,34 @@ class LlamaEngine:
             p = f"model.layers.{i}."
             ly = self.layers[i]
             wqkv = put(torch.cat([sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"],
-                                  sd[p + "self_attn.v_proj.weight"]], 0))
-            wo = put(sd[p + "self_attn.o_proj.weight"])
-            wgu = put(torch.cat([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]], 0))
-            wdown = put(sd[p + "mlp.down_proj.weight"])
-            ly.ln1_w = put(sd[p + "input_layernorm.weight"]).data_ptr()
-            ly.ln2_w = put(sd[p + "post_attention_layernorm.weight"]).data_ptr()
+                                  sd[p + "self_attn.v_proj.weight"]], 0), (i, "qkv"))
+            wo = put_sd(p + "self_attn.o_proj.weight")
+            wgu = put(torch.cat([sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"]], 0), (i, "gu"))
+            wdown = put_sd(p + "mlp.down_proj.weight")
+            ly.ln1_w = put_sd(p + "input_layernorm.weight").data_ptr()
+            ly.ln2_w = put_sd(p + "post_attention_layernorm.weight").data_ptr()
             ly.wqkv, ly.wo, ly.wgu, ly.wdown = wqkv.data_ptr(), wo.data_ptr(), wgu.data_ptr(), wdown.data_ptr()
             # frozen attention biases (Qwen2: q|k|v; attention_bias: o as well), in the model dtype, one [d + 2 dkv] vector like wqkv's rows
             if getattr(cfg, "qkv_bias", False):
-                ly.bqkv = put(torch.cat([sd[p + f"self_attn.{nm}.bias"] for nm in LORA_TARGETS[:3]], 0)).data_ptr()
+                ly.bqkv = put(torch.cat([sd[p + f"self_attn.{nm}.bias"] for nm in LORA_TARGETS[:3]], 0), (i, "bqkv")).data_ptr()
             if getattr(cfg, "o_bias", False):
-                ly.bo = put(sd[p + "self_attn.o_proj.bias"]).data_ptr()
+                ly.bo = put_sd(p + "self_attn.o_proj.bias").data_ptr()
             # frozen per-head q/k RMSNorm weights [hd] (Qwen3), in the model dtype like every norm weight (fp32 mode keeps them fp32)
             if getattr(cfg, "qk_norm", False):
-                ly.q_norm_w = put(sd[p + "self_attn.q_norm.weight"]).data_ptr()
-                ly.k_norm_w = put(sd[p + "self_attn.k_norm.weight"]).data_ptr()
+                ly.q_norm_w = put_sd(p + "self_attn.q_norm.weight").data_ptr()
+                ly.k_norm_w = put_sd(p + "self_attn.k_norm.weight").data_ptr()
             if training:
-                ly.wqkv_t, ly.wo_t = put(wqkv.t()).data_ptr(), put(wo.t()).data_ptr()
+                self.attn_wt[i] = (put(wqkv.t()), put(wo.t()))
+                ly.wqkv_t, ly.wo_t = (t.data_ptr() for t in self.attn_wt[i])
                 ly.wgu_t, ly.wdown_t = put(wgu.t()).data_ptr(), put(wdown.t()).data_ptr()
             if self.fp8 or self.decode_fp8:
-                ly.wqkv8, ly.sqkv8, ly.eqkv8 = images(wqkv)
-                ly.wo8, ly.so8, ly.eo8 = images(wo)
+                ly.wqkv8, ly.sqkv8, ly.eqkv8 = images(wqkv, key=(i, "qkv"))
+                ly.wo8, ly.so8, ly.eo8 = images(wo, key=(i, "o"))
                 ly.wgu8, ly.sgu8, ly.egu8 = images(wgu)
                 ly.wdown8, ly.sdown8, ly.edown8 = images(wdown)
             if self.decode_fp4:
-                self._fp4_images(ly, wqkv, wo, wgu, wdown)
+                img4 = self._fp4_images(ly, wqkv, wo, wgu, wdown)
+                self.img4[i, "qkv"], self.img4[i, "o"] = img4["qkv"], img4["o"]
             if self.use_lora:
                 es = self.img_A.element_size()
                 for j in range(4):
@@ -327,12 +345,15 @@ class LlamaEngine:
             self.pack_lora()
 
     def _fp4_images(self, ly, wqkv, wo, wgu, wdown):
-        """MXFP4 codes + exponents of one layer's four frozen matrices into its descriptor (tensors parked in self.keep)."""
+        """MXFP4 codes + exponents of one layer's four frozen matrices into its descriptor (tensors parked in self.keep); returns them by
+        matrix name."""
+        out = {}
         for nm, wt in (("qkv", wqkv), ("o", wo), ("gu", wgu), ("down", wdown)):
-            q4, e4 = ops.mx4_quantize(wt)
+            q4, e4 = out[nm] = ops.mx4_quantize(wt)
             self.keep += [q4, e4]
             setattr(ly, "w" + nm + "4", q4.data_ptr())
             setattr(ly, "e" + nm + "4", e4.data_ptr())
+        return out
 
     # flat-buffer offsets of module j (0..3 = q,k,v,o) in layer i: (A range, B range)
     def _slices(self, i, j):
@@ -352,7 +373,12 @@ class LlamaEngine:
                 out[f"layers.{i}.{nm}.lora_B"] = buf[b[0]:b[1]].view(self.douts[j], r)
         return out
 
+    def _refuse_merged(self, what):
+        if self.merged:
+            raise RuntimeError(f"{what} needs the separate adapters, which merge_lora() folded into the LLM weights for good")
+
     def load_lora(self, lora_sd):
+        self._refuse_merged("load_lora()")
         v = self.lora_views()
         for k, t in lora_sd.items():
             v[k].copy_(t.to(device=self.device, dtype=torch.float32))
@@ -360,6 +386,7 @@ class LlamaEngine:
     def pack_lora(self):
         """Refresh the padded operand images from the fp32 masters (after every optimizer step): one launch for all adapters,
         driven by a device-side table of (master, image) pointers built on first use."""
+        self._refuse_merged("pack_lora()")
         lib = L.load()
         if getattr(self, "_pack_table", None) is None:
             rows = []
@@ -378,6 +405,7 @@ class LlamaEngine:
         """x [B,S,d] (engine dtype), labels int64 [B,S] (-100 applied).  Leaves loss_sum,count in self.acc.
         `dropout`/`seed`: lora_dropout probability and the step's mask seed (kept in the descriptor for bwd()); `seed_dev`: device
         pointer (int) of a uint32 added to `seed` at run time -- the step state of a graph-replayable step."""
+        self._refuse_merged("fwd_loss()")
         lib = L.load()
         self.desc.lora_dropout = float(dropout) if self.use_lora else 0.0
         self.desc.dropout_seed = int(seed) & 0xFFFFFFFF
@@ -400,6 +428,7 @@ class LlamaEngine:
         backward pass (decoder layers layer_hi .. layer_lo; pieces in descending order, avllm_llama_lora_bwd_layers).
         dx_embeds: [B,S,d] tensor of the engine dtype that receives d loss / d inputs_embeds when the piece reaches layer 0
         (avllm_llama_lora_bwd_layers_dx; the connectors' gradient starts there)."""
+        self._refuse_merged("bwd()")
         lib = L.load()
         if self._last is None:
             raise RuntimeError("LlamaEngine.bwd() without a preceding fwd_loss()")
@@ -423,6 +452,7 @@ class LlamaEngine:
     def adapters_disabled(self):
         """Context manager: the LLM without its LoRA adapters, as scripts/clip_whisper/decode.py of the reference runs it (it rebuilds the
         model with use_lora=False and loads the connector weights only, decode.py:186-197,236-260)."""
+        self._refuse_merged("adapters_disabled()")
         eng = self
 
         class _Ctx:
@@ -438,6 +468,71 @@ class LlamaEngine:
                     for j in range(4):
                         ly.lora[j].A_pad, ly.lora[j].B_pad = sv[j]
         return _Ctx()
+
+    def merge_lora(self):
+        """Fold the adapters into the LLM weights for decoding, for good: W' = W + scale * B.A on q, k, v (row slices of wqkv) and o from the
+        fp32 masters (avllm_lora_merge), every fp8 / fp4 image of the two matrices rebuilt in place by the quantisers that made it, and the
+        adapter pointers cleared, so that prefill and the token step take the adapter-free kernels.  lora_p stays (state_dict() still returns
+        the adapters); the transposed training copies of wqkv and wo are stale afterwards and freed, and everything that would need the
+        separate adapters back raises."""
+        if not self.use_lora:
+            raise ValueError("merge_lora(): this engine has no LoRA adapters (use_lora=False)")
+        self._refuse_merged("a second merge_lora()")
+        v = self.lora_views()
+        rows = self._qkv_rows()
+        for i in range(self.cfg.layers):
+            ly = self.layers[i]
+            # wqkv was concatenated here, but wo may be the caller's own tensor (a state dict already on the device in the engine dtype is
+            # taken as it is): the merge writes into a copy the engine owns
+            okey = f"model.layers.{i}.self_attn.o_proj.weight"
+            wqkv, old = self.llm_w[i, "qkv"], self.llm_w[okey]
+            wo = self.llm_w[okey] = old.clone()
+            self.keep = [wo if t is old else t for t in self.keep]
+            ly.wo = wo.data_ptr()
+            for j, nm in enumerate(LORA_TARGETS):
+                W = wo if j == 3 else wqkv[rows[j][0]:rows[j][1]]
+                ops.lora_merge_(W, v[f"layers.{i}.{nm}.lora_A"], v[f"layers.{i}.{nm}.lora_B"], self.lcfg.scale)
+                ly.lora[j].A_pad = None
+                ly.lora[j].B_pad = None
+            for nm, W in (("qkv", wqkv), ("o", wo)):
+                if (i, nm) in self.img8:
+                    q, s, e = self.img8[i, nm]
+                    if s is not None:
+                        ops.mx_quantize(W, 1, q=q, s=s)
+                    if e is not None:
+                        ops.mx_quantize(W, 2, q=q, s=e)
+                if (i, nm) in self.img4:
+                    ops.mx4_quantize(W, out=self.img4[i, nm])
+            if i in self.attn_wt:
+                stale = {t.data_ptr() for t in self.attn_wt.pop(i)}
+                self.keep = [t for t in self.keep if t.data_ptr() not in stale]
+                ly.wqkv_t = ly.wo_t = None
+        self.merged = True
+
+    def merged_llm_state_dict(self):
+        """The whole LLM after merge_lora() under its HuggingFace names: clones in the engine dtype, wqkv split back into q_proj, k_proj and
+        v_proj, the fused gate/up matrix into its halves.  A use_lora=False model built from it computes what this engine computes."""
+        if not self.merged:
+            raise RuntimeError("merged_llm_state_dict() comes after merge_lora()")
+        out, f = {}, self.cfg.ffn
+        for name, t in self.llm_w.items():
+            if isinstance(name, str):
+                out[name] = t.clone()
+                continue
+            i, what = name
+            p = f"model.layers.{i}."
+            if what == "gu":
+                out[p + "mlp.gate_proj.weight"], out[p + "mlp.up_proj.weight"] = t[:f].clone(), t[f:].clone()
+            else:                                  # "qkv" (weight rows) or "bqkv" (the bias vector laid out like them)
+                kind = "weight" if what == "qkv" else "bias"
+                for nm, (lo, hi) in zip(LORA_TARGETS[:3], self._qkv_rows()):
+                    out[p + f"self_attn.{nm}.{kind}"] = t[lo:hi].clone()
+        return out
+
+    def _qkv_rows(self):
+        """Row ranges of q, k and v in the fused wqkv."""
+        d, dkv = self.cfg.hidden, self.dkv
+        return (0, d), (d, d + dkv), (d + dkv, d + 2 * dkv)
 
     def frozen_weight_bytes(self):
         """Bytes of frozen weights ONE decode token step streams from HBM: every projection of every layer + lm_head (the embedding

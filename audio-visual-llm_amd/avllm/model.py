@@ -182,6 +182,8 @@ class ClipWhisperModel:
         return sd
 
     def load_state_dict(self, sd, strict=False):
+        if self.llm_engine.merged and any(".lora_A." in k or ".lora_B." in k for k in sd):      # refused before anything is loaded
+            raise RuntimeError("load_state_dict(): LoRA tensors cannot be loaded after merge_lora() folded the adapters into the LLM weights")
         a = {k.split("audio_connector.")[1]: v for k, v in sd.items() if "audio_connector." in k}
         v_ = {k.split("video_connector.")[1]: v for k, v in sd.items() if "video_connector." in k}
         if a:
@@ -218,12 +220,25 @@ class ClipWhisperModel:
             os.makedirs(os.path.join(output_dir, "llm"), exist_ok=True)
             torch.save({k: v for k, v in self.state_dict().items() if "lora_" in k}, os.path.join(output_dir, "llm", "adapter_model.pt"))
 
+    def merge_lora(self):
+        """peft's merge_and_unload() for decoding: W' = W + (alpha/r) B.A on q/k/v/o of every layer, once (LlamaEngine.merge_lora), so that
+        generate() and an eval forward() run the adapter-free kernels.  For good: the model is set to eval, and a training forward and
+        load_state_dict with LoRA tensors raise afterwards; state_dict() and save_pretrained() still hold the adapters as loaded."""
+        self.eval()
+        self.llm_engine.merge_lora()
+        return self
+
+    def merged_llm_state_dict(self):
+        """The whole LLM after merge_lora() as HuggingFace-named tensors (LlamaEngine.merged_llm_state_dict)."""
+        return self.llm_engine.merged_llm_state_dict()
+
     @classmethod
-    def from_pretrained(cls, model_dir, tokenizer=None, **kwargs):
+    def from_pretrained(cls, model_dir, tokenizer=None, merge_lora=False, **kwargs):
         """clip_whisper_model.py:821-864.  The reference's own pair is not closed: its save_pretrained writes `config.pt` / `config.json` while its
         from_pretrained demands `model_config.json` (and `whisper/`, `clip/` directories that are only written with freeze_encoders=False), so it
         cannot reload what it saved.  This one reloads what save_pretrained above wrote -- connectors, adapters, the saved settings -- on top of
-        base checkpoints named by the usual constructor keywords (`llm_path=`, `whisper_model=`, `clip_model=`, or `config=` + `synthetic_weights=`)."""
+        base checkpoints named by the usual constructor keywords (`llm_path=`, `whisper_model=`, `clip_model=`, or `config=` + `synthetic_weights=`).
+        merge_lora=True: merge_lora() once the adapters are loaded."""
         import json
         if not os.path.exists(model_dir):
             raise ValueError(f"Model directory {model_dir} does not exist")
@@ -240,6 +255,8 @@ class ClipWhisperModel:
         adapters = os.path.join(model_dir, "llm", "adapter_model.pt")
         if model.use_lora and os.path.exists(adapters):
             model.load_state_dict(torch.load(adapters, map_location="cpu", weights_only=True))
+        if merge_lora:
+            model.merge_lora()
         return model
 
     def _setup_projections(self, W=None):
@@ -433,6 +450,8 @@ class ClipWhisperModel:
         else:
             labels = None
         if self.training and labels is not None:
+            if self.llm_engine.merged:
+                raise RuntimeError("forward(): a training forward needs the separate adapters, which merge_lora() folded into the LLM weights")
             x = self._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors)       # adaptive pool / interpolate (:577-585)
             logits = self.llm_engine.fwd_loss(x, labels, want_logits=True, **self._dropout_args())
             acc = self.llm_engine.acc

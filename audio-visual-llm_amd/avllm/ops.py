@@ -765,30 +765,44 @@ def gemm_tn_multi(big, smalls, outs, r, alpha=1.0, seeds=None, p=0.0, shared=Fal
     return outs
 
 
-def mx_quantize(x, layout=0, q=None):
+def lora_merge_(W, A, B, scale):
+    """In place W[n,k] <- round(W[n,k] + scale * sum_j B[n,j] A[j,k]) (avllm_lora_merge): the decode-time merge of one LoRA pair.
+    W [N,K] f32 or bf16 with unit column stride (a row slice of a larger matrix is fine); A [r,K], B [N,r] contiguous fp32 masters."""
+    if W.dim() != 2 or A.dim() != 2 or B.dim() != 2 or A.shape[1] != W.shape[1] or B.shape[0] != W.shape[0] or A.shape[0] != B.shape[1]:
+        raise ValueError(f"lora_merge: shapes W {tuple(W.shape)}, A {tuple(A.shape)}, B {tuple(B.shape)} are not [N,K], [r,K], [N,r]")
+    if W.dtype not in (torch.float32, torch.bfloat16) or A.dtype != torch.float32 or B.dtype != torch.float32:
+        raise ValueError(f"lora_merge: W must be float32 or bfloat16 and A, B float32, got {W.dtype}, {A.dtype}, {B.dtype}")
+    if W.stride(1) != 1 or not (A.is_contiguous() and B.is_contiguous()):
+        raise ValueError("lora_merge: W needs unit column stride, A and B must be contiguous")
+    N, K = W.shape
+    L.check(L.load().avllm_lora_merge(L.ptr(W), W.stride(0), N, K, L.ptr(A), L.ptr(B), A.shape[0], float(scale), L.dt_of(W), L.stream_ptr()))
+    return W
+
+
+def mx_quantize(x, layout=0, q=None, s=None):
     """x [R,K] bf16/f32 -> (q uint8 [R,K] e4m3, scale image uint8 tensor): OCP-MX block scaling, 32 elements per E8M0 scale.
     layout 0 = activation side, 1 = weight side of avllm_gemm_f8; layout 2 = decode side: the scales are the exponent matrix uint8 [R, K/32]
-    (E8M0 biased by 127) of dec_proj's fp8 weight form.  `q`: optional [R, K] uint8 output for the codes (the same for every layout)."""
+    (E8M0 biased by 127) of dec_proj's fp8 weight form.  `q`: optional [R, K] uint8 output for the codes (the same for every layout); `s`: the
+    scale image of an earlier call with the same shape and layout, rewritten in place (a weight that changed keeps its buffers)."""
     lib = L.load()
     R, K = x.shape
     if q is None:
         q = torch.empty(R, K, device=x.device, dtype=torch.uint8)
-    if layout == 2:
-        s = torch.zeros(R, K // 32, device=x.device, dtype=torch.uint8)
-    else:
-        s = torch.zeros(lib.avllm_mx_scale_bytes(R, K), device=x.device, dtype=torch.uint8)
+    if s is None:
+        s = torch.zeros((R, K // 32) if layout == 2 else lib.avllm_mx_scale_bytes(R, K), device=x.device, dtype=torch.uint8)
     L.check(lib.avllm_mx_quantize(L.ptr(x), _ld(x), R, K, L.ptr(q), K, L.ptr(s), layout, L.dt_of(x), L.stream_ptr()))
     return q, s
 
 
-def mx4_quantize(x):
+def mx4_quantize(x, out=None):
     """x [R,K] bf16/f32 (K % 32 == 0) -> (codes uint8 [R, K/2], exponents uint8 [R, K/32]): OCP MXFP4 -- e2m1 elements, two per byte with
-    element 2i in the low nibble, one E8M0 exponent (biased by 127) per 32 elements; the W4 / E8 of dec_proj's fp4 weight form."""
+    element 2i in the low nibble, one E8M0 exponent (biased by 127) per 32 elements; the W4 / E8 of dec_proj's fp4 weight form.
+    `out`: the (codes, exponents) pair of an earlier call with the same shape, rewritten in place."""
     R, K = x.shape
     if K % 32:
         raise ValueError(f"mx4_quantize: K={K} must be a multiple of 32")
-    q = torch.empty(R, K // 2, device=x.device, dtype=torch.uint8)
-    e = torch.empty(R, K // 32, device=x.device, dtype=torch.uint8)
+    q, e = out if out is not None else (torch.empty(R, K // 2, device=x.device, dtype=torch.uint8),
+                                        torch.empty(R, K // 32, device=x.device, dtype=torch.uint8))
     L.check(L.load().avllm_mx4_quantize(L.ptr(x), _ld(x), R, K, L.ptr(q), K // 2, L.ptr(e), L.dt_of(x), L.stream_ptr()))
     return q, e
 

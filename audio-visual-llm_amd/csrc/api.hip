@@ -192,4 +192,6 @@ int avllm_act_residual(const void* x, const void* r, void* y, int64_t n, int32_t
 int avllm_step_advance(avllm_step_state* state, const avllm_schedule* sched, void* stream) { return av_step_advance(state, sched, ST); }
 int avllm_lora_pack(const float* A, const float* Bm, int32_t r, int32_t din, int32_t dout, void* A_pad, void* AT_pad, int64_t ld_at,
                     void* B_pad, void* BT_pad, int32_t dtype, void* stream) { return av_lora_pack(A, Bm, r, din, dout, A_pad, AT_pad, ld_at, B_pad, BT_pad, dtype, ST); }
+int avllm_lora_merge(void* W, int64_t ldw, int32_t N, int32_t K, const float* A, const float* B, int32_t r, float scale, int32_t dtype,
+                     void* stream) { return av_lora_merge(W, ldw, N, K, A, B, r, scale, dtype, ST); }
 }

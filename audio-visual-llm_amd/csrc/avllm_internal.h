@@ -82,6 +82,7 @@ int av_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr
                   const avllm_step_state* state, hipStream_t st);
 int av_lora_pack(const float* A, const float* Bm, int r, int din, int dout, void* A_pad, void* AT_pad, long ld_at,
                  void* B_pad, void* BT_pad, int dtype, hipStream_t st);
+int av_lora_merge(void* W, long ldw, int N, int K, const float* A, const float* B, int r, float scale, int dtype, hipStream_t st);
 int av_kv_append(const void* k, const void* v, long ld, void* kc, void* vc, int B, int T, int pos0, int Tmax, int d,
                  int dtype, hipStream_t st);
 int av_attention_decode(const void* q, long ldq, const void* kc, const void* vc, void* o, long ldo, int B, int H, int hd,

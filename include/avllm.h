@@ -450,6 +450,13 @@ typedef struct avllm_lora_pack_item {
     int64_t ld_at, dout;
 } avllm_lora_pack_item;
 int avllm_lora_pack_batch(const avllm_lora_pack_item* items_dev, int32_t n, int32_t r, int32_t din, int32_t dtype, void* stream);
+/* fold one LoRA pair into its frozen matrix, in place (decode-time merge, once per load): W[n,k] <- round(W[n,k] + scale * sum_{j<r} B[n*r+j] *
+ * A[j*K+k]).  W [N,K] in `dtype` (f32 or bf16), row stride ldw elements, 16-byte aligned, K % 8 == 0, ldw % 8 == 0; it may be a row slice of a
+ * larger matrix (k_proj inside wqkv).  A [r,K], B [N,r]: the contiguous fp32 masters (not the padded images), 1 <= r <= AVLLM_LORA_PAD.
+ * fp32 arithmetic: one fma chain over j ascending, one fma with scale and W, one round-to-nearest-even store; no atomics, so equal inputs give
+ * equal bytes.  scale == 0 leaves W untouched. */
+int avllm_lora_merge(void* W, int64_t ldw, int32_t N, int32_t K, const float* A, const float* B, int32_t r, float scale, int32_t dtype,
+                     void* stream);
 
 /* ---------------------------------------------------------------- input features on device ----------------
  * The reference builds the hot path's inputs on CPU workers, one sample at a time (src/clip_whisper/data/simple_dataset.py):

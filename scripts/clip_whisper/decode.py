@@ -18,7 +18,8 @@ passed as bad_words_ids), --hotwords FILE (one word or phrase per line) / --hotw
 path of a hotword; generate(hotwords=, hotword_bias=)), --nbest N (beam search returns the N best hypotheses of each utterance; needs
 --num_beams >= N; WER stays on the 1-best), --confidence (adds tokens, token_logprobs, avg_logprob and word_confidences of the 1-best to each
 utterance of the --output_file JSON, and with --nbest > 1 an nbest list of {hypothesis, score}), --min_avg_logprob F (utterances whose mean
-token log-probability is below F are listed in the log; they still count in the WER), --load_lora (also load the adapters from the checkpoint), --synthetic N / --tiny /
+token log-probability is below F are listed in the log; they still count in the WER), --load_lora (also load the adapters from the checkpoint), --merge_lora (with --load_lora: fold the loaded
+adapters into the LLM weights once, ClipWhisperModel.merge_lora(), so that decoding runs the adapter-free kernels), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -80,12 +81,16 @@ def parse_args(argv=None):
                    help="fp8: the KV cache is block-scaled e4m3 (33/64 of the bf16 bytes; needs bf16, token steps of at most 16 rows, else "
                         "the bf16 cache is used; effect on WER not measured)")
     p.add_argument("--load_lora", action="store_true")
+    p.add_argument("--merge_lora", action="store_true",
+                   help="with --load_lora: fold the adapters into the LLM weights after the checkpoint is loaded (effect on WER not measured)")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
     p.add_argument("--tiny", action="store_true")
     p.add_argument("--frames", type=int, default=125)
     p.add_argument("--synthetic-weights", action="store_true", help="seeded random weights + byte tokenizer (implied by --tiny)")
     a = p.parse_args(argv)
+    if a.merge_lora and not a.load_lora:
+        p.error("--merge_lora needs --load_lora: without it the model has no adapters to merge")
     if a.nbest < 1:
         p.error(f"--nbest must be at least 1, got {a.nbest}")
     if a.nbest > 1 and a.do_sample:
@@ -187,6 +192,9 @@ def main(argv=None):
         mc = ck.get("config") if isinstance(ck, dict) else None
         if isinstance(mc, dict):
             model.max_seq_len = mc.get("max_seq_len", 256); model.fusion_scale = mc.get("fusion_scale", 0.5)
+    if a.merge_lora:
+        model.merge_lora()
+        logging.info("LoRA adapters merged into the LLM weights")
 
     from avllm.tokenizer import phrase_token_ids
     bad_words = lines_of(a.bad_words)
