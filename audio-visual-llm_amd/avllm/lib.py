@@ -212,6 +212,7 @@ _SIGS = {
     "avllm_pos_advance": ([vp, i32, vp], i32),
     "avllm_dec_proj": ([C.POINTER(DecProjDesc), vp], i32),
     "avllm_gemm_f8_takes_quantised_output": ([C.POINTER(GemmF8Desc)], i32),
+    "avllm_gemm_f8_takes_fast": ([C.POINTER(GemmF8Desc)], i32),
     "avllm_norm_mxq": ([vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, f32, vp], i32),
     "avllm_lora_rank3": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, i32, vp], i32),
     "avllm_gemm_tn_multi": ([vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, i32, i32, vp], i32),

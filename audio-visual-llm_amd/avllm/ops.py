@@ -782,7 +782,7 @@ def lora_merge_(W, A, B, scale):
 def mx_quantize(x, layout=0, q=None, s=None):
     """x [R,K] bf16/f32 -> (q uint8 [R,K] e4m3, scale image uint8 tensor): OCP-MX block scaling, 32 elements per E8M0 scale.
     layout 0 = activation side, 1 = weight side of avllm_gemm_f8; layout 2 = decode side: the scales are the exponent matrix uint8 [R, K/32]
-    (E8M0 biased by 127) of dec_proj's fp8 weight form.  `q`: optional [R, K] uint8 output for the codes (the same for every layout); `s`: the
+    (E8M0 biased by 127) of dec_proj's fp8 weight form.  `q`: optional [R, K] uint8 output for the codes (the same for every layout; a column slice of a wider buffer passes its row stride); `s`: the
     scale image of an earlier call with the same shape and layout, rewritten in place (a weight that changed keeps its buffers)."""
     lib = L.load()
     R, K = x.shape
@@ -790,7 +790,7 @@ def mx_quantize(x, layout=0, q=None, s=None):
         q = torch.empty(R, K, device=x.device, dtype=torch.uint8)
     if s is None:
         s = torch.zeros((R, K // 32) if layout == 2 else lib.avllm_mx_scale_bytes(R, K), device=x.device, dtype=torch.uint8)
-    L.check(lib.avllm_mx_quantize(L.ptr(x), _ld(x), R, K, L.ptr(q), K, L.ptr(s), layout, L.dt_of(x), L.stream_ptr()))
+    L.check(lib.avllm_mx_quantize(L.ptr(x), _ld(x), R, K, L.ptr(q), _ld(q), L.ptr(s), layout, L.dt_of(x), L.stream_ptr()))
     return q, s
 
 
@@ -807,9 +807,11 @@ def mx4_quantize(x, out=None):
     return q, e
 
 
-def gemm_f8(Aq, As, Bq, Bs, out=None, bias=None, R=None, act=L.ACT_NONE, quantised_out=False):
+def gemm_f8(Aq, As, Bq, Bs, out=None, bias=None, R=None, act=L.ACT_NONE, quantised_out=False, plan=False):
     """out[M,N] (bf16) = act(A.B^T + bias) + R on the block-scaled fp8 matrix pipe; (Aq, As) / (Bq, Bs) from mx_quantize(layout 0 / 1).
-    quantised_out=True: returns (codes uint8 [M,N], scale image) = the e4m3 block-scaled result, quantised in the epilogue (no bf16 copy)."""
+    quantised_out=True: returns (codes uint8 [M,N], scale image) = the e4m3 block-scaled result, quantised in the epilogue (no bf16 copy).
+    plan=True: launches nothing and returns the kernel avllm_gemm_f8 would run this very call on: "fast" (the persistent 256x256 kernel) or
+    "ref" (the reference-grade one; with quantised_out that is a call avllm_gemm_f8 refuses)."""
     M, K = Aq.shape
     N = Bq.shape[0]
     d = L.GemmF8Desc()
@@ -820,6 +822,8 @@ def gemm_f8(Aq, As, Bq, Bs, out=None, bias=None, R=None, act=L.ACT_NONE, quantis
         q = torch.empty(M, N, device=Aq.device, dtype=torch.uint8)
         sc = torch.zeros(L.load().avllm_mx_scale_bytes(M, N), device=Aq.device, dtype=torch.uint8)
         d.Cq, d.SCq, d.ldcq = L.ptr(q), L.ptr(sc), N
+        if plan:
+            return "fast" if L.load().avllm_gemm_f8_takes_fast(C.byref(d)) else "ref"
         L.check(L.load().avllm_gemm_f8(C.byref(d), L.stream_ptr()))
         return q, sc
     if out is None:
@@ -827,19 +831,23 @@ def gemm_f8(Aq, As, Bq, Bs, out=None, bias=None, R=None, act=L.ACT_NONE, quantis
     d.C, d.ldc = L.ptr(out), _ld(out)
     if R is not None:
         d.R, d.ldr = L.ptr(R), _ld(R)
+    if plan:
+        return "fast" if L.load().avllm_gemm_f8_takes_fast(C.byref(d)) else "ref"
     L.check(L.load().avllm_gemm_f8(C.byref(d), L.stream_ptr()))
     return out
 
 
-def norm_mxq(x, w, b=None, eps=1e-5, want_y=False, want_rstd=False):
+def norm_mxq(x, w, b=None, eps=1e-5, want_y=False, want_rstd=False, q=None):
     """LayerNorm (b given) / RMSNorm (b None) of bf16 rows, block-scaled to e4m3 in the same pass (avllm_norm_mxq):
-    -> (codes uint8 [rows, d], scale image, y bf16 | None, rstd | None)."""
+    -> (codes uint8 [rows, d], scale image, y bf16 | None, rstd | None).  `q`: optional [rows, d] uint8 output for the codes; its row stride is
+    passed as ldq (a column slice of a wider buffer)."""
     rows, d = x.shape
-    q = torch.empty(rows, d, device=x.device, dtype=torch.uint8)
+    if q is None:
+        q = torch.empty(rows, d, device=x.device, dtype=torch.uint8)
     sc = torch.zeros(L.load().avllm_mx_scale_bytes(rows, d), device=x.device, dtype=torch.uint8)
     y = torch.empty_like(x) if want_y else None
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32) if want_rstd else None
-    L.check(L.load().avllm_norm_mxq(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(rstd), L.ptr(q), d, L.ptr(sc), rows, d, eps, L.stream_ptr()))
+    L.check(L.load().avllm_norm_mxq(L.ptr(x), L.ptr(w), L.ptr(b), L.ptr(y), L.ptr(rstd), L.ptr(q), _ld(q), L.ptr(sc), rows, d, eps, L.stream_ptr()))
     return q, sc, y, rstd
 
 

@@ -374,10 +374,13 @@ static bool f8_fast_takes(const avllm_gemm_f8_desc* d) {
     const bool aligned = (d->Cq || (uintptr_t)d->C % 16 == 0) && (!d->bias || (uintptr_t)d->bias % 16 == 0) && (!d->R || (uintptr_t)d->R % 16 == 0) && d->N % 8 == 0 &&
                          ((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0);
     const bool fits = (double)d->M * (double)d->lda < 4.0e9 && (double)d->N * (double)d->ldb < 4.0e9 && d->lda < (1 << 24) && d->ldb < (1 << 24);
-    const bool qok = !d->Cq || (d->SCq && !d->R && d->N % 32 == 0 && d->ldcq % 8 == 0 && (uintptr_t)d->Cq % 8 == 0);
+    // N % 128: the epilogue writes scale plane tn * 2 + wc per 128-column group, and avllm_mx_scale_bytes(M, N) holds N / 128 planes (a partial last
+    // group would land one plane past the image; its consumer needs K = N % 128 == 0 anyway)
+    const bool qok = !d->Cq || (d->SCq && !d->R && d->N % 128 == 0 && d->ldcq % 8 == 0 && (uintptr_t)d->Cq % 8 == 0);
     return !(off || d->M <= 128 || xtiles < 64 || d->K < 2 * KB || !aligned || !fits || !qok);
 }
 extern "C" int avllm_gemm_f8_takes_quantised_output(const avllm_gemm_f8_desc* d) { return d && d->Cq && f8_fast_takes(d) ? 1 : 0; }
+extern "C" int avllm_gemm_f8_takes_fast(const avllm_gemm_f8_desc* d) { return d && f8_fast_takes(d) ? 1 : 0; }
 
 int av_gemm_f8_fast(const avllm_gemm_f8_desc* d, hipStream_t st, bool* taken) {
     *taken = false;

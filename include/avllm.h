@@ -148,12 +148,15 @@ typedef struct avllm_gemm_f8_desc {
     int32_t act;
     /* Quantised output (the activation of the NEXT fp8 projection, e.g. fc1 -> fc2): when Cq != NULL the result act(A.B^T + bias) is
      * block-scaled to e4m3 in the epilogue, straight from the fp32 accumulators -- codes uint8 [M,N] (row stride ldcq bytes) + the layout-0
-     * scale image of avllm_mx_scale_bytes(M,N) bytes in SCq -- and the bf16 C is NOT written (C may be NULL; R must be NULL; N % 32 == 0).
+     * scale image of avllm_mx_scale_bytes(M,N) bytes in SCq -- and the bf16 C is NOT written (C may be NULL; R must be NULL; N % 128 == 0:
+     * the image holds N / 128 planes).
      * Only the persistent kernel implements it: AVLLM_ERR_UNSUPPORTED for calls it does not take (avllm_gemm_f8_takes_quantised_output). */
     void* Cq; void* SCq;
     int64_t ldcq;
 } avllm_gemm_f8_desc;
 int avllm_gemm_f8_takes_quantised_output(const avllm_gemm_f8_desc* d);
+/* 1 where avllm_gemm_f8 runs the call on the persistent 256x256 kernel, 0 where the reference-grade kernel takes it (or, with Cq, refuses). */
+int avllm_gemm_f8_takes_fast(const avllm_gemm_f8_desc* d);
 int avllm_gemm_f8(const avllm_gemm_f8_desc* d, void* stream);
 /* nn.LayerNorm (b != NULL; HF whisper / clip encoder layers) or LlamaRMSNorm (b == NULL) of bf16 rows with the result block-scaled to e4m3 in
  * the same pass: q uint8 [rows, d] (row stride ldq) + the layout-0 scale image, ready as the A operand of avllm_gemm_f8.  y (bf16 copy of the
