@@ -589,6 +589,15 @@ class LlamaEngine:
         shape = (self.cfg.layers, B, Tmax, self.dkv)
         return torch.empty(shape, dtype=self.dtype, device=self.device), torch.empty(shape, dtype=self.dtype, device=self.device)
 
+    def decode_shares_prefix(self, R):
+        """True when a token step of R rows can read a prefix stored once per item (decode_step_shared): exactly where decode_is_fused(R)."""
+        return bool(L.load().avllm_llama_decode_shares_prefix(C.byref(self.desc), R))
+
+    def alloc_suffix_cache(self, R, N):
+        """(K, V) suffix caches of a shared-prefix decode: R rows of N generated positions, in the form alloc_cache(..., rows=R) gives the
+        prefix cache they go with."""
+        return self.alloc_cache(R, N)
+
     def _cache_form(self, fp8):
         """Context manager: the descriptor's kv_fp8 says the form of the cache of the call inside, then is the engine's option again."""
         eng = self
@@ -636,4 +645,26 @@ class LlamaEngine:
         with self._cache_form(self._check_caches(kc, vc)):
             L.check(lib.avllm_llama_decode_step_at(C.byref(self.desc), L.ptr(ids.contiguous()), B, pos, L.ptr(pos_dev), L.ptr(kc), L.ptr(vc),
                                                    kc.shape[2], L.ptr(logits), L.ptr(ws), ws.numel(), L.stream_ptr()))
+        return logits
+
+    def decode_step_shared(self, ids, pos, k_prefix, v_prefix, k_suffix, v_suffix, group, pos_dev=None, logits=None):
+        """One token per row of R = B * group rows whose `group` rows per item share the item's prefix: k_prefix, v_prefix [layers, B, S, dkv]
+        are the caches prefill() wrote (exactly S positions; read only), k_suffix, v_suffix [layers, R, N, dkv] (alloc_suffix_cache) hold each
+        row's generated positions.  The token runs at position S + pos (+ *pos_dev) and its K/V go to suffix row pos.  Needs
+        decode_shares_prefix(R); only the attention launch differs from decode_step()."""
+        lib = L.load()
+        R = ids.shape[0]
+        fp8 = self._check_caches(k_suffix, v_suffix)
+        if self._check_caches(k_prefix, v_prefix) != fp8 or k_prefix.shape != v_prefix.shape or k_suffix.shape != v_suffix.shape:
+            raise ValueError("decode_step_shared: prefix and suffix caches must be K/V pairs of one form (alloc_cache(B, S, rows=R), alloc_suffix_cache(R, N))")
+        if group < 1 or k_prefix.shape[1] * group != R or k_suffix.shape[1] != R:
+            raise ValueError(f"decode_step_shared: {R} rows need a prefix cache of {R} / group rows and a suffix cache of {R} rows, got group = {group}, "
+                             f"{k_prefix.shape[1]} and {k_suffix.shape[1]}")
+        ws = self.ws_infer.get(lib.avllm_llama_decode_shared_workspace_bytes(C.byref(self.desc), R))
+        if logits is None:
+            logits = torch.empty(R, self.cfg.vocab, device=self.device, dtype=torch.float32)
+        with self._cache_form(fp8):
+            L.check(lib.avllm_llama_decode_step_shared(C.byref(self.desc), L.ptr(ids.contiguous()), R, group, pos, L.ptr(pos_dev), L.ptr(k_prefix),
+                                                       L.ptr(v_prefix), k_prefix.shape[2], L.ptr(k_suffix), L.ptr(v_suffix), k_suffix.shape[2],
+                                                       L.ptr(logits), L.ptr(ws), ws.numel(), L.stream_ptr()))
         return logits

@@ -77,12 +77,14 @@ class LogitsProcessors:
 
 def parse_arguments(tokenizer, vocab, eos, device, *, max_new_tokens, max_length, do_sample, temperature, top_k, top_p, seed, num_beams,
                     early_stopping, return_sequence_scores, repetition_penalty, no_repeat_ngram_size, min_new_tokens, sequence_bias,
-                    bad_words_ids, suppress_tokens, begin_suppress_tokens, hotwords, hotword_bias, num_return_sequences):
+                    bad_words_ids, suppress_tokens, begin_suppress_tokens, hotwords, hotword_bias, num_return_sequences, share_prefix=False):
     """generate()'s argument rules, all of them, before any GPU work but the processors' small tables: ValueError / NotImplementedError
     that name the argument and its limit.  Returns (max_new_tokens, num_return_sequences, sample, processors); sample is (temperature,
     top_k, top_p, seed) or None, and seed=None is drawn here, once, from torch's default CPU generator."""
     if max_new_tokens is None:
         max_new_tokens = max_length if max_length is not None else 100
+    if not isinstance(share_prefix, bool):
+        raise ValueError(f"share_prefix must be True or False, got {share_prefix!r}")
     if int(num_beams) != num_beams or num_beams < 1:
         raise ValueError(f"num_beams must be a positive integer, got {num_beams}")
     if num_beams > 1:
@@ -114,15 +116,31 @@ def parse_arguments(tokenizer, vocab, eos, device, *, max_new_tokens, max_length
         vocab=vocab, eos=eos, device=device, max_new_tokens=max_new_tokens)
 
 
-def token_loop(engine, x, eos, pad, max_new_tokens, processors, sample=None, token_scores=False):
+def shares_prefix(engine, share_prefix, rows, group):
+    """Whether a decode of `rows` rows, `group` per item, runs on one prefix cache per item: asked for, something to share, and the fused
+    token step (LlamaEngine.decode_shares_prefix).  Otherwise today's path, whose result is bit-equal to share_prefix=False."""
+    return bool(share_prefix) and group > 1 and engine.decode_shares_prefix(rows)
+
+
+def token_loop(engine, x, eos, pad, max_new_tokens, processors, sample=None, token_scores=False, group=1):
     """GenerationMixin's greedy search, or with sample = (temperature, top_k, top_p, seed) its sampling, for inputs_embeds x [B, S, d]: the
     prefill, then per token the processors, one selection step and the next decode step.  Returns the new tokens int64 [B, L], pad after a
     row's EOS, L <= max_new_tokens (the loop ends when every row has its EOS: one host sync per step, only with an EOS id); with
     token_scores a GenerateOutput: the chosen token's log-probability and its row's entropy (ops.row_scores, at the token step; no second
-    prefill), 0.0 for rows that were finished before the step."""
+    prefill), 0.0 for rows that were finished before the step.
+    group > 1 (sampled n-best on a shared prefix; the caller has asked shares_prefix): x holds each item ONCE, the prefill runs on its B rows
+    and the B * group rows of the loop (item-major, as x.repeat_interleave(group) would order them) read the item's prefix cache and keep
+    only their generated positions in a suffix cache (LlamaEngine.decode_step_shared).  Seeds, history and EOS stay per row."""
     B, S, _ = x.shape
-    kc, vc = engine.alloc_cache(B, S + max_new_tokens)
-    logits, _ = engine.prefill(x, kc, vc)
+    if group > 1:
+        kc0, vc0 = engine.alloc_cache(B, S, rows=B * group)
+        logits, _ = engine.prefill(x, kc0, vc0)
+        logits = logits.repeat_interleave(group, dim=0)
+        B *= group
+        kc, vc = engine.alloc_suffix_cache(B, max_new_tokens)
+    else:
+        kc, vc = engine.alloc_cache(B, S + max_new_tokens)
+        logits, _ = engine.prefill(x, kc, vc)
     unfinished = torch.ones(B, dtype=torch.bool, device=x.device)
     # the processors' history: row b's generated tokens (pad after its EOS, as HF feeds them); the kernel itself appends the last token
     hist = torch.full((B, max_new_tokens), pad, dtype=torch.int64, device=x.device) if processors.reads_history else None
@@ -162,13 +180,13 @@ def token_loop(engine, x, eos, pad, max_new_tokens, processors, sample=None, tok
             tok_ent.append(torch.where(alive, ent, torch.zeros_like(ent)))
         if step + 1 == max_new_tokens or (eos is not None and not bool(unfinished.any())):
             break
-        logits = engine.decode_step(nxt, S + step, kc, vc)
+        logits = engine.decode_step_shared(nxt, step, kc0, vc0, kc, vc, group) if group > 1 else engine.decode_step(nxt, S + step, kc, vc)
     seqs = torch.stack(out, dim=1)
     return GenerateOutput(seqs, None, torch.stack(tok_lp, dim=1), torch.stack(tok_ent, dim=1)) if token_scores else seqs
 
 
 def beam_search(engine, x, eos, pad, max_new_tokens, nb, length_penalty, early_stopping, processors, n_ret=1, return_scores=False,
-                token_scores=False):
+                token_scores=False, share_prefix=False):
     """GenerationMixin._beam_search (transformers 5.x, generation/utils.py) for inputs_embeds x [B, S, d]: decoder_prompt_len = 0, so a
     hypothesis of n tokens (its EOS included) is normalised by n ** length_penalty, and max_length = max_new_tokens.  Per token step:
     the B*nb-row decode step, ops.beam_topk (log_softmax + _get_top_k_continuations, k = 2*nb), HF's bookkeeping
@@ -184,16 +202,24 @@ def beam_search(engine, x, eos, pad, max_new_tokens, nb, length_penalty, early_s
     with pad; with return_scores also HF's sequences_scores [B*n_ret]; with token_scores a GenerateOutput: every candidate's own
     log-probability, read from the row it came from (the processed log-probability with processors on; logit - logsumexp of the raw row
     otherwise, ops.row_scores), and that row's entropy ride with the sequences as payloads [B, nb, N] through every reordering.  Never
-    derived as topk_lp - running_scores[parent]: that difference loses the low bits of a long hypothesis."""
+    derived as topk_lp - running_scores[parent]: that difference loses the low bits of a long hypothesis.
+    share_prefix (and shares_prefix(engine, ..., B*nb, nb)): no broadcast; the B-row prefill cache stays the prefix of every beam, the R rows
+    keep only their generated positions [0, N) in a suffix cache, which is what the reordering moves, and the step is
+    LlamaEngine.decode_step_shared.  More than 16 rows, fp32, or the fused step switched off: the path above, bit for bit."""
     dev = x.device
     B, S, _ = x.shape
     R, k, N = B * nb, 2 * nb, max_new_tokens
     kc0, vc0 = engine.alloc_cache(B, S, rows=R)                 # in the form of the R-row cache it is broadcast into
     logits, _ = engine.prefill(x, kc0, vc0)
-    kc, vc = engine.alloc_cache(R, S + N)
+    share = shares_prefix(engine, share_prefix, R, nb)
+    # shared: kc0 / vc0 stay the items' prefix, the R rows keep their generated positions [0, N) alone; else the prefix is broadcast into [0, S)
+    # of an R-row cache whose generated positions start at g0 = S
+    kc, vc = engine.alloc_suffix_cache(R, N) if share else engine.alloc_cache(R, S + N)
+    g0 = 0 if share else S
     gather_rows = ops.kv8_gather_rows if kc.dtype == torch.uint8 else ops.kv_gather_rows      # fp8 images: codes and exponents together
-    gather_rows(kc0, vc0, kc, vc, torch.arange(R, device=dev, dtype=torch.int32) // nb, 0, S)    # prefix broadcast
-    del kc0, vc0
+    if not share:
+        gather_rows(kc0, vc0, kc, vc, torch.arange(R, device=dev, dtype=torch.int32) // nb, 0, S)    # prefix broadcast
+        del kc0, vc0
     logits = logits.repeat_interleave(nb, dim=0)                # step 0: every beam of an item sees the prefill logits
     NEG = -1.0e9
     # the per-hypothesis payloads of the running beams, and (fin) of the finished ones
@@ -259,8 +285,9 @@ def beam_search(engine, x, eos, pad, max_new_tokens, nb, length_penalty, early_s
         done_host.copy_(done.view(1), non_blocking=True)
         ev.record()
         # the next token step is queued before the host waits on the stopping test (only the small copy above is awaited)
-        gather_rows(kc, vc, kc, vc, parent.view(-1).to(torch.int32), S, S + cur)
-        logits = engine.decode_step(run["seq"][:, :, cur].reshape(-1), S + cur, kc, vc)
+        gather_rows(kc, vc, kc, vc, parent.view(-1).to(torch.int32), g0, g0 + cur)
+        ids = run["seq"][:, :, cur].reshape(-1)
+        logits = engine.decode_step_shared(ids, cur, kc0, vc0, kc, vc, nb) if share else engine.decode_step(ids, S + cur, kc, vc)
         ev.synchronize()
         if bool(done_host[0]):
             break

@@ -204,6 +204,13 @@ _SIGS = {
     "avllm_llama_decode_streams_fp8": ([C.POINTER(Llama), i32], i32),
     "avllm_llama_decode_streams_fp4": ([C.POINTER(Llama), i32], i32),
     "avllm_llama_decode_caches_fp8": ([C.POINTER(Llama), i32], i32),
+    "avllm_llama_decode_shared_workspace_bytes": ([C.POINTER(Llama), i32], sz),
+    "avllm_llama_decode_step_shared": ([C.POINTER(Llama), vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, sz, vp], i32),
+    "avllm_llama_decode_shares_prefix": ([C.POINTER(Llama), i32], i32),
+    "avllm_attention_decode_shared_workspace_bytes": ([i32, i32, i32], sz),
+    "avllm_attention_decode_shared": ([vp, i64, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, i64, i32, i32, i32, i32, f32, i32, vp, sz, vp], i32),
+    "avllm_attention_decode_shared_kv8": ([vp, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, i64, i32, i32, i32, i32, f32, i32, vp, sz,
+                                           vp], i32),
     "avllm_llama_kv_cache_bytes": ([C.POINTER(Llama), i32, i32], sz),
     "avllm_kv8_append": ([vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     "avllm_kv8_rope_append": ([vp, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp], i32),

@@ -26,7 +26,7 @@ from . import ops
 from .arch import ModelCfg, resolve_arch
 from .connector import ModalityConnector, create_modality_connector
 from .engine import ClipEngine, LlamaEngine, WhisperEngine
-from .generation import GenerateOutput, beam_search, hotword_sequence_bias, parse_arguments, token_loop  # noqa: F401  (the first and third are re-exported)
+from .generation import GenerateOutput, beam_search, hotword_sequence_bias, parse_arguments, shares_prefix, token_loop  # noqa: F401  (the first and third are re-exported)
 from .tokenizer import load_tokenizer
 
 
@@ -484,7 +484,7 @@ class ClipWhisperModel:
                  temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                  return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sequence_bias=None,
                  bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, hotwords=None, hotword_bias=0.0,
-                 return_token_scores=False, num_return_sequences=1):
+                 return_token_scores=False, num_return_sequences=1, share_prefix=False):
         """clip_whisper_model.py:1240-1348 -> GenerationMixin's greedy search, sampling or beam search on the fused inputs (avllm/generation.py).
         Returns NEW tokens only, int64 [B, <= max_new_tokens], pad_token_id after a row's EOS.  With every keyword at its default nothing but
         the greedy loop is launched or allocated.  video is also taken as pixel_values; max_new_tokens=None means max_length, else 100.
@@ -514,7 +514,15 @@ class ClipWhisperModel:
           beam scorer added it (processed, with processors on), carried through the beam reorderings; sequences_scores as HF.
         num_return_sequences=n: HF's keyword: rows [B*n, L], item-major; beam search returns the n best hypotheses of each item, best first
           (n <= num_beams); sampling draws n sequences per clip (encoders and connectors run once per clip; the result equals a call on the
-          clips repeated n times); greedy decoding with n > 1 is a ValueError, as in HF."""
+          clips repeated n times); greedy decoding with n > 1 is a ValueError, as in HF.
+        share_prefix=True: the beams of an item (num_beams > 1), or its n sampled sequences (num_return_sequences = n > 1), read ONE copy of
+          the item's prefix -- the B-row cache of the prefill, which for sampling then runs on B rows, not B*n -- and keep only their own
+          generated positions in a suffix cache of max_new_tokens rows (csrc/attention_decode_shared.hip): a memory saving first (B*S + R*N
+          cached positions for R*(S + N)), and fewer cache bytes read per step.  The keys and values every row attends are the same; sums
+          are taken in another order, so scores agree to bf16 rounding, not bit for bit.  It goes with the fused token step
+          (LlamaEngine.decode_shares_prefix: at most 16 rows, bf16, head dim 64 or 128): with more rows, precision="fp32" or the fused step
+          switched off, and for greedy decoding and n = 1 sampling, which have nothing to share, the keyword is accepted and the call takes
+          the default path, bit-equal to share_prefix=False."""
         if video is None and pixel_values is not None:
             video = pixel_values
         eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
@@ -523,7 +531,8 @@ class ClipWhisperModel:
             temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, num_beams=num_beams, early_stopping=early_stopping,
             return_sequence_scores=return_sequence_scores, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
             min_new_tokens=min_new_tokens, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
-            begin_suppress_tokens=begin_suppress_tokens, hotwords=hotwords, hotword_bias=hotword_bias, num_return_sequences=num_return_sequences)
+            begin_suppress_tokens=begin_suppress_tokens, hotwords=hotwords, hotword_bias=hotword_bias, num_return_sequences=num_return_sequences,
+            share_prefix=share_prefix)
         original = self.modality
         if audio is not None and video is not None:
             self.modality = "both"
@@ -537,7 +546,10 @@ class ClipWhisperModel:
             self.modality = original
         if num_beams > 1:
             return beam_search(self.llm_engine, x, eos, pad, max_new_tokens, int(num_beams), float(length_penalty), early_stopping,
-                               processors, n_ret=n_ret, return_scores=return_sequence_scores, token_scores=bool(return_token_scores))
-        if n_ret > 1:
+                               processors, n_ret=n_ret, return_scores=return_sequence_scores, token_scores=bool(return_token_scores),
+                               share_prefix=share_prefix)
+        group = n_ret if shares_prefix(self.llm_engine, share_prefix, x.shape[0] * n_ret, n_ret) else 1
+        if n_ret > 1 and group == 1:
             x = x.repeat_interleave(n_ret, dim=0)                   # after the encoders and connectors, which ran once per clip
-        return token_loop(self.llm_engine, x, eos, pad, max_new_tokens, processors, sample=sample, token_scores=bool(return_token_scores))
+        return token_loop(self.llm_engine, x, eos, pad, max_new_tokens, processors, sample=sample, token_scores=bool(return_token_scores),
+                          group=group)

@@ -979,6 +979,55 @@ def attention_decode_kv8(q, kc, vc, H, Tk, tk_dev=None, scale=None):
     return o
 
 
+def _shared_args(name, q, k_prefix, v_prefix, S, k_suffix, v_suffix, H, n, group, tk_dev):
+    """The checks both cache forms of attention_decode_shared share -> (R, hd, N, workspace)."""
+    if q.dim() != 2 or q.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: q must be bf16 [R, H*hd], got {tuple(q.shape)} {q.dtype}")
+    R, hd = q.shape[0], q.shape[1] // H
+    for what, t, rows in (("k_prefix", k_prefix, None), ("v_prefix", v_prefix, None), ("k_suffix", k_suffix, R), ("v_suffix", v_suffix, R)):
+        if t.dim() != 3 or not t.is_contiguous() or (rows is not None and t.shape[0] != rows):
+            raise ValueError(f"{name}: {what} must be a contiguous cache [{'R' if rows else 'B'}, T, dkv], got {tuple(t.shape)}")
+    if k_prefix.shape != v_prefix.shape or k_suffix.shape != v_suffix.shape or k_prefix.dtype != k_suffix.dtype:
+        raise ValueError(f"{name}: the K and V caches of the prefix, and of the suffix, must have one shape each and all one dtype")
+    if group < 1 or R != k_prefix.shape[0] * group:
+        raise ValueError(f"{name}: group = {group} rows per item of the {k_prefix.shape[0]}-row prefix cache, but q has {R} rows")
+    N = k_suffix.shape[1]
+    if tk_dev is None and not 0 <= n < N:
+        raise ValueError(f"{name}: n = {n} outside the suffix cache (N = {N})")
+    ws = torch.empty(L.load().avllm_attention_decode_shared_workspace_bytes(R, H, hd), dtype=torch.uint8, device=q.device)
+    return R, hd, N, ws
+
+
+def attention_decode_shared(q, k_prefix, v_prefix, S, k_suffix, v_suffix, H, n, group, tk_dev=None, scale=None):
+    """q [R, H*hd] bf16, R = B*group; k_prefix, v_prefix [B, Tp, Hkv*hd]; k_suffix, v_suffix [R, N, Hkv*hd] -> [R, H*hd]: row r attends rows
+    [0, S) of item r // group of the prefix cache, then rows [0, n] (+ *tk_dev, clamped to N) of its own suffix rows
+    (avllm_attention_decode_shared)."""
+    R, hd, N, ws = _shared_args("attention_decode_shared", q, k_prefix, v_prefix, S, k_suffix, v_suffix, H, n, group, tk_dev)
+    if k_prefix.dtype != torch.bfloat16:
+        raise ValueError(f"attention_decode_shared: caches must be bf16 (fp8 images: attention_decode_shared_kv8), got {k_prefix.dtype}")
+    Hkv = k_prefix.shape[2] // hd
+    o = torch.empty_like(q)
+    L.check(L.load().avllm_attention_decode_shared(L.ptr(q), _ld(q), L.ptr(k_prefix), L.ptr(v_prefix), S, k_prefix.shape[1], L.ptr(k_suffix), L.ptr(v_suffix),
+                                                   n + 1, L.ptr(tk_dev), N, L.ptr(o), _ld(o), R, group, H, hd,
+                                                   float(scale if scale is not None else hd ** -0.5), H // Hkv, L.ptr(ws), ws.numel(), L.stream_ptr()))
+    return o
+
+
+def attention_decode_shared_kv8(q, k_prefix, v_prefix, S, k_suffix, v_suffix, H, n, group, tk_dev=None, scale=None):
+    """attention_decode_shared over fp8 images: k_prefix, v_prefix of [B, Tp, Hkv*hd], k_suffix, v_suffix of [R, N, Hkv*hd]
+    (avllm_attention_decode_shared_kv8)."""
+    R, hd, N, ws = _shared_args("attention_decode_shared_kv8", q, k_prefix, v_prefix, S, k_suffix, v_suffix, H, n, group, tk_dev)
+    Hkv = kv8_dkv(k_prefix) // hd
+    if kv8_dkv(k_suffix) != Hkv * hd:
+        raise ValueError("attention_decode_shared_kv8: prefix and suffix images differ in dkv")
+    o = torch.empty_like(q)
+    L.check(L.load().avllm_attention_decode_shared_kv8(L.ptr(q), _ld(q), *_kv8_planes(k_prefix), *_kv8_planes(v_prefix), S, k_prefix.shape[1],
+                                                       *_kv8_planes(k_suffix), *_kv8_planes(v_suffix), n + 1, L.ptr(tk_dev), N, L.ptr(o), _ld(o), R, group, H,
+                                                       hd, float(scale if scale is not None else hd ** -0.5), H // Hkv, L.ptr(ws), ws.numel(),
+                                                       L.stream_ptr()))
+    return o
+
+
 def kv8_gather_rows(k_src, v_src, k_dst, v_dst, parent, t0, t1):
     """kv_gather_rows on fp8 images of [layers, rows, T, dkv]: codes and exponents of positions [t0, t1) move together
     (avllm_kv8_gather_rows)."""

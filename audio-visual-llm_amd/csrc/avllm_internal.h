@@ -95,6 +95,14 @@ int av_kv8_rope_append(void* qkv, long ld, int B, int H, int Hkv, int hd, const 
                        int pos, const int* pos_dev, hipStream_t st);
 int av_attention_decode_kv8(const void* q, long ldq, const void* kq, const void* ke, const void* vq, const void* ve, void* o, long ldo, int B, int H, int hd,
                             int Tk, const int* tk_dev, int Tmax, float scale, int G, hipStream_t st);
+// shared-prefix single-token attention (attention_decode_shared.hip): R = B group rows; row r attends prefix rows [0, S) of item r / group in the
+// B-row cache [B, Tp, dkv], then its own suffix rows [0, Tk + *tk_dev) (clamped to N) of [R, N, dkv].  bf16; ws: av_attention_decode_shared_ws bytes
+size_t av_attention_decode_shared_ws(int R, int H, int hd);
+int av_attention_decode_shared(const void* q, long ldq, const void* kp, const void* vp, int S, int Tp, const void* ks, const void* vs, int Tk, const int* tk_dev,
+                               int N, void* o, long ldo, int R, int group, int H, int hd, float scale, int GQ, void* ws, size_t ws_bytes, hipStream_t st);
+int av_attention_decode_shared_kv8(const void* q, long ldq, const void* kpq, const void* kpe, const void* vpq, const void* vpe, int S, int Tp, const void* ksq,
+                                   const void* kse, const void* vsq, const void* vse, int Tk, const int* tk_dev, int N, void* o, long ldo, int R, int group, int H,
+                                   int hd, float scale, int GQ, void* ws, size_t ws_bytes, hipStream_t st);
 int av_kv8_gather_rows(const void* k_src, const void* v_src, int src_rows, long src_T, void* k_dst, void* v_dst, int dst_rows, long dst_T, int layers,
                        int dkv, const int32_t* parent, int t0, int t1, hipStream_t st);
 int av_norm_mxq(const void* x, const void* w, const void* b, void* y, float* rstd_out, void* q, long ldq, void* scales, long rows, int d, float eps,

@@ -22,9 +22,10 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 // A/B switches (tools/*_bench.py, the tests that compare two forms of one computation): ONE table in api.hip, filled once per process
 // from the environment (AVLLM_<NAME>) at first use and changed afterwards only through avllm_set_knob(name, value) -- never a getenv per
 // layer or per launch.  Knobs that change what a production kernel computes or stores (GEMM_DBG) exist only in builds made with
-// -DAVLLM_EXPERIMENT_KNOBS.
+// -DAVLLM_EXPERIMENT_KNOBS; a knob that picks among the launch forms a dispatcher picks by itself at other shapes (GEMM_VARIANT, ATTN_SHORT,
+// SHARED_SPLIT: the same computation in another fp32 summation order) is read in every build.
 enum AvKnob { AV_KNOB_DECODE_FUSED, AV_KNOB_DEC_AL, AV_KNOB_LORA_UNBATCHED, AV_KNOB_F8_UNFUSED_QUANT, AV_KNOB_F8_FAST, AV_KNOB_ATTN_SHORT,
-              AV_KNOB_NARROW_EPILOGUE, AV_KNOB_TN_CHUNK, AV_KNOB_GEMM_DBG, AV_KNOB_GEMM_GW, AV_KNOB_GEMM_VARIANT, AV_KNOB_COUNT };
+              AV_KNOB_NARROW_EPILOGUE, AV_KNOB_TN_CHUNK, AV_KNOB_GEMM_DBG, AV_KNOB_GEMM_GW, AV_KNOB_GEMM_VARIANT, AV_KNOB_SHARED_SPLIT, AV_KNOB_COUNT };
 int av_knob(int id);
 
 // ---- status / error string (thread local), SURVEY.md §8b "Errors" row

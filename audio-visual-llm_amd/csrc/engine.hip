@@ -767,8 +767,12 @@ static void dec_weights(const avllm_llama* m, avllm_dec_proj_desc& p, int K, con
     if (m->decode_fp4) { p.W4 = W4; p.E8 = E4; p.ldw = K / 2; }
 }
 
+// The prefix of a shared-prefix token step (avllm_llama_decode_step_shared): the step's B rows are `group` rows per item of the rows-row cache
+// kp / vp [layers, rows, S, dkv] the prefill wrote; kc / vc of the layer function are then the suffix caches, Tmax their N, pos the suffix row.
+struct SharedPrefix { const void *kp, *vp; int rows, S, group; void* ws; size_t ws_bytes; };
+
 static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w, int B, int pos, const int* pos_dev, void* kc, void* vc, int Tmax,
-                                    hipStream_t st) {
+                                    hipStream_t st, const SharedPrefix* sp = nullptr) {
     const avllm_llama_layer& P = m->layer[l];
     const int d = m->d, f = m->ffn, H = m->heads, hd = d / H, Hkv = llama_kv_heads(m), dkv = llama_dkv(m), qw = llama_qw(m);
     char* kcl = (char*)kc + (size_t)l * B * Tmax * dkv * 2;
@@ -802,10 +806,20 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
         if (P.q_norm_w) AV_TRY(av_qk_norm_rope(w.qkv, qw, B, 1, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, nullptr, nullptr, 0, 0,
                                                nullptr, AV_BF16, st));
         AV_TRY(av_kv8_rope_append(w.qkv, qw, B, H, Hkv, hd, w.rope_tab, P.q_norm_w == nullptr, c.kq, c.ke, c.vq, c.ve, Tmax, pos, pos_dev, st));
+        if (sp) {
+            const Kv8Layer c0 = kv8_layer(m, const_cast<void*>(sp->kp), const_cast<void*>(sp->vp), l, sp->rows, sp->S);
+            AV_TRY(av_attention_decode_shared_kv8(w.qkv, qw, c0.kq, c0.ke, c0.vq, c0.ve, sp->S, sp->S, c.kq, c.ke, c.vq, c.ve, pos + 1, pos_dev, Tmax, w.att, d, B,
+                                                  sp->group, H, hd, 1.0f / sqrtf((float)hd), H / Hkv, sp->ws, sp->ws_bytes, st));
+        } else
         AV_TRY(av_attention_decode_kv8(w.qkv, qw, c.kq, c.ke, c.vq, c.ve, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), H / Hkv, st));
     } else {
         if (P.q_norm_w) AV_TRY(av_qk_norm_rope(w.qkv, qw, B, 1, H, Hkv, hd, P.q_norm_w, P.k_norm_w, m->eps, w.rope_tab, nullptr, nullptr, kcl, vcl, Tmax, pos,
                                                pos_dev, AV_BF16, st));
+        if (sp) {
+            const size_t off = (size_t)l * sp->rows * sp->S * dkv * 2;
+            AV_TRY(av_attention_decode_shared(w.qkv, qw, (const char*)sp->kp + off, (const char*)sp->vp + off, sp->S, sp->S, kcl, vcl, pos + 1, pos_dev, Tmax, w.att,
+                                              d, B, sp->group, H, hd, 1.0f / sqrtf((float)hd), H / Hkv, sp->ws, sp->ws_bytes, st));
+        } else
         AV_TRY(av_attention_decode1(w.qkv, qw, kcl, vcl, w.att, d, B, H, hd, pos + 1, pos_dev, Tmax, 1.0f / sqrtf((float)hd), AV_BF16, st, H / Hkv));
     }
     p = {};
@@ -828,6 +842,22 @@ static int llama_decode_layer_fused(const avllm_llama* m, int l, LlamaInferWs& w
     return av_dec_proj(&p, st);
 }
 
+// final norm + lm_head of a token step -> logits [B, vocab] f32.  fold: the norm rides in the lm_head stream (fused step, where dec_proj takes the vocab)
+static int llama_decode_head(const avllm_llama* m, LlamaInferWs& w, int B, float* logits, bool fold, hipStream_t st) {
+    const int dt = m->dtype, d = m->d;
+    if (fold && av_dec_proj_supported(AV_BF16, B, d, m->vocab, 0, 0)) {
+        avllm_dec_proj_desc p = {};
+        p.A = w.x; p.lda = d; p.W = m->lm_head; p.ldw = d; p.norm_w = m->norm_w; p.eps = m->eps; p.M = B; p.K = d; p.N = m->vocab; p.mode = 0;
+        p.C = logits; p.ldc = m->vocab; p.out_f32 = 1;
+        if (m->decode_fp8 || m->decode_fp4) { p.W8 = m->lm_head8; p.E8 = m->elm_head8; }      // decode_fp4: lm_head stays e4m3
+        return av_dec_proj(&p, st);
+    }
+    AV_TRY(av_rmsnorm_fwd(w.x, m->norm_w, w.xn, nullptr, B, d, m->eps, dt, st));
+    avllm_gemm_desc g = gemm_desc(dt, w.xn, d, m->lm_head, d, logits, m->vocab, B, m->vocab, d);
+    g.out_f32 = 1;
+    return av_gemm(&g, st);
+}
+
 extern "C" int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* ids, int32_t B, int32_t pos, const int32_t* pos_dev, void* kcache,
                                           void* vcache, int32_t Tmax, float* logits, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -841,25 +871,55 @@ extern "C" int avllm_llama_decode_step_at(const avllm_llama* m, const int64_t* i
     AV_TRY(av_embedding(m->embed, ids, w.x, B, d, dt, st));
     AV_CHECK_ARG(!m->kv_fp8 || llama_decode_fused_ok(m, B),
                  "llama_decode_step: kv_fp8 needs the fused token step (bf16, B <= 16 (B=%d), head dim 64 or 128): see avllm_llama_decode_caches_fp8", B);
-    if (llama_decode_fused_ok(m, B)) {
+    const bool fused = llama_decode_fused_ok(m, B);
+    if (fused) {
         AV_TRY(av_rope_table(w.rope_tab, 1, d / m->heads, pos, m->theta, st, pos_dev, llama_rope_scale(m)));
         for (int l = 0; l < m->layers; ++l) AV_TRY(llama_decode_layer_fused(m, l, w, B, pos, pos_dev, kcache, vcache, Tmax, st));
-        if (av_dec_proj_supported(AV_BF16, B, d, m->vocab, 0, 0)) {          // final norm folded into the lm_head stream
-            avllm_dec_proj_desc p = {};
-            p.A = w.x; p.lda = d; p.W = m->lm_head; p.ldw = d; p.norm_w = m->norm_w; p.eps = m->eps; p.M = B; p.K = d; p.N = m->vocab; p.mode = 0;
-            p.C = logits; p.ldc = m->vocab; p.out_f32 = 1;
-            if (m->decode_fp8 || m->decode_fp4) { p.W8 = m->lm_head8; p.E8 = m->elm_head8; }      // decode_fp4: lm_head stays e4m3
-            return av_dec_proj(&p, st);
-        }
     } else {
         AV_CHECK_ARG(!pos_dev, "llama_decode_step: a device-side position needs the fused bf16 token step (B <= 16, adapters of rank <= 16 or none)");
         for (int l = 0; l < m->layers; ++l) AV_TRY(llama_infer_layer(m, l, w, B, 1, pos, kcache, vcache, Tmax, st));
     }
-    AV_TRY(av_rmsnorm_fwd(w.x, m->norm_w, w.xn, nullptr, B, d, m->eps, dt, st));
-    avllm_gemm_desc g = gemm_desc(dt, w.xn, d, m->lm_head, d, logits, m->vocab, B, m->vocab, d);
-    g.out_f32 = 1;
-    return av_gemm(&g, st);
+    return llama_decode_head(m, w, B, logits, fused, st);
 }
+
+// The token step of R = B group rows whose items' prefixes [0, S) are stored once (k_prefix / v_prefix: the R / group-row cache of S positions the
+// prefill wrote).  Fused path only.  Only the attention launch differs from avllm_llama_decode_step_at: the RoPE table is that of position
+// S + pos, the cache row written is `pos` of the suffix caches [layers, R, N, dkv] (both + *pos_dev), by the same writers.
+extern "C" size_t avllm_llama_decode_shared_workspace_bytes(const avllm_llama* m, int32_t R) {
+    Bump b(nullptr, (size_t)-1);
+    LlamaInferWs w;
+    carve_llama_infer(m, R, 1, b, w, true);
+    b.take(av_attention_decode_shared_ws(R, m->heads, m->d / m->heads));
+    return bump_size(b);
+}
+
+extern "C" int avllm_llama_decode_step_shared(const avllm_llama* m, const int64_t* ids, int32_t R, int32_t group, int32_t pos, const int32_t* pos_dev,
+                                              const void* k_prefix, const void* v_prefix, int32_t S, void* k_suffix, void* v_suffix, int32_t N, float* logits,
+                                              void* ws, size_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    AV_TRY(check_llama(m));
+    AV_CHECK_ARG(ids && logits && ws, "llama_decode_step_shared: ids, logits or ws is null");
+    AV_CHECK_ARG(k_prefix && v_prefix && S > 0, "llama_decode_step_shared: k_prefix / v_prefix null or S=%d not positive", S);
+    AV_CHECK_ARG(k_suffix && v_suffix && N > 0, "llama_decode_step_shared: k_suffix / v_suffix null or N=%d not positive", N);
+    AV_CHECK_ARG(R > 0 && group > 0 && R % group == 0, "llama_decode_step_shared: R=%d rows must be whole groups of group=%d", R, group);
+    AV_CHECK_ARG(pos >= 0 && (pos_dev || pos < N), "llama_decode_step_shared: pos=%d outside the suffix cache (N=%d)", pos, N);
+    AV_CHECK_ARG(llama_decode_fused_ok(m, R),
+                 "llama_decode_step_shared: needs the fused token step (bf16, R <= 16 (R=%d), head dim 64 or 128): see avllm_llama_decode_shares_prefix", R);
+    Bump b(ws, ws_bytes);
+    LlamaInferWs w;
+    carve_llama_infer(m, R, 1, b, w, true);
+    SharedPrefix sp = {k_prefix, v_prefix, R / group, S, group, nullptr, av_attention_decode_shared_ws(R, m->heads, m->d / m->heads)};
+    sp.ws = b.take(sp.ws_bytes);
+    if (!b.ok) return av_set_error(AV_ERR_WORKSPACE, "llama_decode_step_shared: workspace %zu < %zu bytes", ws_bytes, bump_size(b));
+    const int d = m->d;
+    AV_TRY(av_embedding(m->embed, ids, w.x, R, d, m->dtype, st));
+    AV_TRY(av_rope_table(w.rope_tab, 1, d / m->heads, S + pos, m->theta, st, pos_dev, llama_rope_scale(m)));
+    for (int l = 0; l < m->layers; ++l) AV_TRY(llama_decode_layer_fused(m, l, w, R, pos, pos_dev, k_suffix, v_suffix, N, st, &sp));
+    return llama_decode_head(m, w, R, logits, true, st);
+}
+
+// sharing goes with the fused step, as the weight and cache forms do
+extern "C" int avllm_llama_decode_shares_prefix(const avllm_llama* m, int32_t R) { return m && check_llama(m) == AV_OK && llama_decode_fused_ok(m, R) ? 1 : 0; }
 
 extern "C" int avllm_llama_decode_is_fused(const avllm_llama* m, int32_t B) { return m && check_llama(m) == AV_OK && llama_decode_fused_ok(m, B) ? 1 : 0; }
 // decode_fp8 is honoured on the fused path only (check_llama guarantees vocab % 16 == 0, so lm_head is folded there too); B > 16 and a

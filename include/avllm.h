@@ -76,7 +76,8 @@ int avllm_set_gemm_variant(int v);
  * "DEC_AL" (force an activation-load form of avllm_dec_proj: 2 | 4), "LORA_UNBATCHED" (1 = one launch per adapter), "F8_UNFUSED_QUANT"
  * (1 = separate quantiser passes), "F8_FAST" (0 = reference-grade fp8 GEMM), "ATTN_SHORT" (0 = general attention kernel for T <= 272),
  * "NARROW_EPILOGUE", "TN_CHUNK", "GEMM_VARIANT" (avllm_set_gemm_variant above), "GEMM_GW" (tile-column group width of the persistent GEMM's walk on tall shapes: 0 = row-major walk,
- * n = groups of n columns), "GEMM_DBG" (only read by builds made with -DAVLLM_EXPERIMENT_KNOBS).  Unknown name -> error. */
+ * n = groups of n columns), "GEMM_DBG" (only read by builds made with -DAVLLM_EXPERIMENT_KNOBS), "SHARED_SPLIT" (A/B testing: forces the launch form
+ * of avllm_attention_decode_shared: 1 .. 16 = two launches with that many prefix slices, -1 = one launch; 0 = its own choice).  Unknown name -> error. */
 int avllm_set_knob(const char* name, int32_t value);
 int avllm_get_knob(const char* name, int32_t* value);      /* the value in force (to put it back after an A/B block) */
 
@@ -677,6 +678,19 @@ int avllm_llama_decode_streams_fp4(const avllm_llama* m, int32_t B);
 /* 1 when a token step of B sequences reads and writes the fp8 cache image (kv_fp8 set and the fused path taken), 0 otherwise: the caller
  * decides the cache's form with it when it allocates (more rows, or the fused path switched off: kv_fp8 = 0 and the bf16 cache). */
 int avllm_llama_decode_caches_fp8(const avllm_llama* m, int32_t B);
+/* The token step of R = B * group rows whose `group` rows per item (beams, or sampled sequences) share the item's prefix.  k_prefix / v_prefix
+ * [layers][B][S][dkv] is the cache avllm_llama_prefill wrote for the B items (Tmax = S), read only; k_suffix / v_suffix [layers][R][N][dkv] hold
+ * each row's own generated positions.  The token of row r runs at position S + pos (+ *pos_dev), its K/V go to suffix row pos (+ *pos_dev; a
+ * device-side row outside [0, N) writes nothing), and it attends prefix rows [0, S) of item r / group followed by suffix rows [0, pos] of row
+ * r (the device-side length is clamped to N).  Fused path only (avllm_llama_decode_shares_prefix), else AV_ERR_ARG; caches in the model's form
+ * (kv_fp8: both are images).  Only the attention launch differs from avllm_llama_decode_step_at (avllm_attention_decode_shared).
+ * ws: avllm_llama_decode_shared_workspace_bytes(m, R) bytes. */
+size_t avllm_llama_decode_shared_workspace_bytes(const avllm_llama* m, int32_t R);
+int avllm_llama_decode_step_shared(const avllm_llama* m, const int64_t* ids, int32_t R, int32_t group, int32_t pos, const int32_t* pos_dev,
+                                   const void* k_prefix, const void* v_prefix, int32_t S, void* k_suffix, void* v_suffix, int32_t N, float* logits,
+                                   void* ws, size_t ws_bytes, void* stream);
+/* 1 when a token step of R rows can share prefixes: exactly where avllm_llama_decode_is_fused(m, R) is 1. */
+int avllm_llama_decode_shares_prefix(const avllm_llama* m, int32_t R);
 /* Bytes of ONE of the two caches (K or V) of B sequences and Tmax positions in the model's form: layers * B * Tmax * dkv elements of the model
  * dtype, or with kv_fp8 that many code bytes plus one exponent byte per 32. */
 size_t avllm_llama_kv_cache_bytes(const avllm_llama* m, int32_t B, int32_t Tmax);
@@ -699,6 +713,21 @@ int avllm_kv8_rope_append(void* qkv, int64_t ld, int32_t B, int32_t heads, int32
 int avllm_attention_decode_kv8(const void* q, int64_t ldq, const void* k_codes, const void* k_exps, const void* v_codes, const void* v_exps, void* o,
                                int64_t ldo, int32_t B, int32_t H, int32_t hd, int32_t Tk, const int32_t* tk_dev, int32_t Tmax, float scale,
                                int32_t kv_group, void* stream);
+/* Single-token attention over a shared prefix (csrc/attention_decode_shared.hip; bf16 q and o [R, H hd]).  Row r of R = B * group attends rows
+ * [0, S) of item r / group in the prefix cache [B, Tprefix, dkv], followed by rows [0, Tk + *tk_dev) (clamped to N) of its own row of the suffix
+ * cache [R, N, dkv]: the softmax over the concatenation, fp32 throughout, no atomics (identical inputs give identical bits, in every group
+ * slot).  Two launches: prefix partials per (row, head, slice) into ws, then suffix + merge.  hd 64 or 128; R % group == 0; 0 < S <= Tprefix;
+ * ws of avllm_attention_decode_shared_workspace_bytes(R, H, hd) bytes.  _kv8: both caches are fp8 images (planes as above), dequantised as
+ * avllm_attention_decode_kv8 does. */
+size_t avllm_attention_decode_shared_workspace_bytes(int32_t R, int32_t H, int32_t hd);
+int avllm_attention_decode_shared(const void* q, int64_t ldq, const void* k_prefix, const void* v_prefix, int32_t S, int32_t Tprefix,
+                                  const void* k_suffix, const void* v_suffix, int32_t Tk, const int32_t* tk_dev, int32_t N, void* o, int64_t ldo,
+                                  int32_t R, int32_t group, int32_t H, int32_t hd, float scale, int32_t kv_group, void* ws, size_t ws_bytes,
+                                  void* stream);
+int avllm_attention_decode_shared_kv8(const void* q, int64_t ldq, const void* kp_codes, const void* kp_exps, const void* vp_codes, const void* vp_exps,
+                                      int32_t S, int32_t Tprefix, const void* ks_codes, const void* ks_exps, const void* vs_codes, const void* vs_exps,
+                                      int32_t Tk, const int32_t* tk_dev, int32_t N, void* o, int64_t ldo, int32_t R, int32_t group, int32_t H,
+                                      int32_t hd, float scale, int32_t kv_group, void* ws, size_t ws_bytes, void* stream);
 /* avllm_kv_gather_rows on whole fp8 images (all layers: k_src .. v_dst are the bases of [layers, rows, T, dkv] images): codes and exponents of
  * positions [t0, t1) move together, two launches of the same kernel on rows of dkv and of dkv/32 bytes.  dkv % 64 == 0. */
 int avllm_kv8_gather_rows(const void* k_src, const void* v_src, int32_t src_rows, int64_t src_T, void* k_dst, void* v_dst, int32_t dst_rows,

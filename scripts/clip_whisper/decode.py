@@ -18,7 +18,8 @@ passed as bad_words_ids), --hotwords FILE (one word or phrase per line) / --hotw
 path of a hotword; generate(hotwords=, hotword_bias=)), --nbest N (beam search returns the N best hypotheses of each utterance; needs
 --num_beams >= N; WER stays on the 1-best), --confidence (adds tokens, token_logprobs, avg_logprob and word_confidences of the 1-best to each
 utterance of the --output_file JSON, and with --nbest > 1 an nbest list of {hypothesis, score}), --min_avg_logprob F (utterances whose mean
-token log-probability is below F are listed in the log; they still count in the WER), --load_lora (also load the adapters from the checkpoint), --merge_lora (with --load_lora: fold the loaded
+token log-probability is below F are listed in the log; they still count in the WER), --share_prefix (generate(share_prefix=True): the beams
+of an utterance share one prefix cache), --load_lora (also load the adapters from the checkpoint), --merge_lora (with --load_lora: fold the loaded
 adapters into the LLM weights once, ClipWhisperModel.merge_lora(), so that decoding runs the adapter-free kernels), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
@@ -80,6 +81,11 @@ def parse_args(argv=None):
     p.add_argument("--kv_cache", type=str, choices=["bf16", "fp8"], default="bf16",
                    help="fp8: the KV cache is block-scaled e4m3 (33/64 of the bf16 bytes; needs bf16, token steps of at most 16 rows, else "
                         "the bf16 cache is used; effect on WER not measured)")
+    p.add_argument("--share_prefix", action="store_true",
+                   help="generate(share_prefix=True): the beams of an utterance (--num_beams > 1) read one copy of its prefix cache and keep only "
+                        "their generated positions (token steps of at most 16 rows, bf16; otherwise the default path is taken).  generate() "
+                        "shares the same way among the n sampled sequences of num_return_sequences=n; this script samples one per utterance, "
+                        "and greedy decoding has nothing to share")
     p.add_argument("--load_lora", action="store_true")
     p.add_argument("--merge_lora", action="store_true",
                    help="with --load_lora: fold the adapters into the LLM weights after the checkpoint is loaded (effect on WER not measured)")
@@ -247,7 +253,8 @@ def main(argv=None):
             ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
                                  do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k, num_beams=a.num_beams,
                                  length_penalty=a.length_penalty, repetition_penalty=a.repetition_penalty,
-                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, **bias_kw, **score_kw)
+                                 no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, share_prefix=a.share_prefix,
+                                 **bias_kw, **score_kw)
             extras = None
             if scored:
                 extras = utterance_scores(model.tokenizer, ids, a.nbest, model.eos_token_id)
