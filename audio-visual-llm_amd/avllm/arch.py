@@ -61,10 +61,85 @@ class LlamaCfg:
         return self.hidden // self.heads
 
 
+# the projections of a decoder layer a LoRA adapter can wrap, in the canonical order of the flat parameter buffer; the first four (the
+# reference's own target_modules) are the default
+LORA_MODULES = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+LORA_DEFAULT_TARGETS = LORA_MODULES[:4]
+LORA_MLP_MODULES = LORA_MODULES[4:]
+
+
+def parse_lora_targets(spec):
+    """`lora_target_modules` -> tuple of module names in canonical order (LORA_MODULES).  None: the four attention modules; "all-linear"
+    (peft's name): all seven; else a list / tuple or a comma-separated string of names, any non-empty subset, the order given ignored.
+    ValueError, naming the offender, for an unknown name, a duplicate and an empty list."""
+    if spec is None:
+        return LORA_DEFAULT_TARGETS
+    if isinstance(spec, str):
+        if spec.strip() == "all-linear":
+            return LORA_MODULES
+        names = [n.strip() for n in spec.split(",")]
+        if names == [""]:
+            names = []
+    elif isinstance(spec, (list, tuple)):
+        names = list(spec)
+    else:
+        raise ValueError(f"lora_target_modules must be None, 'all-linear', a list of names or a comma-separated string, got {spec!r}")
+    if not names:
+        raise ValueError(f"lora_target_modules is empty ({spec!r}): name at least one of {', '.join(LORA_MODULES)}")
+    for n in names:
+        if n not in LORA_MODULES:
+            raise ValueError(f"lora_target_modules: unknown module {n!r} (known: {', '.join(LORA_MODULES)}, or 'all-linear')")
+    for n in names:
+        if names.count(n) > 1:
+            raise ValueError(f"lora_target_modules: duplicate module {n!r}")
+    return tuple(n for n in LORA_MODULES if n in names)
+
+
+def lora_module_section(name):
+    """The HuggingFace sub-module of a decoder layer that holds projection `name`: self_attn or mlp."""
+    return "mlp" if name in LORA_MLP_MODULES else "self_attn"
+
+
+def lora_state_key(i, name, ab):
+    """peft's state-dict key of adapter tensor `ab` (lora_A | lora_B) of module `name` in layer i, as ClipWhisperModel.state_dict() writes it."""
+    return f"llm.base_model.model.model.layers.{i}.{lora_module_section(name)}.{name}.{ab}.default.weight"
+
+
+def parse_lora_state_key(key):
+    """A peft LoRA key (any prefix before `layers.`) -> (layer, module name, lora_A | lora_B); None for any other key."""
+    if ".lora_A." not in key and ".lora_B." not in key:
+        return None
+    parts = key.split(".")
+    ab = "lora_A" if ".lora_A." in key else "lora_B"
+    return int(parts[parts.index("layers") + 1]), parts[parts.index(ab) - 1], ab
+
+
+def lora_shapes(c, r, name):
+    """(A shape, B shape) of module `name`'s adapter in LlamaCfg c at rank r: A [r, in], B [out, r]."""
+    dkv = (c.kv_heads or c.heads) * c.head_dim
+    din = c.ffn if name == "down_proj" else c.hidden
+    dout = {"k_proj": dkv, "v_proj": dkv, "gate_proj": c.ffn, "up_proj": c.ffn}.get(name, c.hidden)
+    return (r, din), (dout, r)
+
+
+def lora_layout(c, r, targets):
+    """The flat LoRA buffer of LlamaEngine (lora_p / lora_g): -> (elements per layer, {module: ((A begin, A end), (B begin, B end))} within a
+    layer's slice).  A layer holds the selected modules only, in canonical order, A then B; layer i starts at i * per_layer."""
+    off, out = 0, {}
+    for nm in LORA_MODULES:
+        if nm not in targets:
+            continue
+        (_, din), (dout, _) = lora_shapes(c, r, nm)
+        out[nm] = ((off, off + r * din), (off + r * din, off + r * din + dout * r))
+        off += r * (din + dout)
+    return off, out
+
+
 @dataclass
 class LoraCfg:
     r: int = 16
     alpha: float = 32.0
+    targets: tuple = LORA_DEFAULT_TARGETS      # canonical order (parse_lora_targets)
 
     @property
     def scale(self):
@@ -211,11 +286,20 @@ def synth_lora(c, l, device, seed):
     """peft init_lora_weights="gaussian": A ~ N(0, 1/r), B = 0; then x0.01 (clip_whisper_model.py:973-1000)."""
     g = _Gen(device, torch.float32, seed + 4)
     sd = {}
+    targets = getattr(l, "targets", LORA_DEFAULT_TARGETS)
+    # the four attention modules draw first, in the order they always did, whatever else is adapted: their tensors do not depend on the rest
     for i in range(c.layers):
-        for nm in ("q_proj", "k_proj", "v_proj", "o_proj"):
-            sd[f"layers.{i}.{nm}.lora_A"] = g.n((l.r, c.hidden), (1.0 / l.r) * 0.01)
-            rows = (c.kv_heads or c.heads) * c.head_dim if nm in ("k_proj", "v_proj") else c.hidden
-            sd[f"layers.{i}.{nm}.lora_B"] = torch.zeros(rows, l.r, device=device)
+        for nm in LORA_DEFAULT_TARGETS:
+            a = g.n((l.r, c.hidden), (1.0 / l.r) * 0.01)
+            if nm in targets:
+                sd[f"layers.{i}.{nm}.lora_A"] = a
+                sd[f"layers.{i}.{nm}.lora_B"] = torch.zeros(lora_shapes(c, l.r, nm)[1], device=device)
+    for i in range(c.layers):
+        for nm in LORA_MLP_MODULES:
+            if nm in targets:
+                sa, sb = lora_shapes(c, l.r, nm)
+                sd[f"layers.{i}.{nm}.lora_A"] = g.n(sa, (1.0 / l.r) * 0.01)
+                sd[f"layers.{i}.{nm}.lora_B"] = torch.zeros(sb, device=device)
     return sd
 
 
@@ -307,7 +391,7 @@ def weights_from_reference_state_dict(sd):
                 n = n[len("base_model.model."):]
             if ".lora_A." in n or ".lora_B." in n:                        # model.layers.N.self_attn.q_proj.lora_A.default.weight
                 parts = n.split(".")
-                i, mod = parts[parts.index("layers") + 1], parts[parts.index("self_attn") + 1]
+                i, mod = parts[parts.index("layers") + 1], parts[parts.index("lora_A" if ".lora_A." in n else "lora_B") - 1]
                 W["lora"][f"layers.{i}.{mod}.{'lora_A' if '.lora_A.' in n else 'lora_B'}"] = v
             else:
                 W["llama"][n.replace(".base_layer.", ".")] = v            # peft keeps the frozen nn.Linear as `base_layer`
@@ -315,7 +399,7 @@ def weights_from_reference_state_dict(sd):
 
 
 def resolve_arch(llm_path, whisper_model, clip_model, config, weights, seed, lora_r, lora_alpha, use_lora, p_llm, p_whisper,
-                 p_clip, device, dtype, synthetic_weights=False):
+                 p_clip, device, dtype, synthetic_weights=False, lora_targets=None):
     """-> (ModelCfg, weights).  A component's tensors come from `weights[kind]`, a `_provided_*` module, or a local HF directory with
     safetensors.  Seeded random tensors of the named architecture are an explicit opt-in (`synthetic_weights=True`: bench, tests, the
     scripts' --synthetic-weights); without it a path that is not a local checkpoint raises FileNotFoundError instead of silently
@@ -352,6 +436,9 @@ def resolve_arch(llm_path, whisper_model, clip_model, config, weights, seed, lor
         cfg = ModelCfg(parts["whisper"], parts["clip"], parts["llama"], LoraCfg(lora_r, float(lora_alpha)))
     else:
         cfg.lora = LoraCfg(lora_r, float(lora_alpha)) if not hasattr(cfg, "lora") or cfg.lora is None else cfg.lora
+    if lora_targets is not None:                                      # the constructor keyword; a `config=` keeps its own LoraCfg.targets otherwise
+        import dataclasses
+        cfg = dataclasses.replace(cfg, lora=dataclasses.replace(cfg.lora, targets=tuple(lora_targets)))
     for kind, path, prov, synth, c in (("whisper", whisper_model, p_whisper, synth_whisper, cfg.whisper),
                                        ("clip", clip_model, p_clip, synth_clip, cfg.clip),
                                        ("llama", llm_path, p_llm, synth_llama, cfg.llama)):
@@ -377,4 +464,9 @@ def resolve_arch(llm_path, whisper_model, clip_model, config, weights, seed, lor
         W[kind] = sd
     if use_lora and "lora" not in W:
         W["lora"] = synth_lora(cfg.llama, cfg.lora, device, seed)
+    elif use_lora and any(nm in LORA_MLP_MODULES for nm in cfg.lora.targets):
+        # adapters given for some modules only (a q/k/v/o checkpoint that now gets MLP adapters as well): an MLP adapter that is not given
+        # starts from the reference's init, not from A = B = 0, which would never receive a gradient
+        fresh = synth_lora(cfg.llama, cfg.lora, device, seed)
+        W["lora"] = {**{k: v for k, v in fresh.items() if k.split(".")[2] in LORA_MLP_MODULES and k not in W["lora"]}, **W["lora"]}
     return cfg, W

@@ -13,7 +13,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .arch import check_llama_keys
+from .arch import LORA_MLP_MODULES, LORA_MODULES, check_llama_keys, lora_layout, lora_shapes
 
 
 class Workspace:
@@ -188,6 +188,9 @@ class LlamaEngine:
 
     Trainable state: one flat fp32 buffer `lora_p` holding, per layer, [A_q,B_q,A_k,B_k,A_v,B_v,A_o,B_o]
     (A [r,d], B [dout,r]; dout = d, or kv_heads*head_dim for k/v under grouped-query attention) so a layer's gradient bucket is one contiguous slice of `lora_g` for the DDP all-reduce.
+    `lora_cfg.targets` (arch.parse_lora_targets) selects the adapted modules out of q, k, v, o, gate, up, down: a layer's slice then holds the
+    selected ones only, in that canonical order, A then B (gate, up: A [r,d], B [ffn,r]; down: A [r,ffn], B [d,r]).  The default four give the
+    layout above.  An unmerged adapter on gate, up or down keeps the token step off the fused path (decode_is_fused); merge_lora() folds them.
     """
 
     def __init__(self, sd, cfg, lora_cfg=None, lora_sd=None, dtype=torch.bfloat16, device="cuda", training=True, fp8=False, decode_fp8=False,
@@ -212,6 +215,12 @@ class LlamaEngine:
         self.use_lora = lora_cfg is not None
         r = lora_cfg.r if self.use_lora else 0
         self.r = r
+        # the adapted modules in canonical order (without LoRA: the default four, which only size the -- unused -- layout)
+        self.targets = tuple(getattr(lora_cfg, "targets", None) or LORA_TARGETS) if self.use_lora else LORA_TARGETS
+        self.mlp_targets = tuple(nm for nm in self.targets if nm in LORA_MLP_MODULES)
+        if self.fp8 and self.mlp_targets:
+            raise NotImplementedError(f"precision='fp8' with a LoRA adapter on {', '.join(self.mlp_targets)} is not implemented: "
+                                      "the fp8 training forward takes adapters on q_proj, k_proj, v_proj and o_proj only")
         m = L.Llama()
         m.dtype, m.d, m.heads, m.layers, m.ffn, m.vocab, m.lora_r = (
             L.F32 if dtype == torch.float32 else L.BF16, d, cfg.heads, cfg.layers, f, cfg.vocab, r)
@@ -274,9 +283,10 @@ class LlamaEngine:
         # what else merge_lora() touches: the fp8 (codes, layout-1 image, layout-2 exponents) and fp4 (codes, exponents) images of the
         # attention matrices by (layer, "qkv" | "o"), which it rewrites, and their transposed training copies, which it frees
         self.merged = False
-        self.img8, self.img4, self.attn_wt = {}, {}, {}
+        self.img8, self.img4, self.attn_wt, self.mlp_wt = {}, {}, {}, {}
         # ---- LoRA masters / grads / padded operand images
-        self.per_layer = sum(r * (d + do) for do in self.douts)
+        self.mod_shapes = {nm: lora_shapes(cfg, r, nm) for nm in LORA_MODULES}      # name -> ((r, din), (dout, r))
+        self.per_layer, self._layout = lora_layout(cfg, r, self.targets)
         n = cfg.layers * self.per_layer
         if self.use_lora:
             self.lora_p = torch.zeros(n, dtype=torch.float32, device=device)
@@ -287,6 +297,21 @@ class LlamaEngine:
             self.img_ATo = torch.zeros(cfg.layers, d, P, dtype=dtype, device=device)
             self.img_B = [[torch.zeros(do, P, dtype=dtype, device=device) for do in self.douts] for _ in range(cfg.layers)]
             self.img_BT = [[torch.zeros(P, do, dtype=dtype, device=device) for do in self.douts] for _ in range(cfg.layers)]
+            # gate / up / down, the selected ones only: name -> per-layer images.  gate and up share one [d, 2*64] transposed-A image when both
+            # are adapted (the second K segment of the dxn product), as q, k, v share img_ATqkv
+            z = lambda *shape: [torch.zeros(*shape, dtype=dtype, device=device) for _ in range(cfg.layers)]
+            self.mlp_img = {}
+            gu_shared = z(d, 2 * P) if "gate_proj" in self.targets and "up_proj" in self.targets else None
+            for k, nm in enumerate(LORA_MLP_MODULES):
+                if nm not in self.targets:
+                    continue
+                (_, din), (dout, _) = self.mod_shapes[nm]
+                im = {"A": z(P, din), "B": z(dout, P), "BT": z(P, dout)}
+                if gu_shared is not None and k < 2:
+                    im["AT"], im["ld_at"], im["at_col"] = gu_shared, 2 * P, k * P
+                else:
+                    im["AT"], im["ld_at"], im["at_col"] = z(din, P), P, 0
+                self.mlp_img[nm] = im
             if lora_sd is not None:
                 self.load_lora(lora_sd)
         for i in range(cfg.layers):
@@ -312,18 +337,31 @@ class LlamaEngine:
             if training:
                 self.attn_wt[i] = (put(wqkv.t()), put(wo.t()))
                 ly.wqkv_t, ly.wo_t = (t.data_ptr() for t in self.attn_wt[i])
-                ly.wgu_t, ly.wdown_t = put(wgu.t()).data_ptr(), put(wdown.t()).data_ptr()
+                self.mlp_wt[i] = (put(wgu.t()), put(wdown.t()))
+                ly.wgu_t, ly.wdown_t = (t.data_ptr() for t in self.mlp_wt[i])
             if self.fp8 or self.decode_fp8:
                 ly.wqkv8, ly.sqkv8, ly.eqkv8 = images(wqkv, key=(i, "qkv"))
                 ly.wo8, ly.so8, ly.eo8 = images(wo, key=(i, "o"))
-                ly.wgu8, ly.sgu8, ly.egu8 = images(wgu)
-                ly.wdown8, ly.sdown8, ly.edown8 = images(wdown)
+                ly.wgu8, ly.sgu8, ly.egu8 = images(wgu, key=(i, "gu"))
+                ly.wdown8, ly.sdown8, ly.edown8 = images(wdown, key=(i, "down"))
             if self.decode_fp4:
                 img4 = self._fp4_images(ly, wqkv, wo, wgu, wdown)
-                self.img4[i, "qkv"], self.img4[i, "o"] = img4["qkv"], img4["o"]
+                for nm4 in ("qkv", "o", "gu", "down"):
+                    self.img4[i, nm4] = img4[nm4]
             if self.use_lora:
                 es = self.img_A.element_size()
+                for k, nm in enumerate(LORA_MLP_MODULES):
+                    if nm not in self.targets:
+                        continue
+                    lm, im = ly.lora_mlp[k], self.mlp_img[nm]
+                    lm.A_pad, lm.B_pad, lm.BT_pad = im["A"][i].data_ptr(), im["B"][i].data_ptr(), im["BT"][i].data_ptr()
+                    lm.AT_pad, lm.ld_at = im["AT"][i].data_ptr() + im["at_col"] * es, im["ld_at"]
+                    a, b = self._slices(i, nm)
+                    lm.gA = self.lora_g[a[0]:a[1]].data_ptr()
+                    lm.gB = self.lora_g[b[0]:b[1]].data_ptr()
                 for j in range(4):
+                    if LORA_TARGETS[j] not in self.targets:
+                        continue
                     lm = ly.lora[j]
                     lm.A_pad = self.img_A[i, j].data_ptr()
                     lm.B_pad = self.img_B[i][j].data_ptr()
@@ -355,22 +393,25 @@ class LlamaEngine:
             setattr(ly, "e" + nm + "4", e4.data_ptr())
         return out
 
-    # flat-buffer offsets of module j (0..3 = q,k,v,o) in layer i: (A range, B range)
+    # flat-buffer offsets of module j (its name, or 0..6 = q,k,v,o,gate,up,down) in layer i: (A range, B range).  A layer holds the selected
+    # modules only, in canonical order
     def _slices(self, i, j):
-        r, d = self.r, self.cfg.hidden
-        base = i * self.per_layer + sum(r * (d + do) for do in self.douts[:j])
-        return (base, base + r * d), (base + r * d, base + r * d + self.douts[j] * r)
+        nm = j if isinstance(j, str) else LORA_MODULES[j]
+        if nm not in self.targets:
+            raise KeyError(f"{nm} carries no LoRA adapter in this engine (lora_target_modules = {', '.join(self.targets)})")
+        base = i * self.per_layer
+        (a0, a1), (b0, b1) = self._layout[nm]
+        return (base + a0, base + a1), (base + b0, base + b1)
 
     def lora_views(self, buf=None):
         """dict key -> fp32 view into the flat buffer, keys `layers.{i}.{module}.lora_A|B` (oracle naming)."""
         buf = self.lora_p if buf is None else buf
-        r, d = self.r, self.cfg.hidden
         out = {}
         for i in range(self.cfg.layers):
-            for j, nm in enumerate(LORA_TARGETS):
-                a, b = self._slices(i, j)
-                out[f"layers.{i}.{nm}.lora_A"] = buf[a[0]:a[1]].view(r, d)
-                out[f"layers.{i}.{nm}.lora_B"] = buf[b[0]:b[1]].view(self.douts[j], r)
+            for nm in self.targets:
+                a, b = self._slices(i, nm)
+                out[f"layers.{i}.{nm}.lora_A"] = buf[a[0]:a[1]].view(self.mod_shapes[nm][0])
+                out[f"layers.{i}.{nm}.lora_B"] = buf[b[0]:b[1]].view(self.mod_shapes[nm][1])
         return out
 
     def _refuse_merged(self, what):
@@ -381,6 +422,9 @@ class LlamaEngine:
         self._refuse_merged("load_lora()")
         v = self.lora_views()
         for k, t in lora_sd.items():
+            if k not in v:      # never dropped in silence: a tensor of a module this model does not adapt is a mismatch of the two
+                raise KeyError(f"load_lora(): {k} is a LoRA tensor of a module this model does not adapt "
+                               f"(lora_target_modules = {', '.join(self.targets)})")
             v[k].copy_(t.to(device=self.device, dtype=torch.float32))
 
     def pack_lora(self):
@@ -389,16 +433,21 @@ class LlamaEngine:
         self._refuse_merged("pack_lora()")
         lib = L.load()
         if getattr(self, "_pack_table", None) is None:
-            rows = []
+            rows, rows_f = [], []                       # adapters that read d-wide inputs; down_proj's, which read ffn-wide ones
             for i in range(self.cfg.layers):
-                for j in range(4):
-                    a, b = self._slices(i, j)
-                    lm = self.layers[i].lora[j]
-                    rows.append([self.lora_p[a[0]:a[1]].data_ptr(), self.lora_p[b[0]:b[1]].data_ptr(), lm.A_pad, lm.AT_pad, lm.B_pad, lm.BT_pad,
-                                 lm.ld_at, self.douts[j]])
-            self._pack_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
-        L.check(lib.avllm_lora_pack_batch(L.ptr(self._pack_table), self._pack_table.shape[0], self.r, self.cfg.hidden, self.desc.dtype,
-                                          L.stream_ptr()))
+                for nm in self.targets:
+                    j = LORA_MODULES.index(nm)
+                    a, b = self._slices(i, nm)
+                    lm = self.layers[i].lora[j] if j < 4 else self.layers[i].lora_mlp[j - 4]
+                    (rows_f if nm == "down_proj" else rows).append(
+                        [self.lora_p[a[0]:a[1]].data_ptr(), self.lora_p[b[0]:b[1]].data_ptr(), lm.A_pad, lm.AT_pad, lm.B_pad, lm.BT_pad, lm.ld_at,
+                         self.mod_shapes[nm][1][0]])
+            self._pack_table = torch.tensor(rows, dtype=torch.int64, device=self.device) if rows else None
+            self._pack_table_f = torch.tensor(rows_f, dtype=torch.int64, device=self.device) if rows_f else None
+        # avllm_lora_pack_batch takes one input width per call
+        for table, din in ((self._pack_table, self.cfg.hidden), (self._pack_table_f, self.cfg.ffn)):
+            if table is not None:
+                L.check(lib.avllm_lora_pack_batch(L.ptr(table), table.shape[0], self.r, din, self.desc.dtype, L.stream_ptr()))
 
     # ------------------------------------------------------------------ training
     def fwd_loss(self, x, labels, want_logits=False, dropout=0.0, seed=0, seed_dev=None):
@@ -455,46 +504,65 @@ class LlamaEngine:
         self._refuse_merged("adapters_disabled()")
         eng = self
 
+        mods = lambda ly: [ly.lora[j] for j in range(4)] + [ly.lora_mlp[k] for k in range(3)]      # all seven modules
+
         class _Ctx:
             def __enter__(self_):
-                self_.saved = [[(ly.lora[j].A_pad, ly.lora[j].B_pad) for j in range(4)] for ly in eng.layers]
+                self_.saved = [[(lm.A_pad, lm.B_pad) for lm in mods(ly)] for ly in eng.layers]
                 for ly in eng.layers:
-                    for j in range(4):
-                        ly.lora[j].A_pad = None
-                        ly.lora[j].B_pad = None
+                    for lm in mods(ly):
+                        lm.A_pad = None
+                        lm.B_pad = None
 
             def __exit__(self_, *a):
                 for ly, sv in zip(eng.layers, self_.saved):
-                    for j in range(4):
-                        ly.lora[j].A_pad, ly.lora[j].B_pad = sv[j]
+                    for lm, (pa, pb) in zip(mods(ly), sv):
+                        lm.A_pad, lm.B_pad = pa, pb
         return _Ctx()
 
     def merge_lora(self):
-        """Fold the adapters into the LLM weights for decoding, for good: W' = W + scale * B.A on q, k, v (row slices of wqkv) and o from the
-        fp32 masters (avllm_lora_merge), every fp8 / fp4 image of the two matrices rebuilt in place by the quantisers that made it, and the
-        adapter pointers cleared, so that prefill and the token step take the adapter-free kernels.  lora_p stays (state_dict() still returns
-        the adapters); the transposed training copies of wqkv and wo are stale afterwards and freed, and everything that would need the
-        separate adapters back raises."""
+        """Fold the adapters into the LLM weights for decoding, for good: W' = W + scale * B.A on q, k, v (row slices of wqkv), o, gate, up
+        (the row halves of wgu) and down -- the adapted ones among them -- from the fp32 masters (avllm_lora_merge), every fp8 / fp4 image of
+        the matrices written to rebuilt in place by the quantisers that made it, and the adapter pointers cleared, so that prefill and the
+        token step take the adapter-free kernels (the fused token step, which an adapter on gate, up or down keeps a model from).  lora_p
+        stays (state_dict() still returns the adapters); the transposed training copies of wqkv and wo, and with an MLP adapter those of wgu
+        and wdown, are stale afterwards and freed, and everything that would need the separate adapters back raises."""
         if not self.use_lora:
             raise ValueError("merge_lora(): this engine has no LoRA adapters (use_lora=False)")
         self._refuse_merged("a second merge_lora()")
         v = self.lora_views()
         rows = self._qkv_rows()
+        f = self.cfg.ffn
         for i in range(self.cfg.layers):
             ly = self.layers[i]
-            # wqkv was concatenated here, but wo may be the caller's own tensor (a state dict already on the device in the engine dtype is
-            # taken as it is): the merge writes into a copy the engine owns
-            okey = f"model.layers.{i}.self_attn.o_proj.weight"
-            wqkv, old = self.llm_w[i, "qkv"], self.llm_w[okey]
-            wo = self.llm_w[okey] = old.clone()
-            self.keep = [wo if t is old else t for t in self.keep]
-            ly.wo = wo.data_ptr()
-            for j, nm in enumerate(LORA_TARGETS):
-                W = wo if j == 3 else wqkv[rows[j][0]:rows[j][1]]
-                ops.lora_merge_(W, v[f"layers.{i}.{nm}.lora_A"], v[f"layers.{i}.{nm}.lora_B"], self.lcfg.scale)
-                ly.lora[j].A_pad = None
-                ly.lora[j].B_pad = None
-            for nm, W in (("qkv", wqkv), ("o", wo)):
+
+            def own(key, field):
+                # wqkv and wgu were concatenated here, but wo and wdown may be the caller's own tensors (a state dict already on the device in
+                # the engine dtype is taken as it is): the merge writes into a copy the engine owns
+                old = self.llm_w[key]
+                new = self.llm_w[key] = old.clone()
+                self.keep = [new if t is old else t for t in self.keep]
+                setattr(ly, field, new.data_ptr())
+                return new
+
+            wqkv, wgu = self.llm_w[i, "qkv"], self.llm_w[i, "gu"]
+            wo = own(f"model.layers.{i}.self_attn.o_proj.weight", "wo")
+            wdown = own(f"model.layers.{i}.mlp.down_proj.weight", "wdown") if "down_proj" in self.targets else None
+            where = {"q_proj": lambda: wqkv[rows[0][0]:rows[0][1]], "k_proj": lambda: wqkv[rows[1][0]:rows[1][1]],
+                     "v_proj": lambda: wqkv[rows[2][0]:rows[2][1]], "o_proj": lambda: wo,
+                     "gate_proj": lambda: wgu[:f], "up_proj": lambda: wgu[f:], "down_proj": lambda: wdown}
+            for nm in self.targets:
+                j = LORA_MODULES.index(nm)
+                ops.lora_merge_(where[nm](), v[f"layers.{i}.{nm}.lora_A"], v[f"layers.{i}.{nm}.lora_B"], self.lcfg.scale)
+                lm = ly.lora[j] if j < 4 else ly.lora_mlp[j - 4]
+                lm.A_pad = None
+                lm.B_pad = None
+            touched = [("qkv", wqkv), ("o", wo)]
+            if "gate_proj" in self.targets or "up_proj" in self.targets:
+                touched.append(("gu", wgu))
+            if wdown is not None:
+                touched.append(("down", wdown))
+            for nm, W in touched:
                 if (i, nm) in self.img8:
                     q, s, e = self.img8[i, nm]
                     if s is not None:
@@ -507,6 +575,10 @@ class LlamaEngine:
                 stale = {t.data_ptr() for t in self.attn_wt.pop(i)}
                 self.keep = [t for t in self.keep if t.data_ptr() not in stale]
                 ly.wqkv_t = ly.wo_t = None
+            if i in self.mlp_wt and self.mlp_targets:      # the transposed copies of wgu and wdown are stale as well
+                stale = {t.data_ptr() for t in self.mlp_wt.pop(i)}
+                self.keep = [t for t in self.keep if t.data_ptr() not in stale]
+                ly.wgu_t = ly.wdown_t = None
         self.merged = True
 
     def merged_llm_state_dict(self):

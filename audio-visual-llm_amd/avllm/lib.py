@@ -57,7 +57,7 @@ class LlamaLayer(C.Structure):
                [("lora", LoraMod * 4)] + [(n, vp) for n in ("wqkv8", "sqkv8", "wo8", "so8", "wgu8", "sgu8", "wdown8", "sdown8")] + \
                [(n, vp) for n in ("eqkv8", "eo8", "egu8", "edown8")] + \
                [(n, vp) for n in ("wqkv4", "wo4", "wgu4", "wdown4", "eqkv4", "eo4", "egu4", "edown4")] + \
-               [(n, vp) for n in ("bqkv", "bo")] + [(n, vp) for n in ("q_norm_w", "k_norm_w")]
+               [(n, vp) for n in ("bqkv", "bo")] + [(n, vp) for n in ("q_norm_w", "k_norm_w")] + [("lora_mlp", LoraMod * 3)]
 
 
 class Llama(C.Structure):
@@ -141,6 +141,7 @@ _SIGS = {
     "avllm_kv_append": ([vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     "avllm_swiglu_fwd": ([vp, vp, i64, i32, i32, vp], i32),
     "avllm_swiglu_bwd": ([vp, vp, vp, i64, i32, i32, vp], i32),
+    "avllm_swiglu_bwd_h": ([vp, vp, vp, vp, i64, i32, i32, vp], i32),
     "avllm_attention_fwd": ([vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, f32, i32, i32, i32, i32, vp], i32),
     "avllm_attention_bwd": ([vp] * 10 + [i32] * 4 + [i64] * 7 + [f32, i32, i32, i32, i32, vp], i32),
     "avllm_attention_bwd_rope": ([vp] * 10 + [i32] * 4 + [i64] * 7 + [f32, i32, i32, i32, i32, vp, vp], i32),

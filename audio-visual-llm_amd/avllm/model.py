@@ -9,6 +9,9 @@ Differences that are deliberate and documented:
     modules' state_dict()s, from `weights=`, or -- only with `synthetic_weights=True` -- from a seeded synthetic
     initialisation of the named architecture (a path that is none of these raises FileNotFoundError).
   * freeze_encoders=False / use_4bit=True are refused (out of scope).
+  * lora_target_modules (default None = q_proj, k_proj, v_proj, o_proj, the reference's own list): any non-empty subset of those four and
+    gate_proj, up_proj, down_proj, or "all-linear" (peft's name) for all seven.  An adapter on an MLP projection trains, evaluates and
+    generates like the others, but keeps generate()'s token steps off the fused path until merge_lora() folds it (see generate()).
   * train_connectors=True (default False) trains the two modality connectors with the encoders frozen: the reference's freeze_encoders=False
     gradient (clip_whisper_model.py:1096-1106,1136-1146) restricted to the four connector tensors, which does not depend on whether the
     encoders receive one too.  connector_type "simple", precision fp32 | bf16, use_lora=True.
@@ -23,7 +26,7 @@ import torch
 
 from . import lib as L
 from . import ops
-from .arch import ModelCfg, resolve_arch
+from .arch import LORA_MLP_MODULES, LORA_MODULES, ModelCfg, lora_state_key, parse_lora_state_key, parse_lora_targets, resolve_arch
 from .connector import ModalityConnector, create_modality_connector
 from .engine import ClipEngine, LlamaEngine, WhisperEngine
 from .generation import GenerateOutput, beam_search, hotword_sequence_bias, parse_arguments, shares_prefix, token_loop  # noqa: F401  (the first and third are re-exported)
@@ -62,7 +65,7 @@ class ClipWhisperModel:
                  max_seq_len=256, fusion_scale=0.5, connector_type="simple", _provided_tokenizer=None, _provided_llm=None,
                  _provided_whisper=None, _provided_clip=None, *, precision=None, config: ModelCfg | None = None,
                  weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16",
-                 train_connectors: bool = False, kv_cache: str = "bf16"):
+                 train_connectors: bool = False, kv_cache: str = "bf16", lora_target_modules=None):
         if use_4bit:
             raise NotImplementedError("use_4bit (bitsandbytes nf4) is out of scope of the MI355X hot path (SURVEY.md §8)")
         if not freeze_encoders:
@@ -79,6 +82,9 @@ class ClipWhisperModel:
             logging.warning("LLM path %r does not contain 'llama': the reference would train without LoRA here; "
                             "this build applies LoRA to q_proj/k_proj/v_proj/o_proj", llm_path)
         self.lora_r, self.lora_alpha, self.lora_dropout = lora_r, lora_alpha, lora_dropout
+        if lora_target_modules is not None and not use_lora:
+            raise ValueError(f"lora_target_modules={lora_target_modules!r} together with use_lora=False: there are no adapters to place")
+        lora_targets = parse_lora_targets(lora_target_modules) if lora_target_modules is not None else None
         self.freeze_encoders, self.freeze_llm = freeze_encoders, freeze_llm
         self.modality, self.max_seq_len, self.fusion_scale = modality, max_seq_len, fusion_scale
         self.connector_type = connector_type
@@ -117,13 +123,18 @@ class ClipWhisperModel:
                 raise NotImplementedError("train_connectors=True supports precision fp32 | bf16, not fp8")
             if not use_lora:
                 raise ValueError("train_connectors=True needs use_lora=True: the LoRA backward pass is the only LLM backward pass in the library")
+        if precision == "fp8" and lora_targets is not None and any(nm in LORA_MLP_MODULES for nm in lora_targets):
+            raise NotImplementedError("precision='fp8' with lora_target_modules on " + ", ".join(nm for nm in lora_targets if nm in LORA_MLP_MODULES) +
+                                      " is not implemented: the fp8 training forward takes adapters on q_proj, k_proj, v_proj and o_proj only")
         self.dtype = torch.float32 if precision == "fp32" else torch.bfloat16
         self.training = True
         self._drop_step = 0
         self._seed = int(seed or 0)
 
         cfg, W = resolve_arch(llm_path, whisper_model, clip_model, config, weights, seed, lora_r, lora_alpha, use_lora,
-                              _provided_llm, _provided_whisper, _provided_clip, device, self.dtype, synthetic_weights)
+                              _provided_llm, _provided_whisper, _provided_clip, device, self.dtype, synthetic_weights, lora_targets=lora_targets)
+        # the adapted modules in canonical order (a `config=` may carry its own in LoraCfg.targets); saved by save_pretrained()
+        self.lora_target_modules = tuple(cfg.lora.targets) if use_lora else ()
         cfg.max_seq_len, cfg.fusion_scale = max_seq_len, fusion_scale
         self.cfg = cfg
         # explicit `weights=` / `config=` builds (tests, bench) are synthetic by construction: they carry no tokenizer either
@@ -178,7 +189,7 @@ class ClipWhisperModel:
         if self.use_lora:
             for k, v in self.llm_engine.lora_views().items():
                 _, i, mod, ab = k.split(".")
-                sd[f"llm.base_model.model.model.layers.{i}.self_attn.{mod}.{ab}.default.weight"] = v.detach().clone()
+                sd[lora_state_key(i, mod, ab)] = v.detach().clone()
         return sd
 
     def load_state_dict(self, sd, strict=False):
@@ -192,11 +203,12 @@ class ClipWhisperModel:
             self.video_connector.load_state_dict(v_)
         lora = {}
         for k, t in sd.items():
-            if ".lora_A." in k or ".lora_B." in k:
-                parts = k.split(".")
-                i = parts[parts.index("layers") + 1]
-                mod = parts[parts.index("self_attn") + 1]
-                ab = "lora_A" if ".lora_A." in k else "lora_B"
+            if parse_lora_state_key(k) is not None:
+                i, mod, ab = parse_lora_state_key(k)
+                if self.use_lora and mod not in self.lora_target_modules:      # refused before anything of the adapters is loaded
+                    known = "" if mod in LORA_MODULES else " (not a module name this build knows)"
+                    raise ValueError(f"load_state_dict(): {k} is a LoRA tensor of {mod}{known}, which this model does not adapt "
+                                     f"(lora_target_modules = {', '.join(self.lora_target_modules)})")
                 lora[f"layers.{i}.{mod}.{ab}"] = t
         if lora and self.use_lora:
             self.llm_engine.load_lora(lora)
@@ -213,6 +225,7 @@ class ClipWhisperModel:
         import json
         cfg = dict(modality=self.modality, max_seq_len=self.max_seq_len, fusion_scale=self.fusion_scale, use_lora=self.use_lora,
                    lora_r=self.lora_r, lora_alpha=self.lora_alpha, connector_type=self.connector_type,
+                   lora_target_modules=list(self.lora_target_modules) if self.use_lora else None,
                    audio_dim=self.audio_dim, video_dim=self.video_dim, llm_dim=self.llm_dim)
         json.dump(cfg, open(os.path.join(output_dir, "config.json"), "w"), indent=2)
         torch.save(cfg, os.path.join(output_dir, "config.pt"))
@@ -221,7 +234,7 @@ class ClipWhisperModel:
             torch.save({k: v for k, v in self.state_dict().items() if "lora_" in k}, os.path.join(output_dir, "llm", "adapter_model.pt"))
 
     def merge_lora(self):
-        """peft's merge_and_unload() for decoding: W' = W + (alpha/r) B.A on q/k/v/o of every layer, once (LlamaEngine.merge_lora), so that
+        """peft's merge_and_unload() for decoding: W' = W + (alpha/r) B.A on every adapted projection of every layer, once (LlamaEngine.merge_lora), so that
         generate() and an eval forward() run the adapter-free kernels.  For good: the model is set to eval, and a training forward and
         load_state_dict with LoRA tensors raise afterwards; state_dict() and save_pretrained() still hold the adapters as loaded."""
         self.eval()
@@ -246,9 +259,11 @@ class ClipWhisperModel:
         if not os.path.exists(cfg_path):
             raise ValueError(f"Model config {cfg_path} does not exist")
         cfg = json.load(open(cfg_path))
-        for k in ("modality", "max_seq_len", "fusion_scale", "use_lora", "lora_r", "lora_alpha", "connector_type"):
+        for k in ("modality", "max_seq_len", "fusion_scale", "use_lora", "lora_r", "lora_alpha", "connector_type", "lora_target_modules"):
             if k in cfg:
                 kwargs.setdefault(k, cfg[k])
+        if not kwargs.get("use_lora", True):
+            kwargs.pop("lora_target_modules", None)               # a directory saved with adapters, reloaded without them
         model = cls(_provided_tokenizer=tokenizer, **kwargs)
         model.audio_connector.load_state_dict(torch.load(os.path.join(model_dir, "audio_connector.pt"), map_location=model.device, weights_only=True))
         model.video_connector.load_state_dict(torch.load(os.path.join(model_dir, "video_connector.pt"), map_location=model.device, weights_only=True))
@@ -522,7 +537,12 @@ class ClipWhisperModel:
           are taken in another order, so scores agree to bf16 rounding, not bit for bit.  It goes with the fused token step
           (LlamaEngine.decode_shares_prefix: at most 16 rows, bf16, head dim 64 or 128): with more rows, precision="fp32" or the fused step
           switched off, and for greedy decoding and n = 1 sampling, which have nothing to share, the keyword is accepted and the call takes
-          the default path, bit-equal to share_prefix=False."""
+          the default path, bit-equal to share_prefix=False.
+        lora_target_modules with gate_proj, up_proj or down_proj: while such an adapter is attached (not merged) every token step takes the
+          general path (LlamaEngine.decode_is_fused is False): correct, but without the fused step's speed and without what goes with it --
+          decode_weights="fp8" | "fp4" stream bf16 weights, kv_cache="fp8" keeps a bf16 cache, share_prefix takes the default path.  The
+          remedy is merge_lora() (or from_pretrained(..., merge_lora=True)): the model is then adapter-free and takes the fused step in
+          every weight and cache form."""
         if video is None and pixel_values is not None:
             video = pixel_values
         eos, pad = self.eos_token_id, self.tokenizer.pad_token_id

@@ -162,6 +162,18 @@ def swiglu_bwd(dh, gu):
     return dgu
 
 
+def swiglu_bwd_h(dh, gu):
+    """-> (dgu, h): swiglu_bwd(dh, gu) and, from the same pass over gu, h = silu(g) * u as swiglu_fwd(gu) writes it (avllm_swiglu_bwd_h)."""
+    if gu.dim() != 2 or gu.shape[1] % 8 or dh.shape != (gu.shape[0], gu.shape[1] // 2) or dh.dtype != gu.dtype:
+        raise ValueError(f"swiglu_bwd_h: gu [M, 2F] with F % 4 == 0 and dh [M, F] of one dtype, got {tuple(gu.shape)} and {tuple(dh.shape)}")
+    if not (gu.is_contiguous() and dh.is_contiguous()):
+        raise ValueError("swiglu_bwd_h: contiguous tensors")
+    dgu = torch.empty_like(gu)
+    h = torch.empty_like(dh)
+    L.check(L.load().avllm_swiglu_bwd_h(L.ptr(dh), L.ptr(gu), L.ptr(dgu), L.ptr(h), gu.shape[0], gu.shape[1] // 2, L.dt_of(gu), L.stream_ptr()))
+    return dgu, h
+
+
 def attention_plan(B, Tq, Tk, H, hd, causal, dtype, impl=0, kv_heads=None):
     """-> (forward, backward) names (L.ATTN_FORMS) of the kernels avllm_attention_fwd / _bwd give the call; backward None where Tq != Tk."""
     f, b = L.i32(-1), L.i32(-1)

@@ -370,12 +370,11 @@ class ClipWhisperTrainer:
         return tot / max(1, cnt)
 
     def _lora_keys(self):
-        """peft-named LoRA keys in the order torch's optimizer indexes them (state-dict order: per layer q,k,v,o; A then B) == the order of
-        the flat LoRA buffer."""
+        """peft-named LoRA keys in the order torch's optimizer indexes them (state-dict order: per layer the adapted modules out of q,k,v,o,
+        gate,up,down; A then B) == the order of the flat LoRA buffer."""
         eng = self.model.llm_engine
-        from .engine import LORA_TARGETS
-        return [f"llm.base_model.model.model.layers.{i}.self_attn.{nm}.{ab}.default.weight" for i in range(eng.cfg.layers) for nm in LORA_TARGETS
-                for ab in ("lora_A", "lora_B")]
+        from .arch import lora_state_key
+        return [lora_state_key(i, nm, ab) for i in range(eng.cfg.layers) for nm in eng.targets for ab in ("lora_A", "lora_B")]
 
     def _save_checkpoint(self, epoch, name):
         """Same top-level keys as trainer:752-760.  model_state_dict holds the tensors this build owns (connectors + LoRA under peft's key
@@ -412,13 +411,29 @@ class ClipWhisperTrainer:
                     "scheduler_state_dict": {"T_max": self.total_steps, "eta_min": 0.0, "base_lrs": [self.learning_rate], "last_epoch": self.global_step,
                                              "_step_count": self.global_step + 1, "_last_lr": [self.lr_at(self.global_step)]},
                     "train_losses": self.train_losses, "val_losses": self.val_losses, "best_val_loss": self.best_val_loss}, path)
-        json.dump({"epoch": epoch, "global_step": self.global_step, "best_val_loss": self.best_val_loss},
+        json.dump({"epoch": epoch, "global_step": self.global_step, "best_val_loss": self.best_val_loss,
+                   "lora_target_modules": list(self.model.lora_target_modules) if self.model.use_lora else None},
                   open(path.replace(".pt", "_meta.json"), "w"))
+
+    @staticmethod
+    def checkpoint_lora_targets(path):
+        """The lora_target_modules a checkpoint of _save_checkpoint() was trained with, from the `_meta.json` beside it; None when the file or
+        the entry is absent (a checkpoint of the reference trainer, or of a build before the keyword: the default four).  A resume builds
+        its model with this (scripts/clip_whisper/train.py --resume_from)."""
+        meta = str(path).replace(".pt", "_meta.json")
+        if not os.path.exists(meta):
+            return None
+        t = json.load(open(meta)).get("lora_target_modules")
+        return None if t is None else list(t)
 
     def load_checkpoint(self, path):
         """trainer:796-854.  Reads a checkpoint of this build AND one written by the reference trainer: connectors + LoRA from
         model_state_dict, Adam moments from torch's optimizer state (the only parameters with state are the ones that ever received a
         gradient -- the LoRA tensors, SURVEY.md fact 4 -- in state-dict order), the step count from the scheduler's last_epoch."""
+        saved = self.checkpoint_lora_targets(path)
+        if saved is not None and self.model.use_lora and tuple(saved) != tuple(self.model.lora_target_modules):
+            raise ValueError(f"load_checkpoint(): {path} was trained with lora_target_modules = {', '.join(saved)}, this model has "
+                             f"{', '.join(self.model.lora_target_modules)}: build the model with checkpoint_lora_targets(path)")
         ck = torch.load(path, map_location="cpu", weights_only=True)
         self.model.load_state_dict(ck["model_state_dict"])
         eng = self.model.llm_engine

@@ -96,6 +96,7 @@ int avllm_kv_append(const void* k, const void* v, int64_t ld, void* kc, void* vc
                     int32_t d, int32_t dtype, void* stream) { return av_kv_append(k, v, ld, kc, vc, B, T, pos0, Tmax, d, dtype, ST); }
 int avllm_swiglu_fwd(const void* gu, void* h, int64_t M, int32_t F, int32_t dtype, void* stream) { return av_swiglu_fwd(gu, h, M, F, dtype, ST); }
 int avllm_swiglu_bwd(const void* dh, const void* gu, void* dgu, int64_t M, int32_t F, int32_t dtype, void* stream) { return av_swiglu_bwd(dh, gu, dgu, M, F, dtype, ST); }
+int avllm_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int64_t M, int32_t F, int32_t dtype, void* stream) { return av_swiglu_bwd_h(dh, gu, dgu, h, M, F, dtype, ST); }
 int avllm_attention_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int32_t B, int32_t Tq, int32_t Tk,
                         int32_t H, int32_t hd, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, int32_t causal,
                         int32_t dtype, int32_t impl, int32_t kv_heads, void* stream) {

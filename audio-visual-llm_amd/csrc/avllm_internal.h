@@ -20,6 +20,7 @@ int av_rmsnorm_bwd(const void* dy, const void* x, const void* w, const float* rs
 int av_rope(void* x, long ld, long rows, int T, int heads, int hd, int pos0, float theta, int inverse, int dtype, hipStream_t st);
 int av_swiglu_fwd(const void* gu, void* h, long M, int F, int dtype, hipStream_t st);
 int av_swiglu_bwd(const void* dh, const void* gu, void* dgu, long M, int F, int dtype, hipStream_t st);
+int av_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, long M, int F, int dtype, hipStream_t st);
 // Which kernel an attention call gets (AVLLM_ATTN_<form> of avllm.h): every dispatch below switches on these two
 int av_attention_fwd_form(int B, int Tq, int Tk, int hd, int causal, int dtype, int impl);
 int av_attention_bwd_form(int hd, int dtype, int impl);

@@ -99,8 +99,9 @@ __global__ void swiglu_fwd_kernel(const T* __restrict__ gu, T* __restrict__ h, l
         store_f<4>(h + m * F + c, o);
     }
 }
-template <typename T>
-__global__ void swiglu_bwd_kernel(const T* __restrict__ dh, const T* __restrict__ gu, T* __restrict__ dgu, long M, int F) {
+// WITH_H: also h = silu(g) * u, by swiglu_fwd_kernel's expression (the same bytes), for the backward pass of a down_proj adapter
+template <typename T, bool WITH_H>
+__global__ void swiglu_bwd_kernel(const T* __restrict__ dh, const T* __restrict__ gu, T* __restrict__ dgu, T* __restrict__ h, long M, int F) {
     const long total = M * (F >> 2);
     for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const long m = idx / (F >> 2);
@@ -118,6 +119,12 @@ __global__ void swiglu_bwd_kernel(const T* __restrict__ dh, const T* __restrict_
         }
         store_f<4>(dgu + m * 2 * F + c, dg);
         store_f<4>(dgu + m * 2 * F + F + c, du);
+        if (WITH_H) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = g[j] / (1.0f + __expf(-g[j])) * u[j];
+            store_f<4>(h + m * F + c, o);
+        }
     }
 }
 
@@ -480,8 +487,17 @@ int av_swiglu_fwd(const void* gu, void* h, long M, int F, int dtype, hipStream_t
 
 int av_swiglu_bwd(const void* dh, const void* gu, void* dgu, long M, int F, int dtype, hipStream_t st) {
     AV_CHECK_ARG(dh && gu && dgu && M > 0 && F % 4 == 0, "swiglu_bwd: bad args");
-    if (dtype == AV_F32) hipLaunchKernelGGL((swiglu_bwd_kernel<float>), dim3(grid_for(M * (F / 4))), dim3(256), 0, st, (const float*)dh, (const float*)gu, (float*)dgu, M, F);
-    else hipLaunchKernelGGL((swiglu_bwd_kernel<bf16>), dim3(grid_for(M * (F / 4))), dim3(256), 0, st, (const bf16*)dh, (const bf16*)gu, (bf16*)dgu, M, F);
+    if (dtype == AV_F32) hipLaunchKernelGGL((swiglu_bwd_kernel<float, false>), dim3(grid_for(M * (F / 4))), dim3(256), 0, st, (const float*)dh, (const float*)gu, (float*)dgu, (float*)nullptr, M, F);
+    else hipLaunchKernelGGL((swiglu_bwd_kernel<bf16, false>), dim3(grid_for(M * (F / 4))), dim3(256), 0, st, (const bf16*)dh, (const bf16*)gu, (bf16*)dgu, (bf16*)nullptr, M, F);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, long M, int F, int dtype, hipStream_t st) {
+    AV_CHECK_ARG(dh && gu && dgu && h && M > 0 && F > 0 && F % 4 == 0, "swiglu_bwd_h: bad args");
+    AV_CHECK_ARG(dtype == AV_F32 || dtype == AV_BF16, "swiglu_bwd_h: dtype %d", dtype);
+    if (dtype == AV_F32) hipLaunchKernelGGL((swiglu_bwd_kernel<float, true>), dim3(grid_for(M * (F / 4))), dim3(256), 0, st, (const float*)dh, (const float*)gu, (float*)dgu, (float*)h, M, F);
+    else hipLaunchKernelGGL((swiglu_bwd_kernel<bf16, true>), dim3(grid_for(M * (F / 4))), dim3(256), 0, st, (const bf16*)dh, (const bf16*)gu, (bf16*)dgu, (bf16*)h, M, F);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

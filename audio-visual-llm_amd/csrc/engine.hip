@@ -178,11 +178,23 @@ inline const void* llama_bias(const avllm_llama* m, const avllm_llama_layer& P, 
 
 // per-head q/k RMSNorm (Qwen3): a model has it on every layer or on none (check_llama)
 inline bool llama_qk_norm(const avllm_llama* m) { return m->layer && m->layer[0].q_norm_w != nullptr; }
+// adapters on gate_proj / up_proj / down_proj (avllm_llama_layer.lora_mlp): k = 0 gate, 1 up, 2 down
+inline bool layer_mlp_lora(const avllm_llama_layer& P) { return P.lora_mlp[0].A_pad || P.lora_mlp[1].A_pad || P.lora_mlp[2].A_pad; }
+inline bool llama_mlp_lora(const avllm_llama* m, int k0 = 0, int k1 = 3) {
+    if (!m->layer) return false;
+    for (int l = 0; l < m->layers; ++l)
+        for (int k = k0; k < k1; ++k)
+            if (m->layer[l].lora_mlp[k].A_pad) return true;
+    return false;
+}
+// the kernels that read an adapter's [M, K] input can generate its dropout mask themselves (lora_drop below)
+inline bool lora_mask_fusable(const avllm_llama* m, int K) { return m->dtype == AV_BF16 && K % 256 == 0 && m->lora_r <= 16; }
 
 struct LlamaLayerAct {
     void *xn1, *qkv, *att, *tqkv, *to, *h1, *gu;
     float *rstd1, *rstd2, *lse;
     void* qk_pre; float* qk_rstd;      // q/k head norm only: the pre-norm q|k [M, d + dkv] and rstd [M, H + Hkv] for avllm_qk_norm_bwd
+    void *tgu, *tdown;                 // MLP adapters only: the rank-side products of gate | up [M, 2*64] and of down [M, 64]
 };
 struct LlamaTrainWs {
     void** resid;            // host array [layers+1]
@@ -192,6 +204,8 @@ struct LlamaTrainWs {
     // backward scratch
     void *dres, *dxn, *dgu, *dhmid, *dqkv, *datt, *dtqkv, *dto;
     F8Buf f8;                // fp8 mode: the quantised input of the projection being computed
+    void *dtgu, *dtdown;     // MLP adapters only: the gradients of tgu / tdown
+    void* xdf;               //   and dropout(hmid) [M, ffn] where down's mask is materialised (lora_mask_fusable fails for K = ffn)
 };
 
 void carve_llama_train(const avllm_llama* m, int B, int S, Bump& b, LlamaTrainWs& w, void** resid, LlamaLayerAct* act) {
@@ -238,6 +252,20 @@ void carve_llama_train(const avllm_llama* m, int B, int S, Bump& b, LlamaTrainWs
         act[l].qk_pre = b.take((size_t)M * (d + llama_dkv(m)) * es);
         act[l].qk_rstd = (float*)b.take((size_t)M * (m->heads + llama_kv_heads(m)) * 4);
     }
+    // the same rule for a model with an adapter on gate, up or down
+    w.dtgu = w.dtdown = w.xdf = nullptr;
+    const bool mlp = llama_mlp_lora(m);
+    for (int l = 0; l < m->layers; ++l) {
+        act[l].tgu = act[l].tdown = nullptr;
+        if (!mlp) continue;
+        act[l].tgu = b.take((size_t)M * 2 * AVLLM_LORA_PAD * es);
+        act[l].tdown = b.take((size_t)M * AVLLM_LORA_PAD * es);
+    }
+    if (mlp) {
+        w.dtgu = b.take((size_t)M * 2 * AVLLM_LORA_PAD * es);
+        w.dtdown = b.take((size_t)M * AVLLM_LORA_PAD * es);
+        if (llama_mlp_lora(m, 2, 3) && !lora_mask_fusable(m, f)) w.xdf = b.take((size_t)M * f * es);
+    }
 }
 // The training workspace laid out in ws (null with an unlimited size: the dry run that sizes it), with the host arrays its layout points into
 struct LlamaTrainFrame {
@@ -256,6 +284,7 @@ int check_llama(const avllm_llama* m) {
                      "llama layer %d: q_norm_w and k_norm_w go together, on every layer or on none", l);
     }
     AV_CHECK_ARG(!llama_qk_norm(m) || m->d / m->heads == 64 || m->d / m->heads == 128, "llama: q/k head norms need a head dim of 64 or 128 (%d)", m->d / m->heads);
+    AV_CHECK_ARG(!m->fp8 || !llama_mlp_lora(m), "llama: fp8 mode does not take adapters on gate_proj / up_proj / down_proj (lora_mlp)");
     if (m->fp8)
         for (int l = 0; l < m->layers; ++l) {
             const avllm_llama_layer& P = m->layer[l];
@@ -285,30 +314,52 @@ struct LoraDrop {
     float p; bool fused;
     float fused_p() const { return fused ? p : 0.f; }
 };
-inline LoraDrop lora_drop(const avllm_llama* m) {
+// K: the input width of the modules meant (d; ffn for down_proj).  The mask index of an element is row * K + col.
+inline LoraDrop lora_drop(const avllm_llama* m, int K) {
     const float p = m->lora_dropout > 0.f ? m->lora_dropout : 0.f;
-    return {p, p > 0.f && m->dtype == AV_BF16 && m->d % 256 == 0 && m->lora_r <= 16};
+    return {p, p > 0.f && lora_mask_fusable(m, K)};
 }
-// the mask of layer l, module j (q, k, v, o); the step's base seed may live in device memory instead (m->dropout_seed_dev, see avllm_step_state)
-inline uint32_t lora_seed(const avllm_llama* m, int l, int j) { return m->dropout_seed + 4u * l + j; }
-// the adapter branch's input: x itself, or dropout(x) in xd after an av_dropout launch when masks are materialised
-int lora_input(const avllm_llama* m, const LoraDrop& dr, const void* x, void* xd, int M, uint32_t seed, const void*& xl, hipStream_t st) {
+inline LoraDrop lora_drop(const avllm_llama* m) { return lora_drop(m, m->d); }
+// the mask of layer l, module j (q, k, v, o; then 4 gate, 5 up, 6 down, whose seeds follow those of all layers' attention modules: the
+// attention seeds stay what they were).  The step's base seed may live in device memory instead (m->dropout_seed_dev, see avllm_step_state)
+inline uint32_t lora_seed(const avllm_llama* m, int l, int j) {
+    return j < 4 ? m->dropout_seed + 4u * l + j : m->dropout_seed + 4u * m->layers + 3u * l + (j - 4);
+}
+// the adapter branch's input: x [M, K] itself, or dropout(x) in xd after an av_dropout launch when masks are materialised
+int lora_input(const avllm_llama* m, const LoraDrop& dr, const void* x, void* xd, int M, int K, uint32_t seed, const void*& xl, hipStream_t st) {
     xl = x;
-    if (dr.p > 0.f && !dr.fused) { AV_TRY(av_dropout(x, xd, M, m->d, seed, dr.p, m->dtype, st, m->dropout_seed_dev)); xl = xd; }
+    if (dr.p > 0.f && !dr.fused) {
+        AV_CHECK_ARG(xd, "llama: no dropout buffer for an adapter input of width %d", K);
+        AV_TRY(av_dropout(x, xd, M, K, seed, dr.p, m->dtype, st, m->dropout_seed_dev));
+        xl = xd;
+    }
     return AV_OK;
 }
 
-// Adapter j of layer l in the training workspace: q, k, v (j = 0..2) share the [M, 3*64] buffers tqkv / dtqkv, o (j = 3) has to / dto
+// Adapter j of layer l in the training workspace: q, k, v (j = 0..2) share the [M, 3*64] buffers tqkv / dtqkv, o (j = 3) has to / dto,
+// gate and up (j = 4, 5) share the [M, 2*64] buffers tgu / dtgu, down (j = 6) has tdown / dtdown
 struct LoraView {
     const avllm_lora_mod* mod;
     uint32_t seed;
     void *t, *dt; long ldt;      // forward t_j = s dropout_j(x) A_j^T, backward d t_j, and the row stride of both
-    int off, wid;                // its columns of the fused q|k|v row (o: its own d columns)
-    bool at_slice;               // AT_pad is the j-th 64-column slice of one [d, 3*64] matrix that starts at q's
+    int off, wid;                // its columns of the fused q|k|v (gate|up) row (o, down: its own d columns)
+    bool at_slice;               // AT_pad is the j-th 64-column slice of one [d, 3*64] matrix that starts at q's (gate, up: [d, 2*64], gate's)
+    int K;                       // width of its input: d, or ffn for down
 };
 inline LoraView lora_view(const avllm_llama* m, int l, int j, const LlamaLayerAct& a, const LlamaTrainWs& w) {
     const avllm_lora_mod* lora = m->layer[l].lora;
-    LoraView v = {&lora[j], lora_seed(m, l, j), a.to, w.dto, AVLLM_LORA_PAD, 0, m->d, false};
+    const size_t es_ = av_dtype_size(m->dtype);
+    if (j >= 4) {
+        const avllm_lora_mod* lm = m->layer[l].lora_mlp;
+        const int k = j - 4;
+        if (k == 2) return {&lm[2], lora_seed(m, l, j), a.tdown, w.dtdown, AVLLM_LORA_PAD, 0, m->d, false, m->ffn};
+        const size_t slot = (size_t)k * AVLLM_LORA_PAD * es_;
+        LoraView g = {&lm[k], lora_seed(m, l, j), a.tgu ? (char*)a.tgu + slot : nullptr, w.dtgu ? (char*)w.dtgu + slot : nullptr, 2 * AVLLM_LORA_PAD,
+                      k * m->ffn, m->ffn, false, m->d};
+        g.at_slice = lm[k].ld_at == 2 * AVLLM_LORA_PAD && (const char*)lm[k].AT_pad == (const char*)lm[0].AT_pad + slot;
+        return g;
+    }
+    LoraView v = {&lora[j], lora_seed(m, l, j), a.to, w.dto, AVLLM_LORA_PAD, 0, m->d, false, m->d};
     if (j < 3) {
         const size_t es = av_dtype_size(m->dtype), slot = (size_t)j * AVLLM_LORA_PAD * es;
         v.t = (char*)a.tqkv + slot; v.dt = (char*)w.dtqkv + slot; v.ldt = 3 * AVLLM_LORA_PAD;
@@ -348,20 +399,21 @@ int lora_linear(const avllm_llama* m, const void* x, int K, const void* W, const
 // dA += dt^T dropout(x)
 int lora_wgrad(const avllm_llama* m, const LoraDrop& dr, const LoraView& v, const void* dy, long ldy, const void* x, void* xd, int M, hipStream_t st) {
     const avllm_lora_mod& lm = *v.mod;
-    const int dt = m->dtype, d = m->d, R = m->lora_r;
+    const int dt = m->dtype, d = v.K, R = m->lora_r;
     AV_TRY(av_gemm_tn(dy, ldy, v.wid, v.t, v.ldt, R, M, lm.gB, R, 1.0f, dt, st));
     avllm_gemm_desc gt = gemm_desc(dt, dy, ldy, lm.BT_pad, v.wid, v.dt, v.ldt, M, AVLLM_LORA_PAD, v.wid);
     gt.alpha = m->lora_scale; gt.n_valid = R;
     AV_TRY(av_gemm(&gt, st));
     const void* xin;
-    AV_TRY(lora_input(m, dr, x, xd, M, v.seed, xin, st));
+    AV_TRY(lora_input(m, dr, x, xd, M, d, v.seed, xin, st));
     return av_gemm_tn(v.dt, v.ldt, R, xin, d, d, M, lm.gA, d, 1.0f, dt, st, v.seed, dr.fused_p(), m->dropout_seed_dev);
 }
 
 // dx += sum_j mask_j * (dt_j . A_j) / (1-p) over the adapters present among v[0..n): their input gradients pass back through their dropout.
-// One pass over dx for all of them when the fused kernel applies (csrc/lora_dx.hip), a masked K = 64 GEMM each otherwise.
-int lora_dx_dropped(const avllm_llama* m, const LoraDrop& dr, const LoraView* v, int n, void* dx, int M, hipStream_t st) {
-    const int dt = m->dtype, d = m->d;
+// One pass over dx for all of them when the fused kernel applies (csrc/lora_dx.hip), a masked K = 64 GEMM each otherwise (p = 0: a plain
+// accumulating one, for adapters whose AT images are not the slices of one matrix).  dx is [M, d_in], d_in the adapters' input width.
+int lora_dx_dropped(const avllm_llama* m, const LoraDrop& dr, const LoraView* v, int n, void* dx, int M, hipStream_t st, int d_in = 0) {
+    const int dt = m->dtype, d = d_in ? d_in : m->d;
     const void* Tp[3]; const void* Ap[3]; long lt[3], la[3]; uint32_t sd[3]; int nj = 0;
     for (int j = 0; j < n; ++j) {
         if (!v[j].mod->A_pad) continue;
@@ -374,6 +426,68 @@ int lora_dx_dropped(const avllm_llama* m, const LoraDrop& dr, const LoraView* v,
         gm.R = dx; gm.ldr = d; gm.drop_seed = sd[k]; gm.drop_p = dr.p; gm.seed_dev = m->dropout_seed_dev;
         AV_TRY(av_gemm(&gm, st));
     }
+    return AV_OK;
+}
+
+// The MLP half of one layer's backward pass when the layer has an adapter on gate, up or down: from dres = d resid[l+1] to dxn = d xn2
+// (the caller's post-attention RMSNorm backward follows).  `gd` is the caller's dhmid = dres Wdown_t product, not yet launched.
+// The workspace keeps one xn2 and one hmid for all layers, so both adapter inputs are made again: xn2 by the forward's norm kernel from the
+// saved h1, hmid by the SwiGLU backward itself (av_swiglu_bwd_h), which therefore runs before dA_down.
+int llama_mlp_lora_bwd(const avllm_llama* m, int l, LlamaTrainWs& w, avllm_gemm_desc gd, int M, hipStream_t st) {
+    const avllm_llama_layer& P = m->layer[l];
+    LlamaLayerAct& a = w.act[l];
+    const int dt = m->dtype, d = m->d, f = m->ffn, R = m->lora_r;
+    const size_t es = av_dtype_size(dt);
+    const LoraDrop dr = lora_drop(m), drf = lora_drop(m, f);
+    const bool drop = dr.p > 0.f;
+    const LoraView vm[3] = {lora_view(m, l, 4, a, w), lora_view(m, l, 5, a, w), lora_view(m, l, 6, a, w)};
+    // ---- down: resid[l+1] = h1 + hmid Wdown^T + t_down B_down^T;  dy = dres
+    const bool down = vm[2].mod->A_pad != nullptr;
+    if (down) {
+        const avllm_lora_mod& lm = *vm[2].mod;
+        AV_TRY(av_gemm_tn(w.dres, d, d, vm[2].t, vm[2].ldt, R, M, lm.gB, R, 1.0f, dt, st));                         // dB = dy^T t
+        avllm_gemm_desc gt = gemm_desc(dt, w.dres, d, lm.BT_pad, d, vm[2].dt, vm[2].ldt, M, AVLLM_LORA_PAD, d);   // dt = s dy B
+        gt.alpha = m->lora_scale; gt.n_valid = R;
+        AV_TRY(av_gemm(&gt, st));
+        if (!drop) { gd.A2 = vm[2].dt; gd.lda2 = vm[2].ldt; gd.B2 = lm.AT_pad; gd.ldb2 = lm.ld_at; gd.K2 = AVLLM_LORA_PAD; }
+    }
+    AV_TRY(av_gemm(&gd, st));
+    if (down && drop) AV_TRY(lora_dx_dropped(m, drf, &vm[2], 1, w.dhmid, M, st, f));
+    if (down) {
+        AV_TRY(av_swiglu_bwd_h(w.dhmid, a.gu, w.dgu, w.hmid, M, f, dt, st));
+        const void* xin;
+        AV_TRY(lora_input(m, drf, w.hmid, w.xdf, M, f, vm[2].seed, xin, st));
+        AV_TRY(av_gemm_tn(vm[2].dt, vm[2].ldt, R, xin, f, f, M, vm[2].mod->gA, f, 1.0f, dt, st, vm[2].seed, drf.fused_p(), m->dropout_seed_dev));   // dA = dt^T dropout(hmid)
+    } else AV_TRY(av_swiglu_bwd(w.dhmid, a.gu, w.dgu, M, f, dt, st));
+    // ---- gate, up: gu = xn2 Wgu^T + [t_gate B_gate^T | t_up B_up^T];  dy_k = the k-th column half of dgu
+    const bool gate = vm[0].mod->A_pad != nullptr, up = vm[1].mod->A_pad != nullptr, any = gate || up;
+    char* dgu = (char*)w.dgu;
+    if (any) AV_TRY(av_rmsnorm_fwd(a.h1, P.ln2_w, w.xn2, nullptr, M, d, m->eps, dt, st));
+    const bool batch = dt == AV_BF16 && gate && up && (!drop || dr.fused) && d % 256 == 0 && f % 256 == 0 && av_lora_batch_supported(dt, R, 2) &&
+                       !av_knob(AV_KNOB_LORA_UNBATCHED);
+    if (batch) {      // three launches for the two adapters' dB, dt and dA (csrc/lora_batch.hip) instead of six
+        const void* Tq[2]; long ldt2[2]; float* gBp[2]; long lgb[2]; int c0[2], nc[2];
+        const void* dyp[2]; long ldy[2]; const void* BTp[2]; long lbt[2]; void* dtp[2];
+        const void* dtc[2]; float* gAp[2]; long lga[2]; uint32_t sd[2];
+        for (int k = 0; k < 2; ++k) {
+            const avllm_lora_mod& lk = *vm[k].mod;
+            Tq[k] = vm[k].t; dtp[k] = vm[k].dt; dtc[k] = vm[k].dt; ldt2[k] = vm[k].ldt; sd[k] = vm[k].seed;
+            c0[k] = vm[k].off; nc[k] = f; lbt[k] = f;
+            dyp[k] = dgu + (size_t)vm[k].off * es; ldy[k] = 2 * f; BTp[k] = lk.BT_pad;
+            gBp[k] = lk.gB; lgb[k] = R; gAp[k] = lk.gA; lga[k] = d;
+        }
+        AV_TRY(av_gemm_tn_multi(dgu, 2 * f, 2 * f, Tq, ldt2, gBp, lgb, c0, nc, nullptr, 2, R, M, 1.0f, 0.f, nullptr, 0, dt, st));
+        AV_TRY(av_lora_rank3(dyp, ldy, nc, BTp, lbt, dtp, ldt2, nullptr, 2, M, R, m->lora_scale, 0.f, nullptr, 0, dt, st));
+        AV_TRY(av_gemm_tn_multi(w.xn2, d, d, dtc, ldt2, gAp, lga, nullptr, nullptr, sd, 2, R, M, 1.0f, dr.p, m->dropout_seed_dev, 1, dt, st));
+    } else
+    for (int k = 0; k < 2; ++k)
+        if (vm[k].mod->A_pad) AV_TRY(lora_wgrad(m, dr, vm[k], dgu + (size_t)vm[k].off * es, 2 * f, w.xn2, w.xd, M, st));
+    // both adapters as one [d,128] AT image ride in the frozen product; one alone, or with dropout, adds its term afterwards
+    const bool seg = gate && up && !drop && vm[0].at_slice && vm[1].at_slice;
+    avllm_gemm_desc g = gemm_desc(dt, w.dgu, 2 * f, P.wgu_t, 2 * f, w.dxn, d, M, d, 2 * f);
+    if (seg) { g.A2 = w.dtgu; g.lda2 = 2 * AVLLM_LORA_PAD; g.B2 = vm[0].mod->AT_pad; g.ldb2 = 2 * AVLLM_LORA_PAD; g.K2 = 2 * AVLLM_LORA_PAD; }
+    AV_TRY(av_gemm(&g, st));
+    if (any && !seg) AV_TRY(lora_dx_dropped(m, dr, vm, 2, w.dxn, M, st));
     return AV_OK;
 }
 
@@ -491,7 +605,7 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
         }
         for (int j = 0; j < 3; ++j) {
             const void* xl = a.xn1;
-            if (v[j].mod->A_pad) AV_TRY(lora_input(m, dr, a.xn1, w.xd, M, v[j].seed, xl, st));
+            if (v[j].mod->A_pad) AV_TRY(lora_input(m, dr, a.xn1, w.xd, M, d, v[j].seed, xl, st));
             AV_TRY(lora_linear(m, a.xn1, d, fq ? nullptr : (const char*)P.wqkv + (size_t)v[j].off * d * es, llama_bias(m, P, j), v[j].wid, *v[j].mod,
                                xl, v[j].seed, dr.fused_p(), v[j].t, v[j].ldt, batch_qkv, (char*)a.qkv + (size_t)v[j].off * es, qw, nullptr, 0, M, st));
         }
@@ -503,14 +617,40 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
         AV_TRY(av_attention_fwd(qkv, qkv + (size_t)d * es, qkv + (size_t)(d + dkv) * es, a.att, a.lse, B, S, S, H, hd, qw, qw,
                                 qw, d, 1.0f / sqrtf((float)hd), 1, dt, 0, st, Hkv));
         const void* xl = a.att;
-        if (v[3].mod->A_pad) AV_TRY(lora_input(m, dr, a.att, w.xd, M, v[3].seed, xl, st));
+        if (v[3].mod->A_pad) AV_TRY(lora_input(m, dr, a.att, w.xd, M, d, v[3].seed, xl, st));
         if (fq) AV_TRY(linear(dt, fq, false, {nullptr, P.wo8, P.so8, P.bo}, a.att, d, M, d, d, a.h1, d, AV_ACT_NONE, w.resid[l], d, st));
         AV_TRY(lora_linear(m, a.att, d, fq ? nullptr : P.wo, P.bo, d, *v[3].mod, xl, v[3].seed, dr.fused_p(), v[3].t, v[3].ldt, false, a.h1, d,
                            w.resid[l], d, M, st));
         AV_TRY(av_rmsnorm_fwd(a.h1, P.ln2_w, w.xn2, a.rstd2, M, d, m->eps, dt, st));
-        AV_TRY(linear(dt, fq, false, {P.wgu, P.wgu8, P.sgu8, nullptr}, w.xn2, d, M, d, 2 * f, a.gu, 2 * f, AV_ACT_NONE, nullptr, 0, st));
+        if (!layer_mlp_lora(P)) {      // the frozen MLP: exactly the launches of a model without MLP adapters
+            AV_TRY(linear(dt, fq, false, {P.wgu, P.wgu8, P.sgu8, nullptr}, w.xn2, d, M, d, 2 * f, a.gu, 2 * f, AV_ACT_NONE, nullptr, 0, st));
+            AV_TRY(av_swiglu_fwd(a.gu, w.hmid, M, f, dt, st));
+            AV_TRY(linear(dt, fq, false, {P.wdown, P.wdown8, P.sdown8, nullptr}, w.hmid, f, M, f, d, w.resid[l + 1], d, AV_ACT_NONE, a.h1, d, st));
+            continue;
+        }
+        // ---- MLP with adapters: gu = xn2 Wgu^T + [t_gate B_gate^T | t_up B_up^T], resid[l+1] = h1 + hmid Wdown^T + t_down B_down^T.  gate and
+        // up are the row halves of wgu and the column halves of gu: two N = f products, each with its adapter as second K segment
+        const LoraView vm[3] = {lora_view(m, l, 4, a, w), lora_view(m, l, 5, a, w), lora_view(m, l, 6, a, w)};
+        const bool batch_gu = dt == AV_BF16 && vm[0].mod->A_pad && vm[1].mod->A_pad && (dr.p == 0.f || dr.fused) && d % 256 == 0 &&
+                              av_lora_batch_supported(dt, m->lora_r, 2) && !av_knob(AV_KNOB_LORA_UNBATCHED);
+        if (batch_gu) {      // both rank-side products of xn2 in one launch
+            const void* Ap[2] = {w.xn2, w.xn2}; const long la[2] = {d, d}; const int Kk[2] = {d, d};
+            const void* Bp[2] = {vm[0].mod->A_pad, vm[1].mod->A_pad}; const long lb[2] = {d, d};
+            void* Cp[2] = {vm[0].t, vm[1].t}; const long lc[2] = {vm[0].ldt, vm[1].ldt}; const uint32_t sd[2] = {vm[0].seed, vm[1].seed};
+            AV_TRY(av_lora_rank3(Ap, la, Kk, Bp, lb, Cp, lc, sd, 2, M, m->lora_r, m->lora_scale, dr.p, m->dropout_seed_dev, 1, dt, st));
+        }
+        for (int k = 0; k < 2; ++k) {
+            const void* xg = w.xn2;
+            if (vm[k].mod->A_pad) AV_TRY(lora_input(m, dr, w.xn2, w.xd, M, d, vm[k].seed, xg, st));
+            AV_TRY(lora_linear(m, w.xn2, d, (const char*)P.wgu + (size_t)vm[k].off * d * es, nullptr, f, *vm[k].mod, xg, vm[k].seed, dr.fused_p(), vm[k].t,
+                               vm[k].ldt, batch_gu, (char*)a.gu + (size_t)vm[k].off * es, 2 * f, nullptr, 0, M, st));
+        }
         AV_TRY(av_swiglu_fwd(a.gu, w.hmid, M, f, dt, st));
-        AV_TRY(linear(dt, fq, false, {P.wdown, P.wdown8, P.sdown8, nullptr}, w.hmid, f, M, f, d, w.resid[l + 1], d, AV_ACT_NONE, a.h1, d, st));
+        const LoraDrop drf = lora_drop(m, f);      // down's input is ffn wide: its own fused-mask condition and mask index
+        const void* xdn = w.hmid;
+        if (vm[2].mod->A_pad) AV_TRY(lora_input(m, drf, w.hmid, w.xdf, M, f, vm[2].seed, xdn, st));
+        AV_TRY(lora_linear(m, w.hmid, f, P.wdown, nullptr, d, *vm[2].mod, xdn, vm[2].seed, drf.fused_p(), vm[2].t, vm[2].ldt, false, w.resid[l + 1], d,
+                           a.h1, d, M, st));
     }
     AV_TRY(av_rmsnorm_fwd(w.resid[m->layers], m->norm_w, w.xf, w.rstd_f, M, d, m->eps, dt, st));
     AV_TRY(linear(dt, fq, false, {m->lm_head, m->lm_head8, m->slm_head8, nullptr}, w.xf, d, M, d, m->vocab, w.logits, m->vocab, AV_ACT_NONE, nullptr, 0, st));
@@ -563,10 +703,12 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
         AV_CHECK_ARG(P.wqkv_t && P.wo_t && P.wgu_t && P.wdown_t, "llama_lora_bwd: layer %d has no transposed weights", l);
         // ---- MLP: resid[l+1] = h1 + down(silu(g)*u)
         g = gemm_desc(dt, w.dres, d, P.wdown_t, d, w.dhmid, f, M, f, d);
-        AV_TRY(av_gemm(&g, st));
-        AV_TRY(av_swiglu_bwd(w.dhmid, a.gu, w.dgu, M, f, dt, st));
-        g = gemm_desc(dt, w.dgu, 2 * f, P.wgu_t, 2 * f, w.dxn, d, M, d, 2 * f);
-        AV_TRY(av_gemm(&g, st));
+        if (!layer_mlp_lora(P)) {      // the frozen MLP: exactly the launches of a model without MLP adapters
+            AV_TRY(av_gemm(&g, st));
+            AV_TRY(av_swiglu_bwd(w.dhmid, a.gu, w.dgu, M, f, dt, st));
+            g = gemm_desc(dt, w.dgu, 2 * f, P.wgu_t, 2 * f, w.dxn, d, M, d, 2 * f);
+            AV_TRY(av_gemm(&g, st));
+        } else AV_TRY(llama_mlp_lora_bwd(m, l, w, g, M, st));
         AV_TRY(av_rmsnorm_bwd(w.dxn, a.h1, P.ln2_w, a.rstd2, w.dres, w.dres, M, d, dt, st));      // dres = d h1
         // ---- o_proj (+LoRA): h1 = resid[l] + att Wo^T + to Bo^T
         const avllm_lora_mod& lo = *v[3].mod;
@@ -612,11 +754,12 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
         for (int j = 0; j < 3; ++j)
             if (v[j].mod->A_pad) AV_TRY(lora_wgrad(m, dr, v[j], dqkv + (size_t)v[j].off * es, qw, a.xn1, w.xd, M, st));
         if (l > 0 || dx_embeds) {      // layer 0: d(inputs_embeds) only when the caller trains the connectors (frozen otherwise: SURVEY.md fact 4)
-            AV_CHECK_ARG(!any || contiguous || drop, "llama_lora_bwd: q/k/v AT_pad images must be the three 64-column slices of one [d,192] matrix");
+            // the second K segment takes all three adapters as one [d,192] AT image; a subset of q, k, v adds its terms one by one
+            const bool seg = any && !drop && contiguous;
             g = gemm_desc(dt, w.dqkv, qw, P.wqkv_t, qw, w.dxn, d, M, d, qw);
-            if (any && !drop) { g.A2 = w.dtqkv; g.lda2 = 3 * AVLLM_LORA_PAD; g.B2 = P.lora[0].AT_pad; g.ldb2 = 3 * AVLLM_LORA_PAD; g.K2 = 3 * AVLLM_LORA_PAD; }
+            if (seg) { g.A2 = w.dtqkv; g.lda2 = 3 * AVLLM_LORA_PAD; g.B2 = P.lora[0].AT_pad; g.ldb2 = 3 * AVLLM_LORA_PAD; g.K2 = 3 * AVLLM_LORA_PAD; }
             AV_TRY(av_gemm(&g, st));
-            if (any && drop) AV_TRY(lora_dx_dropped(m, dr, v, 3, w.dxn, M, st));
+            if (any && !seg) AV_TRY(lora_dx_dropped(m, dr, v, 3, w.dxn, M, st));
             AV_TRY(av_rmsnorm_bwd(w.dxn, w.resid[l], P.ln1_w, a.rstd1, w.dres, l > 0 ? w.dres : dx_embeds, M, d, dt, st));      // layer 0: d resid[0]
         }
         if (after_layer) after_layer(l, user);
@@ -690,12 +833,15 @@ int llama_infer_layer(const avllm_llama* m, int l, LlamaInferWs& w, int B, int S
     }
     AV_TRY(lora_linear(m, w.att, d, P.wo, P.bo, d, P.lora[3], w.att, 0, 0.f, w.t, AVLLM_LORA_PAD, false, w.x, d, w.x, d, M, st));
     AV_TRY(av_rmsnorm_fwd(w.x, P.ln2_w, w.xn, nullptr, M, d, m->eps, dt, st));
-    avllm_gemm_desc g = gemm_desc(dt, w.xn, d, P.wgu, d, w.gu, 2 * f, M, 2 * f, d);
-    AV_TRY(av_gemm(&g, st));
+    if (!P.lora_mlp[0].A_pad && !P.lora_mlp[1].A_pad) {      // no adapter on gate or up: one fused gate|up projection
+        avllm_gemm_desc g = gemm_desc(dt, w.xn, d, P.wgu, d, w.gu, 2 * f, M, 2 * f, d);
+        AV_TRY(av_gemm(&g, st));
+    } else
+    for (int k = 0; k < 2; ++k)
+        AV_TRY(lora_linear(m, w.xn, d, (const char*)P.wgu + (size_t)k * f * d * es, nullptr, f, P.lora_mlp[k], w.xn, 0, 0.f, w.t, AVLLM_LORA_PAD, false,
+                           (char*)w.gu + (size_t)k * f * es, 2 * f, nullptr, 0, M, st));
     AV_TRY(av_swiglu_fwd(w.gu, w.hmid, M, f, dt, st));
-    g = gemm_desc(dt, w.hmid, f, P.wdown, f, w.x, d, M, d, f);
-    g.R = w.x; g.ldr = d;
-    return av_gemm(&g, st);
+    return lora_linear(m, w.hmid, f, P.wdown, nullptr, d, P.lora_mlp[2], w.hmid, 0, 0.f, w.t, AVLLM_LORA_PAD, false, w.x, d, w.x, d, M, st);
 }
 }  // namespace
 
@@ -736,6 +882,7 @@ extern "C" int avllm_llama_prefill(const avllm_llama* m, const void* x, int32_t 
 // One decoder block of a token step in 5 launches (decode.hip): bf16, B <= 16 sequences; 7 with adapters (rank <= 16: the rank-side
 // products of q|k|v and of o are two more -- tiny -- launches over the A images, the B side rides in the projections' epilogues).
 static bool llama_decode_lora_ok(const avllm_llama* m, const avllm_llama_layer& P, bool& any) {
+    if (layer_mlp_lora(P)) { any = true; return false; }      // the epilogue form covers q, k, v, o only: merge the adapters (merge_lora) to get the fused step back
     int n = 0;
     for (int j = 0; j < 4; ++j) n += P.lora[j].A_pad != nullptr;
     any = n > 0;

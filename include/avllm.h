@@ -220,6 +220,9 @@ int avllm_rope_tab(void* x, int64_t ld, int64_t rows, int32_t T, int32_t heads, 
 /* h = silu(g)*u with gu = [g | u] ([M,2F]); HF:models/llama/modeling_llama.py:175 */
 int avllm_swiglu_fwd(const void* gu, void* h, int64_t M, int32_t F, int32_t dtype, void* stream);
 int avllm_swiglu_bwd(const void* dh, const void* gu, void* dgu, int64_t M, int32_t F, int32_t dtype, void* stream);
+/* avllm_swiglu_bwd that also writes h [M,F] = silu(g) * u in the same pass over gu (what avllm_swiglu_fwd wrote, bit for bit): the backward
+ * pass of a down_proj adapter needs the MLP's hidden activation, which the training workspace does not keep per layer. */
+int avllm_swiglu_bwd_h(const void* dh, const void* gu, void* dgu, void* h, int64_t M, int32_t F, int32_t dtype, void* stream);
 /* softmax(QK^T*scale [+causal]) V.  q/k/v/o: row = token (b*T+t), head h at column h*hd; row strides in elements.
  * lse [B,H,Tq] (natural log) optional.  impl 0 = MFMA flash kernel (bf16 only), 1 = reference-grade scalar kernel.
  * kv_heads (0 = H): grouped-query attention, k/v (and dk/dv) hold kv_heads heads and query head h reads head h/(H/kv_heads)
@@ -580,6 +583,13 @@ typedef struct avllm_llama_layer {
      * with its bias, plus the adapter term, then the head norm, then RoPE.  Frozen: no gradient is formed for them.  Qwen3-1.7B / 8B / 14B
      * geometry (hd = d / heads = 128); hd is 64 or 128. */
     const void *q_norm_w, *k_norm_w;
+    /* adapters on the MLP projections: gate_proj, up_proj, down_proj (peft target_modules beyond the four attention modules, up to
+     * "all-linear"); A_pad == NULL = none, any subset.  gate, up: A [r, d], B [ffn, r], input the post-attention RMSNorm output; down: A [r, ffn],
+     * B [d, r], input silu(gate) * up.  Images as for lora[] (avllm_lora_pack with din = the module's input width); gate and up may share
+     * one [d, 128] AT image (ld_at 128, up's at column 64) as q, k, v share one of 192 columns.  Honoured by avllm_llama_lora_fwd_loss / _bwd,
+     * avllm_llama_prefill and the general token step; while any is attached the fused token step is not taken (avllm_llama_decode_is_fused
+     * returns 0) and avllm_llama.fp8 is refused.  Appended last: no earlier offset moves. */
+    avllm_lora_mod lora_mlp[3];      /* gate, up, down */
 } avllm_llama_layer;
 
 typedef struct avllm_llama {
@@ -588,7 +598,10 @@ typedef struct avllm_llama {
                                       * the k/v adapters' B is [kv_heads*hd, r], the KV cache rows are kv_heads*hd wide */
     float eps, theta, lora_scale;
     float lora_dropout;              /* applied by avllm_llama_lora_fwd_loss/_bwd only (training); 0 = off */
-    uint32_t dropout_seed;           /* module j of layer l uses seed dropout_seed + 4*l + j; change it every step */
+    uint32_t dropout_seed;           /* attention module j (q, k, v, o) of layer l uses seed dropout_seed + 4*l + j; MLP module k (0 gate, 1 up,
+                                      * 2 down) of layer l uses dropout_seed + 4*layers + 3*l + k.  The mask index of an element is row * K + col
+                                      * with K the module's input width (d; ffn for down): what avllm_dropout gives on [M, K].  Change it
+                                      * every step */
     const uint32_t* dropout_seed_dev;/* optional DEVICE word added to dropout_seed at run time (graph-replayable steps: avllm_step_state) */
     const void* embed;               /* [vocab,d] */
     const void* norm_w;

@@ -19,7 +19,8 @@ path of a hotword; generate(hotwords=, hotword_bias=)), --nbest N (beam search r
 --num_beams >= N; WER stays on the 1-best), --confidence (adds tokens, token_logprobs, avg_logprob and word_confidences of the 1-best to each
 utterance of the --output_file JSON, and with --nbest > 1 an nbest list of {hypothesis, score}), --min_avg_logprob F (utterances whose mean
 token log-probability is below F are listed in the log; they still count in the WER), --share_prefix (generate(share_prefix=True): the beams
-of an utterance share one prefix cache), --load_lora (also load the adapters from the checkpoint), --merge_lora (with --load_lora: fold the loaded
+of an utterance share one prefix cache), --load_lora (also load the adapters from the checkpoint), --lora_target_modules (with --load_lora: the modules those adapters sit on,
+default what the checkpoint's metadata records; adapters on gate/up/down keep the token step off the fused path until --merge_lora folds them),--merge_lora (with --load_lora: fold the loaded
 adapters into the LLM weights once, ClipWhisperModel.merge_lora(), so that decoding runs the adapter-free kernels), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
@@ -87,6 +88,11 @@ def parse_args(argv=None):
                         "shares the same way among the n sampled sequences of num_return_sequences=n; this script samples one per utterance, "
                         "and greedy decoding has nothing to share")
     p.add_argument("--load_lora", action="store_true")
+    p.add_argument("--lora_target_modules", type=str, default=None,
+                   help="with --load_lora: the modules the checkpoint's adapters sit on (comma-separated names out of q_proj,k_proj,v_proj,o_proj,"
+                        "gate_proj,up_proj,down_proj, or all-linear).  Default: the YAML's model.lora_target_modules, else what the checkpoint's "
+                        "_meta.json records, else the four attention modules.  An unmerged adapter on gate/up/down keeps the token step off "
+                        "the fused path: add --merge_lora")
     p.add_argument("--merge_lora", action="store_true",
                    help="with --load_lora: fold the adapters into the LLM weights after the checkpoint is loaded (effect on WER not measured)")
     p.add_argument("--data_path", type=str, default=None)
@@ -95,6 +101,8 @@ def parse_args(argv=None):
     p.add_argument("--frames", type=int, default=125)
     p.add_argument("--synthetic-weights", action="store_true", help="seeded random weights + byte tokenizer (implied by --tiny)")
     a = p.parse_args(argv)
+    if a.lora_target_modules and not a.load_lora:
+        p.error("--lora_target_modules needs --load_lora: without it the model has no adapters")
     if a.merge_lora and not a.load_lora:
         p.error("--merge_lora needs --load_lora: without it the model has no adapters to merge")
     if a.nbest < 1:
@@ -180,6 +188,13 @@ def main(argv=None):
     if not dev.startswith("cuda"):
         raise ValueError(f"--device {a.device}: this build runs the path on an MI355X only (there is no CPU fallback)")
     kw = {}
+    if a.load_lora:
+        targets = a.lora_target_modules or cfg.get("lora_target_modules")
+        if targets is None and a.model_path:
+            from avllm.trainer import ClipWhisperTrainer
+            targets = ClipWhisperTrainer.checkpoint_lora_targets(a.model_path)
+        if targets is not None:
+            kw["lora_target_modules"] = targets
     if a.tiny:
         from avllm.arch import ClipCfg, LlamaCfg, LoraCfg, ModelCfg, WhisperCfg
         kw["config"] = ModelCfg(WhisperCfg(128, 2, 2, 256), ClipCfg(128, 2, 2, 256, 48, 16), LlamaCfg(256, 2, 2, 512, 512), LoraCfg(16, 32.0))

@@ -26,6 +26,10 @@ def parse_args():
     p.add_argument("--connector_type", default=None); p.add_argument("--max_grad_norm", type=float)
     p.add_argument("--train_connectors", action="store_true", default=None,
                    help="train the two modality connectors (encoders stay frozen); YAML key model.train_connectors")
+    p.add_argument("--lora_target_modules", default=None,
+                   help="modules that get a LoRA adapter: comma-separated names out of q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj, or "
+                        "all-linear; default the four attention modules (YAML key model.lora_target_modules; a --resume_from checkpoint's own "
+                        "value is used when neither is given)")
     p.add_argument("--log_interval", type=int); p.add_argument("--save_every", type=int); p.add_argument("--resume_from")
     p.add_argument("--save_steps", type=int, default=None, help="stored by the trainer and never acted on, as in the reference (clip_whisper_trainer.py:94-102)")
     p.add_argument("--log_param_updates", action="store_true", help="accepted for command-line compatibility; the reference stores it and never reads it (:118)")
@@ -62,7 +66,7 @@ def main():
                             "clip_model": a.clip_model, "modality": a.modality, "batch_size": a.batch_size, "num_epochs": a.max_epochs,
                             "learning_rate": a.learning_rate, "max_seq_len": a.max_seq_len, "use_fp16": a.fp16, "use_4bit": a.use_4bit,
                             "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type, "train_connectors": a.train_connectors,
-                            "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
+                            "lora_target_modules": a.lora_target_modules, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
                             "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None})
     os.makedirs(cfg["output_dir"], exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s",
@@ -75,6 +79,11 @@ def main():
     from avllm.model import ClipWhisperModel
     from avllm.trainer import ClipWhisperTrainer
     kw = {}
+    targets = cfg.get("lora_target_modules")
+    if targets is None and a.resume_from and not a.no_lora:
+        targets = ClipWhisperTrainer.checkpoint_lora_targets(a.resume_from)      # a resume trains the modules the checkpoint holds
+    if targets is not None:
+        kw["lora_target_modules"] = targets
     if a.tiny:
         from avllm.arch import ClipCfg, LlamaCfg, LoraCfg, ModelCfg, WhisperCfg
         kw["config"] = ModelCfg(WhisperCfg(128, 2, 2, 256), ClipCfg(128, 2, 2, 256, 48, 16), LlamaCfg(256, 2, 2, 512, 512), LoraCfg(16, 32.0))
