@@ -7,8 +7,10 @@ of a head) and read back, the token's own row included.  llama_hidden(past=...) 
   * a later call stores its k (after the head norm, where the weights have one, and RoPE) and v first and attends over nothing but stored rows.
 
 `store` is the storage: mx_store (the rule), or identity (then this file is llama_hidden with a cache; tests/test_kv8_refs_cpu.py compares them).
-Plain weights only (HF names, float tensors), adapters as the oracle's `layers.N.<module>.lora_A|B` dict.  The quantiser is restated here in
-float64 from the rule's text, not taken from oracle/mxfp8.py, and the same CPU file shows the two agree."""
+Plain weights only (HF names, float tensors; projection biases under `<module>.bias` where the model has them), adapters as the oracle's
+`layers.N.<module>.lora_A|B` dict.  The quantiser is restated here in float64 from the rule's text, not taken from oracle/mxfp8.py, and the
+same CPU file shows the two agree.  tests/test_token_step_cases_cpu.py ties the bias and head-norm terms to stored transformers logits and uses
+`rnd` / `wrong` of llama_hidden (a model of the bf16 engine's roundings; planted defects) to state what the GPU bars can and cannot tell."""
 import torch
 
 from oracle import avsr_oracle as O
@@ -49,8 +51,16 @@ def _d(t):
     return t.to(F64)
 
 
+def round_bf16(x):
+    """A value as a bf16 tensor holds it (round to nearest even), float64: the `rnd` of llama_hidden for the bf16 engine's stored tensors."""
+    return x.to(torch.float32).to(torch.bfloat16).to(F64)
+
+
 def _lin(x, sd, lora, wkey, lkey, scale):
     y = x @ _d(sd[wkey]).T
+    bkey = wkey[:-len("weight")] + "bias"                        # Qwen2: q, k, v; attention_bias: o as well (peft: base_layer(x) with its bias, + adapter)
+    if bkey in sd:
+        y = y + _d(sd[bkey])
     if lora is not None and (lkey + ".lora_A") in lora:
         y = y + scale * ((x @ _d(lora[lkey + ".lora_A"]).T) @ _d(lora[lkey + ".lora_B"]).T)
     return y
@@ -60,9 +70,17 @@ def _rms(x, w, eps):
     return _d(w) * (x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps))
 
 
-def llama_hidden(sd, lora, c, lc, x, past, pos0=0, store=mx_store):
+def llama_hidden(sd, lora, c, lc, x, past, pos0=0, store=mx_store, rnd=identity, wrong=()):
     """x [B, T, d] -> the hidden states after the final norm [B, T, d], float64.  past: list of (k, v) [B, Hkv, t, hd] per layer (None = empty),
-    the STORED rows, extended in place."""
+    the STORED rows, extended in place.  Projection biases (`<module>.bias` under HF names) are added where the state dict has them.
+
+    rnd: applied wherever the bf16 engine holds a bf16 tensor -- the normed input of a layer's projections, q|k|v after the bias, q and k after
+    head norm and RoPE, the attention output, hmid, the residual stream after each add.  identity (the default): the float64 arithmetic;
+    round_bf16: a float64 model of the engine's roundings, which tests/test_token_step_cases_cpu.py uses to state how far from the float64
+    arithmetic a correct bf16 step may land.
+    wrong: defects of the kind a token step can have, for that file's sensitivity checks only -- "kv_head_mod": query head h reads kv head
+    h % Hkv instead of h // (H / Hkv); "attend_before_append": the step's own row is stored after the attention has run (with a zero row put
+    at the first generated position by the caller, this is a writer that is one position late)."""
     x = _d(x)
     B, T, d = x.shape
     H, hd = c.heads, c.hidden // c.heads
@@ -72,29 +90,33 @@ def llama_hidden(sd, lora, c, lc, x, past, pos0=0, store=mx_store):
     scale = lc.scale if lc is not None else 0.0
     for i in range(c.layers):
         L, K = f"model.layers.{i}.", f"layers.{i}."
-        h = _rms(x, sd[L + "input_layernorm.weight"], c.eps)
+        h = rnd(_rms(x, sd[L + "input_layernorm.weight"], c.eps))
         sp = lambda t, n: t.view(B, T, n, hd).transpose(1, 2)    # noqa: E731
-        q = sp(_lin(h, sd, lora, L + "self_attn.q_proj.weight", K + "q_proj", scale), H)
-        k = sp(_lin(h, sd, lora, L + "self_attn.k_proj.weight", K + "k_proj", scale), Hkv)
-        v = sp(_lin(h, sd, lora, L + "self_attn.v_proj.weight", K + "v_proj", scale), Hkv)
+        q = sp(rnd(_lin(h, sd, lora, L + "self_attn.q_proj.weight", K + "q_proj", scale)), H)
+        k = sp(rnd(_lin(h, sd, lora, L + "self_attn.k_proj.weight", K + "k_proj", scale)), Hkv)
+        v = sp(rnd(_lin(h, sd, lora, L + "self_attn.v_proj.weight", K + "v_proj", scale)), Hkv)
         if (L + "self_attn.q_norm.weight") in sd:                # Qwen3: per-head RMSNorm before RoPE
             q, k = _rms(q, sd[L + "self_attn.q_norm.weight"], c.eps), _rms(k, sd[L + "self_attn.k_norm.weight"], c.eps)
-        q, k = O.apply_rope(q, cos, sin), O.apply_rope(k, cos, sin)
+        q, k = rnd(O.apply_rope(q, cos, sin)), rnd(O.apply_rope(k, cos, sin))
         if past[i] is None:                                      # prefill: attends over its own k, v; the append stores
             past[i] = (store(k), store(v))
+        elif "attend_before_append" in wrong:
+            k, v, past[i] = past[i][0], past[i][1], (torch.cat([past[i][0], store(k)], 2), torch.cat([past[i][1], store(v)], 2))
         else:
             past[i] = (torch.cat([past[i][0], store(k)], 2), torch.cat([past[i][1], store(v)], 2))
             k, v = past[i]
         Tk = k.shape[2]
-        if Hkv != H:
+        if Hkv != H and "kv_head_mod" in wrong:
+            k, v = k.repeat(1, H // Hkv, 1, 1), v.repeat(1, H // Hkv, 1, 1)
+        elif Hkv != H:
             k, v = k.repeat_interleave(H // Hkv, 1), v.repeat_interleave(H // Hkv, 1)
         s = (q @ k.transpose(-1, -2)) * hd ** -0.5
         vis = torch.arange(Tk)[None, :] <= torch.arange(Tk - T, Tk)[:, None]
-        a = (torch.softmax(s.masked_fill(~vis, float("-inf")), -1) @ v).transpose(1, 2).reshape(B, T, d)
-        x = x + _lin(a, sd, lora, L + "self_attn.o_proj.weight", K + "o_proj", scale)
-        h = _rms(x, sd[L + "post_attention_layernorm.weight"], c.eps)
+        a = rnd((torch.softmax(s.masked_fill(~vis, float("-inf")), -1) @ v).transpose(1, 2).reshape(B, T, d))
+        x = rnd(x + _lin(a, sd, lora, L + "self_attn.o_proj.weight", K + "o_proj", scale))
+        h = rnd(_rms(x, sd[L + "post_attention_layernorm.weight"], c.eps))
         g, u = h @ _d(sd[L + "mlp.gate_proj.weight"]).T, h @ _d(sd[L + "mlp.up_proj.weight"]).T
-        x = x + (torch.nn.functional.silu(g) * u) @ _d(sd[L + "mlp.down_proj.weight"]).T
+        x = rnd(x + rnd(torch.nn.functional.silu(g) * u) @ _d(sd[L + "mlp.down_proj.weight"]).T)
     return _rms(x, sd["model.norm.weight"], c.eps)
 
 

@@ -236,15 +236,7 @@ def test_dec_proj_fp4_refusals(dev):
 
 
 # ------------------------------------------------------------------------------------------------ 7. token step
-def dequantised4(sd):
-    """The state dict with every frozen projection replaced by its MXFP4 W~ and lm_head by its e4m3 W~ (what the fp4 token step multiplies)."""
-    out = dict(sd)
-    for k, v in sd.items():
-        if k == "lm_head.weight":
-            out[k] = mxfp8.fake_quant(v.to(BF).float())
-        elif any(k.endswith(p + ".weight") for p in PROJ):
-            out[k] = mx4.fake_quant(v.to(BF).float())
-    return out
+from dequant_weights import dequantised4  # noqa: E402,F401  (host code: tests/dequant_weights.py; other test files import it from here)
 
 
 def _engines(dev, sd, cfg, lora_sd, with_lora):

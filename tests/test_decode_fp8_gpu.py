@@ -212,16 +212,7 @@ def test_dec_proj_fp8_refusals(dev):
 
 
 # ------------------------------------------------------------------------------------------------ 5. token step
-PROJ = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
-
-
-def dequantised(sd):
-    """The state dict with every frozen projection and lm_head replaced by W~ (what the fp8 token step multiplies)."""
-    out = dict(sd)
-    for k, v in sd.items():
-        if k == "lm_head.weight" or any(k.endswith(p + ".weight") for p in PROJ):
-            out[k] = mxfp8.fake_quant(v.to(BF).float())
-    return out
+from dequant_weights import PROJ, dequantised  # noqa: E402,F401  (host code: tests/dequant_weights.py; other test files import it from here)
 
 
 def _sd(hidden, heads, kvh, layers, ffn, vocab, seed=5):
