@@ -174,6 +174,17 @@ def test_fp8_training_forward(dev, cases, name):
     print(f"{name} fp8 forward vs bf16: logits {cost:.3e}, loss {loss8:.4f} vs {loss16:.4f}; vs the fixture {rel_l2(l8, gold['logits']):.3e}")
     assert torch.isfinite(l8).all() and torch.isfinite(e8.lora_g).all()
     assert cost < Bar.FP8_VS_UNQUANTISED_REL_L2
+    # and against the float64 step with the frozen products fake-quantised (tests/refs64_lora_mlp.py fp8_proj, tied to the oracle's fp8 mode by
+    # tests/test_train_step_cases_cpu.py), on the bf16 values the engine holds: logits, loss and the adapter gradients at the fp8 bars
+    import refs64_lora_mlp as R64
+    as_held = lambda t: {k: v.bfloat16().float() for k, v in t.items()}      # noqa: E731
+    rl, rlogits, rg, _ = R64.step(as_held(sd), as_held(lora), c, AW.ALPHA / AW.RANK, gold["inputs_embeds"], gold["labels"], proj=R64.fp8_proj)
+    g8 = {k: v.cpu() for k, v in e8.lora_views(e8.lora_g).items()}
+    keys = sorted(rg)
+    e_l, e_g = rel_l2(l8, rlogits), rel_l2(torch.cat([g8[k].flatten() for k in keys]), torch.cat([rg[k].flatten() for k in keys]))
+    print(f"{name} fp8 vs the fake-quantised float64 step: logits {e_l:.3e}, |dloss| {abs(loss8 - float(rl)):.3e}, LoRA grads {e_g:.3e}")
+    assert set(g8) == set(rg)
+    assert e_l < Bar.FP8_LOGITS_REL_L2 and abs(loss8 - float(rl)) < Bar.FP8_LOSS_ABS and e_g < Bar.FP8_GRAD_REL_L2
 
 
 @pytest.mark.parametrize("form", ["fp8", "fp4"])
