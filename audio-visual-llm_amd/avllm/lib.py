@@ -171,6 +171,9 @@ _SIGS = {
     "avllm_clip_cls_rows": ([vp, vp, vp, i32, i32, i32, i32, vp], i32),
     "avllm_fuse_pool": ([vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, i32, vp], i32),
     "avllm_fuse_pool_bwd": ([vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp], i32),
+    "avllm_fuse_pool_rows": ([vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp], i32),
+    "avllm_fuse_pool_rows_bwd": ([vp, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, f32, i32, vp], i32),
+    "avllm_modality_draw": ([vp, vp, i32, f32, f32, C.c_uint32, vp, vp], i32),
     "avllm_gemm_wgrad": ([vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, f32, i32, vp], i32),
     "avllm_grad_sumsq_det_multi": ([C.POINTER(vp), C.POINTER(i64), i32, vp, i32, vp, vp], i32),
     "avllm_adamw_step_multi": ([C.POINTER(AdamwSeg), i32, f32, f32, f32, f32, i32, vp, f32, f32, vp, vp, vp, vp], i32),

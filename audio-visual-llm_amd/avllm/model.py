@@ -15,6 +15,9 @@ Differences that are deliberate and documented:
   * train_connectors=True (default False) trains the two modality connectors with the encoders frozen: the reference's freeze_encoders=False
     gradient (clip_whisper_model.py:1096-1106,1136-1146) restricted to the four connector tensors, which does not depend on whether the
     encoders receive one too.  connector_type "simple", precision fp32 | bf16, use_lora=True.
+  * modality_dropout_audio / modality_dropout_video (default 0 = off) and the modality_mask keyword of forward() / encode() / generate() are
+    additions: one mode per clip (both | audio only | video only) at the geometry of the two-stream call, drawn per step in train() mode or
+    given by the caller (see forward()).  Without them the model launches what it launched.
 """
 from __future__ import annotations
 
@@ -58,6 +61,39 @@ class _LoraLoss(torch.autograd.Function):
         return (eng.lora_g.clone(), None, None) + tuple(g.clone() for g in m.connector_grad_views())
 
 
+MODALITY_MODES = {"both": 0, "audio": 1, "video": 2}      # AVLLM_MODE_* of include/avllm.h
+
+
+def parse_modality_mask(mask, B, device=None):
+    """A modality_mask as an int32 tensor [B]: a list / tuple / CPU tensor of 0 | 1 | 2 or "both" | "audio" | "video" is checked (length B, values
+    in range) and moved to `device` (None: left on the CPU); an int32 device tensor [B] is taken as given."""
+    if isinstance(mask, torch.Tensor) and mask.is_cuda:
+        if mask.dtype != torch.int32 or mask.dim() != 1 or mask.shape[0] != B:
+            raise ValueError(f"modality_mask on the device must be int32 [{B}], got {mask.dtype} {tuple(mask.shape)}")
+        return mask.contiguous()
+    if isinstance(mask, torch.Tensor):
+        if mask.dim() != 1 or mask.dtype.is_floating_point or mask.dtype == torch.bool:
+            raise ValueError(f"modality_mask must be a 1-d integer tensor, got {mask.dtype} {tuple(mask.shape)}")
+        vals = mask.tolist()
+    elif isinstance(mask, (list, tuple)):
+        vals = list(mask)
+    else:
+        raise ValueError(f"modality_mask must be a list or a tensor with one entry per clip, got {type(mask).__name__}")
+    if len(vals) != B:
+        raise ValueError(f"modality_mask has {len(vals)} entries for a batch of {B} clips (one per clip, not per beam or returned sequence)")
+    out = []
+    for i, m in enumerate(vals):
+        if isinstance(m, str):
+            if m not in MODALITY_MODES:
+                raise ValueError(f"modality_mask[{i}] = {m!r}: must be both | audio | video (or 0 | 1 | 2)")
+            m = MODALITY_MODES[m]
+        if isinstance(m, bool) or not isinstance(m, int) or m not in (0, 1, 2):
+            raise ValueError(f"modality_mask[{i}] = {m!r}: must be 0 (both) | 1 (audio) | 2 (video)")
+        out.append(m)
+    t = torch.tensor(out, dtype=torch.int32)
+    return t if device is None else t.to(device)
+
+
 class ClipWhisperModel:
     def __init__(self, llm_path="meta-llama/Llama-2-7b-hf", whisper_model="openai/whisper-small",
                  clip_model="openai/clip-vit-base-patch16", device="cuda", use_fp16=False, use_4bit=False, use_lora=True,
@@ -65,13 +101,32 @@ class ClipWhisperModel:
                  max_seq_len=256, fusion_scale=0.5, connector_type="simple", _provided_tokenizer=None, _provided_llm=None,
                  _provided_whisper=None, _provided_clip=None, *, precision=None, config: ModelCfg | None = None,
                  weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16",
-                 train_connectors: bool = False, kv_cache: str = "bf16", lora_target_modules=None):
+                 train_connectors: bool = False, kv_cache: str = "bf16", lora_target_modules=None,
+                 modality_dropout_audio: float = 0.0, modality_dropout_video: float = 0.0):
         if use_4bit:
             raise NotImplementedError("use_4bit (bitsandbytes nf4) is out of scope of the MI355X hot path (SURVEY.md §8)")
         if not freeze_encoders:
             raise NotImplementedError("freeze_encoders=False is not supported: the hot path trains LoRA only (SURVEY.md fact 4)")
         if modality not in ("audio", "video", "both"):
             raise ValueError(f"modality must be audio|video|both, got {modality}")
+        # modality dropout (AV-HuBERT's training recipe; not in the reference): in train() mode every clip of a two-stream call loses its audio
+        # with probability modality_dropout_audio or its video with modality_dropout_video, never both; drawn on the device per step
+        # (ops.modality_draw) and applied by the fusion (ops.fuse_pool_rows).  The encoders still run on every clip.  Its effect on WER is
+        # not measured.
+        for nm, p in (("modality_dropout_audio", modality_dropout_audio), ("modality_dropout_video", modality_dropout_video)):
+            if not isinstance(p, (int, float)) or isinstance(p, bool) or not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"{nm} must be a probability in [0, 1], got {p!r}")
+        if float(modality_dropout_audio) + float(modality_dropout_video) > 1.0:
+            raise ValueError(f"modality_dropout_audio + modality_dropout_video must be at most 1 (a clip never loses both streams), got "
+                             f"{modality_dropout_audio} + {modality_dropout_video}")
+        if modality != "both" and (modality_dropout_audio or modality_dropout_video):
+            nm = "modality_dropout_audio" if modality_dropout_audio else "modality_dropout_video"
+            raise ValueError(f"{nm}={modality_dropout_audio or modality_dropout_video} needs modality='both', got modality={modality!r}: "
+                             f"there is no second stream to fall back on")
+        self.modality_dropout_audio, self.modality_dropout_video = float(modality_dropout_audio), float(modality_dropout_video)
+        self.last_modality_modes = None            # int32 [B] device buffer of the last call that used per-clip modes, else None
+        self.last_modality_seed = None             # the by-value seed of that call's draw (None: no draw, or the seed came from device memory)
+        self._mode_bufs = {}
         L.load()                                   # fail loudly when the HIP library is missing
         self.device = device
         self.use_fp16, self.use_4bit, self.use_lora = use_fp16, use_4bit, use_lora
@@ -329,18 +384,21 @@ class ClipWhisperModel:
 
     def _dx_embeds_buffer(self):
         """Static [B,S,d] buffer for d loss / d inputs_embeds of the last training forward (LlamaEngine.bwd(dx_embeds=...))."""
-        _, _, _, _, S, B = self._conn_geo
+        _, _, _, _, S, B, _ = self._conn_geo
         return self._static("dx", (B, S, self.llm_dim))
 
     def connector_backward(self):
         """dx_embeds -> fuse / pool adjoint -> the two weight gradients and bias gradients, written into conn_g (overwritten, not
         accumulated).  The connectors' INPUT gradient is not formed: the encoders are frozen.  An input that was absent in the forward
         leaves its connector's gradient as zeros."""
-        Ta, Tv, P, Lc, S, B = self._conn_geo
+        Ta, Tv, P, Lc, S, B, modes = self._conn_geo
         D = self.llm_dim
         da = self._static("da", (B, Ta, D)) if Ta else None
         dv = self._static("dv", (B, Tv, D)) if Tv else None
-        ops.fuse_pool_bwd(self._dx_embeds_buffer(), Ta, Tv, P, Lc, self.fusion_scale, da=da, dv=dv)
+        if modes is not None:               # per-clip modes: a clip's unused stream gets zero rows, which add nothing to dW / db below
+            ops.fuse_pool_rows_bwd(self._dx_embeds_buffer(), modes, Ta, Tv, P, Lc, self.fusion_scale, da=da, dv=dv)
+        else:
+            ops.fuse_pool_bwd(self._dx_embeds_buffer(), Ta, Tv, P, Lc, self.fusion_scale, da=da, dv=dv)
         gWa, gba, gWv, gbv = self.connector_grad_views()
         for dy, conn, gW, gb in ((da, self.audio_connector, gWa, gba), (dv, self.video_connector, gWv, gbv)):
             if dy is None:
@@ -411,9 +469,38 @@ class ClipWhisperModel:
             return None, v, v.shape[1]
         raise ValueError("No valid inputs provided - both audio and video are None")
 
-    def _llm_inputs(self, audio, video, prompt, S_out=None, keep=False):
+    def _modes_for(self, modality_mask, audio, video, draw_seed, seed_dev):
+        """The per-clip mode buffer of this call (int32 [B] on the device), or None for the default path.  Before the encoders run, so that a
+        bad mask costs nothing.  A draw happens in train() mode on a two-stream call when a dropout probability is set: ops.modality_draw into a
+        static buffer (one per batch size: a captured step replays the launch on the same address), with the mask as mode_in."""
+        both = self.modality == "both" and audio is not None and video is not None
+        if modality_mask is not None and not both:
+            raise ValueError("modality_mask needs a call with both audio and video on a modality='both' model: a call on one stream has "
+                             "nothing to choose between")
+        draw = self.training and both and (self.modality_dropout_audio > 0.0 or self.modality_dropout_video > 0.0)
+        self.last_modality_modes = self.last_modality_seed = None
+        if modality_mask is None and not draw:
+            return None
+        B = audio.shape[0]
+        modes = parse_modality_mask(modality_mask, B, self.device) if modality_mask is not None else None
+        if draw:
+            buf = self._mode_bufs.get(B)
+            if buf is None:
+                buf = self._mode_bufs[B] = torch.zeros(B, dtype=torch.int32, device=self.device)
+            if seed_dev is None and draw_seed is None:
+                draw_seed = self._next_seed()
+            self.last_modality_seed = None if seed_dev is not None else int(draw_seed)
+            modes = ops.modality_draw(B, self.modality_dropout_audio, self.modality_dropout_video, seed=draw_seed or 0, seed_dev=seed_dev,
+                                      mode_in=modes, out=buf)
+        self.last_modality_modes = modes
+        return modes
+
+    def _llm_inputs(self, audio, video, prompt, S_out=None, keep=False, modality_mask=None, draw_seed=None, seed_dev=None):
         """keep (train_connectors=True, training forward): the connectors keep the rows they project and the fusion geometry is recorded,
-        which is all connector_backward() needs -- no second encoder pass."""
+        which is all connector_backward() needs -- no second encoder pass.
+        modality_mask / a modality-dropout draw (_modes_for; draw_seed by value or seed_dev, the address of a device word): the fusion
+        takes one mode per clip (ops.fuse_pool_rows) at the geometry of the two-stream call; without either it is ops.fuse_pool as ever."""
+        modes = self._modes_for(modality_mask, audio, video, draw_seed, seed_dev)
         self.audio_connector.keep_input = self.video_connector.keep_input = bool(keep)
         try:
             a, v, Lc = self._features(audio, video)
@@ -424,24 +511,31 @@ class ClipWhisperModel:
         B = (a if a is not None else v).shape[0]
         S = P + Lc if S_out is None else S_out
         if keep:
-            self._conn_geo = (a.shape[1] if a is not None else 0, v.shape[1] if v is not None else 0, P, Lc, S, B)
+            self._conn_geo = (a.shape[1] if a is not None else 0, v.shape[1] if v is not None else 0, P, Lc, S, B, modes)
+        if modes is not None:
+            return ops.fuse_pool_rows(a, v, pe, modes, Lc, S, self.fusion_scale, self.llm_dim, B)
         return ops.fuse_pool(a, v, pe, Lc, S, self.fusion_scale, self.llm_dim, B)
 
-    def encode(self, audio=None, video=None, prompt=None):
-        """-> (inputs_embeds [B,P+L,D], attention_mask ones int64 [B,P+L])  (clip_whisper_model.py:407-462)."""
-        x = self._llm_inputs(audio, video, prompt)
+    def encode(self, audio=None, video=None, prompt=None, modality_mask=None):
+        """-> (inputs_embeds [B,P+L,D], attention_mask ones int64 [B,P+L])  (clip_whisper_model.py:407-462).
+        modality_mask: one mode per clip, see forward()."""
+        x = self._llm_inputs(audio, video, prompt, modality_mask=modality_mask)
         return x, torch.ones(x.shape[0], x.shape[1], dtype=torch.long, device=x.device)
 
     # ------------------------------------------------------------------ forward / loss
-    def _dropout_args(self):
-        """lora_dropout is active in train() mode only; every training forward draws a fresh mask seed."""
-        if not (self.training and self.use_lora and self.lora_dropout):
-            return {"dropout": 0.0, "seed": 0}
+    def _next_seed(self):
+        """The seed of the next training forward: the formula of avllm_step_state.dropout_seed on a host-side step count."""
         self._drop_step += 1
         rank = 0
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             rank = torch.distributed.get_rank()           # data-parallel ranks draw independent masks, as independent processes would
-        return {"dropout": float(self.lora_dropout), "seed": (self._drop_step * 0x9E3779B1 + rank * 0x85EBCA6B + 12345) & 0xFFFFFFFF}
+        return (self._drop_step * 0x9E3779B1 + rank * 0x85EBCA6B + 12345) & 0xFFFFFFFF
+
+    def _dropout_args(self):
+        """lora_dropout is active in train() mode only; every training forward draws a fresh mask seed."""
+        if not (self.training and self.use_lora and self.lora_dropout):
+            return {"dropout": 0.0, "seed": 0}
+        return {"dropout": float(self.lora_dropout), "seed": self._next_seed()}
 
     def _prep_labels(self, labels):
         if isinstance(labels, list):
@@ -454,8 +548,13 @@ class ClipWhisperModel:
         # cannot be captured in a graph)
         return torch.where(labels == self.tokenizer.pad_token_id, torch.full_like(labels, -100), labels)
 
-    def forward(self, audio=None, video=None, prompt=None, labels=None, return_loss=True):
-        """clip_whisper_model.py:489-619 -> {"loss","logits"} | {"logits"}."""
+    def forward(self, audio=None, video=None, prompt=None, labels=None, return_loss=True, modality_mask=None):
+        """clip_whisper_model.py:489-619 -> {"loss","logits"} | {"logits"}.
+        modality_mask (not in the reference): one entry per clip of a two-stream call, 0 | "both", 1 | "audio" (video ignored), 2 | "video"
+        (audio ignored), as a list or CPU tensor (checked here: length B, values in range) or an int32 device tensor [B] (taken as given;
+        any value other than 1 or 2 reads as 0).  The batch keeps the two-stream geometry; a clip's ignored stream is not read by the fusion and
+        may hold anything.  In train() mode with modality_dropout_audio / _video set, the clips the mask leaves at 0 are drawn per call
+        (ops.modality_draw) with the seed of this forward's LoRA dropout; model.last_modality_modes holds the modes used."""
         if labels is not None and return_loss:
             try:
                 labels = self._prep_labels(labels)
@@ -467,8 +566,10 @@ class ClipWhisperModel:
         if self.training and labels is not None:
             if self.llm_engine.merged:
                 raise RuntimeError("forward(): a training forward needs the separate adapters, which merge_lora() folded into the LLM weights")
-            x = self._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors)       # adaptive pool / interpolate (:577-585)
-            logits = self.llm_engine.fwd_loss(x, labels, want_logits=True, **self._dropout_args())
+            drop = self._dropout_args()                # first: a modality-dropout draw shares this forward's seed
+            x = self._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors, modality_mask=modality_mask,
+                                 draw_seed=drop["seed"] if drop["dropout"] else None)       # adaptive pool / interpolate (:577-585)
+            logits = self.llm_engine.fwd_loss(x, labels, want_logits=True, **drop)
             acc = self.llm_engine.acc
             loss = acc[0] / acc[1]
             if self.train_connectors:
@@ -477,7 +578,7 @@ class ClipWhisperModel:
             elif self.lora_param is not None and self.lora_param.requires_grad:
                 loss = _LoraLoss.apply(self.lora_param, self, loss)
             return {"loss": loss, "logits": logits}
-        x = self._llm_inputs(audio, video, prompt)
+        x = self._llm_inputs(audio, video, prompt, modality_mask=modality_mask)
         B, S, _ = x.shape
         kc, vc = self.llm_engine.alloc_cache(B, S, fp8=False)
         _, logits = self.llm_engine.prefill(x, kc, vc, all_logits=True)
@@ -499,7 +600,7 @@ class ClipWhisperModel:
                  temperature=1.0, top_p=0.9, max_length=None, top_k=50, seed=None, num_beams=1, length_penalty=1.0, early_stopping=False,
                  return_sequence_scores=False, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sequence_bias=None,
                  bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, hotwords=None, hotword_bias=0.0,
-                 return_token_scores=False, num_return_sequences=1, share_prefix=False):
+                 return_token_scores=False, num_return_sequences=1, share_prefix=False, modality_mask=None):
         """clip_whisper_model.py:1240-1348 -> GenerationMixin's greedy search, sampling or beam search on the fused inputs (avllm/generation.py).
         Returns NEW tokens only, int64 [B, <= max_new_tokens], pad_token_id after a row's EOS.  With every keyword at its default nothing but
         the greedy loop is launched or allocated.  video is also taken as pixel_values; max_new_tokens=None means max_length, else 100.
@@ -542,7 +643,9 @@ class ClipWhisperModel:
           general path (LlamaEngine.decode_is_fused is False): correct, but without the fused step's speed and without what goes with it --
           decode_weights="fp8" | "fp4" stream bf16 weights, kv_cache="fp8" keeps a bf16 cache, share_prefix takes the default path.  The
           remedy is merge_lora() (or from_pretrained(..., merge_lora=True)): the model is then adapter-free and takes the fused step in
-          every weight and cache form."""
+          every weight and cache form.
+        modality_mask: one mode per CLIP (not per beam or returned sequence) of a two-stream call, as in forward(): it acts on the fused inputs,
+          before beams or n-best expand the rows, so every decoding mode, weight form and cache form takes it unchanged."""
         if video is None and pixel_values is not None:
             video = pixel_values
         eos, pad = self.eos_token_id, self.tokenizer.pad_token_id
@@ -561,7 +664,7 @@ class ClipWhisperModel:
         elif video is not None:
             self.modality = "video"
         try:
-            x = self._llm_inputs(audio, video, prompt)
+            x = self._llm_inputs(audio, video, prompt, modality_mask=modality_mask)
         finally:
             self.modality = original
         if num_beams > 1:

@@ -684,6 +684,70 @@ def fuse_pool_bwd(dx, Ta, Tv, P, L_, fusion_scale, want_a=True, want_v=True, da=
     return da, dv
 
 
+def _check_modes(name, mode, B, device):
+    if not isinstance(mode, torch.Tensor) or mode.dtype != torch.int32 or mode.dim() != 1 or mode.shape[0] != B or not mode.is_contiguous():
+        raise ValueError(f"{name}: mode must be a contiguous int32 tensor [{B}], got "
+                         f"{(tuple(mode.shape), mode.dtype) if isinstance(mode, torch.Tensor) else type(mode).__name__}")
+    if mode.device != device:
+        raise ValueError(f"{name}: mode lives on {mode.device}, the inputs on {device}")
+
+
+def fuse_pool_rows(a, v, prompt_emb, mode, L_, S_out, fusion_scale, D, B):
+    """fuse_pool with one mode per clip (avllm_fuse_pool_rows): mode int32 [B] on the device, 0 both | 1 audio only | 2 video only.
+    a [B,Ta,D] and v [B,Tv,D] are both required; prompt_emb [B,P,D] | None.  The stream a row does not use is not read for that row."""
+    if a is None or v is None:
+        raise ValueError(f"fuse_pool_rows: modes need both inputs ({'a' if a is None else 'v'} is None); a call on one stream is fuse_pool")
+    if a.dtype != v.dtype or a.shape[0] != B or v.shape[0] != B or a.shape[2] != D or v.shape[2] != D:
+        raise ValueError(f"fuse_pool_rows: a {tuple(a.shape)} {a.dtype} and v {tuple(v.shape)} {v.dtype} do not match B={B}, D={D}")
+    _check_modes("fuse_pool_rows", mode, B, a.device)
+    a, v = a.contiguous(), v.contiguous()
+    out = torch.empty(B, S_out, D, device=a.device, dtype=a.dtype)
+    P = prompt_emb.shape[1] if prompt_emb is not None else 0
+    L.check(L.load().avllm_fuse_pool_rows(L.ptr(a), a.shape[1], L.ptr(v), v.shape[1], L.ptr(prompt_emb), P, L.ptr(mode), L.ptr(out), B, L_, S_out, D,
+                                          fusion_scale, L.dt_of(a), L.stream_ptr()))
+    return out
+
+
+def fuse_pool_rows_bwd(dx, mode, Ta, Tv, P, L_, fusion_scale, da=None, dv=None):
+    """The adjoint of fuse_pool_rows (avllm_fuse_pool_rows_bwd): dx [B,S_out,D] -> (da [B,Ta,D], dv [B,Tv,D]), both overwritten; a row's unused
+    stream gets exact zeros.  da / dv: preallocated outputs (static buffers of a captured step)."""
+    dx = dx.contiguous()
+    B, S_out, D = dx.shape
+    if Ta <= 0 or Tv <= 0:
+        raise ValueError(f"fuse_pool_rows_bwd: modes need both inputs (Ta={Ta}, Tv={Tv}); the adjoint of a call on one stream is fuse_pool_bwd")
+    _check_modes("fuse_pool_rows_bwd", mode, B, dx.device)
+    if da is None:
+        da = torch.empty(B, Ta, D, device=dx.device, dtype=dx.dtype)
+    if dv is None:
+        dv = torch.empty(B, Tv, D, device=dx.device, dtype=dx.dtype)
+    for nm, t, T in (("da", da, Ta), ("dv", dv, Tv)):
+        if tuple(t.shape) != (B, T, D) or t.dtype != dx.dtype or not t.is_contiguous():
+            raise ValueError(f"fuse_pool_rows_bwd: {nm} {tuple(t.shape)} {t.dtype} is not a contiguous [{B}, {T}, {D}] {dx.dtype}")
+    L.check(L.load().avllm_fuse_pool_rows_bwd(L.ptr(dx), L.ptr(da), Ta, L.ptr(dv), Tv, P, L.ptr(mode), B, L_, S_out, D, fusion_scale, L.dt_of(dx),
+                                              L.stream_ptr()))
+    return da, dv
+
+
+def modality_draw(B, p_drop_audio, p_drop_video, seed=0, seed_dev=None, mode_in=None, out=None, device="cuda"):
+    """Draws one mode per clip on the device (avllm_modality_draw; the rule is in include/avllm.h): int32 [B], 2 with probability p_drop_audio
+    (audio dropped), 1 with p_drop_video, else 0.  mode_in int32 [B] | None: entries 1 / 2 are kept.  seed_dev: the address of a device uint32
+    (or a one-element int32 device tensor) added to seed at run time; out: a preallocated result (static buffer of a captured step)."""
+    pa, pv = float(p_drop_audio), float(p_drop_video)
+    if not (0.0 <= pa <= 1.0 and 0.0 <= pv <= 1.0 and pa + pv <= 1.0):
+        raise ValueError(f"modality_draw: p_drop_audio={pa} and p_drop_video={pv} must lie in [0, 1] with a sum of at most 1")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=mode_in.device if mode_in is not None else device)
+    _check_modes("modality_draw (out)", out, B, out.device)
+    if mode_in is not None:
+        _check_modes("modality_draw (mode_in)", mode_in, B, out.device)
+    if isinstance(seed_dev, torch.Tensor):
+        if seed_dev.numel() != 1 or seed_dev.element_size() != 4:
+            raise ValueError(f"modality_draw: seed_dev must hold one 32-bit word, got {tuple(seed_dev.shape)} {seed_dev.dtype}")
+        seed_dev = L.ptr(seed_dev)
+    L.check(L.load().avllm_modality_draw(L.ptr(mode_in), L.ptr(out), B, pa, pv, int(seed) & 0xFFFFFFFF, seed_dev, L.stream_ptr()))
+    return out
+
+
 def gemm_wgrad(dY, X, alpha=1.0, dW=None, db=None, want_db=True):
     """dW [N,K] (fp32) = alpha * dY^T . X and db [N] (fp32) = alpha * column sums of dY, for dY [M,N], X [M,K] (avllm_gemm_wgrad: no atomics)."""
     M, N = dY.shape

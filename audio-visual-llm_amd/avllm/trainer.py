@@ -109,7 +109,9 @@ class ClipWhisperTrainer:
         model, eng = self.model, self.model.llm_engine
         ops.step_advance(self.state, self.learning_rate, self.total_steps, self.warmup_steps, rank=self._rank)
         labels = model._prep_labels(labels)
-        x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors)
+        # modality dropout (model.modality_dropout_*): drawn here, after step_advance, from this step's seed in device memory -- a replayed
+        # graph redraws
+        x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors, seed_dev=self._seed_ptr)
         p = float(model.lora_dropout) if (model.training and model.use_lora and model.lora_dropout) else 0.0
         eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr)
 
@@ -223,6 +225,7 @@ class ClipWhisperTrainer:
             st["opt"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(st["opt"], pool=pool):
                 self._part_opt()
+        st["modes"] = self.model.last_modality_modes          # the static mode buffer this signature's graph writes (None without modes)
         return st
 
     def _replay(self, st):
@@ -278,6 +281,7 @@ class ClipWhisperTrainer:
                 if dst is not None and src.data_ptr() != dst.data_ptr():
                     dst.copy_(src, non_blocking=True)
             self._replay(st)
+            self.model.last_modality_modes = st["modes"]
         else:
             self._eager_step(audio, video, labels, prompt)
         return self._loss_buf.clone()
@@ -304,7 +308,7 @@ class ClipWhisperTrainer:
     def _train_epoch(self, epoch):
         self.model.train()
         total, n, t0 = 0.0, 0, time.time()
-        pending = []
+        pending, pending_modes = [], []
         failures = unstable = worst = 0
         for i, batch in enumerate(self.train_dataloader):
             # the reference logs and skips a batch on ANY exception (:492-507).  Host-side preparation (everything before the first
@@ -332,6 +336,8 @@ class ClipWhisperTrainer:
                 continue
             failures = 0
             pending.append(loss)
+            if self.model.last_modality_modes is not None:       # stays on the device until the log interval, like the loss
+                pending_modes.append(self.model.last_modality_modes.clone())
             if (i + 1) % self.log_interval == 0 or i + 1 == len(self.train_dataloader):
                 vals = torch.stack(pending).float().cpu()
                 pending.clear()
@@ -351,7 +357,18 @@ class ClipWhisperTrainer:
                     break
                 logging.info(f"epoch {epoch} batch {i + 1}/{len(self.train_dataloader)} loss {float(vals[-1]):.4f} "
                              f"avg {total / max(1, n):.4f} lr {self.lr_at(self.global_step):.3e} {(time.time() - t0) / (i + 1):.3f}s/it")
+                if pending_modes:
+                    share = self.mode_shares(torch.cat(pending_modes).cpu())
+                    pending_modes.clear()
+                    logging.info(f"epoch {epoch} batch {i + 1}: clips with both streams {share[0]:.3f}, audio only {share[1]:.3f}, video only {share[2]:.3f}")
         return total / max(1, n)
+
+    @staticmethod
+    def mode_shares(modes):
+        """The share of clips in mode 0 (both), 1 (audio only) and 2 (video only) of an int32 tensor of modes; any other value counts as 0."""
+        n = max(1, modes.numel())
+        one, two = int((modes == 1).sum()), int((modes == 2).sum())
+        return [(modes.numel() - one - two) / n, one / n, two / n]
 
     @torch.no_grad()
     def _validate(self):

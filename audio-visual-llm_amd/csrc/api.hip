@@ -173,6 +173,16 @@ int avllm_fuse_pool(const void* a, int32_t Ta, const void* v, int32_t Tv, const 
                     int32_t S_out, int32_t D, float fs, int32_t dtype, void* stream) { return av_fuse_pool(a, Ta, v, Tv, pe, P, out, B, L, S_out, D, fs, dtype, ST); }
 int avllm_fuse_pool_bwd(const void* dx, void* da, int32_t Ta, void* dv, int32_t Tv, int32_t P, int32_t B, int32_t L, int32_t S_out, int32_t D,
                         float fs, int32_t dtype, void* stream) { return av_fuse_pool_bwd(dx, da, Ta, dv, Tv, P, B, L, S_out, D, fs, dtype, ST); }
+int avllm_fuse_pool_rows(const void* a, int32_t Ta, const void* v, int32_t Tv, const void* pe, int32_t P, const int32_t* mode, void* out, int32_t B,
+                         int32_t L, int32_t S_out, int32_t D, float fs, int32_t dtype, void* stream) {
+    return av_fuse_pool_rows(a, Ta, v, Tv, pe, P, mode, out, B, L, S_out, D, fs, dtype, ST);
+}
+int avllm_fuse_pool_rows_bwd(const void* dx, void* da, int32_t Ta, void* dv, int32_t Tv, int32_t P, const int32_t* mode, int32_t B, int32_t L,
+                             int32_t S_out, int32_t D, float fs, int32_t dtype, void* stream) {
+    return av_fuse_pool_rows_bwd(dx, da, Ta, dv, Tv, P, mode, B, L, S_out, D, fs, dtype, ST);
+}
+int avllm_modality_draw(const int32_t* mode_in, int32_t* mode_out, int32_t B, float p_drop_audio, float p_drop_video, uint32_t seed,
+                        const uint32_t* seed_dev, void* stream) { return av_modality_draw(mode_in, mode_out, B, p_drop_audio, p_drop_video, seed, seed_dev, ST); }
 int avllm_gemm_wgrad(const void* dY, int64_t ldy, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, float* dW, int64_t ldw, float* db,
                      float alpha, int32_t dtype, void* stream) { return av_gemm_wgrad(dY, ldy, X, ldx, M, N, K, dW, ldw, db, alpha, dtype, ST); }
 int avllm_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int32_t nbuf, float* partials, int32_t nparts, float* sumsq, void* stream) {

@@ -71,6 +71,12 @@ int av_clip_cls_rows(const void* class_emb, const void* pos, void* x, int N, int
 int av_fuse_pool(const void* a, int Ta, const void* v, int Tv, const void* prompt_emb, int P, void* out, int B, int L,
                  int S_out, int D, float fs, int dtype, hipStream_t st);
 int av_fuse_pool_bwd(const void* dx, void* da, int Ta, void* dv, int Tv, int P, int B, int L, int S_out, int D, float fs, int dtype, hipStream_t st);
+int av_fuse_pool_rows(const void* a, int Ta, const void* v, int Tv, const void* prompt_emb, int P, const int* mode, void* out, int B, int L,
+                      int S_out, int D, float fs, int dtype, hipStream_t st);
+int av_fuse_pool_rows_bwd(const void* dx, void* da, int Ta, void* dv, int Tv, int P, const int* mode, int B, int L, int S_out, int D, float fs,
+                          int dtype, hipStream_t st);
+int av_modality_draw(const int* mode_in, int* mode_out, int B, float p_drop_audio, float p_drop_video, uint32_t seed, const uint32_t* seed_dev,
+                     hipStream_t st);
 int av_gemm_wgrad(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
                   hipStream_t st);
 int av_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int nbuf, float* partials, int nparts, float* sumsq, hipStream_t st);

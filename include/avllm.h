@@ -414,6 +414,35 @@ int avllm_fuse_pool(const void* a, int32_t Ta, const void* v, int32_t Tv, const 
  * launches are bit-identical. */
 int avllm_fuse_pool_bwd(const void* dx, void* da, int32_t Ta, void* dv, int32_t Tv, int32_t P, int32_t B, int32_t L, int32_t S_out,
                         int32_t D, float fusion_scale, int32_t dtype, void* stream);
+/* Per-clip modality (modality dropout in training, a mask at inference; the reference has neither: its fusion, clip_whisper_model.py:426-450,
+ * treats every clip of a call alike).  One int32 mode word per batch row; any other value is read as AVLLM_MODE_BOTH. */
+enum { AVLLM_MODE_BOTH = 0, AVLLM_MODE_AUDIO = 1, AVLLM_MODE_VIDEO = 2 };
+/* avllm_fuse_pool with `mode` (DEVICE int32 [B]); a and v both non-NULL, the geometry (Ta, Tv, L, P, S_out) that of the two-input call.
+ * Virtual row t < L of clip b (clip_whisper_model.py:426-450, then the pooling / interpolation of :621-707 as in avllm_fuse_pool):
+ *   AVLLM_MODE_BOTH   fs*a[b,t] + (1-fs)*v[b,t] (zero past each length)
+ *   AVLLM_MODE_AUDIO  a[b,t], scale 1, zero for t >= Ta
+ *   AVLLM_MODE_VIDEO  v[b,t], scale 1, zero for t >= Tv
+ * i.e. per row what avllm_fuse_pool does for a NULL input.  The stream a row does not use is NOT READ for that row (it may hold NaN).
+ * Window bounds and weights are avllm_fuse_pool's expressions: modes all 0 / all 1 / all 2 give the bits of avllm_fuse_pool(a, v) /
+ * (a, NULL) / (NULL, v) at the same L. */
+int avllm_fuse_pool_rows(const void* a, int32_t Ta, const void* v, int32_t Tv, const void* prompt_emb, int32_t P, const int32_t* mode,
+                         void* out, int32_t B, int32_t L, int32_t S_out, int32_t D, float fusion_scale, int32_t dtype, void* stream);
+/* Its adjoint, in the gather form of avllm_fuse_pool_bwd (ascending dx rows, fp32, no atomics: two launches are bit-identical).  da [B,Ta,D] and
+ * dv [B,Tv,D] are both required and OVERWRITTEN: a row's used stream carries scale 1 (modes 1, 2) or fusion_scale / 1 - fusion_scale (mode 0),
+ * its unused stream exact zeros; rows t >= L are zeros. */
+int avllm_fuse_pool_rows_bwd(const void* dx, void* da, int32_t Ta, void* dv, int32_t Tv, int32_t P, const int32_t* mode, int32_t B, int32_t L,
+                             int32_t S_out, int32_t D, float fusion_scale, int32_t dtype, void* stream);
+/* Draws the modes of B clips: one launch, no host sync.  With s = (seed_dev ? *seed_dev : 0) + seed + 0x6D6F6461 (apart from the LoRA mask
+ * seeds base + 0 .. base + 7*layers - 1 of the same step), u = av_pair_hash(s, b) >> 8 (24 bits; csrc/common.h),
+ * ta = (uint32_t)(p_drop_audio * 2^24 + 0.5) and tv likewise (of the float arguments, evaluated in double):
+ *   u < ta          -> AVLLM_MODE_VIDEO (audio dropped)
+ *   u >= 2^24 - tv  -> AVLLM_MODE_AUDIO (video dropped)
+ *   otherwise       -> AVLLM_MODE_BOTH
+ * Both probabilities in [0, 1], sum <= 1: the ranges are disjoint and no clip loses both streams.  mode_in (nullable, DEVICE int32 [B]): a row
+ * given as 1 or 2 keeps it -- a clip that has one stream only is never turned into the other; mode_out may alias it.  seed_dev given
+ * (avllm_step_state.dropout_seed): the launch sits in a captured step and redraws on every replay. */
+int avllm_modality_draw(const int32_t* mode_in, int32_t* mode_out, int32_t B, float p_drop_audio, float p_drop_video, uint32_t seed,
+                        const uint32_t* seed_dev, void* stream);
 /* clip_grad_norm_ + AdamW (trainer/clip_whisper_trainer.py:457-464,171-232) on a flat fp32 buffer, no host sync:
  * sumsq accumulates sum(g^2); the step reads it, clips with coef=min(1,max_norm/(sqrt(sumsq)+1e-6)).
  * Non-finite guard (trainer :444-452 skips backward + optimizer on a NaN/Inf loss): when *sumsq or *guard (e.g. the step's

@@ -21,7 +21,10 @@ utterance of the --output_file JSON, and with --nbest > 1 an nbest list of {hypo
 token log-probability is below F are listed in the log; they still count in the WER), --share_prefix (generate(share_prefix=True): the beams
 of an utterance share one prefix cache), --load_lora (also load the adapters from the checkpoint), --lora_target_modules (with --load_lora: the modules those adapters sit on,
 default what the checkpoint's metadata records; adapters on gate/up/down keep the token step off the fused path until --merge_lora folds them),--merge_lora (with --load_lora: fold the loaded
-adapters into the LLM weights once, ClipWhisperModel.merge_lora(), so that decoding runs the adapter-free kernels), --synthetic N / --tiny /
+adapters into the LLM weights once, ClipWhisperModel.merge_lora(), so that decoding runs the adapter-free kernels), --drop_audio_prob F /
+--drop_video_prob F (robustness evaluation with --modality both: every clip loses its audio / its video with that probability, never both;
+the modes of batch k are drawn on the device with seed --seed + k, so a run repeats, and go to generate(modality_mask=); the results JSON
+records the two probabilities and the number of clips per mode), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -95,6 +98,10 @@ def parse_args(argv=None):
                         "the fused path: add --merge_lora")
     p.add_argument("--merge_lora", action="store_true",
                    help="with --load_lora: fold the adapters into the LLM weights after the checkpoint is loaded (effect on WER not measured)")
+    p.add_argument("--drop_audio_prob", type=float, default=0.0,
+                   help="robustness evaluation: each clip is decoded without its audio with this probability (needs --modality both)")
+    p.add_argument("--drop_video_prob", type=float, default=0.0,
+                   help="... or without its video with this one; the two add up to at most 1, a clip never loses both")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
     p.add_argument("--tiny", action="store_true")
@@ -105,6 +112,10 @@ def parse_args(argv=None):
         p.error("--lora_target_modules needs --load_lora: without it the model has no adapters")
     if a.merge_lora and not a.load_lora:
         p.error("--merge_lora needs --load_lora: without it the model has no adapters to merge")
+    if not (0.0 <= a.drop_audio_prob <= 1.0 and 0.0 <= a.drop_video_prob <= 1.0 and a.drop_audio_prob + a.drop_video_prob <= 1.0):
+        p.error(f"--drop_audio_prob {a.drop_audio_prob} and --drop_video_prob {a.drop_video_prob} must lie in [0, 1] and add up to at most 1")
+    if (a.drop_audio_prob or a.drop_video_prob) and a.modality != "both":
+        p.error(f"--drop_audio_prob / --drop_video_prob need --modality both, got --modality {a.modality}")
     if a.nbest < 1:
         p.error(f"--nbest must be at least 1, got {a.nbest}")
     if a.nbest > 1 and a.do_sample:
@@ -258,6 +269,8 @@ def main(argv=None):
     scored = a.confidence or a.nbest > 1 or a.min_avg_logprob is not None
     score_kw = dict(return_token_scores=True, num_return_sequences=a.nbest) if scored else {}
     low_confidence = []
+    drop = bool(a.drop_audio_prob or a.drop_video_prob)
+    mode_counts = [0, 0, 0]                                       # clips decoded with both streams / audio only / video only
     results, all_refs, all_hyps, losses = [], [], [], []
     seen = 0
     print(f"Starting decoding with modality: {a.modality}\nEach hypothesis will be shown as it's generated.\n")
@@ -265,11 +278,19 @@ def main(argv=None):
         try:
             audio = None if (audio is None or a.modality == "video") else audio.to(dev)
             video = None if (video is None or a.modality == "audio") else video.to(dev)
+            mask_kw = {}
+            if drop:
+                from avllm import ops
+                modes = ops.modality_draw(audio.shape[0], a.drop_audio_prob, a.drop_video_prob, seed=a.seed + bi, device=dev)
+                mask_kw["modality_mask"] = modes
             ids = model.generate(audio=audio, video=video, max_new_tokens=a.max_new_tokens, temperature=a.temperature,
                                  do_sample=a.do_sample, top_p=a.top_p, top_k=a.top_k, num_beams=a.num_beams,
                                  length_penalty=a.length_penalty, repetition_penalty=a.repetition_penalty,
                                  no_repeat_ngram_size=a.no_repeat_ngram_size, min_new_tokens=a.min_new_tokens, share_prefix=a.share_prefix,
-                                 **bias_kw, **score_kw)
+                                 **bias_kw, **score_kw, **mask_kw)
+            if drop:
+                for m in modes.tolist():
+                    mode_counts[m] += 1
             extras = None
             if scored:
                 extras = utterance_scores(model.tokenizer, ids, a.nbest, model.eos_token_id)
@@ -278,7 +299,7 @@ def main(argv=None):
             if a.calculate_loss:
                 lab = model.tokenizer(list(texts), padding="max_length", truncation=True, max_length=256, return_tensors="pt").input_ids
                 with torch.no_grad():
-                    losses.append(float(model(audio=audio, video=video, labels=lab.to(dev), return_loss=True)["loss"]))
+                    losses.append(float(model(audio=audio, video=video, labels=lab.to(dev), return_loss=True, **mask_kw)["loss"]))
             for j, hyp in enumerate(out):
                 uid = utt_ids[seen + j] if seen + j < len(utt_ids) else f"unknown_{bi}_{j}"
                 hyp = hyp.strip()
@@ -309,6 +330,9 @@ def main(argv=None):
     with open(os.path.join(a.output_dir, f"wer_{ts}.txt"), "w") as f:
         f.write(f"Overall WER: {wer:.4f}\nTotal samples: {len(all_refs)}\n")
     summary = {"modality": a.modality, "overall_wer": wer, "total_samples": len(all_refs), "results": results}
+    if drop:
+        summary.update({"drop_audio_prob": a.drop_audio_prob, "drop_video_prob": a.drop_video_prob,
+                        "clips_per_mode": {"both": mode_counts[0], "audio": mode_counts[1], "video": mode_counts[2]}})
     if losses:
         summary["mean_loss"] = sum(losses) / len(losses)
     json.dump(summary, open(os.path.join(a.output_dir, os.path.basename(a.output_file)), "w"), indent=1)

@@ -30,6 +30,11 @@ def parse_args():
                    help="modules that get a LoRA adapter: comma-separated names out of q_proj,k_proj,v_proj,o_proj,gate_proj,up_proj,down_proj, or "
                         "all-linear; default the four attention modules (YAML key model.lora_target_modules; a --resume_from checkpoint's own "
                         "value is used when neither is given)")
+    p.add_argument("--modality_dropout_audio", type=float, default=None,
+                   help="modality dropout: the probability that a clip of a training batch loses its audio (a draw per clip and step, on the "
+                        "device; never both streams); default 0 = off (YAML key model.modality_dropout_audio)")
+    p.add_argument("--modality_dropout_video", type=float, default=None,
+                   help="the probability that a clip loses its video; the two must add up to at most 1 (YAML key model.modality_dropout_video)")
     p.add_argument("--log_interval", type=int); p.add_argument("--save_every", type=int); p.add_argument("--resume_from")
     p.add_argument("--save_steps", type=int, default=None, help="stored by the trainer and never acted on, as in the reference (clip_whisper_trainer.py:94-102)")
     p.add_argument("--log_param_updates", action="store_true", help="accepted for command-line compatibility; the reference stores it and never reads it (:118)")
@@ -66,7 +71,8 @@ def main():
                             "clip_model": a.clip_model, "modality": a.modality, "batch_size": a.batch_size, "num_epochs": a.max_epochs,
                             "learning_rate": a.learning_rate, "max_seq_len": a.max_seq_len, "use_fp16": a.fp16, "use_4bit": a.use_4bit,
                             "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type, "train_connectors": a.train_connectors,
-                            "lora_target_modules": a.lora_target_modules, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
+                            "lora_target_modules": a.lora_target_modules, "modality_dropout_audio": a.modality_dropout_audio,
+                            "modality_dropout_video": a.modality_dropout_video, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
                             "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None})
     os.makedirs(cfg["output_dir"], exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s",
@@ -93,6 +99,8 @@ def main():
                              freeze_encoders=cfg.get("freeze_encoders", True), modality=cfg.get("modality", "both"),
                              max_seq_len=cfg.get("max_seq_len", 256), fusion_scale=cfg.get("fusion_scale", 0.5),
                              connector_type=cfg.get("connector_type", "simple"), train_connectors=bool(cfg.get("train_connectors", False)),
+                             modality_dropout_audio=float(cfg.get("modality_dropout_audio") or 0.0),
+                             modality_dropout_video=float(cfg.get("modality_dropout_video") or 0.0),
                              synthetic_weights=a.synthetic_weights or a.tiny, **kw)
     if a.synthetic:
         frames = a.frames if not a.tiny else 5
