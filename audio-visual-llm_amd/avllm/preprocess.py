@@ -5,6 +5,7 @@ Mirrors what `AVSRDataset.__getitem__` does per sample on CPU workers (src/clip_
 batch: `WhisperLogMel` = `whisper_processor(audio, sampling_rate=16000).input_features` + `F.layer_norm(f, f.shape)`;
 `ClipFrames` = `clip_processor(images=frame)["pixel_values"]`.  Decoding files (soundfile / cv2) stays with the caller."""
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -25,14 +26,17 @@ class WhisperLogMel:
         L.check(lib.avllm_logmel_table_init(L.ptr(self.table), self.n_mels))
         self._ws = None
 
-    def pad_batch(self, waves):
-        """list of 1-D float arrays/tensors (mono, 16 kHz, any length) -> one zero-padded [B, n] float32 device tensor."""
+    def pad_batch(self, waves, return_lengths=False):
+        """list of 1-D float arrays/tensors (mono, 16 kHz, any length) -> one zero-padded [B, n] float32 device tensor; with return_lengths
+        also the clips' sample counts (after the 30 s cut) as an int32 [B] device tensor."""
         waves = [torch.as_tensor(np.asarray(w, dtype=np.float32) if not torch.is_tensor(w) else w, dtype=torch.float32).reshape(-1)[:N_SAMPLES]
                  for w in waves]
         n = max(1, max(int(w.numel()) for w in waves))
         out = torch.zeros(len(waves), n, dtype=torch.float32, device=self.device)
         for i, w in enumerate(waves):
             out[i, : w.numel()] = w.to(self.device, non_blocking=True)
+        if return_lengths:
+            return out, torch.tensor([int(w.numel()) for w in waves], dtype=torch.int32, device=self.device)
         return out
 
     def __call__(self, wave, out=None):
@@ -97,12 +101,196 @@ class ClipFrames:
         return out
 
 
-def device_collate(samples, logmel, clip_frames, max_video_length=300):
+class NoiseBank:
+    """The noise recordings avllm_wave_add_noise draws from, as one zero-padded float32 image [Nn, W] and their lengths (int32 [Nn]) on the
+    device.  `sources`: a .wav / .npy file, a directory of them (sorted by name), or a list of arrays (or of paths).  Files are read with
+    avllm.data.read_audio and brought to mono float32 the way AVSRDataset brings a clip (mean over channels, int16-range values / 32768); a
+    file at any other rate than 16 kHz is a ValueError that names it: there is no resampler."""
+
+    def __init__(self, sources, device="cuda:0", sampling_rate=16000):
+        self.device = torch.device(device)
+        self.path = sources if isinstance(sources, (str, os.PathLike)) else None
+        if isinstance(sources, (str, os.PathLike)):
+            p = os.fspath(sources)
+            if os.path.isdir(p):
+                sources = [os.path.join(p, f) for f in sorted(os.listdir(p)) if f.lower().endswith((".wav", ".npy"))]
+                if not sources:
+                    raise ValueError(f"{p}: no .wav / .npy noise recordings in this directory")
+            else:
+                sources = [p]
+        rows, self.names = [], []
+        for i, s in enumerate(sources):
+            if isinstance(s, (str, os.PathLike)):
+                from .data import read_audio
+                x, sr = read_audio(os.fspath(s))
+                if int(sr) != sampling_rate:
+                    raise ValueError(f"{s}: noise at {sr} Hz, the clips are {sampling_rate} Hz (resample the file; nothing here does)")
+                name = os.fspath(s)
+            else:
+                x, name = (s.detach().cpu().numpy() if torch.is_tensor(s) else s), f"array {i}"
+            x = np.asarray(x)
+            if x.ndim > 1:
+                x = x.mean(axis=1)
+            x = x.astype(np.float32) / 32768.0 if np.abs(x).max(initial=0.0) > 1.0 else x.astype(np.float32)
+            if x.size < 1:
+                raise ValueError(f"{name}: an empty noise recording")
+            rows.append(np.ascontiguousarray(x.reshape(-1)))
+            self.names.append(name)
+        if not rows:
+            raise ValueError("NoiseBank: no noise recordings given")
+        width = (max(r.size for r in rows) + 3) // 4 * 4
+        image = np.zeros((len(rows), width), np.float32)
+        for i, r in enumerate(rows):
+            image[i, : r.size] = r
+        self.noise = torch.from_numpy(image).to(self.device)
+        self.lengths = torch.tensor([r.size for r in rows], dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return self.noise.shape[0]
+
+
+class AudioAugment:
+    """The two acoustic augmentations (include/avllm.h, avllm_wave_add_noise and avllm_spec_augment; csrc/augment.hip).
+    noise: a NoiseBank | None; snr_db: (lo, hi), drawn per clip, or one value; noise_prob: the share of clips that get noise.
+    time_masks x [0, min(time_width, time_ratio * frames)] frames and freq_masks x [0, freq_width] mel bins are set to `fill`: 0.0 is the clip's
+    mean after the whole-tensor layer norm, and what transformers' Whisper `_mask_input_features` writes."""
+
+    def __init__(self, noise=None, snr_db=(0.0, 20.0), noise_prob=1.0, time_masks=0, time_width=0, time_ratio=1.0, freq_masks=0, freq_width=0,
+                 fill=0.0):
+        lo, hi = (snr_db, snr_db) if isinstance(snr_db, (int, float)) else snr_db
+        self.noise, self.snr_lo, self.snr_hi, self.noise_prob = noise, float(lo), float(hi), float(noise_prob)
+        self.time_masks, self.time_width, self.time_ratio = int(time_masks), int(time_width), float(time_ratio)
+        self.freq_masks, self.freq_width, self.fill = int(freq_masks), int(freq_width), float(fill)
+        if self.snr_lo > self.snr_hi:
+            raise ValueError(f"AudioAugment: snr_db = ({self.snr_lo}, {self.snr_hi}): the lower end is above the upper one")
+        if not 0.0 <= self.noise_prob <= 1.0:
+            raise ValueError(f"AudioAugment: noise_prob = {self.noise_prob} must lie in [0, 1]")
+        if min(self.time_masks, self.freq_masks, self.time_width, self.freq_width) < 0 or self.time_masks + self.freq_masks > 32:
+            raise ValueError(f"AudioAugment: time_masks = {self.time_masks}, freq_masks = {self.freq_masks} (at most 32 together), time_width = "
+                             f"{self.time_width}, freq_width = {self.freq_width}: none may be negative")
+        if not 0.0 <= self.time_ratio <= 1.0:
+            raise ValueError(f"AudioAugment: time_ratio = {self.time_ratio} must lie in [0, 1]")
+        self.last_info = self.last_spans = None      # device tensors of the last .wave() / .features() call: int32 [B, 5] / int32 [B, masks, 2]
+        self._ws = None
+
+    @property
+    def mixes(self):
+        return self.noise is not None
+
+    @property
+    def masks(self):
+        return self.time_masks + self.freq_masks > 0
+
+    @staticmethod
+    def _seed_ptr(seed_dev):
+        if isinstance(seed_dev, torch.Tensor):
+            if seed_dev.numel() != 1 or seed_dev.element_size() != 4:
+                raise ValueError(f"AudioAugment: seed_dev must hold one 32-bit word, got {tuple(seed_dev.shape)} {seed_dev.dtype}")
+            return L.ptr(seed_dev)
+        return seed_dev
+
+    def wave(self, batch, lengths=None, seed=0, seed_dev=None, snr_db=None, out=None):
+        """batch f32 [B, n] on the device (any row stride), lengths int32 [B] on the device | None (= n) -> the batch with noise mixed in, in
+        `out` (default a new tensor; `out=batch` mixes in place).  snr_db: a float32 [B] device tensor overrides the drawn values.  Without a
+        noise bank the batch is returned as it is.  last_info: int32 [B, 5] = applied, row, offset and the bits of snr_db and gain."""
+        if self.noise is None:
+            return batch
+        if batch.dim() != 2 or batch.dtype != torch.float32 or batch.stride(1) != 1 or not batch.is_cuda:
+            raise ValueError(f"AudioAugment.wave: batch should be a float32 [batch_size, samples] device tensor with unit column stride, got {batch.dtype} {tuple(batch.shape)}")
+        B, n = batch.shape
+        if out is None:
+            out = torch.empty(B, n, dtype=torch.float32, device=batch.device)
+        elif tuple(out.shape) != (B, n) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != batch.device:
+            raise ValueError(f"AudioAugment.wave: out should be a float32 [{B}, {n}] tensor on {batch.device}, got {out.dtype} {tuple(out.shape)}")
+        for nm, t, dt in (("lengths", lengths, torch.int32), ("snr_db", snr_db, torch.float32)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (B,) or not t.is_contiguous() or t.device != batch.device):
+                raise ValueError(f"AudioAugment.wave: {nm} should be a contiguous {dt} [{B}] tensor on {batch.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        lib = L.load()
+        need = lib.avllm_wave_add_noise_workspace_bytes(B, n)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != batch.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=batch.device)
+        info = torch.empty(B, 5, dtype=torch.int32, device=batch.device)
+        nb = self.noise
+        L.check(lib.avllm_wave_add_noise(L.ptr(batch), batch.stride(0), L.ptr(lengths), B, n, L.ptr(nb.noise), nb.noise.stride(0), L.ptr(nb.lengths),
+                                         len(nb), L.ptr(snr_db), self.snr_lo, self.snr_hi, self.noise_prob, int(seed) & 0xFFFFFFFF,
+                                         self._seed_ptr(seed_dev), L.ptr(out), out.stride(0), L.ptr(info), L.ptr(self._ws), self._ws.numel(),
+                                         L.stream_ptr()))
+        self.last_info = info
+        return out
+
+    def features(self, feat, valid=None, seed=0, seed_dev=None):
+        """SpecAugment IN PLACE on feat f32 [B, M, T] (contiguous, on the device); valid int32 [B] on the device | None (= T): the frames each
+        clip really has.  Returns feat.  Without masks nothing is launched.  last_spans: int32 [B, time_masks + freq_masks, 2] = (start, width)."""
+        if not self.masks:
+            return feat
+        if feat.dim() != 3 or feat.dtype != torch.float32 or not feat.is_contiguous() or not feat.is_cuda:
+            raise ValueError(f"AudioAugment.features: feat should be a contiguous float32 [batch_size, mels, frames] device tensor, got {feat.dtype} {tuple(feat.shape)}")
+        B, M, T = feat.shape
+        if valid is not None and (valid.dtype != torch.int32 or tuple(valid.shape) != (B,) or not valid.is_contiguous() or valid.device != feat.device):
+            raise ValueError(f"AudioAugment.features: valid should be a contiguous int32 [{B}] tensor on {feat.device}, got {valid.dtype} {tuple(valid.shape)} on {valid.device}")
+        spans = torch.empty(B, self.time_masks + self.freq_masks, 2, dtype=torch.int32, device=feat.device)
+        L.check(L.load().avllm_spec_augment(L.ptr(feat), B, M, T, L.ptr(valid), self.time_masks, self.time_width, self.time_ratio, self.freq_masks,
+                                            self.freq_width, self.fill, int(seed) & 0xFFFFFFFF, self._seed_ptr(seed_dev), L.ptr(spans), L.stream_ptr()))
+        self.last_spans = spans
+        return feat
+
+    @staticmethod
+    def info_fields(info):
+        """last_info (int32 [B, 5], on any device) -> dict of host lists: applied, row, offset (int) and snr_db, gain (float)."""
+        info = info.cpu().contiguous()
+        f = info.view(torch.float32)
+        return {"applied": info[:, 0].tolist(), "row": info[:, 1].tolist(), "offset": info[:, 2].tolist(), "snr_db": f[:, 3].tolist(),
+                "gain": f[:, 4].tolist()}
+
+
+def parse_snr(value):
+    """--noise_snr / the YAML's noise_snr: "LO,HI", [LO, HI], or one number -> (lo, hi)."""
+    if isinstance(value, str):
+        value = [float(t) for t in value.split(",")]
+    if isinstance(value, (int, float)):
+        value = [value]
+    if len(value) not in (1, 2):
+        raise ValueError(f"noise_snr: one value or LO,HI expected, got {value}")
+    return float(value[0]), float(value[-1])
+
+
+def augment_from_config(cfg, device):
+    """The AudioAugment the flat configuration asks for (keys noise_path, noise_snr, noise_prob, spec_time_masks, spec_time_width,
+    spec_time_ratio, spec_freq_masks, spec_freq_width: scripts/clip_whisper/train.py flags and configs/clip_whisper.yaml data: entries), or None
+    when it asks for none: the trainer then runs exactly the path it ran without these keys."""
+    path = cfg.get("noise_path")
+    tm, fm = int(cfg.get("spec_time_masks") or 0), int(cfg.get("spec_freq_masks") or 0)
+    if not path and tm + fm == 0:
+        return None
+    snr = parse_snr(cfg.get("noise_snr") if cfg.get("noise_snr") is not None else (0.0, 20.0))
+    prob = cfg.get("noise_prob")
+    return AudioAugment(noise=NoiseBank(path, device) if path else None, snr_db=snr, noise_prob=1.0 if prob is None else float(prob),
+                        time_masks=tm, time_width=int(cfg.get("spec_time_width") or 0),
+                        time_ratio=1.0 if cfg.get("spec_time_ratio") is None else float(cfg.get("spec_time_ratio")),
+                        freq_masks=fm, freq_width=int(cfg.get("spec_freq_width") or 0))
+
+
+def valid_frames(lengths):
+    """The log-mel frames a clip of `lengths` samples really has: min(3000, ceil(len / 160)) (hop 160), int32 like its input."""
+    return torch.clamp((lengths + 159) // 160, max=N_FRAMES).to(torch.int32)
+
+
+def device_collate(samples, logmel, clip_frames, max_video_length=300, augment=None, seed=None):
     """collate_fn (simple_dataset.py:317-460) for raw samples: `samples` = list of dicts with "wave" (1-D float, 16 kHz) and/or
-    "frames" (uint8 [F,H,W,3]) + "labels"/"text".  -> (audio [B,80,3000] | None, video [B,Fmax,3,S,S] zero-padded | None)."""
+    "frames" (uint8 [F,H,W,3]) + "labels"/"text".  -> (audio [B,80,3000] | None, video [B,Fmax,3,S,S] zero-padded | None).
+    augment: an AudioAugment | None; with one, noise is mixed into the padded waveforms (in place, over each clip's own samples) before the
+    log-mel and the features are masked after it, both drawn with `seed`.  None: the calls and allocations of before."""
     audio = video = None
+    if augment is not None and seed is None:
+        raise ValueError("device_collate: augment needs a seed (the draws of a batch are a function of it)")
     if all(s.get("wave") is not None for s in samples):
-        audio = logmel([s["wave"] for s in samples])
+        if augment is not None:
+            wave, lengths = logmel.pad_batch([s["wave"] for s in samples], return_lengths=True)
+            audio = logmel(augment.wave(wave, lengths, seed, out=wave))
+            if augment.masks:
+                augment.features(audio, valid_frames(lengths), seed)
+        else:
+            audio = logmel([s["wave"] for s in samples])
     if all(s.get("frames") is not None for s in samples):
         clips = [clip_frames(torch.as_tensor(s["frames"])[:max_video_length]) for s in samples]
         Fmax = max(c.shape[0] for c in clips)

@@ -37,8 +37,12 @@ class ClipWhisperTrainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, learning_rate=5e-5, weight_decay=0.01, max_epochs=10,
                  output_dir="outputs/clip_whisper", device="cuda", fp16=False, grad_accum_steps=1, log_interval=10, save_every=1,
                  save_steps=None, grad_clip=0.5, warmup_steps=0, log_param_updates=False, total_steps=None, use_graph=None,
-                 bwd_pieces=None):
+                 bwd_pieces=None, audio_augment=None, augment_seed=0):
         self.model, self.train_dataloader, self.val_dataloader = model, train_dataloader, val_dataloader
+        # acoustic augmentation (avllm.preprocess.AudioAugment | None): applied in _unpack, in front of the captured step, in train() mode only
+        self.audio_augment, self.augment_seed = audio_augment, int(augment_seed)
+        self.last_augment_info = None                      # AudioAugment.last_info of the last augmented batch (device int32 [B, 5])
+        self._augment_notes = set()
         self.learning_rate, self.weight_decay, self.max_epochs = learning_rate, weight_decay, max_epochs
         self.output_dir, self.device, self.fp16 = output_dir, device, fp16
         self.grad_accum_steps = grad_accum_steps           # stored but unused, as in the reference
@@ -83,6 +87,23 @@ class ClipWhisperTrainer:
             return self.learning_rate * max(0.0, 0.5 * (1.0 + math.cos(math.pi * prog)))
         return self.learning_rate * (1 + math.cos(math.pi * step / self.total_steps)) / 2
 
+    def augment_seed_at(self, step, rank=None):
+        """The seed of the augmentation draws for the batch of optimizer step `step` (the count of steps taken before it) on `rank`: by
+        value, so every rank and every step draws its own noise and masks, and a run repeats."""
+        return (self.augment_seed + 1000003 * int(step) + 7919 * (self._rank if rank is None else int(rank))) & 0xFFFFFFFF
+
+    def _augment_features(self, audio):
+        """A batch of precomputed features has no waveform to mix noise into: it gets the SpecAugment half only, every frame counted as
+        valid, on a device copy (the loader's tensor is left as it is)."""
+        aug = self.audio_augment
+        if aug is None or not self.model.training or audio is None or not aug.masks:
+            return audio
+        if "features" not in self._augment_notes:
+            self._augment_notes.add("features")
+            logging.info("audio_augment on precomputed features: SpecAugment only (valid = all frames); noise needs raw waveforms")
+        audio = audio.to(self.model.device, torch.float32, copy=True).contiguous()
+        return aug.features(audio, None, self.augment_seed_at(self.global_step))
+
     # ---- _process_batch :604-680
     def _unpack(self, batch):
         if isinstance(batch, dict) and "raw" in batch:
@@ -91,12 +112,19 @@ class ClipWhisperTrainer:
             if getattr(self, "_featurizers", None) is None:
                 dev = self.model.device
                 self._featurizers = (WhisperLogMel(dev, n_mels=self.model.cfg.whisper.n_mels), ClipFrames(dev, image=self.model.cfg.clip.image))
-            audio, video = device_collate(batch["raw"], *self._featurizers)
+            if self.audio_augment is not None and self.model.training:
+                audio, video = device_collate(batch["raw"], *self._featurizers, augment=self.audio_augment,
+                                              seed=self.augment_seed_at(self.global_step))
+                if audio is not None and self.audio_augment.mixes:
+                    self.last_augment_info = self.audio_augment.last_info
+            else:
+                audio, video = device_collate(batch["raw"], *self._featurizers)
             tok = self.model.tokenizer(batch["texts"], return_tensors="pt", padding=True, truncation=True, max_length=self.model.max_seq_len)
             return audio, video, batch["labels"], tok.input_ids
         if isinstance(batch, dict):
-            return batch.get("audio"), batch.get("video"), batch.get("labels"), batch.get("prompt")
+            return self._augment_features(batch.get("audio")), batch.get("video"), batch.get("labels"), batch.get("prompt")
         audio, video, texts, labels = batch
+        audio = self._augment_features(audio)
         tok = self.model.tokenizer(texts, return_tensors="pt", padding=True, truncation=True, max_length=self.model.max_seq_len)
         bs = labels.shape[0]
         for t in (audio, video):
@@ -308,12 +336,13 @@ class ClipWhisperTrainer:
     def _train_epoch(self, epoch):
         self.model.train()
         total, n, t0 = 0.0, 0, time.time()
-        pending, pending_modes = [], []
+        pending, pending_modes, pending_noise = [], [], []
         failures = unstable = worst = 0
         for i, batch in enumerate(self.train_dataloader):
             # the reference logs and skips a batch on ANY exception (:492-507).  Host-side preparation (everything before the first
             # collective) is where data errors surface; under DDP the skip is agreed between ranks first.
             unpacked, err = None, None
+            self.last_augment_info = None
             try:
                 unpacked = self._unpack(batch)
             except Exception as e:
@@ -338,6 +367,8 @@ class ClipWhisperTrainer:
             pending.append(loss)
             if self.model.last_modality_modes is not None:       # stays on the device until the log interval, like the loss
                 pending_modes.append(self.model.last_modality_modes.clone())
+            if self.last_augment_info is not None:               # a tensor of its own per batch: kept, not copied
+                pending_noise.append(self.last_augment_info)
             if (i + 1) % self.log_interval == 0 or i + 1 == len(self.train_dataloader):
                 vals = torch.stack(pending).float().cpu()
                 pending.clear()
@@ -361,7 +392,19 @@ class ClipWhisperTrainer:
                     share = self.mode_shares(torch.cat(pending_modes).cpu())
                     pending_modes.clear()
                     logging.info(f"epoch {epoch} batch {i + 1}: clips with both streams {share[0]:.3f}, audio only {share[1]:.3f}, video only {share[2]:.3f}")
+                if pending_noise:
+                    share, snr = self.noise_shares(torch.cat(pending_noise).cpu())
+                    pending_noise.clear()
+                    logging.info(f"epoch {epoch} batch {i + 1}: clips with noise mixed in {share:.3f}, their mean SNR {snr:.2f} dB")
         return total / max(1, n)
+
+    @staticmethod
+    def noise_shares(info):
+        """(the share of clips with noise mixed in, their mean requested SNR in dB -- nan when there is none) of AudioAugment.last_info rows."""
+        info = info.contiguous()
+        on = info[:, 0] != 0
+        snr = info.view(torch.float32)[:, 3][on]
+        return float(on.float().mean()) if info.shape[0] else 0.0, float(snr.mean()) if snr.numel() else float("nan")
 
     @staticmethod
     def mode_shares(modes):

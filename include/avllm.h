@@ -521,6 +521,60 @@ size_t avllm_clip_preproc_workspace_bytes(int32_t N, int32_t H, int32_t W, int32
 int avllm_clip_preproc(const void* plan, const uint8_t* frames, int32_t N, int32_t H, int32_t W, int32_t image, void* out,
                        int32_t dtype, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- acoustic augmentation on the device ----------------
+ * No counterpart in the reference (it has no augmentation): additive noise at a target SNR on the raw waveform, in front of avllm_logmel, and
+ * SpecAugment on the features it writes.  Both draw from the counter hash of csrc/common.h (av_pair_hash) with the launch seed
+ * (seed_dev ? *seed_dev : 0) + seed, like avllm_modality_draw, and neither syncs with the host. */
+typedef struct avllm_noise_info {
+    int32_t applied;      /* 1: noise was mixed into the clip */
+    int32_t row, offset;  /* the noise recording and the position in it where the segment starts (always the drawn values) */
+    float snr_db;         /* the SNR asked for (given or drawn) */
+    float gain;           /* the factor on the noise; 0 when applied == 0 */
+} avllm_noise_info;
+/* out[b] = wave[b] + gain_b * (a segment of one noise recording), the gain set so that the clip's signal-to-noise ratio is snr_b dB.
+ *   wave f32 [B, n], row stride ld; len DEVICE int32 [B] | NULL (= n for every clip; values are clamped to [0, n]).
+ *   noise f32 [Nn, .], row stride ld_noise; noise_len DEVICE int32 [Nn], each in [1, ld_noise] (a value outside is read as the nearest bound).
+ *   snr_db DEVICE f32 [B] | NULL (then drawn from [snr_lo, snr_hi]); p_apply in [0, 1]; out f32 [B, n], row stride ld_out; out may BE wave
+ *   (same pointer and stride), no other overlap; info DEVICE [B]; ws: avllm_wave_add_noise_workspace_bytes(B, n) bytes, 8-byte aligned.
+ * The rule, for clip b, with s = (seed_dev ? *seed_dev : 0) + seed + 0x6E6F6973 and h_j = av_pair_hash(s, 4*b + j), j = 0..3:
+ *   applied = (h_0 >> 8) < (uint32_t)(p_apply * 2^24 + 0.5) (of the float argument, evaluated in double) and len_b > 0
+ *   row     = ((uint64_t)h_1 * Nn) >> 32
+ *   offset  = ((uint64_t)h_2 * noise_len[row]) >> 32
+ *   snr     = snr_db ? snr_db[b] : (float)((double)snr_lo + ((double)snr_hi - (double)snr_lo) * ((h_3 >> 8) * 2^-24))      (double, each
+ *             operation rounded once, nothing fused)
+ *   z_i     = noise[row][(offset + i) mod noise_len[row]]: the segment wraps around the end of the recording as often as it has to
+ *   Es = sum_{i < len_b} w_i^2, En = sum_{i < len_b} z_i^2, in double, in a FIXED order: one partial per chunk of
+ *        avllm_wave_add_noise_chunk() samples into ws, the partials folded in index order.  No atomics: a repeated launch gives the same
+ *        bits.  En is the energy of the segment actually used, not of the whole recording.
+ *   gain = (float)sqrt(Es / (En * pow(10, (double)snr / 10))), in double.  If Es or En is zero or not finite, or the gain is zero or not
+ *          finite: gain = 0 and applied = 0.
+ *   out_i = w_i + gain * z_i for i < len_b, in float32: the product rounded, then the sum rounded (no fma).
+ * Positions i >= len_b of every row, and the whole row of a clip that is not mixed, are copied bit for bit (NaN payloads, -0) and never
+ * enter a sum.  NO clipping and NO renormalisation: the mixture can leave [-1, 1]; the log-mel that follows has no range limit.
+ * row and offset do not depend on the SNR: a sweep over SNR values at one seed mixes the same segment into each clip, only the gain changes.
+ * Two launches (energies, then the mix; one when p_apply rounds to 0); 16-byte accesses on wave and out when both bases are 16-byte aligned
+ * and both strides multiples of 4, a scalar form otherwise, with equal bits. */
+int32_t avllm_wave_add_noise_chunk(void);
+size_t avllm_wave_add_noise_workspace_bytes(int32_t B, int32_t n);
+int avllm_wave_add_noise(const float* wave, int64_t ld, const int32_t* len, int32_t B, int32_t n, const float* noise, int64_t ld_noise,
+                         const int32_t* noise_len, int32_t Nn, const float* snr_db, float snr_lo, float snr_hi, float p_apply, uint32_t seed,
+                         const uint32_t* seed_dev, float* out, int64_t ld_out, avllm_noise_info* info, void* ws, size_t ws_bytes,
+                         void* stream);
+/* SpecAugment in place on feat f32 [B, M, T] (contiguous): n_time time masks, then n_freq frequency masks, n_time + n_freq <= 32.
+ *   valid DEVICE int32 [B] | NULL (= T): the frames a clip really has, clamped to [0, T]; spans DEVICE int32 [B, n_time + n_freq, 2] receives
+ *   (start, width) of every mask, time masks first.
+ * The rule, for mask j of clip b, with s = (seed_dev ? *seed_dev : 0) + seed + 0x73706563, h = av_pair_hash(s, 64*b + 2*j) and
+ * h' = av_pair_hash(s, 64*b + 2*j + 1):
+ *   time mask (j < n_time):  extent = valid_b, wmax = min(max_time_width, floor(max_time_ratio * valid_b)) (the product in double)
+ *   frequency mask:          extent = M,       wmax = min(max_freq_width, M); it covers all T frames, valid or not
+ *   w     = ((uint64_t)h * (wmax + 1)) >> 32                  (0 .. wmax, both ends included)
+ *   start = ((uint64_t)h' * (extent - w + 1)) >> 32           (start + w <= extent)
+ * A cell inside any span becomes `fill`; every other cell is neither read nor written and keeps its bits.  valid_b = 0 gives zero-width time
+ * spans.  One launch; with n_time + n_freq == 0 the call returns without a launch (feat and spans may then be NULL). */
+int avllm_spec_augment(float* feat, int32_t B, int32_t M, int32_t T, const int32_t* valid, int32_t n_time, int32_t max_time_width,
+                       float max_time_ratio, int32_t n_freq, int32_t max_freq_width, float fill, uint32_t seed, const uint32_t* seed_dev,
+                       int32_t* spans, void* stream);
+
 /* Live kernel timing for bench.py: between begin and end every avllm_gemm launch (direct or inside the model-level
  * calls) is bracketed by two HIP events on its stream.  out[0]=sum of GEMM ms, out[1]=sum of algorithmic FLOPs
  * (2*M*N*(K+K2)), out[2]=launches timed. */

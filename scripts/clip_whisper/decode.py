@@ -24,7 +24,10 @@ default what the checkpoint's metadata records; adapters on gate/up/down keep th
 adapters into the LLM weights once, ClipWhisperModel.merge_lora(), so that decoding runs the adapter-free kernels), --drop_audio_prob F /
 --drop_video_prob F (robustness evaluation with --modality both: every clip loses its audio / its video with that probability, never both;
 the modes of batch k are drawn on the device with seed --seed + k, so a run repeats, and go to generate(modality_mask=); the results JSON
-records the two probabilities and the number of clips per mode), --synthetic N / --tiny /
+records the two probabilities and the number of clips per mode), --noise_path P --noise_snr F [--noise_prob F] (robustness evaluation at
+a fixed SNR: a segment of a noise recording under P is mixed into each clip's waveform on the device before the log-mel, batch k drawn with
+seed --seed + k, so a sweep over --noise_snr mixes the same segments and only their level changes; needs a manifest dataset, whose audio is
+raw; the results JSON records the path, the SNR and the number of clips mixed), --synthetic N / --tiny /
 --synthetic-weights / --frames (no dataset or checkpoints offline), --data_path (root for relative media paths; default = the
 reference's rule dirname(dirname(test_data))), and --test_manifest / --test_labels as aliases of --test_data / --test_wrd.
 `--output_file` (declared but never written by the reference) receives the per-utterance results as JSON."""
@@ -102,6 +105,10 @@ def parse_args(argv=None):
                    help="robustness evaluation: each clip is decoded without its audio with this probability (needs --modality both)")
     p.add_argument("--drop_video_prob", type=float, default=0.0,
                    help="... or without its video with this one; the two add up to at most 1, a clip never loses both")
+    p.add_argument("--noise_path", type=str, default=None,
+                   help="robustness evaluation: a .wav / .npy noise recording or a directory of them (16 kHz), mixed into every clip's audio")
+    p.add_argument("--noise_snr", type=float, default=None, help="with --noise_path: the SNR in dB of every mixed clip")
+    p.add_argument("--noise_prob", type=float, default=1.0, help="with --noise_path: the share of clips that get noise (default all)")
     p.add_argument("--data_path", type=str, default=None)
     p.add_argument("--synthetic", type=int, default=0)
     p.add_argument("--tiny", action="store_true")
@@ -116,6 +123,14 @@ def parse_args(argv=None):
         p.error(f"--drop_audio_prob {a.drop_audio_prob} and --drop_video_prob {a.drop_video_prob} must lie in [0, 1] and add up to at most 1")
     if (a.drop_audio_prob or a.drop_video_prob) and a.modality != "both":
         p.error(f"--drop_audio_prob / --drop_video_prob need --modality both, got --modality {a.modality}")
+    if (a.noise_path is None) != (a.noise_snr is None):
+        p.error("--noise_path and --noise_snr go together: the recordings and the SNR in dB at which they are mixed in")
+    if a.noise_path is not None and a.synthetic:
+        p.error("--noise_path needs raw audio (a manifest dataset): --synthetic clips are precomputed features")
+    if a.noise_path is not None and a.modality == "video":
+        p.error("--noise_path needs the audio stream, got --modality video")
+    if not 0.0 <= a.noise_prob <= 1.0:
+        p.error(f"--noise_prob {a.noise_prob} must lie in [0, 1]")
     if a.nbest < 1:
         p.error(f"--nbest must be at least 1, got {a.nbest}")
     if a.nbest > 1 and a.do_sample:
@@ -235,6 +250,7 @@ def main(argv=None):
                    hotwords=lines_of(a.hotwords), hotword_bias=a.hotword_bias)
 
     references, utt_ids = {}, None
+    noise_mixed = 0                                               # clips that had noise mixed in (--noise_path)
     if a.synthetic:
         ds = SyntheticClips(a.synthetic, model.cfg, 5 if a.tiny else a.frames, model.tokenizer, 11)
         loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, collate_fn=ds.collate)
@@ -260,10 +276,20 @@ def main(argv=None):
         references = match_references(utt_ids, ds.labels)
         loader = torch.utils.data.DataLoader(ds, batch_size=a.batch_size, shuffle=False, collate_fn=AVSRDataset.collate_fn)
         feats = (WhisperLogMel(dev, n_mels=model.cfg.whisper.n_mels), ClipFrames(dev, image=model.cfg.clip.image))
+        augment = None
+        if a.noise_path is not None:
+            from avllm.preprocess import AudioAugment, NoiseBank
+            augment = AudioAugment(noise=NoiseBank(a.noise_path, dev), snr_db=a.noise_snr, noise_prob=a.noise_prob)
 
         def batches():
-            for b in loader:
-                audio, video = device_collate(b["raw"], *feats)
+            nonlocal noise_mixed
+            for k, b in enumerate(loader):
+                if augment is None:
+                    audio, video = device_collate(b["raw"], *feats)
+                else:
+                    audio, video = device_collate(b["raw"], *feats, augment=augment, seed=a.seed + k)
+                    if audio is not None:
+                        noise_mixed += int(augment.last_info[:, 0].sum())
                 yield audio, video, b["texts"]
 
     scored = a.confidence or a.nbest > 1 or a.min_avg_logprob is not None
@@ -333,6 +359,8 @@ def main(argv=None):
     if drop:
         summary.update({"drop_audio_prob": a.drop_audio_prob, "drop_video_prob": a.drop_video_prob,
                         "clips_per_mode": {"both": mode_counts[0], "audio": mode_counts[1], "video": mode_counts[2]}})
+    if a.noise_path is not None:
+        summary.update({"noise_path": a.noise_path, "noise_snr": a.noise_snr, "noise_prob": a.noise_prob, "clips_with_noise": noise_mixed})
     if losses:
         summary["mean_loss"] = sum(losses) / len(losses)
     json.dump(summary, open(os.path.join(a.output_dir, os.path.basename(a.output_file)), "w"), indent=1)

@@ -35,6 +35,17 @@ def parse_args():
                         "device; never both streams); default 0 = off (YAML key model.modality_dropout_audio)")
     p.add_argument("--modality_dropout_video", type=float, default=None,
                    help="the probability that a clip loses its video; the two must add up to at most 1 (YAML key model.modality_dropout_video)")
+    p.add_argument("--noise_path", default=None,
+                   help="acoustic augmentation: a .wav / .npy noise recording or a directory of them (16 kHz); a segment of one is mixed into "
+                        "each training clip on the device (YAML key data.noise_path; default none = off; effect on WER not measured)")
+    p.add_argument("--noise_snr", default=None, help="the SNR in dB: LO,HI (drawn per clip) or one value; default 0,20 (YAML key data.noise_snr)")
+    p.add_argument("--noise_prob", type=float, default=None, help="the share of training clips that get noise; default 1 (YAML key data.noise_prob)")
+    p.add_argument("--spec_time_masks", type=int, default=None, help="SpecAugment on the log-mel: time masks per clip; default 0 = off (YAML key data.spec_time_masks)")
+    p.add_argument("--spec_time_width", type=int, default=None, help="each time mask covers 0..this many frames (YAML key data.spec_time_width)")
+    p.add_argument("--spec_time_ratio", type=float, default=None,
+                   help="... and at most this share of the clip's own frames; default 1 (YAML key data.spec_time_ratio)")
+    p.add_argument("--spec_freq_masks", type=int, default=None, help="frequency masks per clip; default 0 = off (YAML key data.spec_freq_masks)")
+    p.add_argument("--spec_freq_width", type=int, default=None, help="each frequency mask covers 0..this many mel bins (YAML key data.spec_freq_width)")
     p.add_argument("--log_interval", type=int); p.add_argument("--save_every", type=int); p.add_argument("--resume_from")
     p.add_argument("--save_steps", type=int, default=None, help="stored by the trainer and never acted on, as in the reference (clip_whisper_trainer.py:94-102)")
     p.add_argument("--log_param_updates", action="store_true", help="accepted for command-line compatibility; the reference stores it and never reads it (:118)")
@@ -73,7 +84,10 @@ def main():
                             "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type, "train_connectors": a.train_connectors,
                             "lora_target_modules": a.lora_target_modules, "modality_dropout_audio": a.modality_dropout_audio,
                             "modality_dropout_video": a.modality_dropout_video, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
-                            "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None})
+                            "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None,
+                            "noise_path": a.noise_path, "noise_snr": a.noise_snr, "noise_prob": a.noise_prob, "spec_time_masks": a.spec_time_masks,
+                            "spec_time_width": a.spec_time_width, "spec_time_ratio": a.spec_time_ratio, "spec_freq_masks": a.spec_freq_masks,
+                            "spec_freq_width": a.spec_freq_width})
     os.makedirs(cfg["output_dir"], exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s",
                         handlers=[logging.StreamHandler(), logging.FileHandler(os.path.join(cfg["output_dir"], "training.log"))])
@@ -118,7 +132,9 @@ def main():
             sampler = torch.utils.data.distributed.DistributedSampler(AVSRDataset(mp, lp, root, model.tokenizer, modality=cfg.get("modality", "both")), shuffle=True)
         dl, vdl = create_dataloaders(mp, lp, root, model.tokenizer, batch_size=cfg.get("batch_size", 4), num_workers=cfg.get("num_workers", 0),
                                      modality=cfg.get("modality", "both"), max_video_length=cfg.get("max_video_length", 300), sampler=sampler)
-    tr = ClipWhisperTrainer(model, dl, vdl, learning_rate=float(cfg.get("learning_rate", 5e-5)), weight_decay=float(cfg.get("weight_decay", 0.01)),
+    from avllm.preprocess import augment_from_config
+    augment = augment_from_config(cfg, f"cuda:{local}")
+    tr = ClipWhisperTrainer(model, dl, vdl, audio_augment=augment, augment_seed=cfg.get("seed", 42), learning_rate=float(cfg.get("learning_rate", 5e-5)), weight_decay=float(cfg.get("weight_decay", 0.01)),
                             max_epochs=cfg.get("num_epochs", 10), output_dir=cfg["output_dir"], device=f"cuda:{local}", fp16=bool(cfg.get("use_fp16")),
                             grad_accum_steps=cfg.get("grad_accum_steps", 1), log_interval=cfg.get("log_interval", 10), save_every=cfg.get("save_every", 1),
                             grad_clip=float(cfg.get("max_grad_norm", 0.5)), warmup_steps=cfg.get("warmup_steps", 0),
