@@ -138,6 +138,8 @@ class ClipEngine:
     def __init__(self, sd, cfg, dtype=torch.bfloat16, device="cuda", chunk_frames=0, fp8=False):
         sd = {k[len("vision_model."):] if k.startswith("vision_model.") else k: v for k, v in sd.items()}
         self.cfg, self.dtype, self.device = cfg, dtype, device
+        if cfg.layers < 1:      # avllm_clip_vision_cls_fwd refuses it too: the CLS rows are written by the last block
+            raise ValueError(f"ClipEngine: layers={cfg.layers}: the CLS output is written by the last block, a tower without one has none")
         self.chunk = chunk_frames
         self.keep = []
         d = cfg.hidden

@@ -539,6 +539,8 @@ extern "C" int avllm_clip_vision_cls_fwd(const avllm_clip* c, const void* frames
                                          size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     AV_CHECK_ARG(c && frames && cls && ws && N > 0, "clip_vision_cls_fwd: null/empty");
+    // the CLS rows reach `cls` through the last block's tail alone: without a block nothing would write it
+    AV_CHECK_ARG(c->layers >= 1 && c->layer, "clip_vision_cls_fwd: layers=%d: the output is written by the last block, a tower without one has none", c->layers);
     const int g1 = c->image / c->patch;
     AV_CHECK_ARG(c->tokens == g1 * g1 + 1 && c->d % c->heads == 0 && c->d % 64 == 0 && c->ffn % 64 == 0,
                  "clip: tokens=%d d=%d ffn=%d inconsistent", c->tokens, c->d, c->ffn);

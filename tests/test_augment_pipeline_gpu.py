@@ -159,7 +159,12 @@ def test_trainer_augments_training_batches_only(dev, toy):
     m2.train()
     assert not torch.equal(t2._unpack(batch)[0], a0[0])
     t0.model = m2
-    assert t2._validate() == t0._validate()
+    # _validate() is the mean of the batches' reported losses, each a loss_sum of avllm_ce_fwd's float atomics (see above): two evaluations of
+    # the same model on the same batches are held to the bar of that sum, which is linear in the total and so carries over to the mean (two
+    # runs gave 5.612086534 / 5.612086296 and 5.612086296 / 5.612086058, one float32 ulp apart)
+    v2, v0 = t2._validate(), t0._validate()
+    print("validation losses", repr(v2), repr(v0), "bar", Bar.atomic_sum_term(max(rows), max(abs(v2), abs(v0))))
+    assert abs(v2 - v0) <= Bar.atomic_sum_term(max(rows), max(abs(v2), abs(v0))), (v2, v0)
     # the seed of a step: by value, one per step and rank
     assert t2.augment_seed_at(3, 0) == RA.augment_seed(9, 3, 0) != t2.augment_seed_at(3, 1) == RA.augment_seed(9, 3, 1)
     assert t2.augment_seed_at(4) != t2.augment_seed_at(3) and t2.augment_seed_at(2 ** 20, 5) < 2 ** 32
