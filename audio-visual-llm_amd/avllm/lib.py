@@ -134,6 +134,12 @@ _SIGS = {
     "avllm_wave_add_noise_workspace_bytes": ([i32, i32], C.c_size_t),
     "avllm_wave_add_noise": ([vp, i64, vp, i32, i32, vp, i64, vp, i32, vp, f32, f32, f32, C.c_uint32, vp, vp, i64, vp, vp, C.c_size_t, vp], i32),
     "avllm_spec_augment": ([vp, i32, i32, i32, vp, i32, i32, f32, i32, i32, f32, C.c_uint32, vp, vp, vp], i32),
+    "avllm_clip_preproc_aug_plan_bytes": ([i32, i32, i32, i32], C.c_size_t),
+    "avllm_clip_preproc_aug_plan_init": ([vp, i32, i32, i32, i32, vp, vp], i32),
+    "avllm_clip_preproc_aug_workspace_bytes": ([i32, i32, i32, i32, i32], C.c_size_t),
+    "avllm_clip_preproc_aug": ([vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, f32, f32, C.c_uint32, vp, vp, i32, vp, vp, vp, C.c_size_t,
+                                vp], i32),
+    "avllm_video_frames_augment": ([vp, i32, i32, i32, i32, vp, i32, f32, i32, i32, f32, f32, C.c_uint32, vp, vp, vp, vp], i32),
     "avllm_lora_pack_batch": ([vp, i32, i32, i32, i32, vp], i32),
     "avllm_lora_merge": ([vp, i64, i32, i32, vp, vp, i32, f32, i32, vp], i32),
     "avllm_layernorm": ([vp, vp, vp, vp, i64, i32, f32, i32, vp], i32),

@@ -69,6 +69,16 @@ class ClipFrames:
         self.mean = (C.c_float * 3)(*mean)
         self.std = (C.c_float * 3)(*std)
         self._plans, self._ws = {}, None
+        self._aug_plans = {}                          # (H, W, resize) -> plan of avllm_clip_preproc_aug (VideoAugment.frames)
+
+    def _aug_plan(self, H, W, resize):
+        key = (H, W, resize)
+        if key not in self._aug_plans:
+            lib = L.load()
+            buf = torch.empty(lib.avllm_clip_preproc_aug_plan_bytes(H, W, resize, self.image), dtype=torch.uint8, device=self.device)
+            L.check(lib.avllm_clip_preproc_aug_plan_init(L.ptr(buf), H, W, resize, self.image, self.mean, self.std))
+            self._aug_plans[key] = buf
+        return self._aug_plans[key]
 
     def _plan(self, H, W):
         key = (H, W)
@@ -243,6 +253,117 @@ class AudioAugment:
                 "gain": f[:, 4].tolist()}
 
 
+class VideoAugment:
+    """The visual augmentations (include/avllm.h, "visual augmentation"; csrc/video_augment.hip), one draw per clip: the frames are resized so
+    that the shorter edge is `resize` (None: the image size, i.e. no room to crop), a window of the image size is cut at a drawn corner
+    (random_crop=False: the centre), the clip is mirrored with probability flip_prob, and time_masks spans of
+    [0, min(time_width, time_ratio * frames)] frames are set to `fill` (0.0: the mean pixel after CLIP's normalisation, roughly)."""
+
+    def __init__(self, resize=None, random_crop=True, flip_prob=0.5, time_masks=0, time_width=0, time_ratio=1.0, fill=0.0):
+        self.resize = None if resize is None else int(resize)
+        self.random_crop, self.flip_prob = bool(random_crop), float(flip_prob)
+        self.time_masks, self.time_width, self.time_ratio, self.fill = int(time_masks), int(time_width), float(time_ratio), float(fill)
+        if self.resize is not None and self.resize < 1:
+            raise ValueError(f"VideoAugment: resize = {self.resize} must be at least 1 (None: the image size)")
+        if not 0.0 <= self.flip_prob <= 1.0:
+            raise ValueError(f"VideoAugment: flip_prob = {self.flip_prob} must lie in [0, 1]")
+        if not 0 <= self.time_masks <= 16:
+            raise ValueError(f"VideoAugment: time_masks = {self.time_masks} must lie in [0, 16]")
+        if self.time_width < 0:
+            raise ValueError(f"VideoAugment: time_width = {self.time_width} may not be negative")
+        if not 0.0 <= self.time_ratio <= 1.0:
+            raise ValueError(f"VideoAugment: time_ratio = {self.time_ratio} must lie in [0, 1]")
+        # device tensors of the last call: int32 [clips, 4] = left, top, flip, masked / int32 [clips, time_masks, 2] = (start, width); and the
+        # clips' frame counts as a host list (what `masked` is a share of)
+        self.last_info = self.last_spans = self.last_frames = None
+        self._ws = None
+
+    _seed_ptr = staticmethod(AudioAugment._seed_ptr)
+
+    def frames(self, clip_frames, frames, clip, seed, seed_dev=None, out=None, info=None, spans=None):
+        """One clip through the fused path: frames uint8 [N, H, W, 3] -> pixel_values [N, 3, image, image] of clip_frames' image size and dtype
+        (written into `out` when given).  clip: the clip's index in its batch.  info int32 [4] / spans int32 [time_masks, 2]: device rows to
+        write the draw into (a batch's collector); without them last_info / last_spans are this clip's own [1, 4] / [1, time_masks, 2]."""
+        frames = torch.as_tensor(frames)
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError(f"frames should be uint8 [frames, height, width, 3], but got {frames.dtype} {tuple(frames.shape)}")
+        cf, image = clip_frames, clip_frames.image
+        resize = image if self.resize is None else self.resize
+        if resize < image:
+            raise ValueError(f"VideoAugment: resize = {resize} is below the image size {image}: the crop window must fit the resized frame")
+        if int(clip) < 0:
+            raise ValueError(f"VideoAugment.frames: clip = {clip} may not be negative")
+        frames = frames.to(cf.device).contiguous()
+        N, H, W, _ = frames.shape
+        lib = L.load()
+        plan = cf._aug_plan(H, W, resize)
+        need = lib.avllm_clip_preproc_aug_workspace_bytes(N, H, W, resize, image)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != frames.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=frames.device)
+        if out is None:
+            out = torch.empty(N, 3, image, image, dtype=cf.dtype, device=frames.device)
+        elif out.numel() != N * 3 * image * image or out.dtype != cf.dtype or not out.is_contiguous() or out.device != frames.device:
+            raise ValueError(f"out should be a contiguous {cf.dtype} tensor of {N} x 3 x {image} x {image} elements on {frames.device}, "
+                             f"but got {out.dtype} {tuple(out.shape)}")
+        own = info is None
+        if not own and self.time_masks and spans is None:
+            raise ValueError(f"VideoAugment.frames: info is given but spans is not, with time_masks = {self.time_masks}: both rows or neither")
+        if own:
+            info = torch.empty(1, 4, dtype=torch.int32, device=frames.device)
+            spans = torch.empty(1, self.time_masks, 2, dtype=torch.int32, device=frames.device)
+        L.check(lib.avllm_clip_preproc_aug(L.ptr(plan), L.ptr(frames), N, H, W, resize, image, int(clip), int(self.random_crop), self.flip_prob,
+                                           self.time_masks, self.time_width, self.time_ratio, self.fill, int(seed) & 0xFFFFFFFF,
+                                           self._seed_ptr(seed_dev), L.ptr(out), L.dt_of(out), L.ptr(info), L.ptr(spans) if self.time_masks else None,
+                                           L.ptr(self._ws), self._ws.numel(), L.stream_ptr()))
+        if own:
+            self.last_info, self.last_spans, self.last_frames = info, spans, [N]
+        return out
+
+    def pixels(self, video, nframes=None, seed=0, first_clip=0, seed_dev=None):
+        """Flip and frame masks IN PLACE on pixel_values [B, F, 3, S, S] (contiguous float32 / bfloat16 on the device) that were resized and
+        cropped before; nframes int32 [B] on the device | None (= F): the frames each clip really has.  Clip b draws with the keys of clip
+        first_clip + b.  Returns video.  With flip_prob rounding to 0 and no masks nothing is launched."""
+        if video.dim() != 5 or video.shape[2] != 3 or video.shape[3] != video.shape[4] or not video.is_contiguous() or not video.is_cuda:
+            raise ValueError(f"VideoAugment.pixels: video should be a contiguous [batch_size, frames, 3, size, size] device tensor, got {tuple(video.shape)}")
+        B, F, _, S, _ = video.shape
+        if nframes is not None and (nframes.dtype != torch.int32 or tuple(nframes.shape) != (B,) or not nframes.is_contiguous() or nframes.device != video.device):
+            raise ValueError(f"VideoAugment.pixels: nframes should be a contiguous int32 [{B}] tensor on {video.device}, got {nframes.dtype} {tuple(nframes.shape)} on {nframes.device}")
+        if int(first_clip) < 0:
+            raise ValueError(f"VideoAugment.pixels: first_clip = {first_clip} may not be negative")
+        info = torch.empty(B, 4, dtype=torch.int32, device=video.device)
+        spans = torch.empty(B, self.time_masks, 2, dtype=torch.int32, device=video.device)
+        if int(C.c_float(self.flip_prob).value * 16777216.0 + 0.5) == 0 and self.time_masks == 0:      # no launch: the draw it would have left
+            info[:, :2], info[:, 2:] = -1, 0
+        L.check(L.load().avllm_video_frames_augment(L.ptr(video), L.dt_of(video), B, F, S, L.ptr(nframes), int(first_clip), self.flip_prob,
+                                                    self.time_masks, self.time_width, self.time_ratio, self.fill, int(seed) & 0xFFFFFFFF,
+                                                    self._seed_ptr(seed_dev), L.ptr(info), L.ptr(spans) if self.time_masks else None,
+                                                    L.stream_ptr()))
+        self.last_info, self.last_spans, self.last_frames = info, spans, nframes if nframes is not None else [F] * B
+        return video
+
+    @staticmethod
+    def info_fields(info):
+        """last_info (int32 [clips, 4], on any device) -> dict of host lists: left, top, flip, masked."""
+        info = info.cpu()
+        return {"left": info[:, 0].tolist(), "top": info[:, 1].tolist(), "flip": info[:, 2].tolist(), "masked": info[:, 3].tolist()}
+
+
+def video_augment_from_config(cfg):
+    """The VideoAugment the flat configuration asks for (keys video_resize, video_random_crop, video_flip_prob, video_time_masks,
+    video_time_width, video_time_ratio: scripts/clip_whisper/train.py flags and configs/clip_whisper.yaml data: entries), or None when it asks
+    for none: the trainer then runs exactly the path it ran without these keys.  A resize asks for the random crop unless video_random_crop
+    says otherwise; flip and masks are off until asked for."""
+    resize, crop, flip = cfg.get("video_resize"), cfg.get("video_random_crop"), cfg.get("video_flip_prob")
+    tm = int(cfg.get("video_time_masks") or 0)
+    if isinstance(crop, str):
+        crop = crop.strip().lower() in ("1", "true", "yes", "on")
+    if resize is None and not flip and tm == 0:      # without a resize there is no room to crop: video_random_crop alone asks for nothing
+        return None
+    return VideoAugment(resize=None if resize is None else int(resize), random_crop=resize is not None if crop is None else bool(crop),
+                        flip_prob=float(flip or 0.0), time_masks=tm, time_width=int(cfg.get("video_time_width") or 0),
+                        time_ratio=1.0 if cfg.get("video_time_ratio") is None else float(cfg.get("video_time_ratio")))
+
+
 def parse_snr(value):
     """--noise_snr / the YAML's noise_snr: "LO,HI", [LO, HI], or one number -> (lo, hi)."""
     if isinstance(value, str):
@@ -275,13 +396,15 @@ def valid_frames(lengths):
     return torch.clamp((lengths + 159) // 160, max=N_FRAMES).to(torch.int32)
 
 
-def device_collate(samples, logmel, clip_frames, max_video_length=300, augment=None, seed=None):
+def device_collate(samples, logmel, clip_frames, max_video_length=300, augment=None, seed=None, video_augment=None):
     """collate_fn (simple_dataset.py:317-460) for raw samples: `samples` = list of dicts with "wave" (1-D float, 16 kHz) and/or
     "frames" (uint8 [F,H,W,3]) + "labels"/"text".  -> (audio [B,80,3000] | None, video [B,Fmax,3,S,S] zero-padded | None).
     augment: an AudioAugment | None; with one, noise is mixed into the padded waveforms (in place, over each clip's own samples) before the
-    log-mel and the features are masked after it, both drawn with `seed`.  None: the calls and allocations of before."""
+    log-mel and the features are masked after it, both drawn with `seed`.  None: the calls and allocations of before.
+    video_augment: a VideoAugment | None; with one, each clip's frames take the fused resize / crop / flip / mask path, the sample's index in the
+    batch as its `clip`, drawn with `seed` too (a salt of its own keeps the two streams' draws apart).  None: the calls of before."""
     audio = video = None
-    if augment is not None and seed is None:
+    if (augment is not None or video_augment is not None) and seed is None:
         raise ValueError("device_collate: augment needs a seed (the draws of a batch are a function of it)")
     if all(s.get("wave") is not None for s in samples):
         if augment is not None:
@@ -292,7 +415,15 @@ def device_collate(samples, logmel, clip_frames, max_video_length=300, augment=N
         else:
             audio = logmel([s["wave"] for s in samples])
     if all(s.get("frames") is not None for s in samples):
-        clips = [clip_frames(torch.as_tensor(s["frames"])[:max_video_length]) for s in samples]
+        if video_augment is not None:
+            va, dev = video_augment, clip_frames.device
+            info = torch.empty(len(samples), 4, dtype=torch.int32, device=dev)
+            spans = torch.empty(len(samples), va.time_masks, 2, dtype=torch.int32, device=dev)
+            clips = [va.frames(clip_frames, torch.as_tensor(s["frames"])[:max_video_length], i, seed, info=info[i], spans=spans[i])
+                     for i, s in enumerate(samples)]
+            va.last_info, va.last_spans, va.last_frames = info, spans, [c.shape[0] for c in clips]
+        else:
+            clips = [clip_frames(torch.as_tensor(s["frames"])[:max_video_length]) for s in samples]
         Fmax = max(c.shape[0] for c in clips)
         video = torch.zeros(len(clips), Fmax, *clips[0].shape[1:], dtype=clips[0].dtype, device=clips[0].device)
         for i, c in enumerate(clips):

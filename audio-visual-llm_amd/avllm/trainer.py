@@ -37,12 +37,15 @@ class ClipWhisperTrainer:
     def __init__(self, model, train_dataloader=None, val_dataloader=None, learning_rate=5e-5, weight_decay=0.01, max_epochs=10,
                  output_dir="outputs/clip_whisper", device="cuda", fp16=False, grad_accum_steps=1, log_interval=10, save_every=1,
                  save_steps=None, grad_clip=0.5, warmup_steps=0, log_param_updates=False, total_steps=None, use_graph=None,
-                 bwd_pieces=None, audio_augment=None, augment_seed=0):
+                 bwd_pieces=None, audio_augment=None, augment_seed=0, video_augment=None):
         self.model, self.train_dataloader, self.val_dataloader = model, train_dataloader, val_dataloader
         # acoustic augmentation (avllm.preprocess.AudioAugment | None): applied in _unpack, in front of the captured step, in train() mode only
         self.audio_augment, self.augment_seed = audio_augment, int(augment_seed)
         self.last_augment_info = None                      # AudioAugment.last_info of the last augmented batch (device int32 [B, 5])
         self._augment_notes = set()
+        # visual augmentation (avllm.preprocess.VideoAugment | None): in _unpack too, train() mode only, the same step seed under another salt
+        self.video_augment = video_augment
+        self.last_video_info = None                        # (VideoAugment.last_info, the clips' frame counts) of the last augmented batch
         self.learning_rate, self.weight_decay, self.max_epochs = learning_rate, weight_decay, max_epochs
         self.output_dir, self.device, self.fp16 = output_dir, device, fp16
         self.grad_accum_steps = grad_accum_steps           # stored but unused, as in the reference
@@ -104,6 +107,21 @@ class ClipWhisperTrainer:
         audio = audio.to(self.model.device, torch.float32, copy=True).contiguous()
         return aug.features(audio, None, self.augment_seed_at(self.global_step))
 
+    def _augment_pixels(self, video):
+        """A batch of precomputed pixel_values [B, F, 3, S, S] was resized and cropped by whoever made it: it gets the flip and the frame masks
+        only, every frame counted as the clip's own, on a device copy (the loader's tensor is left as it is)."""
+        aug = self.video_augment
+        if aug is None or not self.model.training or video is None or video.dim() != 5:
+            return video
+        if "pixels" not in self._augment_notes:
+            self._augment_notes.add("pixels")
+            logging.info("video_augment on precomputed pixel_values: flip and frame masks only (all frames counted); the crop needs raw frames")
+        dtype = video.dtype if video.dtype in (torch.float32, torch.bfloat16) else torch.float32      # the kernel moves fp32 or bf16 cells
+        video = video.to(self.model.device, dtype, copy=True).contiguous()
+        aug.pixels(video, None, self.augment_seed_at(self.global_step))
+        self.last_video_info = (aug.last_info, aug.last_frames)
+        return video
+
     # ---- _process_batch :604-680
     def _unpack(self, batch):
         if isinstance(batch, dict) and "raw" in batch:
@@ -112,19 +130,21 @@ class ClipWhisperTrainer:
             if getattr(self, "_featurizers", None) is None:
                 dev = self.model.device
                 self._featurizers = (WhisperLogMel(dev, n_mels=self.model.cfg.whisper.n_mels), ClipFrames(dev, image=self.model.cfg.clip.image))
-            if self.audio_augment is not None and self.model.training:
+            if (self.audio_augment is not None or self.video_augment is not None) and self.model.training:
                 audio, video = device_collate(batch["raw"], *self._featurizers, augment=self.audio_augment,
-                                              seed=self.augment_seed_at(self.global_step))
-                if audio is not None and self.audio_augment.mixes:
+                                              seed=self.augment_seed_at(self.global_step), video_augment=self.video_augment)
+                if audio is not None and self.audio_augment is not None and self.audio_augment.mixes:
                     self.last_augment_info = self.audio_augment.last_info
+                if video is not None and self.video_augment is not None:
+                    self.last_video_info = (self.video_augment.last_info, self.video_augment.last_frames)
             else:
                 audio, video = device_collate(batch["raw"], *self._featurizers)
             tok = self.model.tokenizer(batch["texts"], return_tensors="pt", padding=True, truncation=True, max_length=self.model.max_seq_len)
             return audio, video, batch["labels"], tok.input_ids
         if isinstance(batch, dict):
-            return self._augment_features(batch.get("audio")), batch.get("video"), batch.get("labels"), batch.get("prompt")
+            return self._augment_features(batch.get("audio")), self._augment_pixels(batch.get("video")), batch.get("labels"), batch.get("prompt")
         audio, video, texts, labels = batch
-        audio = self._augment_features(audio)
+        audio, video = self._augment_features(audio), self._augment_pixels(video)
         tok = self.model.tokenizer(texts, return_tensors="pt", padding=True, truncation=True, max_length=self.model.max_seq_len)
         bs = labels.shape[0]
         for t in (audio, video):
@@ -336,13 +356,13 @@ class ClipWhisperTrainer:
     def _train_epoch(self, epoch):
         self.model.train()
         total, n, t0 = 0.0, 0, time.time()
-        pending, pending_modes, pending_noise = [], [], []
+        pending, pending_modes, pending_noise, pending_video = [], [], [], []
         failures = unstable = worst = 0
         for i, batch in enumerate(self.train_dataloader):
             # the reference logs and skips a batch on ANY exception (:492-507).  Host-side preparation (everything before the first
             # collective) is where data errors surface; under DDP the skip is agreed between ranks first.
             unpacked, err = None, None
-            self.last_augment_info = None
+            self.last_augment_info = self.last_video_info = None
             try:
                 unpacked = self._unpack(batch)
             except Exception as e:
@@ -369,6 +389,8 @@ class ClipWhisperTrainer:
                 pending_modes.append(self.model.last_modality_modes.clone())
             if self.last_augment_info is not None:               # a tensor of its own per batch: kept, not copied
                 pending_noise.append(self.last_augment_info)
+            if self.last_video_info is not None:
+                pending_video.append(self.last_video_info)
             if (i + 1) % self.log_interval == 0 or i + 1 == len(self.train_dataloader):
                 vals = torch.stack(pending).float().cpu()
                 pending.clear()
@@ -396,6 +418,11 @@ class ClipWhisperTrainer:
                     share, snr = self.noise_shares(torch.cat(pending_noise).cpu())
                     pending_noise.clear()
                     logging.info(f"epoch {epoch} batch {i + 1}: clips with noise mixed in {share:.3f}, their mean SNR {snr:.2f} dB")
+                if pending_video:
+                    flipped, masked = self.video_shares(torch.cat([v[0] for v in pending_video]).cpu(),
+                                                        [n for v in pending_video for n in (v[1].tolist() if torch.is_tensor(v[1]) else v[1])])
+                    pending_video.clear()
+                    logging.info(f"epoch {epoch} batch {i + 1}: clips flipped {flipped:.3f}, mean share of frames masked {masked:.3f}")
         return total / max(1, n)
 
     @staticmethod
@@ -405,6 +432,15 @@ class ClipWhisperTrainer:
         on = info[:, 0] != 0
         snr = info.view(torch.float32)[:, 3][on]
         return float(on.float().mean()) if info.shape[0] else 0.0, float(snr.mean()) if snr.numel() else float("nan")
+
+    @staticmethod
+    def video_shares(info, frames):
+        """(the share of clips flipped, the mean over clips of masked frames / the clip's frames) of VideoAugment.last_info rows and the clips'
+        frame counts; a clip without frames counts as unmasked."""
+        if not info.shape[0]:
+            return 0.0, 0.0
+        share = [m / n if n > 0 else 0.0 for m, n in zip(info[:, 3].tolist(), frames)]
+        return float((info[:, 2] != 0).float().mean()), sum(share) / len(share)
 
     @staticmethod
     def mode_shares(modes):

@@ -9,6 +9,7 @@
 // the host with Pillow's own double-precision recipe and applied by two uint8 passes.
 #include "common.h"
 #include "avllm_internal.h"
+#include "resize_coeffs.h"
 #include <array>
 #include <cmath>
 #include <cstring>
@@ -120,17 +121,12 @@ __global__ __launch_bounds__(1024) void logmel_finish_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------- video
-constexpr int PBITS = 32 - 8 - 2;            // Resample.c PRECISION_BITS
+using namespace av_resize;                   // csrc/resize_coeffs.h: PBITS, clip8 and the host coefficient recipe, shared with video_augment.hip
 
 struct ResizeHdr {
     int H, W, newH, newW, top, left, image, ksx, ksy;
     int off_bx, off_kx, off_by, off_ky, off_lut;          // byte offsets into the plan
 };
-
-__device__ __forceinline__ int clip8(int v) {
-    v >>= PBITS;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 // horizontal pass: in [N,H,W,3] u8 -> tmp [N,H,image,3] u8, only the columns the centre crop keeps
 __global__ __launch_bounds__(256) void resize_h_kernel(const char* __restrict__ plan, const unsigned char* __restrict__ in,
@@ -241,49 +237,6 @@ __global__ __launch_bounds__(256) void resize_v_norm_kernel(const char* __restri
     }
 }
 
-// ---- host: Pillow's coefficient recipe (Resample.c precompute_coeffs + normalize_coeffs_8bpc), bicubic a = -0.5, support 2
-double bicubic(double x) {
-    const double a = -0.5;
-    if (x < 0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-int coeff_ksize(int in_size, int out_size) {
-    double fs = (double)in_size / out_size;
-    if (fs < 1.0) fs = 1.0;
-    return (int)std::ceil(2.0 * fs) * 2 + 1;
-}
-// coefficients of output samples [o0, o0+cnt_out) of an in_size -> out_size resample
-void coeffs(int in_size, int out_size, int o0, int cnt_out, std::vector<int>& bounds, std::vector<int>& kk, int ksize) {
-    const double scale = (double)in_size / out_size;
-    double filterscale = scale;
-    if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 2.0 * filterscale, ss = 1.0 / filterscale;
-    bounds.assign((size_t)cnt_out * 2, 0);
-    kk.assign((size_t)cnt_out * ksize, 0);
-    std::vector<double> w(ksize);
-    for (int t = 0; t < cnt_out; ++t) {
-        const int xx = o0 + t;
-        const double center = (xx + 0.5) * scale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        double ww = 0.0;
-        for (int x = 0; x < xmax; ++x) { w[x] = bicubic((x + xmin - center + 0.5) * ss); ww += w[x]; }
-        for (int x = 0; x < xmax; ++x) {
-            if (ww != 0.0) w[x] /= ww;
-            kk[(size_t)t * ksize + x] = w[x] < 0 ? (int)(-0.5 + w[x] * (1 << PBITS)) : (int)(0.5 + w[x] * (1 << PBITS));
-        }
-        bounds[2 * t] = xmin; bounds[2 * t + 1] = xmax;
-    }
-}
-void resized_shape(int H, int W, int image, int& nh, int& nw) {     // image_transforms.get_resize_output_image_size(shortest_edge)
-    if (W <= H) { nw = image; nh = (int)((double)image * H / W); }
-    else        { nh = image; nw = (int)((double)image * W / H); }
-}
 size_t plan_layout(int H, int W, int image, ResizeHdr& h) {
     int nh, nw;
     resized_shape(H, W, image, nh, nw);
@@ -382,12 +335,7 @@ extern "C" int avllm_clip_preproc_plan_init(void* plan_dev, int32_t H, int32_t W
     memcpy(buf.data() + h.off_bx, b.data(), b.size() * 4); memcpy(buf.data() + h.off_kx, k.data(), k.size() * 4);
     coeffs(H, h.newH, h.top, image, b, k, h.ksy);
     memcpy(buf.data() + h.off_by, b.data(), b.size() * 4); memcpy(buf.data() + h.off_ky, k.data(), k.size() * 4);
-    float* lut = (float*)(buf.data() + h.off_lut);
-    for (int c = 0; c < 3; ++c)
-        for (int v = 0; v < 256; ++v) {
-            const float r = (float)((double)v * (1.0 / 255.0));          // image_transforms.rescale: float64 product, then float32
-            lut[c * 256 + v] = (r - mean3[c]) / std3[c];                  // image_transforms.normalize in float32
-        }
+    normalize_lut(mean3, std3, (float*)(buf.data() + h.off_lut));
     memcpy(buf.data(), &h, sizeof(h));
     AV_HIP(hipMemcpy(plan_dev, buf.data(), bytes, hipMemcpyHostToDevice));
     { std::lock_guard<std::mutex> lk(g_plan_mu); g_plans[plan_dev] = {H, W, image}; }

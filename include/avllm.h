@@ -575,6 +575,64 @@ int avllm_spec_augment(float* feat, int32_t B, int32_t M, int32_t T, const int32
                        float max_time_ratio, int32_t n_freq, int32_t max_freq_width, float fill, uint32_t seed, const uint32_t* seed_dev,
                        int32_t* spans, void* stream);
 
+/* ---------------------------------------------------------------- visual augmentation on the device ----------------
+ * No counterpart in the reference (it has no augmentation): the video half of the AV-HuBERT / auto-avsr recipe, folded into the two passes of
+ * avllm_clip_preproc: a random crop of a slightly larger resize, a horizontal flip, and masked spans of frames.  ONE draw per clip, so the
+ * mouth motion stays coherent across the frames.  The draws come from the counter hash of csrc/common.h (av_pair_hash) with the launch seed
+ * (seed_dev ? *seed_dev : 0) + seed, like the acoustic augmentation, under a salt of their own; no call syncs with the host.
+ *
+ * The plan: specific to (H, W, resize, image, mean, std), resize >= image.  The resized shape (newH, newW) is avllm_clip_preproc's
+ * shortest-edge rule applied to `resize`: short edge -> resize, long edge -> int(resize * long / short).  The plan holds Pillow's bounds and
+ * coefficients of ALL newW columns and ALL newH rows (a crop window is chosen per call) and the same rescale / normalise table.  It is
+ * registered at init and checked at call time. */
+size_t avllm_clip_preproc_aug_plan_bytes(int32_t H, int32_t W, int32_t resize, int32_t image);      /* 0 for a shape no plan can be made for */
+int avllm_clip_preproc_aug_plan_init(void* plan_dev, int32_t H, int32_t W, int32_t resize, int32_t image, const float* mean3,
+                                     const float* std3);
+typedef struct avllm_video_aug_info {
+    int32_t left, top;    /* the crop window's corner in the resized frame (-1, -1 from avllm_video_frames_augment) */
+    int32_t flip;         /* 1: the clip is mirrored left to right */
+    int32_t masked;       /* the number of frames inside the union of the spans */
+} avllm_video_aug_info;
+/* One clip per call: frames u8 [N, H, W, 3] RGB -> out [N, 3, image, image] (dtype f32 or bf16).  clip >= 0: the clip's index in its batch
+ * (the key of its draw); info DEVICE [1]; spans DEVICE int32 [n_time, 2] (may be NULL when n_time == 0); ws: at least
+ * avllm_clip_preproc_aug_workspace_bytes bytes.
+ * The rule, with s = (seed_dev ? *seed_dev : 0) + seed + 0x76696465 and h_j = av_pair_hash(s, 64*clip + j):
+ *   left  = random_crop ? ((uint64_t)h_0 * (newW - image + 1)) >> 32 : (newW - image) / 2      (0 .. newW - image, both ends included)
+ *   top   = random_crop ? ((uint64_t)h_1 * (newH - image + 1)) >> 32 : (newH - image) / 2
+ *   flip  = (h_2 >> 8) < (uint32_t)(p_flip * 2^24 + 0.5)      (of the float argument, evaluated in double)
+ *   time mask m < n_time <= 16:
+ *     wmax  = min(max_time_width, floor(max_time_ratio * N))  (the product in double)
+ *     w     = ((uint64_t)h_{4+2m} * (wmax + 1)) >> 32         (0 .. wmax, both ends included)
+ *     start = ((uint64_t)h_{5+2m} * (N - w + 1)) >> 32        (start + w <= N)
+ *     spans[m] = (start, w); info.masked = the number of frames n with start <= n < start + w for some m
+ *   R_n = Pillow's BICUBIC resize of frame n to newH x newW: horizontal pass, uint8, vertical pass, avllm_clip_preproc's arithmetic
+ *   out[n, ch, y, x] = lut[ch][ R_n[top + y][left + (flip ? image - 1 - x : x)][ch] ],  lut[ch][v] = ((float)(v / 255.0) - mean[ch]) / std[ch]
+ *     i.e. crop, THEN flip: torchvision's Resize -> RandomCrop -> RandomHorizontalFlip.  One left, top and flip serve every frame of the clip.
+ *   every element of a frame inside a span is `fill` converted to dtype (after the table, not before it); such a frame's pixels are not read.
+ * f32 output is the table's value; bf16 output is rounded the way avllm_clip_preproc rounds.  With resize == image, random_crop = 0,
+ * p_flip = 0 and n_time = 0 the output equals avllm_clip_preproc's bit for bit.  No atomics: a repeated launch repeats its bits.
+ * Two launches, as avllm_clip_preproc: the horizontal pass produces only the `image` columns of the crop window (mirrored there when the clip
+ * flips: the flip is an index change, not a pass) and only the input rows that the vertical taps of rows top .. top + image - 1 reach, and it
+ * skips masked frames; the vertical pass writes `fill` into those.  Every workgroup recomputes the draw from (s, clip): there is no draw launch.
+ * AV_ERR_ARG, naming the argument: resize < image, n_time > 16 or negative, a negative max_time_width, p_flip or max_time_ratio outside
+ * [0, 1], clip < 0, a plan made for another (H, W, resize, image), a workspace that is too small. */
+size_t avllm_clip_preproc_aug_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t resize, int32_t image);
+int avllm_clip_preproc_aug(const void* plan, const uint8_t* frames, int32_t N, int32_t H, int32_t W, int32_t resize, int32_t image,
+                           int32_t clip, int32_t random_crop, float p_flip, int32_t n_time, int32_t max_time_width, float max_time_ratio,
+                           float fill, uint32_t seed, const uint32_t* seed_dev, void* out, int32_t dtype,
+                           avllm_video_aug_info* info, int32_t* spans, void* ws, size_t ws_bytes, void* stream);
+/* Flip and frame masks IN PLACE on pixel_values [B, F, 3, image, image] (contiguous, dtype f32 or bf16) that were resized and cropped before.
+ *   nframes DEVICE int32 [B] | NULL (= F): the frames a clip really has, clamped to [0, F]; info DEVICE [B]; spans DEVICE int32 [B, n_time, 2].
+ * Clip b uses the keys of clip = first_clip + b with N = nframes[b]: exactly the flip and the spans avllm_clip_preproc_aug gives that clip.
+ * left and top are reported as -1.  A masked frame becomes `fill`; a frame of a flipped clip that is not masked has every row of its three
+ * planes reversed (the bits are moved, nothing is computed).  Frames at or past nframes[b], and every cell that neither flips nor is masked
+ * (the centre column of an odd image among them), are neither read nor written.  One launch; with p_flip rounding to 0 and n_time == 0 there
+ * is none and pixels, info and spans may be NULL.  16-byte (f32) / 8-byte (bf16) accesses when image % 4 == 0 and pixels is 16-byte aligned,
+ * a scalar form otherwise, with equal bits. */
+int avllm_video_frames_augment(void* pixels, int32_t dtype, int32_t B, int32_t F, int32_t image, const int32_t* nframes, int32_t first_clip,
+                               float p_flip, int32_t n_time, int32_t max_time_width, float max_time_ratio, float fill, uint32_t seed,
+                               const uint32_t* seed_dev, avllm_video_aug_info* info, int32_t* spans, void* stream);
+
 /* Live kernel timing for bench.py: between begin and end every avllm_gemm launch (direct or inside the model-level
  * calls) is bracketed by two HIP events on its stream.  out[0]=sum of GEMM ms, out[1]=sum of algorithmic FLOPs
  * (2*M*N*(K+K2)), out[2]=launches timed. */

@@ -13,7 +13,10 @@ for p in (ROOT, os.path.join(ROOT, "audio-visual-llm_amd")):
 import torch  # noqa: E402
 
 
-def parse_args():
+VIDEO_KEYS = ("video_resize", "video_random_crop", "video_flip_prob", "video_time_masks", "video_time_width", "video_time_ratio")
+
+
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--config", default=os.path.join(ROOT, "configs", "clip_whisper.yaml"))
     p.add_argument("--output_dir"); p.add_argument("--data_path"); p.add_argument("--llm_path")
@@ -46,6 +49,16 @@ def parse_args():
                    help="... and at most this share of the clip's own frames; default 1 (YAML key data.spec_time_ratio)")
     p.add_argument("--spec_freq_masks", type=int, default=None, help="frequency masks per clip; default 0 = off (YAML key data.spec_freq_masks)")
     p.add_argument("--spec_freq_width", type=int, default=None, help="each frequency mask covers 0..this many mel bins (YAML key data.spec_freq_width)")
+    p.add_argument("--video_resize", type=int, default=None,
+                   help="visual augmentation: resize the frames' shorter edge to this (at least the image size) and cut the image-sized window "
+                        "at a corner drawn per clip, on the device (YAML key data.video_resize; default none = off; effect on WER not measured)")
+    p.add_argument("--video_random_crop", type=int, choices=[0, 1], default=None,
+                   help="1: draw the crop window (the default with --video_resize), 0: the centre crop (YAML key data.video_random_crop)")
+    p.add_argument("--video_flip_prob", type=float, default=None, help="the share of training clips mirrored left to right; default 0 = off (YAML key data.video_flip_prob)")
+    p.add_argument("--video_time_masks", type=int, default=None, help="spans of frames per clip that are blanked; default 0 = off, at most 16 (YAML key data.video_time_masks)")
+    p.add_argument("--video_time_width", type=int, default=None, help="each span covers 0..this many frames (YAML key data.video_time_width)")
+    p.add_argument("--video_time_ratio", type=float, default=None,
+                   help="... and at most this share of the clip's own frames; default 1 (YAML key data.video_time_ratio)")
     p.add_argument("--log_interval", type=int); p.add_argument("--save_every", type=int); p.add_argument("--resume_from")
     p.add_argument("--save_steps", type=int, default=None, help="stored by the trainer and never acted on, as in the reference (clip_whisper_trainer.py:94-102)")
     p.add_argument("--log_param_updates", action="store_true", help="accepted for command-line compatibility; the reference stores it and never reads it (:118)")
@@ -54,7 +67,7 @@ def parse_args():
     p.add_argument("--synthetic-weights", action="store_true",
                    help="seeded random weights + byte tokenizer when the model paths are not local checkpoints (implied by --tiny); "
                         "without it such a path is an error")
-    return p.parse_args()
+    return p.parse_args(argv)
 
 
 class SyntheticClips(torch.utils.data.Dataset):
@@ -87,7 +100,7 @@ def main():
                             "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None,
                             "noise_path": a.noise_path, "noise_snr": a.noise_snr, "noise_prob": a.noise_prob, "spec_time_masks": a.spec_time_masks,
                             "spec_time_width": a.spec_time_width, "spec_time_ratio": a.spec_time_ratio, "spec_freq_masks": a.spec_freq_masks,
-                            "spec_freq_width": a.spec_freq_width})
+                            "spec_freq_width": a.spec_freq_width, **{k: getattr(a, k) for k in VIDEO_KEYS}})
     os.makedirs(cfg["output_dir"], exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s",
                         handlers=[logging.StreamHandler(), logging.FileHandler(os.path.join(cfg["output_dir"], "training.log"))])
@@ -132,9 +145,9 @@ def main():
             sampler = torch.utils.data.distributed.DistributedSampler(AVSRDataset(mp, lp, root, model.tokenizer, modality=cfg.get("modality", "both")), shuffle=True)
         dl, vdl = create_dataloaders(mp, lp, root, model.tokenizer, batch_size=cfg.get("batch_size", 4), num_workers=cfg.get("num_workers", 0),
                                      modality=cfg.get("modality", "both"), max_video_length=cfg.get("max_video_length", 300), sampler=sampler)
-    from avllm.preprocess import augment_from_config
+    from avllm.preprocess import augment_from_config, video_augment_from_config
     augment = augment_from_config(cfg, f"cuda:{local}")
-    tr = ClipWhisperTrainer(model, dl, vdl, audio_augment=augment, augment_seed=cfg.get("seed", 42), learning_rate=float(cfg.get("learning_rate", 5e-5)), weight_decay=float(cfg.get("weight_decay", 0.01)),
+    tr = ClipWhisperTrainer(model, dl, vdl, audio_augment=augment, video_augment=video_augment_from_config(cfg), augment_seed=cfg.get("seed", 42), learning_rate=float(cfg.get("learning_rate", 5e-5)), weight_decay=float(cfg.get("weight_decay", 0.01)),
                             max_epochs=cfg.get("num_epochs", 10), output_dir=cfg["output_dir"], device=f"cuda:{local}", fp16=bool(cfg.get("use_fp16")),
                             grad_accum_steps=cfg.get("grad_accum_steps", 1), log_interval=cfg.get("log_interval", 10), save_every=cfg.get("save_every", 1),
                             grad_clip=float(cfg.get("max_grad_norm", 0.5)), warmup_steps=cfg.get("warmup_steps", 0),
