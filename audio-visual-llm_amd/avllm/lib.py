@@ -191,6 +191,11 @@ _SIGS = {
     "avllm_grad_sumsq_det": ([vp, i64, vp, i32, vp, vp], i32),
     "avllm_adamw_step": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp, f32, f32, vp, vp, vp, vp], i32),
     "avllm_step_advance": ([vp, C.POINTER(Schedule), vp], i32),
+    "avllm_gemm_wgrad_acc": ([vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, f32, i32, vp], i32),
+    "avllm_adamw_step_dev": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, vp, f32, vp, vp, vp, vp, vp], i32),
+    "avllm_adamw_step_multi_dev": ([C.POINTER(AdamwSeg), i32, f32, f32, f32, f32, i32, vp, f32, vp, vp, vp, vp, vp], i32),
+    "avllm_step_advance_micro": ([vp, C.POINTER(Schedule), vp], i32),
+    "avllm_window_add": ([vp, vp, vp, vp], i32),
     "avllm_mx_scale_bytes": ([i32, i32], sz),
     "avllm_mx_quantize": ([vp, i64, i32, i32, vp, i64, vp, i32, i32, vp], i32),
     "avllm_mx4_quantize": ([vp, i64, i32, i32, vp, i64, vp, i32, vp], i32),

@@ -387,10 +387,12 @@ class ClipWhisperModel:
         _, _, _, _, S, B, _ = self._conn_geo
         return self._static("dx", (B, S, self.llm_dim))
 
-    def connector_backward(self):
+    def connector_backward(self, accumulate=False):
         """dx_embeds -> fuse / pool adjoint -> the two weight gradients and bias gradients, written into conn_g (overwritten, not
         accumulated).  The connectors' INPUT gradient is not formed: the encoders are frozen.  An input that was absent in the forward
-        leaves its connector's gradient as zeros."""
+        leaves its connector's gradient as zeros.
+        accumulate=True (a micro-step of a gradient-accumulation window): the gradients are ADDED to conn_g (avllm_gemm_wgrad_acc; whoever
+        opens the window zeroes it) and an absent input adds nothing; da / dv stay per-call temporaries."""
         Ta, Tv, P, Lc, S, B, modes = self._conn_geo
         D = self.llm_dim
         da = self._static("da", (B, Ta, D)) if Ta else None
@@ -401,7 +403,10 @@ class ClipWhisperModel:
             ops.fuse_pool_bwd(self._dx_embeds_buffer(), Ta, Tv, P, Lc, self.fusion_scale, da=da, dv=dv)
         gWa, gba, gWv, gbv = self.connector_grad_views()
         for dy, conn, gW, gb in ((da, self.audio_connector, gWa, gba), (dv, self.video_connector, gWv, gbv)):
-            if dy is None:
+            if accumulate:
+                if dy is not None:
+                    ops.gemm_wgrad_acc(dy.view(-1, D), conn.saved_input, gW, gb)
+            elif dy is None:
                 gW.zero_(); gb.zero_()
             else:
                 ops.gemm_wgrad(dy.view(-1, D), conn.saved_input, dW=gW, db=gb)

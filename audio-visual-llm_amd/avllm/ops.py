@@ -763,6 +763,20 @@ def gemm_wgrad(dY, X, alpha=1.0, dW=None, db=None, want_db=True):
     return dW, db
 
 
+def gemm_wgrad_acc(dY, X, dW, db=None, alpha=1.0):
+    """dW [N,K] (fp32) += alpha * dY^T . X and db [N] (fp32, optional) += alpha * column sums of dY (avllm_gemm_wgrad_acc: the prior value is
+    read once and added once, no atomics)."""
+    M, N = dY.shape
+    K = X.shape[1]
+    if X.shape[0] != M or X.dtype != dY.dtype:
+        raise ValueError(f"gemm_wgrad_acc: dY {tuple(dY.shape)} {dY.dtype} and X {tuple(X.shape)} {X.dtype} do not match")
+    if dW.dtype != torch.float32 or tuple(dW.shape) != (N, K) or (db is not None and (db.dtype != torch.float32 or db.numel() != N)):
+        raise ValueError(f"gemm_wgrad_acc: dW must be fp32 [{N},{K}] and db fp32 [{N}]")
+    L.check(L.load().avllm_gemm_wgrad_acc(L.ptr(dY), _ld(dY), L.ptr(X), _ld(X), M, N, K, L.ptr(dW), _ld(dW), L.ptr(db), alpha, L.dt_of(dY),
+                                          L.stream_ptr()))
+    return dW, db
+
+
 def grad_sumsq_multi(gs, out, partials):
     """out = sum over the buffers `gs` (in order) of sum g^2, in a fixed order (avllm_grad_sumsq_det_multi)."""
     n = len(gs)
@@ -771,11 +785,24 @@ def grad_sumsq_multi(gs, out, partials):
     L.check(L.load().avllm_grad_sumsq_det_multi(ptrs, lens, n, L.ptr(partials), partials.numel(), L.ptr(out), L.stream_ptr()))
 
 
-def adamw_step_multi(segs, lr, step, sumsq=None, max_norm=0.0, beta1=0.9, beta2=0.95, eps=1e-8, prescale=1.0, guard=None, skipped=None, state=None):
-    """One AdamW step over several flat fp32 buffers under one guard decision (avllm_adamw_step_multi).  segs: (p, g, m, v, weight_decay) each."""
+def _grad_div_ptr(grad_div, who):
+    if not (torch.is_tensor(grad_div) and grad_div.dtype == torch.float32 and grad_div.numel() == 1):
+        raise ValueError(f"{who}: grad_div must be a device tensor of one float32")
+    return L.ptr(grad_div)
+
+
+def adamw_step_multi(segs, lr, step, sumsq=None, max_norm=0.0, beta1=0.9, beta2=0.95, eps=1e-8, prescale=1.0, guard=None, skipped=None, state=None,
+                     grad_div=None):
+    """One AdamW step over several flat fp32 buffers under one guard decision (avllm_adamw_step_multi).  segs: (p, g, m, v, weight_decay) each.
+    grad_div: a device float; the prescale is then 1 / grad_div, read on the device (avllm_adamw_step_multi_dev; `prescale` is not used)."""
     arr = (L.AdamwSeg * len(segs))()
     for a, (p, g, m, v, wd) in zip(arr, segs):
         a.p, a.g, a.m, a.v, a.n, a.weight_decay = L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), wd
+    if grad_div is not None:
+        L.check(L.load().avllm_adamw_step_multi_dev(arr, len(segs), lr, beta1, beta2, eps, step, L.ptr(sumsq), max_norm,
+                                                    _grad_div_ptr(grad_div, "adamw_step_multi"), L.ptr(guard), L.ptr(skipped), L.ptr(state),
+                                                    L.stream_ptr()))
+        return
     L.check(L.load().avllm_adamw_step_multi(arr, len(segs), lr, beta1, beta2, eps, step, L.ptr(sumsq), max_norm, prescale, L.ptr(guard),
                                             L.ptr(skipped), L.ptr(state), L.stream_ptr()))
 
@@ -789,9 +816,15 @@ def grad_sumsq(g, out, partials=None):
 
 
 def adamw_step(p, g, m, v, lr, step, sumsq=None, max_norm=0.0, beta1=0.9, beta2=0.95, eps=1e-8, wd=0.01, prescale=1.0, guard=None,
-               skipped=None, state=None):
+               skipped=None, state=None, grad_div=None):
     """guard: device float (e.g. the step's loss_sum); a non-finite guard or sumsq makes the launch a no-op and bumps `skipped`.
-    state: device avllm_step_state (uint8 tensor): lr and Adam's bias corrections are read from it instead of `lr` / `step`."""
+    state: device avllm_step_state (uint8 tensor): lr and Adam's bias corrections are read from it instead of `lr` / `step`.
+    grad_div: a device float; the prescale is then 1 / grad_div, read on the device (avllm_adamw_step_dev; `prescale` is not used)."""
+    if grad_div is not None:
+        L.check(L.load().avllm_adamw_step_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step, L.ptr(sumsq),
+                                              max_norm, _grad_div_ptr(grad_div, "adamw_step"), L.ptr(guard), L.ptr(skipped), L.ptr(state),
+                                              L.stream_ptr()))
+        return
     L.check(L.load().avllm_adamw_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step,
                                       L.ptr(sumsq), max_norm, prescale, L.ptr(guard), L.ptr(skipped), L.ptr(state), L.stream_ptr()))
 
@@ -1131,6 +1164,23 @@ def step_advance(state, base_lr, total_steps, warmup_steps=0, beta1=0.9, beta2=0
     """One-thread kernel: state.step += 1 and this step's lr / bias corrections / dropout seed (include/avllm.h avllm_step_state)."""
     sc = L.Schedule(base_lr, beta1, beta2, int(warmup_steps), int(total_steps), int(rank))
     L.check(L.load().avllm_step_advance(L.ptr(state), C.byref(sc), L.stream_ptr()))
+
+
+MICRO_SEED_STRIDE = 0xC2B2AE35          # AVLLM_MICRO_SEED_STRIDE of include/avllm.h
+
+
+def step_advance_micro(state, base_lr, total_steps, warmup_steps=0, beta1=0.9, beta2=0.95, rank=0):
+    """The micro-step form (avllm_step_advance_micro): advances the optimizer step only when the window's micro-step count (state.reserved[0])
+    is 0, gives every micro-step its own dropout seed, then counts the micro-step."""
+    sc = L.Schedule(base_lr, beta1, beta2, int(warmup_steps), int(total_steps), int(rank))
+    L.check(L.load().avllm_step_advance_micro(L.ptr(state), C.byref(sc), L.stream_ptr()))
+
+
+def window_add(window, acc, state):
+    """window [loss_sum, count] += acc, in a fixed order on the device; overwritten at the first micro-step of a window (avllm_window_add)."""
+    if window.dtype != torch.float32 or acc.dtype != torch.float32 or window.numel() != 2 or acc.numel() != 2:
+        raise ValueError("window_add: window and acc must be float32 tensors of two elements")
+    L.check(L.load().avllm_window_add(L.ptr(window), L.ptr(acc), L.ptr(state), L.stream_ptr()))
 
 
 def whisper_im2col1(mel, Kpad, dtype):

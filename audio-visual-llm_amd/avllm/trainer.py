@@ -14,6 +14,10 @@ seed) lives in a small device record advanced by a one-thread kernel at the top 
 signature into hipGraphs (torch.cuda.CUDAGraph owns capture + memory pool) and replayed: one graph when single-process; under data
 parallelism forward / backward pieces / optimizer are separate graphs with the RCCL collectives issued between them, each backward
 piece's gradient all-reduce running on the side stream under the next piece.
+
+grad_accum_steps = N > 1: a window of N calls of train_step() is ONE optimizer step on the concatenation of their micro-batches (token-mean loss
+over all scored tokens of the window on all ranks).  Micro-steps back-propagate the sum cross entropy and add into the gradient buffers; the
+closing part divides by the window's count on the device (DESIGN.md §4 "Gradient accumulation").  N = 1 is the step described above.
 """
 from __future__ import annotations
 
@@ -48,13 +52,18 @@ class ClipWhisperTrainer:
         self.last_video_info = None                        # (VideoAugment.last_info, the clips' frame counts) of the last augmented batch
         self.learning_rate, self.weight_decay, self.max_epochs = learning_rate, weight_decay, max_epochs
         self.output_dir, self.device, self.fp16 = output_dir, device, fp16
-        self.grad_accum_steps = grad_accum_steps           # stored but unused, as in the reference
+        # N micro-batches per optimizer step: a window of N calls of train_step() is ONE step on their concatenation (the reference stores the
+        # keyword and never reads it).  1 = every call is an optimizer step.
+        if isinstance(grad_accum_steps, bool) or not isinstance(grad_accum_steps, int) or grad_accum_steps < 1:
+            raise ValueError(f"grad_accum_steps must be an int >= 1, got {grad_accum_steps!r}")
+        self.grad_accum_steps = grad_accum_steps
+        self.micro_step = 0                                # micro-batches of the open window (host side; 0 .. N-1)
         self.log_interval, self.save_every, self.save_steps = log_interval, max(1, save_every or 1), save_steps
         self.grad_clip, self.warmup_steps = grad_clip, warmup_steps
         self.global_step = 0
         self.train_losses, self.val_losses, self.best_val_loss = [], [], float("inf")
-        if total_steps is None:
-            total_steps = max_epochs * (len(train_dataloader) if train_dataloader is not None else 1)
+        if total_steps is None:                            # optimizer steps: a partial last window of an epoch is one (flush())
+            total_steps = max_epochs * (-(-len(train_dataloader) // grad_accum_steps) if train_dataloader is not None else 1)
         self.total_steps = max(1, total_steps)
         eng = model.llm_engine
         self.m = torch.zeros_like(eng.lora_p)
@@ -80,6 +89,15 @@ class ClipWhisperTrainer:
         # data parallel + graphs: the backward pass is replayed in pieces so that a piece's gradient all-reduce overlaps the next piece
         self.bwd_pieces = max(1, min(eng.cfg.layers, bwd_pieces if bwd_pieces is not None else (4 if is_dist() else 1)))
         self._graphs = {}
+        if grad_accum_steps > 1:
+            # the window's [loss_sum, count] (avllm_window_add), the divisor 1.0 every micro-step back-propagates the SUM cross entropy with,
+            # this rank's mean loss of the last micro-batch and the global token-mean of the last closed window
+            self._window = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._one = torch.ones(1, dtype=torch.float32, device=dev)
+            self._micro_loss = torch.zeros((), dtype=torch.float32, device=dev)
+            self.window_loss = torch.zeros((), dtype=torch.float32, device=dev)
+            self._close_graph = None                       # None -> "warm" -> captured, as a signature's graphs
+            self._deferred_save = None                     # a checkpoint asked for mid-window, written when the window closes
 
     # ---- _setup_optimizer :171-232: AdamW(beta 0.9/0.95, eps 1e-8); cosine (with optional linear warmup)
     def lr_at(self, step):
@@ -91,9 +109,15 @@ class ClipWhisperTrainer:
         return self.learning_rate * (1 + math.cos(math.pi * step / self.total_steps)) / 2
 
     def augment_seed_at(self, step, rank=None):
-        """The seed of the augmentation draws for the batch of optimizer step `step` (the count of steps taken before it) on `rank`: by
-        value, so every rank and every step draws its own noise and masks, and a run repeats."""
+        """The seed of the augmentation draws for micro-batch number `step` (the count of micro-batches before it, _augment_index(); with
+        grad_accum_steps = 1 the count of optimizer steps taken before it) on `rank`: by value, so every rank and every micro-batch draws
+        its own noise and masks, and a run repeats."""
         return (self.augment_seed + 1000003 * int(step) + 7919 * (self._rank if rank is None else int(rank))) & 0xFFFFFFFF
+
+    def _augment_index(self):
+        """The number of the micro-batch about to be unpacked: optimizer steps taken * grad_accum_steps + the open window's micro-steps, so
+        the micro-batches of a window are not given the same noise and masks."""
+        return self.global_step * self.grad_accum_steps + self.micro_step
 
     def _augment_features(self, audio):
         """A batch of precomputed features has no waveform to mix noise into: it gets the SpecAugment half only, every frame counted as
@@ -105,7 +129,7 @@ class ClipWhisperTrainer:
             self._augment_notes.add("features")
             logging.info("audio_augment on precomputed features: SpecAugment only (valid = all frames); noise needs raw waveforms")
         audio = audio.to(self.model.device, torch.float32, copy=True).contiguous()
-        return aug.features(audio, None, self.augment_seed_at(self.global_step))
+        return aug.features(audio, None, self.augment_seed_at(self._augment_index()))
 
     def _augment_pixels(self, video):
         """A batch of precomputed pixel_values [B, F, 3, S, S] was resized and cropped by whoever made it: it gets the flip and the frame masks
@@ -118,7 +142,7 @@ class ClipWhisperTrainer:
             logging.info("video_augment on precomputed pixel_values: flip and frame masks only (all frames counted); the crop needs raw frames")
         dtype = video.dtype if video.dtype in (torch.float32, torch.bfloat16) else torch.float32      # the kernel moves fp32 or bf16 cells
         video = video.to(self.model.device, dtype, copy=True).contiguous()
-        aug.pixels(video, None, self.augment_seed_at(self.global_step))
+        aug.pixels(video, None, self.augment_seed_at(self._augment_index()))
         self.last_video_info = (aug.last_info, aug.last_frames)
         return video
 
@@ -132,7 +156,7 @@ class ClipWhisperTrainer:
                 self._featurizers = (WhisperLogMel(dev, n_mels=self.model.cfg.whisper.n_mels), ClipFrames(dev, image=self.model.cfg.clip.image))
             if (self.audio_augment is not None or self.video_augment is not None) and self.model.training:
                 audio, video = device_collate(batch["raw"], *self._featurizers, augment=self.audio_augment,
-                                              seed=self.augment_seed_at(self.global_step), video_augment=self.video_augment)
+                                              seed=self.augment_seed_at(self._augment_index()), video_augment=self.video_augment)
                 if audio is not None and self.audio_augment is not None and self.audio_augment.mixes:
                     self.last_augment_info = self.audio_augment.last_info
                 if video is not None and self.video_augment is not None:
@@ -215,6 +239,165 @@ class ClipWhisperTrainer:
         eng.pack_lora()
         torch.div(eng.acc[0], eng.acc[1], out=self._loss_buf)
 
+    # ---- grad_accum_steps > 1: the micro-step (forward, backward, accumulate) and the part that closes a window.  Neither depends on the
+    # micro-step's number: what differs between micro-steps is read from device memory (avllm_step_advance_micro, avllm_window_add), so ONE
+    # capture per input signature serves every position in a window and a window may mix signatures.
+    def _part_micro_fwd(self, audio, video, labels, prompt):
+        model, eng = self.model, self.model.llm_engine
+        ops.step_advance_micro(self.state, self.learning_rate, self.total_steps, self.warmup_steps, rank=self._rank)
+        labels = model._prep_labels(labels)
+        x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors, seed_dev=self._seed_ptr)
+        p = float(model.lora_dropout) if (model.training and model.use_lora and model.lora_dropout) else 0.0
+        eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr)
+        ops.window_add(self._window, eng.acc, self.state)
+        torch.div(eng.acc[0], eng.acc[1], out=self._micro_loss)
+
+    def _part_micro_bwd(self, i):
+        """Backward piece i of the SUM cross entropy (divisor 1.0, grad_scale 1): lora_g and conn_g are added to, never zeroed here."""
+        eng = self.model.llm_engine
+        hi, lo = self._piece_range(i)
+        if self.train_connectors and lo == 0:
+            eng.bwd(grad_scale=1.0, count=self._one, layer_hi=hi, layer_lo=lo, dx_embeds=self.model._dx_embeds_buffer())
+            self.model.connector_backward(accumulate=True)
+            return
+        eng.bwd(grad_scale=1.0, count=self._one, layer_hi=hi, layer_lo=lo)
+
+    def _part_close(self):
+        """One global norm over the window's gradient, one clip, one guard decision, one AdamW step: the gradient buffers hold SUMS over the
+        window's scored tokens and the optimizer divides by their (all-reduced) count, read from device memory.  The guard is the window's
+        loss sum: a non-finite value anywhere in the window skips the window once."""
+        eng = self.model.llm_engine
+        count, guard = self._window[1:2], self._window[0:1]
+        if self.train_connectors:
+            ops.grad_sumsq_multi([self.model.conn_g, eng.lora_g], self.sumsq, self._sumsq_parts)
+            segs = self._connector_segments() + [(eng.lora_p, eng.lora_g, self.m, self.v, self.weight_decay)]
+            ops.adamw_step_multi(segs, 0.0, 0, sumsq=self.sumsq, max_norm=self.grad_clip or 0.0, guard=guard, skipped=self.skipped,
+                                 state=self.state, grad_div=count)
+            eng.pack_lora()
+            self.model.refresh_connectors()
+        else:
+            ops.grad_sumsq(eng.lora_g, self.sumsq, partials=self._sumsq_parts)
+            ops.adamw_step(eng.lora_p, eng.lora_g, self.m, self.v, 0.0, 0, sumsq=self.sumsq, max_norm=self.grad_clip or 0.0, wd=self.weight_decay,
+                           guard=guard, skipped=self.skipped, state=self.state, grad_div=count)
+            eng.pack_lora()
+        torch.div(self._window[0], self._window[1], out=self.window_loss)
+
+    def _eager_micro(self, audio, video, labels, prompt, closing):
+        """The micro-step's launches; only the closing one issues collectives, one all-reduce per backward piece as in _eager_step, whether
+        graphs are on or off (a rank in eager and a rank in replay issue the same ones in the same order)."""
+        self._part_micro_fwd(audio, video, labels, prompt)
+        for i in range(self.bwd_pieces):
+            self._part_micro_bwd(i)
+            if closing:
+                hi, lo = self._piece_range(i)
+                self.reducer.layers_done(lo, hi)
+
+    def _replay_micro(self, st, closing):
+        if "all" in st:
+            st["all"].replay()
+            return
+        st["fwd"].replay()
+        for i, g in enumerate(st["bwd"]):
+            g.replay()
+            if closing:
+                hi, lo = self._piece_range(i)
+                self.reducer.layers_done(lo, hi)
+
+    def _close_window(self, use_graph, reduce_all=False):
+        """The rest of the window's collectives (the connector bucket, then the window's [loss_sum, count] once; reduce_all: a partial window
+        closed by flush() has not all-reduced its LoRA gradient piece by piece), then the closing part, warm -> capture -> replay."""
+        eng = self.model.llm_engine
+        if reduce_all:
+            self.reducer.bucket_done(eng.lora_g)
+        if self.train_connectors:
+            self.reducer.bucket_done(self.model.conn_g)
+        self.reducer.finish()
+        self.reducer.reduce_counts(self._window)
+        g = self._close_graph if use_graph else None
+        if use_graph:
+            if isinstance(g, tuple) and g[1] != Workspace.generation:
+                self._close_graph = g = None
+            if g is None:
+                self._close_graph = "warm"
+            elif g == "warm":
+                graph = torch.cuda.CUDAGraph()
+                torch.cuda.synchronize()
+                with torch.cuda.graph(graph, pool=torch.cuda.graph_pool_handle()):
+                    self._part_close()
+                self._close_graph = g = (graph, Workspace.generation)
+        if isinstance(g, tuple):
+            g[0].replay()
+        else:
+            self._part_close()
+        self.micro_step = 0
+        self.global_step += 1
+        if self._deferred_save is not None:
+            args, self._deferred_save = self._deferred_save, None
+            self._save_checkpoint(*args)
+
+    def _abandon_window(self):
+        """A micro-step raised half way (single process only): its launches may have added part of a gradient, so the open window is given
+        up -- the step its first advance started is taken back, the next call opens a new window that zeroes the sums.  One host sync, on an
+        error path.
+        Single process only: under data parallelism _train_epoch re-raises instead (the other ranks are inside the collectives), and nothing
+        here is agreed between ranks.  It assumes the window's closing launch has NOT run: that launch resets the micro-step count itself and,
+        on a skipped window, has already taken the step back; with the count at 0 this function therefore leaves the device state alone, and
+        it must not be called on a window that has closed."""
+        words = self.state.view(torch.int32)
+        if int(words[6]) > 0:
+            words[0] -= 1
+            words[6] = 0
+        dropped, self.micro_step = self.micro_step, 0
+        return dropped
+
+    def flush(self):
+        """Close a partial window: one optimizer step on the micro-batches accumulated so far.  Does nothing (and returns None) when nothing
+        is pending; otherwise returns the window's loss.  Under data parallelism every rank must call it at the same point."""
+        if self.grad_accum_steps == 1 or self.micro_step == 0:
+            return None
+        self._close_window(self.use_graph, reduce_all=True)
+        return self.window_loss.clone()
+
+    def window_gradients(self):
+        """{"lora_g": ..., "conn_g": ... (None unless the connectors train)}: clones of the gradient of the last closed window's loss -- the
+        token-mean cross entropy over all its scored tokens on all ranks -- before clipping.
+        With grad_accum_steps > 1 the raw buffers (llm_engine.lora_g, model.conn_g) hold something else: the SUM over the window's scored
+        tokens of the per-token gradients, on this rank until the closing micro-step's all-reduce and over all ranks after it; the optimizer
+        divides by the window's count on the fly and never writes the quotient back.  They hold it from the closing micro-step (or flush())
+        until the first micro-step of the next window zeroes them; in between -- mid-window -- they hold that window's partial sums and this
+        method's result is not a gradient of anything.  With grad_accum_steps = 1 the buffers hold the batch's mean gradient itself."""
+        eng = self.model.llm_engine
+        gs = {"lora_g": eng.lora_g.clone(), "conn_g": self.model.conn_g.clone() if self.train_connectors else None}
+        if self.grad_accum_steps > 1:
+            inv = torch.where(self._window[1] > 0, 1.0 / self._window[1], torch.zeros_like(self._window[1]))
+            for g in gs.values():
+                if g is not None:
+                    g.mul_(inv)
+        return gs
+
+    def _micro_train_step(self, audio, video, labels, prompt, use_graph):
+        """train_step() with grad_accum_steps = N > 1: one micro-step; the N-th closes the window."""
+        eng = self.model.llm_engine
+        closing = self.micro_step == self.grad_accum_steps - 1
+        if self.micro_step == 0:                         # a new window: the gradient sums start from zero (the temporaries da / dv / dx_embeds
+            eng.lora_g.zero_()                           # are per micro-step anyway)
+            if self.train_connectors:
+                self.model.conn_g.zero_()
+        st = self._graph_state(audio, video, labels, prompt, micro=True) if use_graph else None
+        if isinstance(st, dict):
+            for dst, src in zip(st["inputs"], (audio, video, labels, prompt)):
+                if dst is not None and src.data_ptr() != dst.data_ptr():
+                    dst.copy_(src, non_blocking=True)
+            self._replay_micro(st, closing)
+            self.model.last_modality_modes = st["modes"]
+        else:
+            self._eager_micro(audio, video, labels, prompt, closing)
+        loss = self._micro_loss.clone()
+        self.micro_step += 1
+        if closing:
+            self._close_window(use_graph)
+        return loss
+
     def _eager_step(self, audio, video, labels, prompt):
         eng = self.model.llm_engine
         self._part_fwd(audio, video, labels, prompt)
@@ -240,9 +423,11 @@ class ClipWhisperTrainer:
         self.reducer.finish()
         self._part_opt()
 
-    def _capture(self, audio, video, labels, prompt):
+    def _capture(self, audio, video, labels, prompt, micro=False):
         """Capture the step for this input signature.  Static input buffers are allocated here (the caller's tensors are copied into
-        them before every replay -- or ARE them, see static_inputs())."""
+        them before every replay -- or ARE them, see static_inputs()).  micro: the micro-step of a gradient-accumulation window instead
+        (forward, backward pieces, accumulate; no optimizer part -- _close_window has its own graph)."""
+        fwd, bwd = (self._part_micro_fwd, self._part_micro_bwd) if micro else (self._part_fwd, self._part_bwd)
         dev = self.model.llm_engine.lora_p.device
         st = {"inputs": [None if t is None else torch.empty(t.shape, dtype=t.dtype, device=dev) for t in (audio, video, labels, prompt)]}
         for dst, src in zip(st["inputs"], (audio, video, labels, prompt)):
@@ -255,24 +440,26 @@ class ClipWhisperTrainer:
         if not self.reducer.enabled:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool):
-                self._part_fwd(a, v, lab, pr)
+                fwd(a, v, lab, pr)
                 for i in range(self.bwd_pieces):
-                    self._part_bwd(i)
-                self._part_opt()
+                    bwd(i)
+                if not micro:
+                    self._part_opt()
             st["all"] = g
         else:
             st["fwd"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(st["fwd"], pool=pool):
-                self._part_fwd(a, v, lab, pr)
+                fwd(a, v, lab, pr)
             st["bwd"] = []
             for i in range(self.bwd_pieces):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool):
-                    self._part_bwd(i)
+                    bwd(i)
                 st["bwd"].append(g)
-            st["opt"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(st["opt"], pool=pool):
-                self._part_opt()
+            if not micro:
+                st["opt"] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(st["opt"], pool=pool):
+                    self._part_opt()
         st["modes"] = self.model.last_modality_modes          # the static mode buffer this signature's graph writes (None without modes)
         return st
 
@@ -302,28 +489,37 @@ class ClipWhisperTrainer:
     def _signature(*tensors):
         return tuple(None if t is None else (tuple(t.shape), t.dtype) for t in tensors)
 
+    def _graph_state(self, audio, video, labels, prompt, micro=False):
+        """The captured graphs of this input signature, or the reason this call runs eager ("warm", "stale", None): warm -> capture ->
+        replay, at most 4 signatures."""
+        key = self._signature(audio, video, labels, prompt)
+        st = self._graphs.get(key)
+        if isinstance(st, dict) and st["generation"] != Workspace.generation:
+            # some workspace was reallocated since capture (a larger batch / more frames / generate() in between): every captured
+            # graph may point into freed memory.  Drop them all; each signature is re-captured at its next-but-one visit.
+            self._graphs = {k: "warm" for k in self._graphs}
+            st = "stale"                             # this call runs eager and re-sizes nothing (workspaces only grow)
+        if st is None and len(self._graphs) < 4:
+            self._graphs[key] = st = "warm"          # first sight of a signature: eager (sizes every workspace); captured at the second
+        elif st == "warm":
+            self._graphs[key] = st = self._capture(audio, video, labels, prompt, micro=micro)
+            if st["generation"] != Workspace.generation:         # cannot happen (Workspace.get refuses to grow under capture); belt and braces
+                self._graphs[key] = st = "warm"
+        return st
+
     def train_step(self, audio, video, labels, prompt, graph=None):
         """One optimizer step on this rank's batch; returns the (global) mean loss as a device scalar.
-        graph=False forces the eager launch sequence for this call (bench.py's instrumented steps)."""
+        graph=False forces the eager launch sequence for this call (bench.py's instrumented steps).
+        With grad_accum_steps = N > 1 a call is a micro-step: forward, backward, accumulate, and it returns THIS rank's mean loss of the
+        micro-batch; every N-th call (micro_step N-1) also closes the window -- one optimizer step on the concatenation of its N
+        micro-batches over all ranks -- after which global_step is one higher and window_loss holds the window's global token-mean."""
         use_graph = self.use_graph if graph is None else (graph and self.use_graph)
-        self.global_step += 1
         if isinstance(labels, list):
             labels = self.model._prep_labels(labels).cpu()
-        st = None
-        if use_graph:
-            key = self._signature(audio, video, labels, prompt)
-            st = self._graphs.get(key)
-            if isinstance(st, dict) and st["generation"] != Workspace.generation:
-                # some workspace was reallocated since capture (a larger batch / more frames / generate() in between): every captured
-                # graph may point into freed memory.  Drop them all; each signature is re-captured at its next-but-one visit.
-                self._graphs = {k: "warm" for k in self._graphs}
-                st = "stale"                             # this call runs eager and re-sizes nothing (workspaces only grow)
-            if st is None and len(self._graphs) < 4:
-                self._graphs[key] = st = "warm"          # first sight of a signature: eager (sizes every workspace); captured at the second
-            elif st == "warm":
-                self._graphs[key] = st = self._capture(audio, video, labels, prompt)
-                if st["generation"] != Workspace.generation:         # cannot happen (Workspace.get refuses to grow under capture); belt and braces
-                    self._graphs[key] = st = "warm"
+        if self.grad_accum_steps > 1:
+            return self._micro_train_step(audio, video, labels, prompt, use_graph)
+        self.global_step += 1
+        st = self._graph_state(audio, video, labels, prompt) if use_graph else None
         if isinstance(st, dict):
             for dst, src in zip(st["inputs"], (audio, video, labels, prompt)):
                 if dst is not None and src.data_ptr() != dst.data_ptr():
@@ -340,7 +536,12 @@ class ClipWhisperTrainer:
 
     def _sync_step(self):
         """global_step := the optimizer steps actually taken (device-side count: skipped steps do not advance it).  One host sync; called
-        where the host already waits for the device (log interval, checkpoint)."""
+        where the host already waits for the device (log interval, checkpoint).  Mid-window (grad_accum_steps > 1) the device count already
+        includes the step the open window will take (avllm_step_advance_micro advances it at micro-step 0): that one is not counted."""
+        if self.grad_accum_steps > 1:
+            words = self.state.view(torch.int32).cpu()
+            self.global_step = int(words[0]) - (1 if int(words[6]) > 0 else 0)          # words[6]: reserved[0], the open window's micro-steps
+            return self.global_step
         self.global_step = int(self.state.view(torch.int32)[0].item())
         return self.global_step
 
@@ -358,6 +559,46 @@ class ClipWhisperTrainer:
         total, n, t0 = 0.0, 0, time.time()
         pending, pending_modes, pending_noise, pending_video = [], [], [], []
         failures = unstable = worst = 0
+        accum, windows = self.grad_accum_steps > 1, 0
+
+        def examine(i):
+            """Read the pending losses (one host sync), count them, apply the unstable-streak rule and log.  True: stop the epoch."""
+            nonlocal total, n, unstable, worst
+            vals = torch.stack(pending).float().cpu()
+            pending.clear()
+            self._sync_step()
+            fin = torch.isfinite(vals)
+            ok = vals[fin]
+            total += float(ok.sum()); n += int(ok.numel())
+            # trainer :444-452: a NaN loss skips the batch; more than 5 unstable batches in a row stop the epoch.  The losses stay on
+            # the device between log intervals (no per-step host sync), so the streak is examined here, over the interval just read.
+            for f in fin.tolist():
+                unstable = 0 if f else unstable + 1
+                worst = max(worst, unstable)
+            if not bool(fin.all()):
+                logging.warning(f"NaN loss detected in {int((~fin).sum())} {'window(s)' if accum else 'batch(es)'} up to batch {i}; {self.skipped_steps} optimizer step(s) skipped so far")
+            if worst > 5:
+                logging.error("Too many unstable batches. Stopping epoch.")
+                return True
+            what = f"window {windows} (batch {i + 1}/{len(self.train_dataloader)})" if accum else f"batch {i + 1}/{len(self.train_dataloader)}"
+            where = f"window {windows}" if accum else f"batch {i + 1}"          # the shares below cover every micro-batch since the last look
+            logging.info(f"epoch {epoch} {what} loss {float(vals[-1]):.4f} "
+                         f"avg {total / max(1, n):.4f} lr {self.lr_at(self.global_step):.3e} {(time.time() - t0) / (i + 1):.3f}s/it")
+            if pending_modes:
+                share = self.mode_shares(torch.cat(pending_modes).cpu())
+                pending_modes.clear()
+                logging.info(f"epoch {epoch} {where}: clips with both streams {share[0]:.3f}, audio only {share[1]:.3f}, video only {share[2]:.3f}")
+            if pending_noise:
+                share, snr = self.noise_shares(torch.cat(pending_noise).cpu())
+                pending_noise.clear()
+                logging.info(f"epoch {epoch} {where}: clips with noise mixed in {share:.3f}, their mean SNR {snr:.2f} dB")
+            if pending_video:
+                flipped, masked = self.video_shares(torch.cat([v[0] for v in pending_video]).cpu(),
+                                                    [n for v in pending_video for n in (v[1].tolist() if torch.is_tensor(v[1]) else v[1])])
+                pending_video.clear()
+                logging.info(f"epoch {epoch} {where}: clips flipped {flipped:.3f}, mean share of frames masked {masked:.3f}")
+            return False
+
         for i, batch in enumerate(self.train_dataloader):
             # the reference logs and skips a batch on ANY exception (:492-507).  Host-side preparation (everything before the first
             # collective) is where data errors surface; under DDP the skip is agreed between ranks first.
@@ -379,50 +620,43 @@ class ClipWhisperTrainer:
                 if is_dist():
                     raise                                        # mid-step: the other ranks are already inside the collectives
                 logging.error(f"Error in batch {i}: {e}")
+                if accum:
+                    logging.error(f"the open window is abandoned with {self._abandon_window()} micro-batch(es) in it")
                 failures += 1
                 if failures > 5:
                     raise RuntimeError("more than 5 consecutive batches failed") from e
                 continue
             failures = 0
-            pending.append(loss)
+            if accum:
+                # the loss that is logged and examined is the WINDOW's (the 5-in-a-row rule counts windows); a partial last window of the
+                # epoch is closed here, so no gradient leaks into the next epoch and no micro-batch is dropped
+                if i + 1 == len(self.train_dataloader):
+                    self.flush()
+                if self.micro_step == 0:
+                    windows += 1
+                    pending.append(self.window_loss.clone())
+            else:
+                pending.append(loss)
             if self.model.last_modality_modes is not None:       # stays on the device until the log interval, like the loss
                 pending_modes.append(self.model.last_modality_modes.clone())
             if self.last_augment_info is not None:               # a tensor of its own per batch: kept, not copied
                 pending_noise.append(self.last_augment_info)
             if self.last_video_info is not None:
                 pending_video.append(self.last_video_info)
-            if (i + 1) % self.log_interval == 0 or i + 1 == len(self.train_dataloader):
-                vals = torch.stack(pending).float().cpu()
-                pending.clear()
-                self._sync_step()
-                fin = torch.isfinite(vals)
-                ok = vals[fin]
-                total += float(ok.sum()); n += int(ok.numel())
-                # trainer :444-452: a NaN loss skips the batch; more than 5 unstable batches in a row stop the epoch.  The losses stay on
-                # the device between log intervals (no per-step host sync), so the streak is examined here, over the interval just read.
-                for f in fin.tolist():
-                    unstable = 0 if f else unstable + 1
-                    worst = max(worst, unstable)
-                if not bool(fin.all()):
-                    logging.warning(f"NaN loss detected in {int((~fin).sum())} batch(es) up to batch {i}; {self.skipped_steps} optimizer step(s) skipped so far")
-                if worst > 5:
-                    logging.error("Too many unstable batches. Stopping epoch.")
-                    break
-                logging.info(f"epoch {epoch} batch {i + 1}/{len(self.train_dataloader)} loss {float(vals[-1]):.4f} "
-                             f"avg {total / max(1, n):.4f} lr {self.lr_at(self.global_step):.3e} {(time.time() - t0) / (i + 1):.3f}s/it")
-                if pending_modes:
-                    share = self.mode_shares(torch.cat(pending_modes).cpu())
-                    pending_modes.clear()
-                    logging.info(f"epoch {epoch} batch {i + 1}: clips with both streams {share[0]:.3f}, audio only {share[1]:.3f}, video only {share[2]:.3f}")
-                if pending_noise:
-                    share, snr = self.noise_shares(torch.cat(pending_noise).cpu())
-                    pending_noise.clear()
-                    logging.info(f"epoch {epoch} batch {i + 1}: clips with noise mixed in {share:.3f}, their mean SNR {snr:.2f} dB")
-                if pending_video:
-                    flipped, masked = self.video_shares(torch.cat([v[0] for v in pending_video]).cpu(),
-                                                        [n for v in pending_video for n in (v[1].tolist() if torch.is_tensor(v[1]) else v[1])])
-                    pending_video.clear()
-                    logging.info(f"epoch {epoch} batch {i + 1}: clips flipped {flipped:.3f}, mean share of frames masked {masked:.3f}")
+            if accum:                                            # log_interval counts optimizer steps: look when a window has just closed
+                due = bool(pending) and ((self.micro_step == 0 and windows % self.log_interval == 0) or i + 1 == len(self.train_dataloader))
+            else:
+                due = (i + 1) % self.log_interval == 0 or i + 1 == len(self.train_dataloader)
+            if due and examine(i):
+                break
+        if accum and (self.micro_step > 0 or pending):
+            # the epoch ended on a batch that was skipped: the open window still becomes a step (every rank takes this path alike: skips are
+            # agreed between ranks), and it is examined, counted and logged like every other window
+            if self.micro_step > 0:
+                self.flush()
+                windows += 1
+                pending.append(self.window_loss.clone())
+            examine(i)
         return total / max(1, n)
 
     @staticmethod
@@ -477,6 +711,11 @@ class ClipWhisperTrainer:
         names: decode.py:236-260 extracts the connectors by substring); the frozen encoders / LLM the reference also dumps into every
         checkpoint (13.5 GB for a 7B LLM) are not repeated -- they are the checkpoints the model was built from.  optimizer_state_dict /
         scheduler_state_dict follow torch.optim.AdamW / CosineAnnealingLR's own layout for the LoRA parameters, in optimizer index order."""
+        if self.grad_accum_steps > 1 and self.micro_step > 0:
+            # checkpoints are written at window boundaries only (the file has no place for half a window's gradient sums): a save asked for
+            # mid-window, on every rank alike, waits for the closing micro-step or flush()
+            self._deferred_save = (epoch, name)
+            return
         if is_dist() and torch.distributed.get_rank() != 0:
             return
         os.makedirs(self.output_dir, exist_ok=True)
@@ -507,7 +746,7 @@ class ClipWhisperTrainer:
                     "scheduler_state_dict": {"T_max": self.total_steps, "eta_min": 0.0, "base_lrs": [self.learning_rate], "last_epoch": self.global_step,
                                              "_step_count": self.global_step + 1, "_last_lr": [self.lr_at(self.global_step)]},
                     "train_losses": self.train_losses, "val_losses": self.val_losses, "best_val_loss": self.best_val_loss}, path)
-        json.dump({"epoch": epoch, "global_step": self.global_step, "best_val_loss": self.best_val_loss,
+        json.dump({"epoch": epoch, "global_step": self.global_step, "best_val_loss": self.best_val_loss, "grad_accum_steps": self.grad_accum_steps,
                    "lora_target_modules": list(self.model.lora_target_modules) if self.model.use_lora else None},
                   open(path.replace(".pt", "_meta.json"), "w"))
 
@@ -567,6 +806,9 @@ class ClipWhisperTrainer:
         if step is not None:
             self.global_step = step
             self.state.view(torch.int32)[0] = step                 # the device-side step count drives lr / bias corrections / seeds
+        if self.grad_accum_steps > 1:                            # a checkpoint is a window boundary: training resumes at micro-step 0
+            self.micro_step, self._deferred_save = 0, None
+            self.state.view(torch.int32)[6] = 0
         self.train_losses, self.val_losses = list(ck.get("train_losses", [])), list(ck.get("val_losses", []))
         self.best_val_loss = ck.get("best_val_loss", float("inf"))
         return ck.get("epoch", 0)

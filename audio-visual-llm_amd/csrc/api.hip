@@ -201,6 +201,20 @@ int avllm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 }
 int avllm_act_residual(const void* x, const void* r, void* y, int64_t n, int32_t act, int32_t dtype, void* stream) { return av_act_residual(x, r, y, n, act, dtype, ST); }
 int avllm_step_advance(avllm_step_state* state, const avllm_schedule* sched, void* stream) { return av_step_advance(state, sched, ST); }
+int avllm_gemm_wgrad_acc(const void* dY, int64_t ldy, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, float* dW, int64_t ldw, float* db,
+                         float alpha, int32_t dtype, void* stream) { return av_gemm_wgrad_acc(dY, ldy, X, ldx, M, N, K, dW, ldw, db, alpha, dtype, ST); }
+int avllm_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                         int32_t step, const float* sumsq, float max_norm, const float* grad_div_dev, const float* guard, float* skipped,
+                         const avllm_step_state* state, void* stream) {
+    return av_adamw_step_dev(p, g, m, v, n, lr, b1, b2, eps, wd, step, sumsq, max_norm, grad_div_dev, guard, skipped, state, ST);
+}
+int avllm_adamw_step_multi_dev(const avllm_adamw_seg* segs, int32_t nseg, float lr, float b1, float b2, float eps, int32_t step, const float* sumsq,
+                               float max_norm, const float* grad_div_dev, const float* guard, float* skipped, const avllm_step_state* state,
+                               void* stream) {
+    return av_adamw_step_multi_dev(segs, nseg, lr, b1, b2, eps, step, sumsq, max_norm, grad_div_dev, guard, skipped, state, ST);
+}
+int avllm_step_advance_micro(avllm_step_state* state, const avllm_schedule* sched, void* stream) { return av_step_advance_micro(state, sched, ST); }
+int avllm_window_add(float* window, const float* acc, const avllm_step_state* state, void* stream) { return av_window_add(window, acc, state, ST); }
 int avllm_lora_pack(const float* A, const float* Bm, int32_t r, int32_t din, int32_t dout, void* A_pad, void* AT_pad, int64_t ld_at,
                     void* B_pad, void* BT_pad, int32_t dtype, void* stream) { return av_lora_pack(A, Bm, r, din, dout, A_pad, AT_pad, ld_at, B_pad, BT_pad, dtype, ST); }
 int avllm_lora_merge(void* W, int64_t ldw, int32_t N, int32_t K, const float* A, const float* B, int32_t r, float scale, int32_t dtype,

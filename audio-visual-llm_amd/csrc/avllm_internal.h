@@ -79,6 +79,16 @@ int av_modality_draw(const int* mode_in, int* mode_out, int B, float p_drop_audi
                      hipStream_t st);
 int av_gemm_wgrad(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
                   hipStream_t st);
+int av_gemm_wgrad_acc(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
+                      hipStream_t st);
+int av_adamw_step_dev(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                      float wd, int step, const float* sumsq, float max_norm, const float* grad_div_dev, const float* guard, float* skipped,
+                      const avllm_step_state* state, hipStream_t st);
+int av_adamw_step_multi_dev(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq,
+                            float max_norm, const float* grad_div_dev, const float* guard, float* skipped, const avllm_step_state* state,
+                            hipStream_t st);
+int av_step_advance_micro(avllm_step_state* state, const avllm_schedule* sched, hipStream_t st);
+int av_window_add(float* window, const float* acc, const avllm_step_state* state, hipStream_t st);
 int av_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int nbuf, float* partials, int nparts, float* sumsq, hipStream_t st);
 int av_adamw_step_multi(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq, float max_norm,
                         float grad_prescale, const float* guard, float* skipped, const avllm_step_state* state, hipStream_t st);

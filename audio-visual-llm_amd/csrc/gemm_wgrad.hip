@@ -22,12 +22,24 @@ __device__ __forceinline__ bf16x8 tr_frag16(const char* img, int stride, int row
     return __builtin_bit_cast(bf16x8, both);
 }
 
+// The epilogue's value: alpha * acc, rounded, and with ACC the cell's prior value added to it in a second rounding (the pragma keeps the compiler
+// from contracting the two into one fma: onto a prior 0 the result is then the overwriting form's bits for every input).
+template <bool ACC> __device__ __forceinline__ void wgrad_store(float* cell, float alpha, float acc) {
+#pragma clang fp contract(off)
+    const float r = alpha * acc;
+    *cell = ACC ? *cell + r : r;
+}
+
 constexpr int WG_T = 128, WG_M = 64;          // output tile 128 (n) x 128 (k); 64 rows of m per slab
 constexpr int WG_STRIDE = WG_T * 2 + 64;      // 320 B: the 4 rows of a transposed read land on distinct bank quarters (gemm_tn.hip)
 constexpr int WG_CHUNKS = WG_M * (WG_T / 8) / 256;       // 4 16-byte chunks of each operand per thread and slab
 
 // 4 waves as 2 (n) x 2 (k), 64 x 64 outputs each = 4 x 4 MFMA tiles.  Ragged edges: rows m >= M and chunks past N / K are zero-filled
 // (N, K multiples of 8: a chunk is in or out as a whole), stores past N / K are dropped.
+// ACC (avllm_gemm_wgrad_acc): the epilogue adds the cell's prior value, read once after the K-loop through the same address the store uses
+// (16 lanes x 4 B contiguous per row, 4 rows per instruction: the 64-byte segments the store already writes), in fp32, after the product with
+// alpha.  The tile's owner is still one workgroup for the whole of M, so the sum needs no atomics.
+template <bool ACC>
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const bf16* __restrict__ dY, long ldy, const bf16* __restrict__ X, long ldx, int M,
                                                          int N, int K, float* __restrict__ dW, long ldw, float alpha) {
     __shared__ __attribute__((aligned(16))) char ys[WG_M * WG_STRIDE];
@@ -87,12 +99,13 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const bf16* __restrict_
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int n = n0 + wn + 16 * x + fq * 4 + i;
-                if (n < N && k < K) dW[(long)n * ldw + k] = alpha * acc[x][y][i];
+                if (n < N && k < K) wgrad_store<ACC>(dW + (long)n * ldw + k, alpha, acc[x][y][i]);
             }
         }
 }
 
 // fp32 (parity mode): 64 x 64 outputs per block, 4 x 4 per thread, plain fp32 FMAs in ascending m
+template <bool ACC>
 __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict__ dY, long ldy, const float* __restrict__ X, long ldx, int M, int N,
                                                         int K, float* __restrict__ dW, long ldw, float alpha) {
     __shared__ float Ys[32][65], Xs[32][65];
@@ -123,13 +136,13 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(const float* __restrict_
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
             const int n = n0 + tn * 4 + x, k = k0 + tk * 4 + y;
-            if (n < N && k < K) dW[(long)n * ldw + k] = alpha * acc[x][y];
+            if (n < N && k < K) wgrad_store<ACC>(dW + (long)n * ldw + k, alpha, acc[x][y]);
         }
 }
 
 // db[n] = alpha * sum_m dY[m,n]: a block owns 64 columns (8 chunks of 8) for the whole of M; 32 row groups each add their rows m = g, g + 32, ...
 // in ascending order, then one thread per column adds the 32 partials in group order.
-template <typename T>
+template <typename T, bool ACC>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ dY, long ldy, int M, int N, float* __restrict__ db, float alpha) {
     __shared__ float part[32][65];
     const int ch = threadIdx.x & 7, rg = threadIdx.x >> 3;
@@ -147,29 +160,40 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ dY, l
     if (threadIdx.x < 64 && blockIdx.x * 64 + (int)threadIdx.x < N) {
         float t = 0.f;
         for (int g = 0; g < 32; ++g) t += part[g][threadIdx.x];
-        db[blockIdx.x * 64 + threadIdx.x] = alpha * t;
+        wgrad_store<ACC>(db + blockIdx.x * 64 + threadIdx.x, alpha, t);
     }
 }
 
 }  // namespace
 
-int av_gemm_wgrad(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
-                  hipStream_t st) {
+template <bool ACC>
+static int wgrad_launch(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
+                        hipStream_t st) {
     AV_CHECK_ARG(dY && X && dW && M >= 1 && N >= 1 && K >= 1, "gemm_wgrad: null / empty (M=%d N=%d K=%d)", M, N, K);
     AV_CHECK_ARG(dtype == AV_F32 || dtype == AV_BF16, "gemm_wgrad: dtype %d", dtype);
     AV_CHECK_ARG(N % 8 == 0 && K % 8 == 0 && ldy % 8 == 0 && ldx % 8 == 0 && ldy >= N && ldx >= K && ldw >= K,
                  "gemm_wgrad: N=%d K=%d ldy=%ld ldx=%ld must be multiples of 8 (16-byte operand chunks), ldw=%ld >= K", N, K, ldy, ldx, ldw);
     AV_CHECK_ARG((((uintptr_t)dY | (uintptr_t)X) & 15) == 0, "gemm_wgrad: dY and X must be 16-byte aligned (the operands are read as 16-byte chunks)");
     if (dtype == AV_BF16)
-        hipLaunchKernelGGL(wgrad_bf16_kernel, dim3(av_cdiv(N, WG_T), av_cdiv(K, WG_T)), dim3(256), 0, st, (const bf16*)dY, ldy, (const bf16*)X, ldx, M,
-                           N, K, dW, ldw, alpha);
+        hipLaunchKernelGGL(wgrad_bf16_kernel<ACC>, dim3(av_cdiv(N, WG_T), av_cdiv(K, WG_T)), dim3(256), 0, st, (const bf16*)dY, ldy, (const bf16*)X, ldx,
+                           M, N, K, dW, ldw, alpha);
     else
-        hipLaunchKernelGGL(wgrad_f32_kernel, dim3(av_cdiv(N, 64), av_cdiv(K, 64)), dim3(256), 0, st, (const float*)dY, ldy, (const float*)X, ldx, M, N,
-                           K, dW, ldw, alpha);
+        hipLaunchKernelGGL(wgrad_f32_kernel<ACC>, dim3(av_cdiv(N, 64), av_cdiv(K, 64)), dim3(256), 0, st, (const float*)dY, ldy, (const float*)X, ldx, M,
+                           N, K, dW, ldw, alpha);
     if (db) {
-        if (dtype == AV_BF16) hipLaunchKernelGGL((colsum_kernel<bf16>), dim3(av_cdiv(N, 64)), dim3(256), 0, st, (const bf16*)dY, ldy, M, N, db, alpha);
-        else hipLaunchKernelGGL((colsum_kernel<float>), dim3(av_cdiv(N, 64)), dim3(256), 0, st, (const float*)dY, ldy, M, N, db, alpha);
+        if (dtype == AV_BF16) hipLaunchKernelGGL((colsum_kernel<bf16, ACC>), dim3(av_cdiv(N, 64)), dim3(256), 0, st, (const bf16*)dY, ldy, M, N, db, alpha);
+        else hipLaunchKernelGGL((colsum_kernel<float, ACC>), dim3(av_cdiv(N, 64)), dim3(256), 0, st, (const float*)dY, ldy, M, N, db, alpha);
     }
     AV_LAUNCH_CHECK();
     return AV_OK;
+}
+
+int av_gemm_wgrad(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
+                  hipStream_t st) {
+    return wgrad_launch<false>(dY, ldy, X, ldx, M, N, K, dW, ldw, db, alpha, dtype, st);
+}
+
+int av_gemm_wgrad_acc(const void* dY, long ldy, const void* X, long ldx, int M, int N, int K, float* dW, long ldw, float* db, float alpha, int dtype,
+                      hipStream_t st) {
+    return wgrad_launch<true>(dY, ldy, X, ldx, M, N, K, dW, ldw, db, alpha, dtype, st);
 }

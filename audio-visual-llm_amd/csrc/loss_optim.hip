@@ -147,12 +147,23 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restric
     if (threadIdx.x == 0) out[0] = s;
 }
 
+// The closing launch of a gradient-accumulation window (avllm_adamw_step_dev / _multi_dev): the gradient prescale is 1 / *grad_div -- the
+// window's count of scored tokens, in device memory -- by IEEE division, 0 where the count is 0 (a window without a scored token: zero
+// gradient, step taken), and thread (0, 0) sets the window's micro-step count (state->reserved[0], avllm_step_advance_micro) back to 0, on a
+// taken and on a skipped window alike.  Nobody reads that word in this launch.
+__device__ __forceinline__ float adamw_window_prescale(const float* __restrict__ grad_div, avllm_step_state* __restrict__ state) {
+    if (state && blockIdx.x == 0 && threadIdx.x == 0) state->reserved[0] = 0u;
+    const float d = grad_div[0];
+    return d > 0.f ? __fdiv_rn(1.0f, d) : 0.f;
+}
+
 // torch.optim.AdamW single-tensor rule (decoupled decay first), preceded by clip_grad_norm_'s scaling
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                              float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
                              const float* __restrict__ sumsq, float max_norm, float prescale, const float* __restrict__ guard,
-                             float* __restrict__ skipped, avllm_step_state* __restrict__ state) {
+                             float* __restrict__ skipped, avllm_step_state* __restrict__ state, const float* __restrict__ grad_div) {
     if (state) { lr = state->lr; bc1 = state->bc1; bc2_sqrt = state->bc2_sqrt; }     // graph-replayable step: per-step scalars live on the device
+    if (grad_div) prescale = adamw_window_prescale(grad_div, state);
     // Non-finite step guard (trainer/clip_whisper_trainer.py:444-452 skips backward and the optimizer on a NaN/Inf loss): decided on the
     // device from values every thread reads alike, so the step costs no host sync and p, m, v stay untouched when it is skipped.
     const bool bad = (sumsq && !isfinite(sumsq[0])) || (guard && !isfinite(guard[0]));
@@ -189,8 +200,9 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 struct AdamSegs { avllm_adamw_seg s[8]; int first[9]; int nseg; };
 __global__ void adamw_multi_kernel(AdamSegs segs, float lr, float b1, float b2, float eps, float bc1, float bc2_sqrt,
                                    const float* __restrict__ sumsq, float max_norm, float prescale, const float* __restrict__ guard,
-                                   float* __restrict__ skipped, avllm_step_state* __restrict__ state) {
+                                   float* __restrict__ skipped, avllm_step_state* __restrict__ state, const float* __restrict__ grad_div) {
     if (state) { lr = state->lr; bc1 = state->bc1; bc2_sqrt = state->bc2_sqrt; }
+    if (grad_div) prescale = adamw_window_prescale(grad_div, state);
     const bool bad = (sumsq && !isfinite(sumsq[0])) || (guard && !isfinite(guard[0]));
     if (bad) {
         if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -312,18 +324,31 @@ int av_grad_sumsq_det(const float* g, long n, float* partials, int nparts, float
     return AV_OK;
 }
 
-int av_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-                  float wd, int step, const float* sumsq, float max_norm, float grad_prescale, const float* guard, float* skipped,
-                  const avllm_step_state* state, hipStream_t st) {
+static int adamw_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                        float wd, int step, const float* sumsq, float max_norm, float grad_prescale, const float* grad_div, const float* guard,
+                        float* skipped, const avllm_step_state* state, hipStream_t st) {
     AV_CHECK_ARG(p && g && m && v && n > 0 && (step >= 1 || state), "adamw: bad args");
     if (step < 1) step = 1;
     const float bc1 = 1.0f - (float)pow((double)b1, step);
     const float bc2s = (float)sqrt(1.0 - pow((double)b2, step));
     long blocks = (n + 255) / 256;
     blocks = blocks > 4096 ? 4096 : blocks;
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, sumsq, max_norm, grad_prescale, guard, skipped, (avllm_step_state*)state);
+    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, sumsq, max_norm, grad_prescale, guard, skipped, (avllm_step_state*)state, grad_div);
     AV_LAUNCH_CHECK();
     return AV_OK;
+}
+
+int av_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                  float wd, int step, const float* sumsq, float max_norm, float grad_prescale, const float* guard, float* skipped,
+                  const avllm_step_state* state, hipStream_t st) {
+    return adamw_launch(p, g, m, v, n, lr, b1, b2, eps, wd, step, sumsq, max_norm, grad_prescale, nullptr, guard, skipped, state, st);
+}
+
+int av_adamw_step_dev(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
+                      float wd, int step, const float* sumsq, float max_norm, const float* grad_div_dev, const float* guard, float* skipped,
+                      const avllm_step_state* state, hipStream_t st) {
+    AV_CHECK_ARG(grad_div_dev, "adamw_dev: grad_div_dev is null");
+    return adamw_launch(p, g, m, v, n, lr, b1, b2, eps, wd, step, sumsq, max_norm, 1.0f, grad_div_dev, guard, skipped, state, st);
 }
 
 int av_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int nbuf, float* partials, int nparts, float* sumsq, hipStream_t st) {
@@ -349,8 +374,9 @@ int av_grad_sumsq_det_multi(const float* const* g, const int64_t* n, int nbuf, f
     return AV_OK;
 }
 
-int av_adamw_step_multi(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq, float max_norm,
-                        float grad_prescale, const float* guard, float* skipped, const avllm_step_state* state, hipStream_t st) {
+static int adamw_multi_launch(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq,
+                              float max_norm, float grad_prescale, const float* grad_div, const float* guard, float* skipped,
+                              const avllm_step_state* state, hipStream_t st) {
     AV_CHECK_ARG(segs && nseg >= 1 && nseg <= 8 && (step >= 1 || state), "adamw_multi: bad args");
     AdamSegs a = {};
     a.nseg = nseg;
@@ -365,15 +391,26 @@ int av_adamw_step_multi(const avllm_adamw_seg* segs, int nseg, float lr, float b
     const float bc1 = 1.0f - (float)pow((double)b1, step);
     const float bc2s = (float)sqrt(1.0 - pow((double)b2, step));
     hipLaunchKernelGGL(adamw_multi_kernel, dim3(a.first[nseg]), dim3(256), 0, st, a, lr, b1, b2, eps, bc1, bc2s, sumsq, max_norm, grad_prescale, guard,
-                       skipped, (avllm_step_state*)state);
+                       skipped, (avllm_step_state*)state, grad_div);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }
 
+int av_adamw_step_multi(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq, float max_norm,
+                        float grad_prescale, const float* guard, float* skipped, const avllm_step_state* state, hipStream_t st) {
+    return adamw_multi_launch(segs, nseg, lr, b1, b2, eps, step, sumsq, max_norm, grad_prescale, nullptr, guard, skipped, state, st);
+}
+
+int av_adamw_step_multi_dev(const avllm_adamw_seg* segs, int nseg, float lr, float b1, float b2, float eps, int step, const float* sumsq,
+                            float max_norm, const float* grad_div_dev, const float* guard, float* skipped, const avllm_step_state* state,
+                            hipStream_t st) {
+    AV_CHECK_ARG(grad_div_dev, "adamw_multi_dev: grad_div_dev is null");
+    return adamw_multi_launch(segs, nseg, lr, b1, b2, eps, step, sumsq, max_norm, 1.0f, grad_div_dev, guard, skipped, state, st);
+}
+
 // One thread advances the step's device-side scalars (include/avllm.h avllm_step_state): the host-side bookkeeping of
 // trainer/clip_whisper_trainer.py:461-464 (optimizer step count, scheduler.step()) and the step's dropout seed.
-__global__ void step_advance_kernel(avllm_step_state* s, avllm_schedule c) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void step_advance_body(avllm_step_state* s, const avllm_schedule& c) {
     const uint32_t step = s->step + 1;
     const float t = (float)(step - 1), total = (float)(c.total_steps > 0 ? c.total_steps : 1);
     float lr;
@@ -388,13 +425,53 @@ __global__ void step_advance_kernel(avllm_step_state* s, avllm_schedule c) {
     s->lr = lr;
     s->bc1 = 1.0f - powf(c.beta1, (float)step);
     s->bc2_sqrt = sqrtf(1.0f - powf(c.beta2, (float)step));
-    // + the skipped count: a step that is retried after a skipped one (same step number) draws fresh masks
-    s->dropout_seed = (step + (uint32_t)s->skipped) * 0x9E3779B1u + c.rank * 0x85EBCA6Bu + 12345u;
+}
+// + the skipped count: a step that is retried after a skipped one (same step number) draws fresh masks
+__device__ __forceinline__ uint32_t step_seed(const avllm_step_state* s, const avllm_schedule& c) {
+    return (s->step + (uint32_t)s->skipped) * 0x9E3779B1u + c.rank * 0x85EBCA6Bu + 12345u;
+}
+
+__global__ void step_advance_kernel(avllm_step_state* s, avllm_schedule c) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    step_advance_body(s, c);
+    s->dropout_seed = step_seed(s, c);
+}
+
+// The micro-step form (avllm_step_advance_micro): reserved[0] counts the micro-steps of the open window.  At count 0 the optimizer step is
+// advanced as above; at any count the seed is the step's plus micro * AVLLM_MICRO_SEED_STRIDE; then the count goes up by one.
+__global__ void step_advance_micro_kernel(avllm_step_state* s, avllm_schedule c) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint32_t micro = s->reserved[0];
+    if (micro == 0) step_advance_body(s, c);
+    s->dropout_seed = step_seed(s, c) + micro * AVLLM_MICRO_SEED_STRIDE;
+    s->reserved[0] = micro + 1;
+}
+
+// window[0..1] (+)= acc[0..1], loss_sum then count, by one thread: the first micro-step of a window (count 1 after its advance) overwrites.
+__global__ void window_add_kernel(float* __restrict__ window, const float* __restrict__ acc, const avllm_step_state* __restrict__ s) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool first = s->reserved[0] <= 1u;
+    window[0] = first ? acc[0] : window[0] + acc[0];
+    window[1] = first ? acc[1] : window[1] + acc[1];
 }
 
 int av_step_advance(avllm_step_state* state, const avllm_schedule* sched, hipStream_t st) {
     AV_CHECK_ARG(state && sched, "step_advance: null");
     hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, st, state, *sched);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_step_advance_micro(avllm_step_state* state, const avllm_schedule* sched, hipStream_t st) {
+    AV_CHECK_ARG(state && sched, "step_advance_micro: null");
+    hipLaunchKernelGGL(step_advance_micro_kernel, dim3(1), dim3(64), 0, st, state, *sched);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_window_add(float* window, const float* acc, const avllm_step_state* state, hipStream_t st) {
+    AV_CHECK_ARG(window && acc && state, "window_add: null");
+    hipLaunchKernelGGL(window_add_kernel, dim3(1), dim3(64), 0, st, window, acc, state);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

@@ -96,6 +96,13 @@ int avllm_gemm_tn_drop(const void* P, int64_t ldp, int32_t I, const void* Q, int
  * kernel (parity mode).  Any M >= 1; N, K, ldy, ldx must be multiples of 8 and dY, X 16-byte aligned (anything else is refused). */
 int avllm_gemm_wgrad(const void* dY, int64_t ldy, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, float* dW, int64_t ldw,
                      float* db, float alpha, int32_t dtype, void* stream);
+/* The accumulating form (gradient accumulation over micro-batches):  dW[n,k] = dW[n,k] + alpha * sum_m dY[m,n] X[m,k]  and
+ * db[n] = db[n] + alpha * sum_m dY[m,n].  The same kernels and K-loop with another epilogue: the cell's prior value is read once, after the
+ * reduction, and added once to the ROUNDED product alpha * acc, in fp32 (two roundings, never one fma).  One workgroup still owns its tile for the
+ * whole of M: no atomics, two launches from the same prior value are bit-identical, and onto a zeroed dW / db the result is avllm_gemm_wgrad's
+ * bits.  Cells of a row past K (ldw > K) are neither read nor written.  Arguments and refusals are those of avllm_gemm_wgrad. */
+int avllm_gemm_wgrad_acc(const void* dY, int64_t ldy, const void* X, int64_t ldx, int32_t M, int32_t N, int32_t K, float* dW, int64_t ldw,
+                         float* db, float alpha, int32_t dtype, void* stream);
 
 /* The q / k / v adapters of one decoder layer batched (bf16, rank <= 16, 1..3 adapters; peft lora.Linear on q_proj, k_proj, v_proj,
  * clip_whisper_model.py:961-1005).  Rank-side products C_j[M,64] = alpha * A_j[M,K_j] B_j[:R,K_j]^T:
@@ -178,7 +185,7 @@ typedef struct avllm_step_state {
     uint32_t dropout_seed;
     float lr, bc1, bc2_sqrt;
     float skipped;                      /* steps whose update was skipped by the non-finite guard (see avllm_adamw_step) */
-    uint32_t reserved[2];
+    uint32_t reserved[2];               /* [0]: micro-steps of the open gradient-accumulation window (avllm_step_advance_micro); [1]: unused */
 } avllm_step_state;
 typedef struct avllm_schedule {
     float base_lr, beta1, beta2;
@@ -186,6 +193,21 @@ typedef struct avllm_schedule {
     uint32_t rank;
 } avllm_schedule;
 int avllm_step_advance(avllm_step_state* state_dev, const avllm_schedule* sched, void* stream);
+/* Gradient accumulation: a window of N micro-batches is ONE optimizer step on their concatenation.  The micro-step form of the advance, a
+ * one-thread kernel run at the top of every micro-step; micro = state->reserved[0] counts the micro-steps since the last optimizer step:
+ *   micro == 0:  step, lr, bc1, bc2_sqrt advance exactly as in avllm_step_advance; otherwise they stay
+ *   any micro:   dropout_seed = (step+skipped)*0x9E3779B1 + rank*0x85EBCA6B + 12345 + micro * AVLLM_MICRO_SEED_STRIDE   (mod 2^32)
+ *                -- micro-step 0 keeps avllm_step_advance's seed; every micro-batch of a window, on every rank, draws its own LoRA dropout
+ *                masks and modality modes
+ *   then         reserved[0] = micro + 1
+ * The window's closing optimizer launch (avllm_adamw_step_dev / avllm_adamw_step_multi_dev) sets reserved[0] back to 0, on a taken and on a
+ * skipped window alike. */
+#define AVLLM_MICRO_SEED_STRIDE 0xC2B2AE35u   /* odd: micro -> micro * stride is a bijection of the 32-bit seeds */
+int avllm_step_advance_micro(avllm_step_state* state_dev, const avllm_schedule* sched, void* stream);
+/* The window's [loss_sum, count] in device memory: window[0] += acc[0], then window[1] += acc[1] (acc = the micro-step's [loss_sum, count]),
+ * by one thread in that order; on the first micro-step of a window (state_dev->reserved[0] <= 1, i.e. right after its advance) the two words
+ * are overwritten instead.  No host sync. */
+int avllm_window_add(float* window, const float* acc, const avllm_step_state* state_dev, void* stream);
 
 /* Sequence operators of the non-default connectors (modality_connector.py:111-380), activations token-major [B, T, C]:
  * im2col for nn.Conv1d(kernel_size 3, padding 1, stride 1 | 2): cols [B * Tout, 3 C], column kw * C + c = x[b, stride t' + kw - 1, c] (zero outside
@@ -457,6 +479,14 @@ int avllm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, fl
 /* state_dev != NULL: lr and the bias corrections come from *state_dev (the `lr` and `step` arguments are ignored); a skipped step is
  * also counted in state_dev->skipped and takes state_dev->step back by one, so that neither the schedule nor Adam's bias corrections
  * advance on it (the reference skips optimizer.step() AND scheduler.step(), trainer/clip_whisper_trainer.py:444-452). */
+/* The closing launch of a gradient-accumulation window: the same kernel with the gradient prescale read from DEVICE memory,
+ * grad_prescale = 1 / *grad_div_dev (IEEE division; 0 where *grad_div_dev <= 0: a window without a scored token has a zero gradient and its
+ * step is taken), used exactly where grad_prescale is used above: norm = sqrt(*sumsq) * prescale, g * prescale * clip coefficient.  The
+ * guard, the skipped bookkeeping and the state_dev rule are the same; in addition state_dev->reserved[0] (avllm_step_advance_micro's count)
+ * is set to 0, whether the step is taken or skipped. */
+int avllm_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int32_t step, const float* sumsq, float max_norm,
+                         const float* grad_div_dev, const float* guard, float* skipped, const avllm_step_state* state_dev, void* stream);
 /* The same two operations over several flat buffers as ONE optimizer step (clip_grad_norm_(model.parameters()) is one global norm,
  * trainer :457-460; _setup_optimizer :183-197 gives weights `weight_decay` and biases 0): the sum of squares runs over the nbuf buffers in
  * index order with fixed-order partials (nparts >= nbuf; the <= 1024 slots are shared in proportion to the buffers' lengths), and the AdamW launch updates every segment (host array, nseg <= 8) under ONE
@@ -474,6 +504,10 @@ typedef struct avllm_adamw_seg {
 int avllm_adamw_step_multi(const avllm_adamw_seg* segs, int32_t nseg, float lr, float beta1, float beta2, float eps, int32_t step,
                            const float* sumsq, float max_norm, float grad_prescale, const float* guard, float* skipped,
                            const avllm_step_state* state_dev, void* stream);
+/* avllm_adamw_step_multi with the device-side divisor of avllm_adamw_step_dev (same kernel, same rule). */
+int avllm_adamw_step_multi_dev(const avllm_adamw_seg* segs, int32_t nseg, float lr, float beta1, float beta2, float eps, int32_t step,
+                               const float* sumsq, float max_norm, const float* grad_div_dev, const float* guard, float* skipped,
+                               const avllm_step_state* state_dev, void* stream);
 /* build the four padded operand images of one LoRA pair from the fp32 masters A [r,din], B [dout,r]:
  * A_pad [64,din], AT_pad [din,64] (row stride ld_at), B_pad [dout,64], BT_pad [64,dout] in `dtype` */
 int avllm_lora_pack(const float* A, const float* Bm, int32_t r, int32_t din, int32_t dout, void* A_pad, void* AT_pad,

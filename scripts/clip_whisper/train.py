@@ -59,6 +59,9 @@ def parse_args(argv=None):
     p.add_argument("--video_time_width", type=int, default=None, help="each span covers 0..this many frames (YAML key data.video_time_width)")
     p.add_argument("--video_time_ratio", type=float, default=None,
                    help="... and at most this share of the clip's own frames; default 1 (YAML key data.video_time_ratio)")
+    p.add_argument("--grad_accum_steps", type=int, default=None,
+                   help="micro-batches per optimizer step: a window of N batches is one step on their concatenation (token-mean loss over the "
+                        "whole window, on all ranks); default 1 (YAML key training.grad_accum_steps; effect on WER not measured)")
     p.add_argument("--log_interval", type=int); p.add_argument("--save_every", type=int); p.add_argument("--resume_from")
     p.add_argument("--save_steps", type=int, default=None, help="stored by the trainer and never acted on, as in the reference (clip_whisper_trainer.py:94-102)")
     p.add_argument("--log_param_updates", action="store_true", help="accepted for command-line compatibility; the reference stores it and never reads it (:118)")
@@ -97,7 +100,7 @@ def main():
                             "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type, "train_connectors": a.train_connectors,
                             "lora_target_modules": a.lora_target_modules, "modality_dropout_audio": a.modality_dropout_audio,
                             "modality_dropout_video": a.modality_dropout_video, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
-                            "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None,
+                            "grad_accum_steps": a.grad_accum_steps, "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None,
                             "noise_path": a.noise_path, "noise_snr": a.noise_snr, "noise_prob": a.noise_prob, "spec_time_masks": a.spec_time_masks,
                             "spec_time_width": a.spec_time_width, "spec_time_ratio": a.spec_time_ratio, "spec_freq_masks": a.spec_freq_masks,
                             "spec_freq_width": a.spec_freq_width, **{k: getattr(a, k) for k in VIDEO_KEYS}})
