@@ -58,6 +58,7 @@ class ClipWhisperTrainer:
             raise ValueError(f"grad_accum_steps must be an int >= 1, got {grad_accum_steps!r}")
         self.grad_accum_steps = grad_accum_steps
         self.micro_step = 0                                # micro-batches of the open window (host side; 0 .. N-1)
+        self._augment_skew = 0                             # micro-batches of skipped windows that _sync_step() took out of global_step (_augment_index)
         self.log_interval, self.save_every, self.save_steps = log_interval, max(1, save_every or 1), save_steps
         self.grad_clip, self.warmup_steps = grad_clip, warmup_steps
         self.global_step = 0
@@ -115,9 +116,11 @@ class ClipWhisperTrainer:
         return (self.augment_seed + 1000003 * int(step) + 7919 * (self._rank if rank is None else int(rank))) & 0xFFFFFFFF
 
     def _augment_index(self):
-        """The number of the micro-batch about to be unpacked: optimizer steps taken * grad_accum_steps + the open window's micro-steps, so
-        the micro-batches of a window are not given the same noise and masks."""
-        return self.global_step * self.grad_accum_steps + self.micro_step
+        """The number of the micro-batch about to be unpacked: grad_accum_steps * the windows closed so far, skipped ones included, + the open
+        window's micro-steps, so the micro-batches of a window are not given the same noise and masks.  The count is the host's own: when
+        _sync_step() takes the skipped steps out of global_step it adds them to _augment_skew, so the index does not move there and the
+        draws of a run do not depend on log_interval or on when a checkpoint was written.  _save_checkpoint() writes it into `_meta.json`."""
+        return self.global_step * self.grad_accum_steps + self.micro_step + self._augment_skew
 
     def _augment_features(self, audio):
         """A batch of precomputed features has no waveform to mix noise into: it gets the SpecAugment half only, every frame counted as
@@ -540,9 +543,11 @@ class ClipWhisperTrainer:
         includes the step the open window will take (avllm_step_advance_micro advances it at micro-step 0): that one is not counted."""
         if self.grad_accum_steps > 1:
             words = self.state.view(torch.int32).cpu()
-            self.global_step = int(words[0]) - (1 if int(words[6]) > 0 else 0)          # words[6]: reserved[0], the open window's micro-steps
-            return self.global_step
-        self.global_step = int(self.state.view(torch.int32)[0].item())
+            taken = int(words[0]) - (1 if int(words[6]) > 0 else 0)                     # words[6]: reserved[0], the open window's micro-steps
+        else:
+            taken = int(self.state.view(torch.int32)[0].item())
+        self._augment_skew += (self.global_step - taken) * self.grad_accum_steps         # the augmentation index stays where it is
+        self.global_step = taken
         return self.global_step
 
     def _all_ranks_ok(self, ok):
@@ -747,7 +752,7 @@ class ClipWhisperTrainer:
                                              "_step_count": self.global_step + 1, "_last_lr": [self.lr_at(self.global_step)]},
                     "train_losses": self.train_losses, "val_losses": self.val_losses, "best_val_loss": self.best_val_loss}, path)
         json.dump({"epoch": epoch, "global_step": self.global_step, "best_val_loss": self.best_val_loss, "grad_accum_steps": self.grad_accum_steps,
-                   "lora_target_modules": list(self.model.lora_target_modules) if self.model.use_lora else None},
+                   "augment_index": self._augment_index(), "skipped_steps": self.skipped_steps, "lora_target_modules": list(self.model.lora_target_modules) if self.model.use_lora else None},
                   open(path.replace(".pt", "_meta.json"), "w"))
 
     @staticmethod
@@ -760,6 +765,26 @@ class ClipWhisperTrainer:
             return None
         t = json.load(open(meta)).get("lora_target_modules")
         return None if t is None else list(t)
+
+    @staticmethod
+    def _meta_count(path, key):
+        meta = str(path).replace(".pt", "_meta.json")
+        if not os.path.exists(meta):
+            return None
+        n = json.load(open(meta)).get(key)
+        return None if n is None else int(n)
+
+    @classmethod
+    def checkpoint_augment_index(cls, path):
+        """The augmentation index (_augment_index) a checkpoint of _save_checkpoint() was written at, from the `_meta.json` beside it; None when
+        the file or the entry is absent (a checkpoint of the reference trainer, or of a build before the entry)."""
+        return cls._meta_count(path, "augment_index")
+
+    @classmethod
+    def checkpoint_skipped_steps(cls, path):
+        """The optimizer steps the run had skipped on a non-finite loss or gradient when the checkpoint was written (`_meta.json`); None when
+        the file or the entry is absent.  The count is part of every step's dropout seed (avllm_step_state)."""
+        return cls._meta_count(path, "skipped_steps")
 
     def load_checkpoint(self, path):
         """trainer:796-854.  Reads a checkpoint of this build AND one written by the reference trainer: connectors + LoRA from
@@ -809,6 +834,15 @@ class ClipWhisperTrainer:
         if self.grad_accum_steps > 1:                            # a checkpoint is a window boundary: training resumes at micro-step 0
             self.micro_step, self._deferred_save = 0, None
             self.state.view(torch.int32)[6] = 0
+        # the augmentation index the run had reached (_augment_index); a checkpoint without the entry: global_step * grad_accum_steps
+        # the steps skipped so far: the seed of a step's LoRA dropout masks and modality modes is a function of step + skipped, so a resumed
+        # run draws what the uninterrupted one draws only with the count restored (without the entry: 0, as before)
+        skipped = self.checkpoint_skipped_steps(path)
+        if skipped is not None:
+            self.skipped.fill_(float(skipped))
+            self.state.view(torch.float32)[5] = float(skipped)
+        index = self.checkpoint_augment_index(path)
+        self._augment_skew = 0 if index is None else index - self.global_step * self.grad_accum_steps
         self.train_losses, self.val_losses = list(ck.get("train_losses", [])), list(ck.get("val_losses", []))
         self.best_val_loss = ck.get("best_val_loss", float("inf"))
         return ck.get("epoch", 0)

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void logmel_frames_kernel(const LogmelTab* __r
         const int lo = tab->lo[m], cnt = tab->cnt[m];
         double acc = 0.0;
         for (int j = 0; j < cnt; ++j) acc += tab->w[m][j] * pw[f][lo + j];
-        acc = acc > 1e-10 ? acc : 1e-10;
+        acc = acc < 1e-10 ? 1e-10 : acc;                       // np.maximum(mel_floor, .): a NaN stays a NaN (a non-finite sample must reach the loss guard)
         logspec[((long)b * NMEL + m) * NFRAME + f0 + f] = (float)log10(acc);
     }
 }
@@ -89,15 +89,17 @@ __global__ __launch_bounds__(1024) void logmel_finish_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const long base = (long)blockIdx.x * NMEL * NFRAME;
     const int n = NMEL * NFRAME;
+    // np.max and np.maximum hand a NaN on (fmaxf drops it): a clip with a non-finite sample comes out NaN, as from the HF extractor
+    auto nanmax = [](float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); };
     float mx = -INFINITY;
-    for (int i = tid; i < n; i += 1024) mx = fmaxf(mx, logspec[base + i]);
-    for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    for (int i = tid; i < n; i += 1024) mx = nanmax(mx, logspec[base + i]);
+    for (int o = 32; o; o >>= 1) mx = nanmax(mx, __shfl_xor(mx, o));
     if (lane == 0) redf[w] = mx;
     __syncthreads();
     mx = redf[0];
-    for (int i = 1; i < 16; ++i) mx = fmaxf(mx, redf[i]);
+    for (int i = 1; i < 16; ++i) mx = nanmax(mx, redf[i]);
     const float floor_v = mx - 8.0f;
-    auto val = [&](int i) { return (fmaxf(logspec[base + i], floor_v) + 4.0f) / 4.0f; };
+    auto val = [&](int i) { return (nanmax(logspec[base + i], floor_v) + 4.0f) / 4.0f; };
     if (!normalize) {
         for (int i = tid; i < n; i += 1024) out[base + i] = val(i);
         return;

@@ -48,6 +48,34 @@ def test_augmentation_seed_counts_micro_batches():
             assert tr._augment_index() == 3 * step + micro
             seen.add(tr.augment_seed_at(tr._augment_index()))
     assert len(seen) == 6
+    # after skipped steps the host count runs ahead of the device's; _sync_step() pulls global_step back and the index stays where it is
+    for t, N in ((one, 1), (tr, 3)):
+        t.global_step, t.micro_step = 5, 0
+        t.state.view(torch.int32)[0] = 3                                                       # two of the five steps were skipped on the device
+        before = t._augment_index()
+        assert before == 5 * N
+        assert t._sync_step() == 3 and t.global_step == 3 and t._augment_index() == before
+        t.global_step += 1                                                                     # the next step: the next index, synced or not
+        assert t._augment_index() == before + N
+        assert t._sync_step() == 3 and t._augment_index() == before + N                        # (as if that step was skipped too)
+    tr.global_step, tr.micro_step = 3, 0
+    tr.state.view(torch.int32)[0], tr.state.view(torch.int32)[6] = 4, 2                        # mid-window: the device count includes the open window
+    tr.micro_step = 2
+    before = tr._augment_index()
+    assert tr._sync_step() == 3 and tr._augment_index() == before
+
+
+def test_checkpoint_carries_the_augmentation_index(tmp_path):
+    """_meta.json's augment_index is restored by load_checkpoint(); a checkpoint without the entry falls back to global_step * grad_accum_steps."""
+    import json
+    from avllm.trainer import ClipWhisperTrainer
+    path = str(tmp_path / "ck.pt")
+    json.dump({"global_step": 4, "augment_index": 17, "skipped_steps": 2}, open(path.replace(".pt", "_meta.json"), "w"))
+    assert ClipWhisperTrainer.checkpoint_augment_index(path) == 17 and ClipWhisperTrainer.checkpoint_skipped_steps(path) == 2
+    json.dump({"global_step": 4}, open(path.replace(".pt", "_meta.json"), "w"))
+    assert ClipWhisperTrainer.checkpoint_augment_index(path) is None and ClipWhisperTrainer.checkpoint_skipped_steps(path) is None
+    assert ClipWhisperTrainer.checkpoint_augment_index(str(tmp_path / "absent.pt")) is None
+    assert ClipWhisperTrainer.checkpoint_skipped_steps(str(tmp_path / "absent.pt")) is None
 
 
 def load_train_script():

@@ -33,6 +33,22 @@ def test_log_mel_batch_vs_oracle_and_fixture(dev, g6):
         assert np.abs(nrm[i][:, ::25] - g6[f"wave{s}_norm_sub"]).max() < 5e-4
 
 
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_log_mel_hands_a_non_finite_sample_on(dev, bad):
+    """np.maximum and np.max (the HF extractor, oracle.preprocess) hand a NaN on, so a clip with one non-finite sample comes out NaN and the
+    trainer's non-finite guard skips its batch; the clip beside it in the batch keeps its bits."""
+    from avllm.preprocess import WhisperLogMel
+    good, hurt = wave_case(1, 20000), wave_case(2, 30000)
+    hurt[12345] = bad
+    for normalize in (False, True):
+        lm = WhisperLogMel(dev, normalize=normalize)
+        out = lm([good, hurt]).cpu()
+        ref = torch.from_numpy(P.audio_features(hurt) if normalize else P.log_mel(hurt))
+        assert bool(torch.isnan(ref).all()) and not bool(torch.isfinite(out[1]).any()), (normalize, int(torch.isfinite(out[1]).sum()))
+        assert bad == bad or bool(torch.isnan(out[1]).all())                      # a NaN sample: NaN everywhere, as on the host
+        assert torch.equal(out[0], lm([good]).cpu()[0]) and bool(torch.isfinite(out[0]).all())
+
+
 def test_log_mel_silence_and_single_row(dev):
     from avllm.preprocess import WhisperLogMel
     lm = WhisperLogMel(dev, normalize=False)
