@@ -381,6 +381,8 @@ class LlamaEngine:
         self.ws_infer = Workspace(device)      # prefill / decode_step scratch: an eval forward or generate() between a training
         self._last = None                      #   forward and its backward must not touch the saved activations
         self.acc = torch.zeros(2, dtype=torch.float32, device=device)     # [loss_sum, count]
+        self.loss_opts = None       # avllm_loss_opts of the last fwd_loss() with label smoothing or z-loss on, else None
+        self.loss_terms = None      # [sum nll, sum (lse - mean logit), sum lse^2]: owned from the first fwd_loss() with label smoothing or z-loss on
         if self.use_lora:
             self.pack_lora()
 
@@ -452,12 +454,24 @@ class LlamaEngine:
                 L.check(lib.avllm_lora_pack_batch(L.ptr(table), table.shape[0], self.r, din, self.desc.dtype, L.stream_ptr()))
 
     # ------------------------------------------------------------------ training
-    def fwd_loss(self, x, labels, want_logits=False, dropout=0.0, seed=0, seed_dev=None):
+    def fwd_loss(self, x, labels, want_logits=False, dropout=0.0, seed=0, seed_dev=None, label_smoothing=0.0, z_loss=0.0):
         """x [B,S,d] (engine dtype), labels int64 [B,S] (-100 applied).  Leaves loss_sum,count in self.acc.
         `dropout`/`seed`: lora_dropout probability and the step's mask seed (kept in the descriptor for bwd()); `seed_dev`: device
-        pointer (int) of a uint32 added to `seed` at run time -- the step state of a graph-replayable step."""
+        pointer (int) of a uint32 added to `seed` at run time -- the step state of a graph-replayable step.
+        `label_smoothing`/`z_loss`: the objective of avllm_ce_smooth_fwd, kept in self.loss_opts (avllm_loss_opts) so that bwd() hands the
+        backward the forward's values; with either on, loss_sum is the sum of the composite terms and self.loss_terms holds the raw sums
+        [nll, lse - mean logit, lse^2], zeroed beside self.acc.  With both 0 the entries without options are called, as ever: the plain cross
+        entropy, nothing allocated, self.loss_opts None."""
         self._refuse_merged("fwd_loss()")
         lib = L.load()
+        eps, zeta = ops.check_loss_options(label_smoothing, z_loss)
+        if eps or zeta:
+            if self.loss_terms is None:
+                self.loss_terms = torch.zeros(3, dtype=torch.float32, device=self.device)
+            self.loss_terms.zero_()
+            self.loss_opts = L.LossOpts(eps, zeta, self.loss_terms.data_ptr())
+        else:
+            self.loss_opts = None
         self.desc.lora_dropout = float(dropout) if self.use_lora else 0.0
         self.desc.dropout_seed = int(seed) & 0xFFFFFFFF
         self.desc.dropout_seed_dev = seed_dev
@@ -467,8 +481,12 @@ class LlamaEngine:
         ws = self.ws.get(lib.avllm_llama_train_workspace_bytes(C.byref(self.desc), B, S))
         logits = torch.empty(B, S, self.cfg.vocab, device=self.device, dtype=self.dtype) if want_logits else None
         self.acc.zero_()
-        L.check(lib.avllm_llama_lora_fwd_loss(C.byref(self.desc), L.ptr(x), L.ptr(labels), B, S, L.ptr(logits), L.ptr(self.acc),
-                                              L.ptr(self.acc) + 4, L.ptr(ws), ws.numel(), L.stream_ptr()))
+        if self.loss_opts is not None:
+            L.check(lib.avllm_llama_lora_fwd_loss_opts(C.byref(self.desc), L.ptr(x), L.ptr(labels), B, S, L.ptr(logits), L.ptr(self.acc),
+                                                       L.ptr(self.acc) + 4, C.byref(self.loss_opts), L.ptr(ws), ws.numel(), L.stream_ptr()))
+        else:
+            L.check(lib.avllm_llama_lora_fwd_loss(C.byref(self.desc), L.ptr(x), L.ptr(labels), B, S, L.ptr(logits), L.ptr(self.acc),
+                                                  L.ptr(self.acc) + 4, L.ptr(ws), ws.numel(), L.stream_ptr()))
         self._last = (B, S, labels, ws.data_ptr(), ws.numel())
         self.gen = getattr(self, "gen", 0) + 1          # identifies whose activations the workspace holds (checked by _LoraLoss.backward)
         return logits
@@ -490,6 +508,12 @@ class LlamaEngine:
         cnt = self.acc[1:2] if count is None else count
         cb = L.LAYER_CB(lambda l, u: after_layer(l)) if after_layer is not None else L.LAYER_CB(0)
         hi = self.cfg.layers - 1 if layer_hi is None else layer_hi
+        if dx_embeds is not None and (dx_embeds.dtype != self.dtype or dx_embeds.numel() != B * S * self.cfg.hidden or not dx_embeds.is_contiguous()):
+            raise ValueError(f"LlamaEngine.bwd(): dx_embeds must be a contiguous [{B},{S},{self.cfg.hidden}] {self.dtype} tensor")
+        if self.loss_opts is not None:      # the objective of the forward whose activations the workspace holds
+            L.check(lib.avllm_llama_lora_bwd_layers_dx_opts(C.byref(self.desc), L.ptr(labels), B, S, L.ptr(cnt), grad_scale, L.ptr(ws), ws.numel(),
+                                                            hi, layer_lo, cb, None, L.ptr(dx_embeds), C.byref(self.loss_opts), L.stream_ptr()))
+            return
         if dx_embeds is not None:
             if dx_embeds.dtype != self.dtype or dx_embeds.numel() != B * S * self.cfg.hidden or not dx_embeds.is_contiguous():
                 raise ValueError(f"LlamaEngine.bwd(): dx_embeds must be a contiguous [{B},{S},{self.cfg.hidden}] {self.dtype} tensor")

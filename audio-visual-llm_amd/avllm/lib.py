@@ -69,6 +69,10 @@ class Llama(C.Structure):
                [("decode_fp8", i32), ("elm_head8", vp), ("decode_fp4", i32), ("kv_fp8", i32)]
 
 
+class LossOpts(C.Structure):
+    _fields_ = [("label_smoothing", f32), ("z_loss", f32), ("loss_terms", vp)]
+
+
 class GemmF8Desc(C.Structure):
     _fields_ = [("A", vp), ("SA", vp), ("B", vp), ("SB", vp), ("C", vp), ("bias", vp), ("R", vp), ("lda", i64), ("ldb", i64), ("ldc", i64),
                 ("ldr", i64), ("M", i32), ("N", i32), ("K", i32), ("act", i32), ("Cq", vp), ("SCq", vp), ("ldcq", i64)]
@@ -160,6 +164,8 @@ _SIGS = {
     "avllm_attention_bwd_fuses_rope": ([i32] * 3, i32),
     "avllm_ce_fwd": ([vp, i64, vp, i32, i32, i32, vp, vp, vp, i32, vp], i32),
     "avllm_ce_bwd": ([vp, i64, vp, vp, vp, f32, vp, i32, i32, i32, i32, vp], i32),
+    "avllm_ce_smooth_fwd": ([vp, i64, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, i32, vp], i32),
+    "avllm_ce_smooth_bwd": ([vp, i64, vp, vp, vp, f32, f32, f32, vp, i32, i32, i32, i32, vp], i32),
     "avllm_argmax_rows": ([vp, i64, i64, i32, vp, i32, vp], i32),
     "avllm_sample_rows": ([vp, i64, i64, i32, f32, i32, f32, C.c_uint32, vp, i32, vp, vp, i64, i64, vp, i32, vp], i32),
     "avllm_sample_rows_scored": ([vp, i64, i64, i32, f32, i32, f32, C.c_uint32, vp, i32, vp, vp, i64, i64, vp, vp, i32, vp], i32),
@@ -214,6 +220,8 @@ _SIGS = {
     "avllm_clip_vision_cls_fwd": ([C.POINTER(Clip), vp, i32, vp, vp, sz, vp], i32),
     "avllm_llama_train_workspace_bytes": ([C.POINTER(Llama), i32, i32], sz),
     "avllm_llama_lora_fwd_loss": ([C.POINTER(Llama), vp, vp, i32, i32, vp, vp, vp, vp, sz, vp], i32),
+    "avllm_llama_lora_fwd_loss_opts": ([C.POINTER(Llama), vp, vp, i32, i32, vp, vp, vp, C.POINTER(LossOpts), vp, sz, vp], i32),
+    "avllm_llama_lora_bwd_layers_dx_opts": ([C.POINTER(Llama), vp, i32, i32, vp, f32, vp, sz, i32, i32, LAYER_CB, vp, vp, C.POINTER(LossOpts), vp], i32),
     "avllm_llama_lora_bwd": ([C.POINTER(Llama), vp, i32, i32, vp, f32, vp, sz, LAYER_CB, vp, vp], i32),
     "avllm_llama_infer_workspace_bytes": ([C.POINTER(Llama), i32, i32], sz),
     "avllm_llama_prefill": ([C.POINTER(Llama), vp, i32, i32, vp, vp, i32, vp, vp, vp, sz, vp], i32),

@@ -18,6 +18,8 @@ Differences that are deliberate and documented:
   * modality_dropout_audio / modality_dropout_video (default 0 = off) and the modality_mask keyword of forward() / encode() / generate() are
     additions: one mode per clip (both | audio only | video only) at the geometry of the two-stream call, drawn per step in train() mode or
     given by the caller (see forward()).  Without them the model launches what it launched.
+  * label_smoothing / z_loss (default 0 = off) are additions: the objective of the training forward only (see the constructor); eval() and
+    everything built on it keep the plain cross entropy.  Without them the model launches what it launched.
 """
 from __future__ import annotations
 
@@ -102,7 +104,8 @@ class ClipWhisperModel:
                  _provided_whisper=None, _provided_clip=None, *, precision=None, config: ModelCfg | None = None,
                  weights: dict | None = None, seed: int = 0, synthetic_weights: bool = False, decode_weights: str = "bf16",
                  train_connectors: bool = False, kv_cache: str = "bf16", lora_target_modules=None,
-                 modality_dropout_audio: float = 0.0, modality_dropout_video: float = 0.0):
+                 modality_dropout_audio: float = 0.0, modality_dropout_video: float = 0.0,
+                 label_smoothing: float = 0.0, z_loss: float = 0.0):
         if use_4bit:
             raise NotImplementedError("use_4bit (bitsandbytes nf4) is out of scope of the MI355X hot path (SURVEY.md §8)")
         if not freeze_encoders:
@@ -124,6 +127,13 @@ class ClipWhisperModel:
             raise ValueError(f"{nm}={modality_dropout_audio or modality_dropout_video} needs modality='both', got modality={modality!r}: "
                              f"there is no second stream to fall back on")
         self.modality_dropout_audio, self.modality_dropout_video = float(modality_dropout_audio), float(modality_dropout_video)
+        # label smoothing and the PaLM z-loss (not in the reference, whose trainer takes HF's loss as it is): the training forward's objective is
+        # (1 - label_smoothing) nll + label_smoothing (lse - mean logit) + z_loss lse^2 per scored token (avllm_ce_smooth_fwd).  The eval()
+        # forward keeps the plain cross entropy, so validation losses compare across runs with and without them.  Effect on WER not measured.
+        for nm, p in (("label_smoothing", label_smoothing), ("z_loss", z_loss)):
+            if not isinstance(p, (int, float)) or isinstance(p, bool):
+                raise ValueError(f"{nm} must be a number, got {p!r}")
+        self.label_smoothing, self.z_loss = ops.check_loss_options(label_smoothing, z_loss)
         self.last_modality_modes = None            # int32 [B] device buffer of the last call that used per-clip modes, else None
         self.last_modality_seed = None             # the by-value seed of that call's draw (None: no draw, or the seed came from device memory)
         self._mode_bufs = {}
@@ -574,15 +584,17 @@ class ClipWhisperModel:
             drop = self._dropout_args()                # first: a modality-dropout draw shares this forward's seed
             x = self._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors, modality_mask=modality_mask,
                                  draw_seed=drop["seed"] if drop["dropout"] else None)       # adaptive pool / interpolate (:577-585)
-            logits = self.llm_engine.fwd_loss(x, labels, want_logits=True, **drop)
+            logits = self.llm_engine.fwd_loss(x, labels, want_logits=True, label_smoothing=self.label_smoothing, z_loss=self.z_loss, **drop)
             acc = self.llm_engine.acc
             loss = acc[0] / acc[1]
+            # with label smoothing or the z-loss on, "loss" is the composite objective and "nll_loss" the plain cross entropy of the same rows
+            nll = {"nll_loss": self.llm_engine.loss_terms[0] / acc[1]} if (self.label_smoothing or self.z_loss) else {}
             if self.train_connectors:
                 cps = [p for c in (self.audio_connector, self.video_connector) for p in c.parameters()]
                 loss = _LoraLoss.apply(self.lora_param, self, loss, *cps)
             elif self.lora_param is not None and self.lora_param.requires_grad:
                 loss = _LoraLoss.apply(self.lora_param, self, loss)
-            return {"loss": loss, "logits": logits}
+            return {"loss": loss, "logits": logits, **nll}
         x = self._llm_inputs(audio, video, prompt, modality_mask=modality_mask)
         B, S, _ = x.shape
         kc, vc = self.llm_engine.alloc_cache(B, S, fp8=False)

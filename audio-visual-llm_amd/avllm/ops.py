@@ -283,6 +283,45 @@ def ce_bwd(logits, labels, row_lse, acc, grad_scale=1.0, out=None):
     return out
 
 
+def check_loss_options(label_smoothing, z_loss):
+    """The ranges of the training objective's two options (include/avllm.h, avllm_ce_smooth_fwd): 0 <= label_smoothing < 1, z_loss >= 0, both
+    finite.  Returns them as floats."""
+    eps, zeta = float(label_smoothing), float(z_loss)
+    if not (0.0 <= eps < 1.0):                                   # a NaN fails both comparisons
+        raise ValueError(f"label_smoothing={label_smoothing} must be in [0, 1)")
+    if not (0.0 <= zeta < math.inf):
+        raise ValueError(f"z_loss={z_loss} must be finite and >= 0")
+    return eps, zeta
+
+
+def ce_smooth_fwd(logits, labels, label_smoothing, z_loss):
+    """ce_fwd with label smoothing and the z-loss (avllm_ce_smooth_fwd's rule) -> (row_lse [B*T], acc = [sum of the rows' objective, count],
+    terms = the raw sums [nll, lse - mean logit, lse^2] over the scored rows)."""
+    eps, zeta = check_loss_options(label_smoothing, z_loss)
+    B, T, V = logits.shape
+    row_lse = torch.empty(B * T, device=logits.device, dtype=torch.float32)
+    acc = torch.zeros(2, device=logits.device, dtype=torch.float32)
+    terms = torch.zeros(3, device=logits.device, dtype=torch.float32)
+    L.check(L.load().avllm_ce_smooth_fwd(L.ptr(logits), _ce_ld(logits), L.ptr(labels), B, T, V, eps, zeta, L.ptr(row_lse), L.ptr(acc),
+                                         L.ptr(acc) + 4, L.ptr(terms), L.dt_of(logits), L.stream_ptr()))
+    return row_lse, acc, terms
+
+
+def ce_smooth_bwd(logits, labels, row_lse, acc, label_smoothing, z_loss, grad_scale=1.0, out=None):
+    """dlogits of ce_smooth_fwd's objective, grad_scale / count * ((1 + 2 z_loss lse) softmax - (1 - label_smoothing) onehot - label_smoothing / V)
+    on scored rows; strides and `out` as ce_bwd."""
+    eps, zeta = check_loss_options(label_smoothing, z_loss)
+    B, T, V = logits.shape
+    ld = _ce_ld(logits)
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), device=logits.device, dtype=logits.dtype)
+    elif out.shape != logits.shape or out.stride() != logits.stride() or out.dtype != logits.dtype or out.device != logits.device:
+        raise ValueError("ce_smooth_bwd: out must have the shape, strides, dtype and device of logits")
+    L.check(L.load().avllm_ce_smooth_bwd(L.ptr(logits), ld, L.ptr(labels), L.ptr(row_lse), L.ptr(acc) + 4, grad_scale, eps, zeta, L.ptr(out),
+                                         B, T, V, L.dt_of(logits), L.stream_ptr()))
+    return out
+
+
 def argmax_rows(logits2d):
     out = torch.empty(logits2d.shape[0], device=logits2d.device, dtype=torch.int64)
     L.check(L.load().avllm_argmax_rows(L.ptr(logits2d), _ld(logits2d), logits2d.shape[0], logits2d.shape[1], L.ptr(out),

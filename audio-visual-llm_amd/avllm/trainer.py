@@ -83,6 +83,10 @@ class ClipWhisperTrainer:
         self.state = torch.zeros(ctypes.sizeof(L.StepState), dtype=torch.uint8, device=dev)
         self._seed_ptr = self.state.data_ptr() + L.StepState.dropout_seed.offset
         self._loss_buf = torch.zeros((), dtype=torch.float32, device=dev)
+        # label smoothing / z-loss (model.label_smoothing, model.z_loss): train_step() returns the composite objective; last_nll holds this
+        # rank's mean plain cross entropy of the last (micro-)batch, a device scalar written inside the (captured) step; None with both off
+        self.label_smoothing, self.z_loss = float(getattr(model, "label_smoothing", 0.0)), float(getattr(model, "z_loss", 0.0))
+        self.last_nll = torch.zeros((), dtype=torch.float32, device=dev) if (self.label_smoothing or self.z_loss) else None
         self._rank = torch.distributed.get_rank() if is_dist() else 0
         if use_graph is None:
             use_graph = os.environ.get("AVLLM_GRAPH", "1") != "0"
@@ -188,7 +192,9 @@ class ClipWhisperTrainer:
         # graph redraws
         x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors, seed_dev=self._seed_ptr)
         p = float(model.lora_dropout) if (model.training and model.use_lora and model.lora_dropout) else 0.0
-        eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr)
+        eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr, label_smoothing=self.label_smoothing, z_loss=self.z_loss)
+        if self.last_nll is not None:
+            torch.div(eng.loss_terms[0], eng.acc[1], out=self.last_nll)
 
     def _piece_range(self, i):
         """Decoder layers (hi, lo) of backward piece i of self.bwd_pieces, last layer first."""
@@ -251,7 +257,9 @@ class ClipWhisperTrainer:
         labels = model._prep_labels(labels)
         x = model._llm_inputs(audio, video, prompt, S_out=labels.shape[1], keep=self.train_connectors, seed_dev=self._seed_ptr)
         p = float(model.lora_dropout) if (model.training and model.use_lora and model.lora_dropout) else 0.0
-        eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr)
+        eng.fwd_loss(x, labels, dropout=p, seed=0, seed_dev=self._seed_ptr, label_smoothing=self.label_smoothing, z_loss=self.z_loss)
+        if self.last_nll is not None:
+            torch.div(eng.loss_terms[0], eng.acc[1], out=self.last_nll)
         ops.window_add(self._window, eng.acc, self.state)
         torch.div(eng.acc[0], eng.acc[1], out=self._micro_loss)
 
@@ -587,7 +595,8 @@ class ClipWhisperTrainer:
                 return True
             what = f"window {windows} (batch {i + 1}/{len(self.train_dataloader)})" if accum else f"batch {i + 1}/{len(self.train_dataloader)}"
             where = f"window {windows}" if accum else f"batch {i + 1}"          # the shares below cover every micro-batch since the last look
-            logging.info(f"epoch {epoch} {what} loss {float(vals[-1]):.4f} "
+            nll = f"nll {float(self.last_nll):.4f} " if self.last_nll is not None else ""      # the last (micro-)batch's, on this rank
+            logging.info(f"epoch {epoch} {what} loss {float(vals[-1]):.4f} {nll}"
                          f"avg {total / max(1, n):.4f} lr {self.lr_at(self.global_step):.3e} {(time.time() - t0) / (i + 1):.3f}s/it")
             if pending_modes:
                 share = self.mode_shares(torch.cat(pending_modes).cpu())
@@ -752,7 +761,8 @@ class ClipWhisperTrainer:
                                              "_step_count": self.global_step + 1, "_last_lr": [self.lr_at(self.global_step)]},
                     "train_losses": self.train_losses, "val_losses": self.val_losses, "best_val_loss": self.best_val_loss}, path)
         json.dump({"epoch": epoch, "global_step": self.global_step, "best_val_loss": self.best_val_loss, "grad_accum_steps": self.grad_accum_steps,
-                   "augment_index": self._augment_index(), "skipped_steps": self.skipped_steps, "lora_target_modules": list(self.model.lora_target_modules) if self.model.use_lora else None},
+                   "augment_index": self._augment_index(), "skipped_steps": self.skipped_steps, "lora_target_modules": list(self.model.lora_target_modules) if self.model.use_lora else None,
+                   "label_smoothing": self.label_smoothing, "z_loss": self.z_loss},
                   open(path.replace(".pt", "_meta.json"), "w"))
 
     @staticmethod
@@ -774,6 +784,18 @@ class ClipWhisperTrainer:
         n = json.load(open(meta)).get(key)
         return None if n is None else int(n)
 
+    @staticmethod
+    def checkpoint_loss_options(path):
+        """(label_smoothing, z_loss) a checkpoint of _save_checkpoint() was trained with, from the `_meta.json` beside it; None when the file or
+        the entries are absent (a checkpoint of the reference trainer, or of a build before the options)."""
+        meta = str(path).replace(".pt", "_meta.json")
+        if not os.path.exists(meta):
+            return None
+        d = json.load(open(meta))
+        if "label_smoothing" not in d and "z_loss" not in d:
+            return None
+        return float(d.get("label_smoothing") or 0.0), float(d.get("z_loss") or 0.0)
+
     @classmethod
     def checkpoint_augment_index(cls, path):
         """The augmentation index (_augment_index) a checkpoint of _save_checkpoint() was written at, from the `_meta.json` beside it; None when
@@ -794,6 +816,11 @@ class ClipWhisperTrainer:
         if saved is not None and self.model.use_lora and tuple(saved) != tuple(self.model.lora_target_modules):
             raise ValueError(f"load_checkpoint(): {path} was trained with lora_target_modules = {', '.join(saved)}, this model has "
                              f"{', '.join(self.model.lora_target_modules)}: build the model with checkpoint_lora_targets(path)")
+        opts = self.checkpoint_loss_options(path)
+        if opts is not None and opts != (self.label_smoothing, self.z_loss):
+            # the objective is not part of the state: the run goes on under the trainer's values, and its losses no longer compare
+            logging.warning(f"load_checkpoint(): {path} was trained with label_smoothing={opts[0]}, z_loss={opts[1]}; this trainer goes on with "
+                            f"label_smoothing={self.label_smoothing}, z_loss={self.z_loss}")
         ck = torch.load(path, map_location="cpu", weights_only=True)
         self.model.load_state_dict(ck["model_state_dict"])
         eng = self.model.llm_engine

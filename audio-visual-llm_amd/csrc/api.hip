@@ -116,6 +116,14 @@ int avllm_attention_bwd_rope(const void* q, const void* k, const void* v, const 
 }
 int avllm_ce_fwd(const void* logits, int64_t ld, const int64_t* labels, int32_t B, int32_t T, int32_t V, float* row_lse,
                  float* loss_sum, float* count, int32_t dtype, void* stream) { return av_ce_fwd(logits, ld, labels, B, T, V, row_lse, loss_sum, count, dtype, ST); }
+int avllm_ce_smooth_fwd(const void* logits, int64_t ld, const int64_t* labels, int32_t B, int32_t T, int32_t V, float label_smoothing, float z_loss,
+                        float* row_lse, float* loss_sum, float* count, float* terms, int32_t dtype, void* stream) {
+    return av_ce_smooth_fwd(logits, ld, labels, B, T, V, label_smoothing, z_loss, row_lse, loss_sum, count, terms, dtype, ST);
+}
+int avllm_ce_smooth_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* row_lse, const float* count, float grad_scale,
+                        float label_smoothing, float z_loss, void* dlogits, int32_t B, int32_t T, int32_t V, int32_t dtype, void* stream) {
+    return av_ce_smooth_bwd(logits, ld, labels, row_lse, count, grad_scale, label_smoothing, z_loss, dlogits, B, T, V, dtype, ST);
+}
 int avllm_ce_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* row_lse, const float* count, float grad_scale,
                  void* dlogits, int32_t B, int32_t T, int32_t V, int32_t dtype, void* stream) { return av_ce_bwd(logits, ld, labels, row_lse, count, grad_scale, dlogits, B, T, V, dtype, ST); }
 int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, int64_t* out, int32_t dtype, void* stream) { return av_argmax_rows(logits, ld, rows, V, out, dtype, ST); }

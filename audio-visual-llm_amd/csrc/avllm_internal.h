@@ -50,6 +50,10 @@ int av_ce_fwd(const void* logits, long ld, const int64_t* labels, int B, int T, 
               float* count, int dtype, hipStream_t st);
 int av_ce_bwd(const void* logits, long ld, const int64_t* labels, const float* row_lse, const float* count,
               float grad_scale, void* dlogits, int B, int T, int V, int dtype, hipStream_t st);
+int av_ce_smooth_fwd(const void* logits, long ld, const int64_t* labels, int B, int T, int V, float eps, float zeta, float* row_lse,
+                     float* loss_sum, float* count, float* terms, int dtype, hipStream_t st);
+int av_ce_smooth_bwd(const void* logits, long ld, const int64_t* labels, const float* row_lse, const float* count, float grad_scale,
+                     float eps, float zeta, void* dlogits, int B, int T, int V, int dtype, hipStream_t st);
 int av_argmax_rows(const void* logits, long ld, long rows, int V, int64_t* out, int dtype, hipStream_t st);
 int av_sample_rows(const void* logits, long ld, long rows, int V, float temperature, int top_k, float top_p, uint32_t seed,
                    const uint32_t* row_seeds, int step, const int* step_dev, uint8_t* unfinished, long long eos, long long pad,

@@ -176,6 +176,8 @@ inline const void* llama_bias(const avllm_llama* m, const avllm_llama_layer& P, 
     return P.bqkv ? (const char*)P.bqkv + (size_t)llama_off(m, j) * av_dtype_size(m->dtype) : nullptr;
 }
 
+// label smoothing or z-loss in the training objective: either value non-zero takes the av_ce_smooth pair, both 0 exactly av_ce_fwd / av_ce_bwd
+inline bool llama_loss_smooth(const avllm_loss_opts* o) { return o && (o->label_smoothing != 0.f || o->z_loss != 0.f); }
 // per-head q/k RMSNorm (Qwen3): a model has it on every layer or on none (check_llama)
 inline bool llama_qk_norm(const avllm_llama* m) { return m->layer && m->layer[0].q_norm_w != nullptr; }
 // adapters on gate_proj / up_proj / down_proj (avllm_llama_layer.lora_mlp): k = 0 gate, 1 up, 2 down
@@ -571,6 +573,11 @@ extern "C" size_t avllm_llama_train_workspace_bytes(const avllm_llama* m, int32_
 
 extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, const int64_t* labels, int32_t B, int32_t S,
                                          void* logits_out, float* loss_sum, float* count, void* ws, size_t ws_bytes, void* stream) {
+    return avllm_llama_lora_fwd_loss_opts(m, x, labels, B, S, logits_out, loss_sum, count, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int avllm_llama_lora_fwd_loss_opts(const avllm_llama* m, const void* x, const int64_t* labels, int32_t B, int32_t S, void* logits_out,
+                                              float* loss_sum, float* count, const avllm_loss_opts* opts, void* ws, size_t ws_bytes, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     AV_TRY(check_llama(m));
     AV_CHECK_ARG(x && ws && B > 0 && S > 0, "llama_lora_fwd_loss: null/empty");
@@ -657,7 +664,11 @@ extern "C" int avllm_llama_lora_fwd_loss(const avllm_llama* m, const void* x, co
     AV_TRY(av_rmsnorm_fwd(w.resid[m->layers], m->norm_w, w.xf, w.rstd_f, M, d, m->eps, dt, st));
     AV_TRY(linear(dt, fq, false, {m->lm_head, m->lm_head8, m->slm_head8, nullptr}, w.xf, d, M, d, m->vocab, w.logits, m->vocab, AV_ACT_NONE, nullptr, 0, st));
     if (logits_out) AV_HIP(hipMemcpyAsync(logits_out, w.logits, (size_t)M * m->vocab * es, hipMemcpyDeviceToDevice, st));
-    if (labels) AV_TRY(av_ce_fwd(w.logits, m->vocab, labels, B, S, m->vocab, w.row_lse, loss_sum, count, dt, st));
+    if (labels) {
+        if (llama_loss_smooth(opts))      // label smoothing / z-loss: the one-pass kernel that also gathers the row's sum of logits
+            AV_TRY(av_ce_smooth_fwd(w.logits, m->vocab, labels, B, S, m->vocab, opts->label_smoothing, opts->z_loss, w.row_lse, loss_sum, count, opts->loss_terms, dt, st));
+        else AV_TRY(av_ce_fwd(w.logits, m->vocab, labels, B, S, m->vocab, w.row_lse, loss_sum, count, dt, st));
+    }
     return AV_OK;
 }
 
@@ -677,6 +688,12 @@ extern "C" int avllm_llama_lora_bwd_layers(const avllm_llama* m, const int64_t* 
 extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
                                               float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
                                               avllm_layer_cb after_layer, void* user, void* dx_embeds, void* stream) {
+    return avllm_llama_lora_bwd_layers_dx_opts(m, labels, B, S, count, grad_scale, ws, ws_bytes, layer_hi, layer_lo, after_layer, user, dx_embeds, nullptr, stream);
+}
+
+extern "C" int avllm_llama_lora_bwd_layers_dx_opts(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
+                                                   float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
+                                                   avllm_layer_cb after_layer, void* user, void* dx_embeds, const avllm_loss_opts* opts, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     AV_TRY(check_llama(m));
     AV_CHECK_ARG(layer_lo >= 0 && layer_lo <= layer_hi && layer_hi < m->layers, "llama_lora_bwd_layers: bad layer range [%d, %d]", layer_lo, layer_hi);
@@ -692,7 +709,8 @@ extern "C" int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_
     const bool drop = dr.p > 0.f;
     avllm_gemm_desc g;
     if (layer_hi == m->layers - 1) {      // the piece that starts at the top also runs loss -> lm_head -> final norm
-        AV_TRY(av_ce_bwd(w.logits, V, labels, w.row_lse, count, grad_scale, w.logits, B, S, V, dt, st));
+        if (llama_loss_smooth(opts)) AV_TRY(av_ce_smooth_bwd(w.logits, V, labels, w.row_lse, count, grad_scale, opts->label_smoothing, opts->z_loss, w.logits, B, S, V, dt, st));
+        else AV_TRY(av_ce_bwd(w.logits, V, labels, w.row_lse, count, grad_scale, w.logits, B, S, V, dt, st));
         g = gemm_desc(dt, w.logits, V, m->lm_head_t, V, w.dxn, d, M, d, V);
         AV_CHECK_ARG(V % 64 == 0, "llama_lora_bwd: vocab %d must be a multiple of 64", V);
         AV_TRY(av_gemm(&g, st));

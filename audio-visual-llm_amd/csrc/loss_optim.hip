@@ -82,6 +82,122 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logit
     }
 }
 
+// block_sum (common.h) of two values behind one pair of barriers; each sum is formed in block_sum's order, so it has block_sum's bits
+__device__ __forceinline__ void block_sum2(float& x, float& y, float* rx, float* ry) {
+    x = wave_sum(x); y = wave_sum(y);
+    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { rx[w] = x; ry[w] = y; }
+    __syncthreads();
+    float tx = 0.f, ty = 0.f;
+    for (int i = 0; i < nw; ++i) { tx += rx[i]; ty += ry[i]; }
+    x = tx; y = ty;
+}
+
+// Cross entropy with label smoothing eps and the z-loss zeta (include/avllm.h, avllm_ce_smooth_fwd): per scored row
+//   l = (1 - eps) (lse - x_y) + eps (lse - mean_v x_v) + zeta lse^2.
+// The (max, sum exp) loop is ce_fwd_kernel's, operation for operation, so row_lse has its bits; the same pass gathers the plain sum of the
+// row's logits.  One running fp32 sum per thread would be a chain of V / 256 additions (594 at V = 152 064); each vector lane keeps its own
+// sum instead, the VN lane sums are folded pairwise and block_sum2 adds the 256 threads as block_sum does: the longest chain of additions is
+// ceil(V / (256 VN)) + log2(VN) + 6 + 4 = 75 + 13 at V = 152 064 in bf16 (149 + 12 in fp32), where torch's pairwise host sum has ~ 20.
+template <typename T>
+__global__ __launch_bounds__(256) void ce_smooth_fwd_kernel(const T* __restrict__ logits, long ld, const int64_t* __restrict__ labels,
+                                                            int Tn, int V, float eps, float zeta, float* __restrict__ row_lse,
+                                                            float* __restrict__ loss_sum, float* __restrict__ count,
+                                                            float* __restrict__ terms) {
+    __shared__ float red[8], red2[8];
+    constexpr int VN = VecN<T>::n;
+    const long row = blockIdx.x;
+    const int t = (int)(row % Tn);
+    const long b = row / Tn;
+    const int64_t tgt = (t + 1 < Tn) ? labels[b * Tn + t + 1] : -100;
+    const T* lr = logits + row * ld;
+    float mx = -INFINITY, sm = 0.f;
+    float a[VN];
+#pragma unroll
+    for (int j = 0; j < VN; ++j) a[j] = 0.f;
+    for (int c = threadIdx.x * VN; c < V; c += 256 * VN) {
+        float v[VN];
+        if (c + VN <= V) {
+            load_f<VN>(lr + c, v);
+#pragma unroll
+            for (int j = 0; j < VN; ++j) a[j] += v[j];
+        } else {
+            for (int j = 0; j < VN; ++j) {
+                const bool in = c + j < V;
+                const float x = in ? to_f(lr[c + j]) : 0.f;
+                a[j] += x;
+                v[j] = in ? x : -INFINITY;
+            }
+        }
+        float lm = v[0];
+#pragma unroll
+        for (int j = 1; j < VN; ++j) lm = fmaxf(lm, v[j]);
+        const float nm = fmaxf(mx, lm);
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < VN; ++j) s += __expf(v[j] - nm);
+        sm = sm * __expf(mx - nm) + s;
+        mx = nm;
+    }
+#pragma unroll
+    for (int w = VN / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int j = 0; j < w; ++j) a[j] += a[j + w];
+    const float gmx = block_max(mx, red);
+    float gs = sm * __expf(mx - gmx), sx = a[0];
+    block_sum2(gs, sx, red, red2);
+    // every thread holds the same gmx, gs and sx: lanes 0 .. 4 of wave 0 add the row's five words in ONE atomic instruction (loss_sum and count in
+    // one cache line, the three terms in another) instead of one lane issuing five in a row onto words every other row's block adds to as well
+    const float lse = gmx + logf(gs);
+    if (threadIdx.x == 0) row_lse[row] = lse;
+    if (tgt >= 0 && tgt < V && threadIdx.x < (terms ? 5 : 2)) {
+        const float nll = lse - to_f(lr[tgt]);
+        const float u = lse - sx / (float)V;
+        const float q = lse * lse;
+        const int k = threadIdx.x;
+        const float val = k == 0 ? (1.0f - eps) * nll + eps * u + zeta * q : k == 1 ? 1.0f : k == 2 ? nll : k == 3 ? u : q;
+        atomicAdd(k == 0 ? loss_sum : k == 1 ? count : terms + (k - 2), val);
+    }
+}
+
+// d l / d x_v = (1 + 2 zeta lse) p_v - (1 - eps) [v = y] - eps / V, times grad_scale / *count; with eps = zeta = 0 the factor is exactly 1 and
+// the two new terms exactly 1 and 0, which leaves ce_bwd_kernel's bits.  Padding columns >= V are neither read nor written.
+template <typename T>
+__global__ __launch_bounds__(256) void ce_smooth_bwd_kernel(const T* __restrict__ logits, long ld, const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ row_lse, const float* __restrict__ count,
+                                                            float grad_scale, float eps, float zeta, T* __restrict__ dl, int Tn, int V) {
+    constexpr int VN = VecN<T>::n;
+    const long row = blockIdx.x;
+    const int t = (int)(row % Tn);
+    const long b = row / Tn;
+    const int64_t tgt = (t + 1 < Tn) ? labels[b * Tn + t + 1] : -100;
+    const bool scored = tgt >= 0 && tgt < V;
+    const float cnt = count[0];
+    const float g = scored && cnt > 0.f ? grad_scale / cnt : 0.f;
+    const float lse = row_lse[row];
+    const float f = 1.0f + 2.0f * zeta * lse;
+    const float keep = 1.0f - eps;
+    const float ev = eps / (float)V;
+    const T* lr = logits + row * ld;
+    T* dr = dl + row * ld;
+    for (int c = threadIdx.x * VN; c < V; c += 256 * VN) {
+        float v[VN];
+        if (c + VN <= V) {
+            load_f<VN>(lr + c, v);
+#pragma unroll
+            for (int j = 0; j < VN; ++j)
+                v[j] = scored ? ((f * __expf(v[j] - lse) - ((int64_t)(c + j) == tgt ? keep : 0.f)) - ev) * g : 0.f;
+            store_f<VN>(dr + c, v);
+        } else {
+            for (int j = 0; j < VN && c + j < V; ++j) {
+                const float x = to_f(lr[c + j]);
+                dr[c + j] = from_f<T>(scored ? ((f * __expf(x - lse) - ((int64_t)(c + j) == tgt ? keep : 0.f)) - ev) * g : 0.f);
+            }
+        }
+    }
+}
+
 // The lowest index of the maximum, with NaN read as -inf: torch.argmax on every row without NaN (exact ties: lowest index), and always an index
 // in [0, V).  A thread that meets nothing above -inf keeps "no index"; a row where that holds for every thread is all -inf / NaN and gives 0,
 // the lowest index of its maximum.  (The scan loop is the hot part and stays one compare per element; the old kernel returned 2^31 - 1 there,
@@ -292,6 +408,31 @@ int av_ce_bwd(const void* logits, long ld, const int64_t* labels, const float* r
     AV_CHECK_ARG(ld % 8 == 0 && ld >= V, "ce_bwd: ld must be a multiple of 8 and >= V (one row stride for logits and dlogits)");
     if (dtype == AV_F32) hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3((long)B * T), dim3(256), 0, st, (const float*)logits, ld, labels, row_lse, count, grad_scale, (float*)dlogits, T, V);
     else hipLaunchKernelGGL((ce_bwd_kernel<bf16>), dim3((long)B * T), dim3(256), 0, st, (const bf16*)logits, ld, labels, row_lse, count, grad_scale, (bf16*)dlogits, T, V);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+// 0 <= label_smoothing < 1 and z_loss >= 0, both finite (a NaN fails every comparison)
+static bool ce_smooth_range_ok(float eps, float zeta) { return eps >= 0.f && eps < 1.f && zeta >= 0.f && zeta < INFINITY; }
+
+int av_ce_smooth_fwd(const void* logits, long ld, const int64_t* labels, int B, int T, int V, float eps, float zeta, float* row_lse,
+                     float* loss_sum, float* count, float* terms, int dtype, hipStream_t st) {
+    AV_CHECK_ARG(logits && labels && row_lse && loss_sum && count && B > 0 && T > 0 && V > 0, "ce_smooth_fwd: bad args");
+    AV_CHECK_ARG(ld % 8 == 0 && ld >= V, "ce_smooth_fwd: ld must be a multiple of 8 and >= V");
+    AV_CHECK_ARG(ce_smooth_range_ok(eps, zeta), "ce_smooth_fwd: label_smoothing %g must be in [0, 1) and z_loss %g finite and >= 0", eps, zeta);
+    if (dtype == AV_F32) hipLaunchKernelGGL((ce_smooth_fwd_kernel<float>), dim3((long)B * T), dim3(256), 0, st, (const float*)logits, ld, labels, T, V, eps, zeta, row_lse, loss_sum, count, terms);
+    else hipLaunchKernelGGL((ce_smooth_fwd_kernel<bf16>), dim3((long)B * T), dim3(256), 0, st, (const bf16*)logits, ld, labels, T, V, eps, zeta, row_lse, loss_sum, count, terms);
+    AV_LAUNCH_CHECK();
+    return AV_OK;
+}
+
+int av_ce_smooth_bwd(const void* logits, long ld, const int64_t* labels, const float* row_lse, const float* count, float grad_scale,
+                     float eps, float zeta, void* dlogits, int B, int T, int V, int dtype, hipStream_t st) {
+    AV_CHECK_ARG(logits && labels && row_lse && count && dlogits && B > 0 && T > 0 && V > 0, "ce_smooth_bwd: bad args");
+    AV_CHECK_ARG(ld % 8 == 0 && ld >= V, "ce_smooth_bwd: ld must be a multiple of 8 and >= V (one row stride for logits and dlogits)");
+    AV_CHECK_ARG(ce_smooth_range_ok(eps, zeta), "ce_smooth_bwd: label_smoothing %g must be in [0, 1) and z_loss %g finite and >= 0", eps, zeta);
+    if (dtype == AV_F32) hipLaunchKernelGGL((ce_smooth_bwd_kernel<float>), dim3((long)B * T), dim3(256), 0, st, (const float*)logits, ld, labels, row_lse, count, grad_scale, eps, zeta, (float*)dlogits, T, V);
+    else hipLaunchKernelGGL((ce_smooth_bwd_kernel<bf16>), dim3((long)B * T), dim3(256), 0, st, (const bf16*)logits, ld, labels, row_lse, count, grad_scale, eps, zeta, (bf16*)dlogits, T, V);
     AV_LAUNCH_CHECK();
     return AV_OK;
 }

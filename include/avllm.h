@@ -289,6 +289,24 @@ int avllm_attention_fwd_mxq(const void* q, const void* k, const void* v, void* o
 /* dlogits = (softmax - onehot) * (grad_scale / *count) for scored rows, 0 elsewhere (may alias logits) */
 int avllm_ce_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* row_lse, const float* count,
                  float grad_scale, void* dlogits, int32_t B, int32_t T, int32_t V, int32_t dtype, void* stream);
+/* The same cross entropy with label smoothing eps = label_smoothing and the auxiliary z-loss zeta = z_loss (PaLM).  Scoring, shift and ld rules
+ * are those of avllm_ce_fwd / avllm_ce_bwd.  For a scored row with logits x over the V real columns (never the padding up to ld),
+ * lse = log sum_v exp x_v, p = exp(x - lse) and target y:
+ *     nll = lse - x_y,   u = lse - (1/V) sum_v x_v,   q = lse^2,   l = (1 - eps) nll + eps u + zeta q,   loss = sum_scored l / count,
+ *     d l / d x_v = (1 + 2 zeta lse) p_v - (1 - eps) [v = y] - eps / V.
+ * The eps part is F.cross_entropy(label_smoothing = eps).  0 <= eps < 1 and zeta >= 0, both finite; anything else is AV_ERR_ARG.
+ * fwd: row_lse [B*T] written for every row; l is ADDED onto *loss_sum and 1 onto *count per scored row (zero them first); terms (optional,
+ * [3], accumulated too) receives the raw sums of nll, u and q, so that a perplexity comparable across eps can be logged.  The row's logits are
+ * read once: their plain fp32 sum is gathered in the pass that forms lse.
+ * bwd: dlogits = d l / d x * (grad_scale / *count) on scored rows, 0 elsewhere and everywhere when *count == 0; may alias logits; columns >= V
+ * are not touched.  With eps = zeta = 0 both give the bits of avllm_ce_fwd / avllm_ce_bwd for row_lse, count and dlogits (loss_sum up to the
+ * order of the float atomics). */
+int avllm_ce_smooth_fwd(const void* logits, int64_t ld, const int64_t* labels, int32_t B, int32_t T, int32_t V,
+                        float label_smoothing, float z_loss, float* row_lse, float* loss_sum, float* count,
+                        float* terms /* [3], optional, accumulated */, int32_t dtype, void* stream);
+int avllm_ce_smooth_bwd(const void* logits, int64_t ld, const int64_t* labels, const float* row_lse, const float* count,
+                        float grad_scale, float label_smoothing, float z_loss, void* dlogits,
+                        int32_t B, int32_t T, int32_t V, int32_t dtype, void* stream);
 int avllm_argmax_rows(const void* logits, int64_t ld, int64_t rows, int32_t V, int64_t* out, int32_t dtype, void* stream);
 /* One sampled token per row (GenerationMixin with do_sample=True, clip_whisper_model.py:1326-1340): HF's TemperatureLogitsWarper
  * (logits / temperature), TopKLogitsWarper (top_k > 0: keys below the k-th largest scaled logit dropped, ties kept; 0 = off) and
@@ -841,6 +859,20 @@ int avllm_llama_lora_bwd_layers(const avllm_llama* m, const int64_t* labels, int
 int avllm_llama_lora_bwd_layers_dx(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
                                    float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
                                    avllm_layer_cb after_layer, void* user, void* dx_embeds, void* stream);
+/* The training objective with label smoothing and the z-loss (avllm_ce_smooth_fwd's rule): label_smoothing in [0, 1), z_loss >= 0, else
+ * AV_ERR_ARG.  loss_terms: optional device memory [3]; with either value non-zero the forward adds the raw sums of nll, u and q onto it (zero
+ * it first).  The two entries below are avllm_llama_lora_fwd_loss and avllm_llama_lora_bwd_layers_dx with that objective: the backward takes
+ * the options its forward took.  opts == NULL, or both values 0: exactly the launches of the entries without options (the plain cross
+ * entropy; loss_terms is left alone).  The options are an argument, not fields of avllm_llama: the descriptor keeps its layout. */
+typedef struct {
+    float label_smoothing, z_loss;
+    float* loss_terms;
+} avllm_loss_opts;
+int avllm_llama_lora_fwd_loss_opts(const avllm_llama* m, const void* x, const int64_t* labels, int32_t B, int32_t S, void* logits,
+                                   float* loss_sum, float* count, const avllm_loss_opts* opts, void* ws, size_t ws_bytes, void* stream);
+int avllm_llama_lora_bwd_layers_dx_opts(const avllm_llama* m, const int64_t* labels, int32_t B, int32_t S, const float* count,
+                                        float grad_scale, void* ws, size_t ws_bytes, int32_t layer_hi, int32_t layer_lo,
+                                        avllm_layer_cb after_layer, void* user, void* dx_embeds, const avllm_loss_opts* opts, void* stream);
 
 /* Inference: prefill on inputs_embeds and single-token steps with a KV cache (llm.generate,
  * clip_whisper_model.py:1337-1340 -> GenerationMixin greedy).  kcache/vcache [layers][B][Tmax][d].

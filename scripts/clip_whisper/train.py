@@ -38,6 +38,12 @@ def parse_args(argv=None):
                         "device; never both streams); default 0 = off (YAML key model.modality_dropout_audio)")
     p.add_argument("--modality_dropout_video", type=float, default=None,
                    help="the probability that a clip loses its video; the two must add up to at most 1 (YAML key model.modality_dropout_video)")
+    p.add_argument("--label_smoothing", type=float, default=None,
+                   help="label smoothing of the training loss, in [0, 1): F.cross_entropy(label_smoothing=...) on the device; validation keeps "
+                        "the plain cross entropy; default 0 = off (YAML key model.label_smoothing; effect on WER not measured)")
+    p.add_argument("--z_loss", type=float, default=None,
+                   help="coefficient of the auxiliary z-loss z * logsumexp(logits)^2 per scored token (PaLM uses 1e-4), >= 0; training loss "
+                        "only; default 0 = off (YAML key model.z_loss)")
     p.add_argument("--noise_path", default=None,
                    help="acoustic augmentation: a .wav / .npy noise recording or a directory of them (16 kHz); a segment of one is mixed into "
                         "each training clip on the device (YAML key data.noise_path; default none = off; effect on WER not measured)")
@@ -99,7 +105,7 @@ def main():
                             "learning_rate": a.learning_rate, "max_seq_len": a.max_seq_len, "use_fp16": a.fp16, "use_4bit": a.use_4bit,
                             "lora_r": a.lora_r, "lora_alpha": a.lora_alpha, "connector_type": a.connector_type, "train_connectors": a.train_connectors,
                             "lora_target_modules": a.lora_target_modules, "modality_dropout_audio": a.modality_dropout_audio,
-                            "modality_dropout_video": a.modality_dropout_video, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
+                            "modality_dropout_video": a.modality_dropout_video, "label_smoothing": a.label_smoothing, "z_loss": a.z_loss, "max_grad_norm": a.max_grad_norm, "log_interval": a.log_interval, "save_every": a.save_every, "seed": a.seed,
                             "grad_accum_steps": a.grad_accum_steps, "save_steps": a.save_steps, "log_param_updates": a.log_param_updates or None,
                             "noise_path": a.noise_path, "noise_snr": a.noise_snr, "noise_prob": a.noise_prob, "spec_time_masks": a.spec_time_masks,
                             "spec_time_width": a.spec_time_width, "spec_time_ratio": a.spec_time_ratio, "spec_freq_masks": a.spec_freq_masks,
@@ -131,6 +137,7 @@ def main():
                              connector_type=cfg.get("connector_type", "simple"), train_connectors=bool(cfg.get("train_connectors", False)),
                              modality_dropout_audio=float(cfg.get("modality_dropout_audio") or 0.0),
                              modality_dropout_video=float(cfg.get("modality_dropout_video") or 0.0),
+                             label_smoothing=float(cfg.get("label_smoothing") or 0.0), z_loss=float(cfg.get("z_loss") or 0.0),
                              synthetic_weights=a.synthetic_weights or a.tiny, **kw)
     if a.synthetic:
         frames = a.frames if not a.tiny else 5
